@@ -436,6 +436,33 @@ def check_picture(wl, s=0, f=0):
     return True
 
 
+DUMP_BYTES = 48 << 20           # --dump-outputs: float32 bytes written at most (under the 64 MB a dump may take)
+DUMP_SEED = 20240               # ... and the seed of the sample positions, fixed: two builds dump the same samples
+
+
+def dump_outputs(wl, path):
+    """--dump-outputs DIR: the pictures of the last timed step, as the caller of the path receives them (the u8 planes
+    of batch set (k - 1) % queues), into DIR/picture_y.npy, picture_u.npy, picture_v.npy as float32, shape (frames, n):
+    the same n positions of the plane in every picture, a seeded sample drawn in proportion to the plane's size when
+    the whole batch would be more than DUMP_BYTES (8 x 2160p: about one sample in eight).  Returns what it wrote."""
+    b = wl.sets[(wl.k - 1) % wl.queues]
+    total = wl.frames * sum(h * w for (h, w) in wl.dims)
+    frac = min(1.0, DUMP_BYTES / 4 / total)
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    for k, name in enumerate(("picture_y", "picture_u", "picture_v")):
+        h, w = wl.dims[k]
+        n = int(h * w * frac)
+        pos = np.sort(np.random.default_rng(DUMP_SEED + k).choice(h * w, n, replace=False)) if n < h * w else None
+        a = np.empty((wl.frames, n), np.float32)
+        for f in range(wl.frames):
+            plane = b.out[f][k].download().reshape(-1)
+            a[f] = plane if pos is None else plane[pos]
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name] = list(a.shape)
+    return written
+
+
 def decode_variant(device, frames=8, steps=24, check=True, queues=2, **geom):
     """The headline's step on another kind of picture (outside the timed region, a context of its own): the whole pixel
     path -- upsample where the precision has one, OBMC prediction, 3-level DD(9,7) transform with the add -- two batches in
@@ -1188,7 +1215,12 @@ def main():
                          "is its own; as one block at the end the two-queue pipeline drains once, not per sample")
     ap.add_argument("--profile-every", type=int, default=0,
                     help="(r02 form) bracket every n-th timed step instead; n > steps: no samples")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the pictures the last one decoded to DIR/*.npy (float32; a fixed, "
+                         "seeded sample of each plane; rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus is None:           # under a launcher the world size is the number of GPUs
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))
 
@@ -1244,6 +1276,10 @@ def main():
         for _ in range(8):
             wl.step()
         ctx.synchronize()
+    # (the prewarm ends where batch set 0 is next, however many steps it took: the set of the last timed step, whose
+    # pictures --dump-outputs writes, follows from --warmup and --steps alone)
+    while wl.k % args.queues:
+        wl.step()
     for _ in range(args.warmup):
         wl.step()
     ctx.profile_enable(True)
@@ -1261,6 +1297,9 @@ def main():
     dt = time.perf_counter() - t0
     prof = ctx.profile_read()
     ctx.profile_enable(False)
+    if args.dump_outputs and rank == 0:
+        # (before anything else runs on the workload's planes; outside the timed region)
+        dump_outputs(wl, args.dump_outputs)
     if dist is not None:
         import torch
         t = torch.tensor([dt], dtype=torch.float64)

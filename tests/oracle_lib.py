@@ -3,7 +3,10 @@
 TEST INFRASTRUCTURE: only tests/, __graft_entry__.smoke() and bench.py's
 cpu_baseline leg may import this.  The product package never does.
 """
+import atexit
 import ctypes as C
+import hashlib
+import json
 import os
 import subprocess
 
@@ -90,6 +93,54 @@ class LowDelayParams(C.Structure):
 
 def ref_available():
     return os.path.exists(os.path.join(ORACLE_DIR, "_ref", "libschro_refdrv.so"))
+
+
+# The reference's compiled kernels' results, stored: tests/golden/ref_kernel_digests.json holds a digest of what they
+# computed for every case the tests pin them on (tests/golden/make_ref_digests.py, where oracle/_ref is built), so that
+# a box without oracle/_ref checks the same cases.
+REF_DIGESTS = os.path.join(ROOT, "tests", "golden", "ref_kernel_digests.json")
+_DIGESTS = None
+_RECORDED = {}
+
+
+def digest(a):
+    """sha256 (first 20 hex digits) of an array's dtype, shape and bytes."""
+    a = np.ascontiguousarray(a)
+    h = hashlib.sha256(("%s %s " % (a.dtype.str, a.shape)).encode())
+    h.update(a.tobytes())
+    return h.hexdigest()[:20]
+
+
+def _write_recorded():
+    d = json.load(open(REF_DIGESTS)) if os.path.exists(REF_DIGESTS) else {}
+    d.update(_RECORDED)
+    with open(REF_DIGESTS, "w") as f:
+        json.dump(dict(sorted(d.items())), f, indent=0)
+        f.write("\n")
+
+
+def assert_reference(key, got, reference):
+    """`got` is what the reference's compiled kernels give for the case `key`: reference() -- their result, computed
+    where oracle/_ref is built -- and everywhere the digest of it that REF_DIGESTS stores.
+    SCHRO_REF_DIGESTS_RECORD=1 (make_ref_digests.py): record reference()'s digest instead of looking it up."""
+    global _DIGESTS
+    if os.environ.get("SCHRO_REF_DIGESTS_RECORD") == "1":
+        assert ref_available(), "recording needs oracle/_ref"
+        if not _RECORDED:
+            atexit.register(_write_recorded)
+        want = reference()
+        assert key not in _RECORDED, "case key used twice: " + key
+        _RECORDED[key] = digest(want)
+        assert np.array_equal(got, want), key
+        return
+    if _DIGESTS is None:
+        _DIGESTS = json.load(open(REF_DIGESTS))
+    assert key in _DIGESTS, "no stored result of the reference kernels for " + key
+    if ref_available():
+        want = reference()
+        assert np.array_equal(got, want), key
+        assert digest(want) == _DIGESTS[key], key + ": the reference kernels' result is not the stored one"
+    assert digest(got) == _DIGESTS[key], key
 
 
 def refdrv():

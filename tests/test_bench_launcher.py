@@ -115,3 +115,49 @@ def test_coherent_motion_field_keeps_the_mode_mix():
     for c in range(4):
         share = np.bincount(v[:, c] & 3, minlength=4) / len(v)
         assert share.min() > 0.2 and share.max() < 0.3, (c, share)
+
+
+def test_dump_outputs_writes_the_last_steps_pictures(tmp_path):
+    """--dump-outputs: the planes of the batch set the last step ran, float32, the same seeded positions in every picture
+    and from run to run, within the size a dump may take."""
+    import numpy as np
+    import bench
+
+    class Plane:
+        def __init__(self, a):
+            self.a = a
+
+        def download(self):
+            return self.a.copy()
+
+    class Set:
+        # (a plane's values are its sample positions: set 0 positive, set 1 negative)
+        def __init__(self, s):
+            self.out = [[Plane((1 - 2 * s) * np.arange(h * w, dtype=np.int32).reshape(h, w)) for (h, w) in wl.dims]
+                        for f in range(wl.frames)]
+
+    class Wl:
+        frames, queues, k = 3, 2, 7                 # the last step (k = 6) ran set 0
+        dims = [(2160, 3840), (1080, 1920), (1080, 1920)]
+
+    wl = Wl()
+    wl.sets = [Set(0), Set(1)]
+    a, b = tmp_path / "a", tmp_path / "b"
+    got = bench.dump_outputs(wl, str(a))
+    bench.dump_outputs(wl, str(b))
+    total = 0
+    for name, (h, w) in zip(("picture_y", "picture_u", "picture_v"), wl.dims):
+        x = np.load(a / (name + ".npy"))
+        assert x.dtype == np.float32 and list(x.shape) == got[name] and x.shape[0] == wl.frames
+        assert np.array_equal(x, np.load(b / (name + ".npy")))      # the same positions from run to run
+        assert 0 < x.shape[1] < h * w
+        assert (x == x[0]).all()                                      # ... and in every picture
+        assert x.min() >= 0 and (np.diff(x[0]) > 0).all() and x.max() < h * w
+        total += x.nbytes
+    assert total <= 64 << 20
+    # small pictures go out whole
+    wl.dims = [(16, 32), (8, 16), (8, 16)]
+    wl.sets = [Set(0), Set(1)]
+    bench.dump_outputs(wl, str(a))
+    y = np.load(a / "picture_y.npy")
+    assert np.array_equal(y, np.stack([p[0].download().reshape(-1) for p in wl.sets[0].out]).astype(np.float32))

@@ -10,57 +10,58 @@ import json
 import os
 
 import numpy as np
-import pytest
 
 import oracle_lib as O
 import stream_lib as S
-
-needs_ref = pytest.mark.skipif(not O.ref_available(), reason="oracle/_ref not built (needs /root/reference)")
-
 
 def test_offset_3_8_table_is_the_references():
     want = json.load(open(os.path.join(S.GOLDEN, "arith_lut.json")))["schro_table_offset_3_8"]
     assert O.quant_offset_3_8() == want
 
 
-@needs_ref
 def test_s16_orc_arithmetic_against_the_compiled_reference_kernels():
-    ref = O.reforc()
     qf, qo12 = O.quant_tables()
     qo38 = O.quant_offset_3_8()
     vals = np.arange(-32768, 32768, dtype=np.int32).astype(np.int16)
+
+    def dequantise_ip(qi, off):
+        # in place, any width: orc_dequantise_s16_ip_2d (the general noarith codeblock)
+        a = vals.reshape(256, 256).copy()
+        O.reforc().orc_dequantise_s16_ip_2d(a.ctypes.data_as(C.c_void_p), a.strides[0], qf[qi], off + 2, 256, 256)
+        return a
+
+    def dequantise_packed(qi, name, src):
+        dst = np.zeros((9, 24), np.int16)
+        getattr(O.reforc(), name)(dst.ctypes.data_as(C.c_void_p), dst.strides[0], src.ctypes.data_as(C.c_void_p),
+                                  src.strides[0], qf[qi], qo38[qi] + 2, 9)
+        return dst
     for qi in range(61):
         for intra, off in ((1, qo12[qi]), (0, qo38[qi])):
-            # in place, any width: orc_dequantise_s16_ip_2d (the general noarith codeblock)
-            a = vals.reshape(256, 256).copy()
-            ref.orc_dequantise_s16_ip_2d(a.ctypes.data_as(C.c_void_p), a.strides[0], qf[qi], off + 2, 256, 256)
             got = np.zeros((256, 256), np.int16)
             O.dequant_codeblock(got, vals.reshape(256, 256), qi, intra, 1)
-            assert np.array_equal(got, a), (qi, intra)
+            O.assert_reference("dequantise_s16_ip_2d/%d/intra%d" % (qi, intra), got, lambda: dequantise_ip(qi, off))
         # the 8- and 4-wide forms read a packed source (schrodecoder.c:3410-3433)
         for n, name in ((8, "orc_dequantise_s16_2d_8xn"), (4, "orc_dequantise_s16_2d_4xn")):
             src = np.ascontiguousarray(vals[1000 * n:1000 * n + 9 * n].reshape(9, n))
-            dst = np.zeros((9, 24), np.int16)
-            getattr(ref, name)(dst.ctypes.data_as(C.c_void_p), dst.strides[0], src.ctypes.data_as(C.c_void_p),
-                               src.strides[0], qf[qi], qo38[qi] + 2, 9)
             got = np.zeros((9, 24), np.int16)
             O.dequant_codeblock(got[:, :n], src, qi, 0, 1)
-            assert np.array_equal(got, dst), (qi, name)
+            O.assert_reference("%s/%d" % (name[4:], qi), got, lambda: dequantise_packed(qi, name, src))
 
 
-@needs_ref
 def test_s32_arithmetic_against_the_compiled_reference_kernel():
-    ref = O.reforc()
     qf, qo12 = O.quant_tables()
     rng = np.random.default_rng(3)
     small = rng.integers(-70000, 70000, (64, 96)).astype(np.int32)
     small[0, :8] = [0, 1, -1, 2, -2, 32767, -32768, 65536]
-    for qi in range(0, 61, 3):
+
+    def dequantise_ip(qi):
         a = small.copy()
-        ref.orc_dequantise_s32_ip_2d(a.ctypes.data_as(C.c_void_p), a.strides[0], qf[qi], qo12[qi] + 2, 96, 64)
+        O.reforc().orc_dequantise_s32_ip_2d(a.ctypes.data_as(C.c_void_p), a.strides[0], qf[qi], qo12[qi] + 2, 96, 64)
+        return a
+    for qi in range(0, 61, 3):
         got = np.zeros((64, 96), np.int32)
         O.dequant_codeblock(got, small, qi, 1, 0)
-        assert np.array_equal(got, a), qi
+        O.assert_reference("dequantise_s32_ip_2d/%d" % qi, got, lambda: dequantise_ip(qi))
 
 
 def test_c_int_arithmetic_is_schro_dequantise():

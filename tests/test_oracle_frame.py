@@ -53,22 +53,26 @@ def test_planes_and_aprons(h, w):
                 assert up.get(i, x, y) == want, (i, x, y)
 
 
-@pytest.mark.skipif(not O.ref_available(), reason="oracle/_ref not built")
 def test_convert_matches_reference_kernels():
-    L = O.reforc()
     s16 = np.arange(-32768, 32768, dtype=np.int32).astype(np.int16)
-    d = np.zeros(65536, np.uint8)
-    L.orc_offsetconvert_u8_s16(d.ctypes.data_as(C.c_void_p), s16.ctypes.data_as(C.c_void_p), C.c_int(65536))
-    assert np.array_equal(O.convert_u8(s16.reshape(256, 256), 256, 256).ravel(), d)
+
+    def ref_s16():
+        d = np.zeros(65536, np.uint8)
+        O.reforc().orc_offsetconvert_u8_s16(d.ctypes.data_as(C.c_void_p), s16.ctypes.data_as(C.c_void_p), C.c_int(65536))
+        return d
+    O.assert_reference("offsetconvert_u8_s16", O.convert_u8(s16.reshape(256, 256), 256, 256).ravel(), ref_s16)
     # s32: the shipped C fallback (schroorc-dist.c:4296-4303, convsuslw) and the Orc source the
     # JIT path runs (schroorc.orc:513-521, convssslw) disagree for sample + 128 > 32767 (fallback
     # -> 0, Orc -> 255); both agree everywhere below, which covers every legal sample.  The oracle
     # and the GPU follow the Orc source.
     s32 = np.concatenate([np.arange(-70000, 32640, 7), [-2**31, -40000, 32639, 0, -129]]).astype(np.int32)
     s32 = np.resize(s32, (100, 200)).copy()
-    d = np.zeros(s32.size, np.uint8)
-    L.orc_offsetconvert_u8_s32(d.ctypes.data_as(C.c_void_p), s32.ctypes.data_as(C.c_void_p), C.c_int(s32.size))
-    assert np.array_equal(O.convert_u8(s32, 200, 100).ravel(), d)
+
+    def ref_s32():
+        d = np.zeros(s32.size, np.uint8)
+        O.reforc().orc_offsetconvert_u8_s32(d.ctypes.data_as(C.c_void_p), s32.ctypes.data_as(C.c_void_p), C.c_int(s32.size))
+        return d
+    O.assert_reference("offsetconvert_u8_s32", O.convert_u8(s32, 200, 100).ravel(), ref_s32)
     big = np.array([[32640, 40000, 70000, 2**31 - 1]], np.int32)
     assert O.convert_u8(big, 4, 1).tolist() == [[255, 255, 255, 0]]     # addl wraps first
 

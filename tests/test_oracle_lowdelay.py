@@ -30,21 +30,23 @@ def test_quant_tables_match_the_reference_constants():
     assert offset == want["schro_table_offset_1_2"]
 
 
-@pytest.mark.skipif(not O.ref_available(), reason="oracle/_ref not built")
 def test_fast_dequantisation_matches_compiled_reference_kernel():
-    ref = O.reforc().orc_dequantise_var_s16_ip
-    ref.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     factor, offset = O.quant_tables()
     q = np.concatenate([np.arange(-300, 301), synth.full_range(1, 4000, np.int16, seed=9).ravel(),
                         np.array([-32768, 32767, -32767, 16384, -16384])]).astype(np.int16)
-    for qi in range(61):
+
+    def dequantise_var(qi):
+        ref = O.reforc().orc_dequantise_var_s16_ip
+        ref.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
         got = q.copy()
         # as schro_lowdelay_init_quant_arrays stores them: int16_t, offset + 2 (schrolowdelay.c:478-479)
         f = np.full(q.size, factor[qi] & 0xffff, np.uint16).view(np.int16)
         o = np.full(q.size, (offset[qi] + 2) & 0xffff, np.uint16).view(np.int16)
         ref(got.ctypes.data, f.ctypes.data, o.ctypes.data, q.size)
+        return got
+    for qi in range(61):
         mine = np.array([O.lib().oracle_dequantise_var_s16(int(v), factor[qi], offset[qi]) for v in q], np.int16)
-        assert np.array_equal(got, mine), qi
+        O.assert_reference("dequantise_var_s16_ip/%d" % qi, mine, lambda: dequantise_var(qi))
 
 
 def pack_bits(bits, nbytes, pad="1"):

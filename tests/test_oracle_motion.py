@@ -126,59 +126,59 @@ def test_rim_weights_fold_to_64():
             assert (out == 77).all(), (blk, k)
 
 
-@pytest.mark.skipif(not O.ref_available(), reason="oracle/_ref not built")
 def test_block_arithmetic_matches_reference_kernels():
     """orc_combine4_nxm_u8, orc_combine2_nxm_u8, orc_avg2_nxm_u8, orc_rrshift6_add_s16_2d from
     the reference's compiled kernels vs the formulas the oracle and the GPU kernel use."""
-    L = O.reforc()
     rng = np.random.default_rng(7)
     n, m = 24, 16
     a, b, c, d = (rng.integers(0, 256, (m, n), dtype=np.uint8) for _ in range(4))
     ai, bi_, ci, di = (x.astype(np.int64) for x in (a, b, c, d))
     vp = C.c_void_p
     ptr = lambda x: x.ctypes.data_as(vp)
+
+    def kernel(name, *args):
+        """One of the reference's kernels writing a fresh m x n u8 block."""
+        out = np.zeros((m, n), np.uint8)
+        getattr(O.reforc(), name)(ptr(out), n, *args)
+        return out
     for ry in range(4):
         for rx in range(4):
             w = [(4 - ry) * (4 - rx), (4 - ry) * rx, ry * (4 - rx), ry * rx]
-            out = np.zeros((m, n), np.uint8)
-            L.orc_combine4_nxm_u8(ptr(out), n, ptr(a), n, ptr(b), n, ptr(c), n, ptr(d), n,
-                                  w[0], w[1], w[2], w[3], n, m)
             want = (w[0] * ai + w[1] * bi_ + w[2] * ci + w[3] * di + 8) >> 4
-            assert np.array_equal(out, want.astype(np.uint8))
-    out = np.zeros((m, n), np.uint8)
-    L.orc_avg2_nxm_u8(ptr(out), n, ptr(a), n, ptr(b), n, n, m)
-    assert np.array_equal(out, ((ai + bi_ + 1) >> 1).astype(np.uint8))
+            O.assert_reference("combine4_nxm_u8/%d_%d" % (ry, rx), want.astype(np.uint8),
+                               lambda: kernel("orc_combine4_nxm_u8", ptr(a), n, ptr(b), n, ptr(c), n, ptr(d), n,
+                                              w[0], w[1], w[2], w[3], n, m))
+    O.assert_reference("avg2_nxm_u8", ((ai + bi_ + 1) >> 1).astype(np.uint8),
+                       lambda: kernel("orc_avg2_nxm_u8", ptr(a), n, ptr(b), n, n, m))
     for (w1, w2, bits) in ((2, 3, 1), (3, 5, 3), (3, -1, 1), (100, 100, 2)):
-        L.orc_combine2_nxm_u8(ptr(out), n, ptr(a), n, ptr(b), n, w1, w2, (1 << bits) >> 1, bits, n, m)
         t = ((a.astype(np.int64) * w1).astype(np.int16).astype(np.int64) + (b.astype(np.int64) * w2).astype(np.int16))
         t = ((t.astype(np.int16).astype(np.int64) + ((1 << bits) >> 1)).astype(np.int16).astype(np.int64)) >> bits
-        assert np.array_equal(out, np.clip(t, 0, 255).astype(np.uint8)), (w1, w2, bits)
+        O.assert_reference("combine2_nxm_u8/%d_%d_%d" % (w1, w2, bits), np.clip(t, 0, 255).astype(np.uint8),
+                           lambda: kernel("orc_combine2_nxm_u8", ptr(a), n, ptr(b), n, w1, w2, (1 << bits) >> 1, bits, n, m))
     res = rng.integers(-32768, 32768, (m, n)).astype(np.int16)
     acc = rng.integers(-32768, 32768, (m, n)).astype(np.int16)
-    L.orc_rrshift6_add_s16_2d(ptr(out), n, ptr(res), 2 * n, ptr(acc), 2 * n, n, m)
     t = ((acc.astype(np.int64) + 32).astype(np.int16).astype(np.int64)) >> 6
     t = (res.astype(np.int64) + t).astype(np.int16)
-    assert np.array_equal(out, np.clip(t, 0, 255).astype(np.uint8))
+    O.assert_reference("rrshift6_add_s16_2d", np.clip(t, 0, 255).astype(np.uint8),
+                       lambda: kernel("orc_rrshift6_add_s16_2d", ptr(res), 2 * n, ptr(acc), 2 * n, n, m))
     res32 = rng.integers(-2**31, 2**31, (m, n)).astype(np.int32)
-    L.orc_rrshift6_add_s32_2d(ptr(out), n, ptr(res32), 4 * n, ptr(acc), 2 * n, n, m)
     t = ((acc.astype(np.int64) + 32).astype(np.int16).astype(np.int64)) >> 6
     t = (res32.astype(np.int16).astype(np.int64) + t).astype(np.int16)      # convlw truncates
-    assert np.array_equal(out, np.clip(t, 0, 255).astype(np.uint8))
+    O.assert_reference("rrshift6_add_s32_2d", np.clip(t, 0, 255).astype(np.uint8),
+                       lambda: kernel("orc_rrshift6_add_s32_2d", ptr(res32), 4 * n, ptr(acc), 2 * n, n, m))
 
 
 def test_rrshift6_s16_and_frame_add_against_the_reference_kernels():
     """r06: the two restatements the S16-destination render and schro_hipframe_add are checked with are the reference's
     own compiled kernels where oracle/_ref exists (orc_rrshift6_s16_ip_2d, orc_add_s16_2d, orc_add_s16_u8_2d); the
     numpy forms (what a box without _ref falls back to) give the same bytes, full range included."""
-    if not O.ref_available():
-        pytest.skip("oracle/_ref not built")
     rng = np.random.default_rng(5)
     acc = rng.integers(-32768, 32768, (37, 53)).astype(np.int16)
     acc[0, :8] = [-32768, 32767, 8159, 8160, 8161, -24609, -24608, 0]
-    assert np.array_equal(O.rrshift6_s16(acc), O.rrshift6_s16_restated(acc))
+    O.assert_reference("rrshift6_s16_ip_2d", O.rrshift6_s16_restated(acc), lambda: O.rrshift6_s16(acc))
     # legal sums: (acc + 32) >> 6 - 128
     legal = rng.integers(0, 255 * 64 + 1, (16, 24)).astype(np.int16)
     assert np.array_equal(O.rrshift6_s16(legal), ((legal.astype(np.int32) + 32) >> 6) - 128)
     d = rng.integers(-32768, 32768, (40, 64)).astype(np.int16)
     for src in (rng.integers(-32768, 32768, (33, 70)).astype(np.int16), rng.integers(0, 256, (44, 60)).astype(np.uint8)):
-        assert np.array_equal(O.frame_add(d, src), O.frame_add_restated(d, src))
+        O.assert_reference("add_s16_2d/%s" % src.dtype.name, O.frame_add_restated(d, src), lambda: O.frame_add(d, src))

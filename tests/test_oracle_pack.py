@@ -65,19 +65,21 @@ def test_pack_matches_the_chain(fmt, chroma):
             assert np.array_equal(got, chain_numpy(pl, hs, vs, fmt, W, H)), (fmt, chroma, w, h, W, H)
 
 
-@pytest.mark.skipif(not O.ref_available(), reason="reference kernels not built (oracle/_ref)")
 def test_yuyv_byte_order_is_the_reference_kernels():
     # orc_packyuyv (schroorc.orc:718-734) compiled from the reference's schroorc-dist.c
     w, h = 64, 4
     pl = planes(w, h, 1, 0, seed=3)
     want = O.pack_u8(pl, 1, 0, O.FORMAT_YUYV, w, h)
-    R = O.reforc()
-    R.orc_packyuyv.argtypes = [C.c_void_p] * 4 + [C.c_int]
-    for i in range(h):
+
+    def packyuyv(i):
+        R = O.reforc()
+        R.orc_packyuyv.argtypes = [C.c_void_p] * 4 + [C.c_int]
         row = np.zeros(2 * w, np.uint8)
         y, u, v = [np.ascontiguousarray(p[i]) for p in pl]
         R.orc_packyuyv(row.ctypes.data, y.ctypes.data, u.ctypes.data, v.ctypes.data, w // 2)
-        assert np.array_equal(row, want[i])
+        return row
+    for i in range(h):
+        O.assert_reference("packyuyv/row%d" % i, want[i], lambda: packyuyv(i))
 
 
 def test_pack_refuses_mixed_crop_and_extension():
@@ -147,38 +149,35 @@ def test_v210_matches_the_chain(dtype):
 
 # ---- v216 / ARGB / AY64 and the > 8-bit output shift --------------------------
 def test_shift_right_against_the_compiled_reference_kernels():
-    if not O.ref_available():
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
     import ctypes as C
-    ref = O.reforc()
     v16 = np.arange(-32768, 32768, dtype=np.int32).astype(np.int16).reshape(256, 256)
     rng = np.random.default_rng(1)
     v32 = rng.integers(-2 ** 31, 2 ** 31, (64, 200)).astype(np.int32)
-    for shift in (1, 2, 4, 6, 8):
-        a = v16.copy()
+
+    def add_const_rshift(v, shift):
+        a = v.copy()
+        f = O.reforc().orc_add_const_rshift_s16 if v.dtype == np.int16 else O.reforc().orc_add_const_rshift_s32
         for row in a:
-            ref.orc_add_const_rshift_s16(row.ctypes.data_as(C.c_void_p), (1 << shift) >> 1, shift, row.size)
-        assert np.array_equal(O.shift_right(v16, shift), a), shift
-        b = v32.copy()
-        for row in b:
-            ref.orc_add_const_rshift_s32(row.ctypes.data_as(C.c_void_p), (1 << shift) >> 1, shift, row.size)
-        assert np.array_equal(O.shift_right(v32, shift), b), shift
+            f(row.ctypes.data_as(C.c_void_p), (1 << shift) >> 1, shift, row.size)
+        return a
+    for shift in (1, 2, 4, 6, 8):
+        for v in (v16, v32):
+            O.assert_reference("add_const_rshift_%s/%d" % (v.dtype.name, shift), O.shift_right(v, shift),
+                               lambda: add_const_rshift(v, shift))
 
 
 def test_depth_conversions_against_the_compiled_reference_kernels():
     # what feeds pack_v216 / pack_argb / pack_ayuv64: x - 128 from u8, truncation from s32
-    if not O.ref_available():
-        pytest.skip("oracle/_ref not built (needs /root/reference)")
     import ctypes as C
-    ref = O.reforc()
     u8 = np.arange(256, dtype=np.uint8)
-    s16 = np.zeros(256, np.int16)
-    ref.orc_offsetconvert_s16_u8(s16.ctypes.data_as(C.c_void_p), u8.ctypes.data_as(C.c_void_p), 256)
-    assert np.array_equal(s16, u8.astype(np.int16) - 128)
     s32 = np.array([0, 1, -1, 32767, 32768, -32768, -32769, 65536 + 5, -70000, 2 ** 31 - 1], np.int32)
-    t16 = np.zeros(s32.size, np.int16)
-    ref.orc_convert_s16_s32(t16.ctypes.data_as(C.c_void_p), s32.ctypes.data_as(C.c_void_p), s32.size)
-    assert np.array_equal(t16, s32.astype(np.int16))
+
+    def convert(name, src):
+        d = np.zeros(src.size, np.int16)
+        getattr(O.reforc(), name)(d.ctypes.data_as(C.c_void_p), src.ctypes.data_as(C.c_void_p), src.size)
+        return d
+    O.assert_reference("offsetconvert_s16_u8", u8.astype(np.int16) - 128, lambda: convert("orc_offsetconvert_s16_u8", u8))
+    O.assert_reference("convert_s16_s32", s32.astype(np.int16), lambda: convert("orc_convert_s16_s32", s32))
     # the oracle applies exactly these before packing: ARGB of (y, 0, 0) is (0xff, y, y, y) mod 256
     y = (u8.astype(np.int16) - 128).reshape(1, 256)
     z = np.zeros((1, 256), np.int16)

@@ -98,15 +98,17 @@ def test_matches_reference_test_model(filt):
         assert np.array_equal(O.iiwt_2d(co, filt), iiwt_ref(co, filt).astype(np.int16)), (filt, h, w)
 
 
-@pytest.mark.skipif(not O.ref_available(), reason="oracle/_ref not built (no /root/reference)")
 @pytest.mark.parametrize("dtype", [np.int16, np.int32])
 @pytest.mark.parametrize("filt", [0, 1, 2, 3, 4, 6])
 def test_matches_reference_kernels_in_reference_schedule(filt, dtype):
+    tag = np.dtype(dtype).name
     for (h, w) in [(2, 2), (4, 6), (6, 4), (16, 16), (18, 34), (48, 64), (2, 40), (40, 2), (256, 256)]:
         co = O.iwt_2d(synth.image_s(h, w, dtype, seed=3), filt)
-        assert np.array_equal(O.iiwt_2d(co, filt), O.refdrv_iiwt_2d(co, filt)), (filt, h, w, "legal")
+        O.assert_reference("iiwt/%s/f%d/%dx%d/legal" % (tag, filt, h, w), O.iiwt_2d(co, filt),
+                           lambda: O.refdrv_iiwt_2d(co, filt))
         fr = synth.full_range(h, w, dtype, seed=5)      # pins every wrap point
-        assert np.array_equal(O.iiwt_2d(fr, filt), O.refdrv_iiwt_2d(fr, filt)), (filt, h, w, "full")
+        O.assert_reference("iiwt/%s/f%d/%dx%d/full" % (tag, filt, h, w), O.iiwt_2d(fr, filt),
+                           lambda: O.refdrv_iiwt_2d(fr, filt))
 
 
 def test_rounding_and_wrap_pins():

@@ -2,14 +2,12 @@
 SchroFrameData / SchroFrame / SchroParams / SchroMemoryDomain (the boundary must
 match the interface it cites).  tests/golden/ref_layout.json holds the reference's offsets,
 recorded from its own headers by scripts/ref_layout.py; here a C program built with OUR header
-prints the mirror structs' offsets and the two are compared member by member.  Where the
-reference's headers are present (the build container), tests/c/layout_check.c also compiles:
-a _Static_assert per member against the real structs."""
+prints the mirror structs' offsets and the two are compared member by member.  (Against the
+reference's headers themselves, tests/c/layout_check.c holds a _Static_assert per member; it
+compiles where those headers are, outside this repository.)"""
 import json
 import os
 import subprocess
-
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MIRROR = {"SchroFrameData": "SchroHipFrameData", "SchroFrame": "SchroHipFrame",
@@ -42,8 +40,3 @@ def test_mirror_structs_have_the_reference_layout(tmp_path):
             if not m.startswith("_"):
                 assert got[t][m] == off, "%s.%s: header %d, reference %d" % (t, m, got[t][m], off)
 
-
-@pytest.mark.skipif(not os.path.isdir("/root/reference/schroedinger"), reason="reference headers not here")
-def test_static_asserts_against_the_reference_headers(tmp_path):
-    subprocess.check_call(["gcc", "-I/root/reference", "-I" + os.path.join(ROOT, "include"), "-c",
-                           os.path.join(ROOT, "tests", "c", "layout_check.c"), "-o", str(tmp_path / "lc.o")])
