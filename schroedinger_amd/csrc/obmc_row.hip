@@ -70,84 +70,47 @@ SCHRO_ROW_KERNEL (obmc_row_kernel_w_h2_uv_3, 6, 3, 1, true, kRTH, false, 1, 2, t
 SCHRO_ROW_KERNEL (obmc_row_kernel_w_h2_4_1, 6, 4, 1, false, kRTH, false, 1, 2, true)
 SCHRO_ROW_KERNEL (obmc_row_kernel_w_h2_uv_4, 6, 4, 1, true, kRTH, false, 1, 2, true)
 
+constexpr RowEntry kHalf[] = {
+  ROW_ENTRY (obmc_row_kernel_2_1), ROW_ENTRY (obmc_row_kernel_2_2), ROW_ENTRY (obmc_row_kernel_3_1), ROW_ENTRY (obmc_row_kernel_3_2),
+  ROW_ENTRY (obmc_row_kernel_4_1), ROW_ENTRY (obmc_row_kernel_4_2),
+  ROW_ENTRY (obmc_row_kernel_uv_2), ROW_ENTRY (obmc_row_kernel_uv_3), ROW_ENTRY (obmc_row_kernel_uv_4),
+  ROW_ENTRY (obmc_row_kernel_p_2_1), ROW_ENTRY (obmc_row_kernel_p_3_1), ROW_ENTRY (obmc_row_kernel_p_4_1),
+  ROW_ENTRY (obmc_row_kernel_p_uv_2), ROW_ENTRY (obmc_row_kernel_p_uv_3), ROW_ENTRY (obmc_row_kernel_p_uv_4),
+  ROW_ENTRY (obmc_row_kernel_h2_3_1), ROW_ENTRY (obmc_row_kernel_h2_uv_3), ROW_ENTRY (obmc_row_kernel_p_h2_3_1), ROW_ENTRY (obmc_row_kernel_p_h2_uv_3),
+  ROW_ENTRY (obmc_row_kernel_h2_4_1), ROW_ENTRY (obmc_row_kernel_h2_uv_4), ROW_ENTRY (obmc_row_kernel_p_h2_4_1), ROW_ENTRY (obmc_row_kernel_p_h2_uv_4),
+  ROW_ENTRY (obmc_row_kernel_w_3_1), ROW_ENTRY (obmc_row_kernel_w_uv_3), ROW_ENTRY (obmc_row_kernel_w_p_3_1), ROW_ENTRY (obmc_row_kernel_w_p_uv_3),
+  ROW_ENTRY (obmc_row_kernel_w_2_1), ROW_ENTRY (obmc_row_kernel_w_4_1), ROW_ENTRY (obmc_row_kernel_w_uv_2), ROW_ENTRY (obmc_row_kernel_w_uv_4),
+  ROW_ENTRY (obmc_row_kernel_w_h2_3_1), ROW_ENTRY (obmc_row_kernel_w_h2_uv_3), ROW_ENTRY (obmc_row_kernel_w_h2_4_1), ROW_ENTRY (obmc_row_kernel_w_h2_uv_4),
+};
+constexpr RowTable kHalfTable = { kHalf, (int) std::size (kHalf) };
+static_assert (row_table_ok (kHalfTable, 1), "obmc_row.hip: one kernel per form");
+static_assert (row_find (kHalfTable, RowForm { 1, 3, 1, 2, true, true }) == obmc_row_kernel_w_h2_3_1
+    && row_find (kHalfTable, RowForm { 1, 2, 2, 1, true, false }) == obmc_row_kernel_2_2 && !row_find (kHalfTable, RowForm { 1, 3, 2, 1, false, true }),
+    "obmc_row.hip: a prediction_only launch without a kernel of its form takes the residual form's; no kernel of two weighted planes");
+
 }                               // namespace
 
-// the kernel of a form: nd dwords per row and segment, np planes per job (3: (U, V) pairs from pair images), ns segments
-// per block row; nores: a prediction_only launch.  NULL: the form has no kernel
-RowKernel
-obmc_row_kernel_half (int nd, int np, int ns, bool nores, bool weighted)
+RowTable
+obmc_row_table_half ()
 {
-  if (weighted) {
-    if (np != 1 && np != 3)
-      return nullptr;           // (two planes per job: the planes run as jobs of their own)
-    const bool uv = np == 3;
-    if (ns == 2)
-      return nd == 3 ? (uv ? obmc_row_kernel_w_h2_uv_3 : obmc_row_kernel_w_h2_3_1) : nd == 4 ? (uv ? obmc_row_kernel_w_h2_uv_4 : obmc_row_kernel_w_h2_4_1) : nullptr;
-    if (nd == 3)
-      return uv ? (nores ? obmc_row_kernel_w_p_uv_3 : obmc_row_kernel_w_uv_3) : (nores ? obmc_row_kernel_w_p_3_1 : obmc_row_kernel_w_3_1);
-    return nd == 2 ? (uv ? obmc_row_kernel_w_uv_2 : obmc_row_kernel_w_2_1) : nd == 4 ? (uv ? obmc_row_kernel_w_uv_4 : obmc_row_kernel_w_4_1) : nullptr;
-  }
-  if (ns == 2) {
-    if (nd == 3 && np == 1)
-      return nores ? obmc_row_kernel_p_h2_3_1 : obmc_row_kernel_h2_3_1;
-    if (nd == 3 && np == 3)
-      return nores ? obmc_row_kernel_p_h2_uv_3 : obmc_row_kernel_h2_uv_3;
-    if (nd == 4 && np == 1)
-      return nores ? obmc_row_kernel_p_h2_4_1 : obmc_row_kernel_h2_4_1;
-    if (nd == 4 && np == 3)
-      return nores ? obmc_row_kernel_p_h2_uv_4 : obmc_row_kernel_h2_uv_4;
-    return nullptr;
-  }
-#ifdef SCHRO_HIP_EXPERIMENTS
-  static const bool pad = SCHRO_ENV ("SCHRO_HIP_OBMC_PAD") && atoi (SCHRO_ENV ("SCHRO_HIP_OBMC_PAD")) != 0;
-  if (pad && nores && nd == 3 && np == 1)
-    return obmc_row_kernel_p_3_1_pad;
-#endif
-  if (nores)
-    switch (nd * 10 + np) {
-      case 23: return obmc_row_kernel_p_uv_2;
-      case 33: return obmc_row_kernel_p_uv_3;
-      case 43: return obmc_row_kernel_p_uv_4;
-      case 21: return obmc_row_kernel_p_2_1;
-      case 31: return obmc_row_kernel_p_3_1;
-      case 41: return obmc_row_kernel_p_4_1;
-    }
-  switch (nd * 10 + np) {
-    case 23: return obmc_row_kernel_uv_2;
-    case 33: return obmc_row_kernel_uv_3;
-    case 43: return obmc_row_kernel_uv_4;
-    case 21: return obmc_row_kernel_2_1;
-    case 22: return obmc_row_kernel_2_2;
-    case 31: return obmc_row_kernel_3_1;
-    case 32: return obmc_row_kernel_3_2;
-    case 41: return obmc_row_kernel_4_1;
-    case 42: return obmc_row_kernel_4_2;
-  }
-  return nullptr;
+  return kHalfTable;
 }
-
-RowKernel obmc_row_kernel_plain (int nd, int np, int ns, bool nores, bool weighted);         // obmc_row_plain.hip
-RowKernel obmc_row_kernel_eighth (int nd, int np, int ns, bool nores, bool weighted);        // obmc_row_eighth.hip
 
 static RowKernel
-row_kernel (int rk, int nd, int np, int ns, bool nores, bool weighted)
+row_kernel (const RowForm & f)
 {
-  return rk == 0 ? obmc_row_kernel_plain (nd, np, ns, nores, weighted) : rk == 3 ? obmc_row_kernel_eighth (nd, np, ns, nores, weighted)
-      : obmc_row_kernel_half (nd, np, ns, nores, weighted);
+#ifdef SCHRO_HIP_EXPERIMENTS
+  static const bool pad = SCHRO_ENV ("SCHRO_HIP_OBMC_PAD") && atoi (SCHRO_ENV ("SCHRO_HIP_OBMC_PAD")) != 0;
+  if (pad && f == obmc_row_kernel_p_3_1_pad_form)
+    return obmc_row_kernel_p_3_1_pad;
+#endif
+  return row_find (f.kind == 0 ? obmc_row_table_plain () : f.kind == 3 ? obmc_row_table_eighth () : obmc_row_table_half (), f);
 }
 
-// the reference kind of a precision: 0 plain planes, 1 half-pel images read at half / quarter pel, 3 at eighth pel
-int
-obmc_row_kind (int prec)
-{
-  return prec == 0 ? 0 : prec == 3 ? 3 : 1;
-}
-
-// weighted: picture weights other than 1, 1 / 2
 bool
-obmc_row_has_kernel (int prec, int nd, int np, int ns, bool weighted)
+obmc_row_has_kernel (const RowForm & form)
 {
-  return row_kernel (obmc_row_kind (prec), nd, np, ns, false, weighted) != nullptr;
+  return row_kernel (form) != nullptr;
 }
 
 // np: planes per job (1, 2); 3: (U, V) pairs from pair images
@@ -155,14 +118,15 @@ obmc_row_has_kernel (int prec, int nd, int np, int ns, bool weighted)
 // over the tiles blockIdx.x + k gridDim.x.  One tile per workgroup 0.167 ms of OBMC per 8 x 2160p step, eight persistent
 // workgroups per CU 0.192, seven 0.192: workgroups that all start together stay in step -- every CU decodes at once,
 // gathers at once, stores at once --, where the dispatcher's own refill staggers them.  HISTORY 9.)
+// (form.nores: a prediction_only launch, whose overflow word the caller passes; every job's residual is NULL)
 int
-launch_obmc_row (hipStream_t stream, const ObmcJob * d_jobs, int njobs, int total_tiles, int prec, int nd, int ns, int np,
-    const uint32_t * d_order, uint32_t * overflow, const uint32_t * d_wtabs, bool weighted)
+launch_obmc_row (hipStream_t stream, const ObmcJob * d_jobs, int njobs, int total_tiles, const RowForm & form,
+    const uint32_t * d_order, uint32_t * overflow, const uint32_t * d_wtabs)
 {
-  // a prediction_only launch (the caller passes its overflow word exactly then: every job's residual is NULL)
-  const RowKernel k = row_kernel (obmc_row_kind (prec), nd, np, ns, overflow != nullptr, weighted);
+  const RowKernel k = row_kernel (form);
   if (!k)
-    return set_error (SCHRO_HIP_EINVAL, "obmc (row): precision %d, %d dwords per row x %d segments x %d planes unsupported", prec, nd, ns, np);
+    return set_error (SCHRO_HIP_EINVAL, "obmc (row): reference kind %d, %d dwords per row x %d segments x %d planes unsupported", form.kind,
+        form.nd, form.ns, form.np);
   // scratch runs: SCHRO_HIP_OBMC_LDS_PAD = bytes of unused dynamic LDS per workgroup (fewer workgroups per CU)
   static const int lds_pad = SCHRO_ENV ("SCHRO_HIP_OBMC_LDS_PAD") ? atoi (SCHRO_ENV ("SCHRO_HIP_OBMC_LDS_PAD")) : 0;
   SCHRO_LAUNCH (k, dim3 (total_tiles), dim3 (kRThreads), (size_t) lds_pad, stream, d_jobs, njobs, d_order, overflow, d_wtabs);
@@ -172,25 +136,37 @@ launch_obmc_row (hipStream_t stream, const ObmcJob * d_jobs, int njobs, int tota
   return 0;
 }
 
-// Prediction dwords per block row (and segment) the row kernels run this plane with, *ns = the segments of a block
-// row; 0: not their case (blocks wider than 32 samples, unaligned references, origins beyond 16 bits, a form without
-// a kernel) -> obmc.hip.
+// RowGeo's tile width and table capacities for nd 2 .. 4 dwords per row and segment, ns segments, (U, V) pairs or not
+struct RowCaps {
+  int tw, blk, item;
+};
+template < int ND, bool UV, int NS > constexpr RowCaps kRowCaps = { RowGeo < ND, UV, NS >::kTW, RowGeo < ND, UV, NS >::kBlk, RowGeo < ND, UV, NS >::kItem };
+template < bool UV, int NS > constexpr RowCaps kRowCapsNd[3] = { kRowCaps < 2, UV, NS >, kRowCaps < 3, UV, NS >, kRowCaps < 4, UV, NS > };
+static RowCaps
+row_caps (int nd, int ns, bool uv)
+{
+  static constexpr const RowCaps *caps[2][2] = { { kRowCapsNd < false, 1 >, kRowCapsNd < false, 2 > }, { kRowCapsNd < true, 1 >, kRowCapsNd < true, 2 > } };
+  return caps[uv][ns - 1][nd - 2];
+}
+
+// The form of the row kernel that runs this plane; false: not their case (blocks wider than 32 samples, unaligned
+// references, origins beyond 16 bits, a form without a kernel) -> obmc.hip.
 // uv: as the U plane of a (U, V) pair from pair images (rows of up to 8 samples = 16 bytes, 64-pixel tiles)
-int
-obmc_row_form (const ObmcJob & j, bool uv, int *ns)
+RowForm
+obmc_row_form (const ObmcJob & j, bool uv, bool nores)
 {
   const int ps = uv ? 1 : 0;
-  *ns = 1;
+  int ns = 1;
   // (pair images go with (U, V) jobs and planes with plane jobs -- except at full pel, where a (U, V) job reads the
   // two PLAIN planes of each reference, j.ref and j.ref_b, and interleaves their rows itself)
   if (j.ref_ps != (j.prec == 0 ? 0 : ps))
-    return 0;
+    return {};
   if (j.prec < 0 || j.prec > 3 || (j.xblen & 1) || j.xblen < 2 || j.yblen > 32)
-    return 0;
+    return {};
   // picture weights: 1, 1 / 2, or (r06) any that are not negative and add up to 1 << bits -- the fades, for which the
   // reference's interior and edge arithmetic agree (obmc_row_body.h: blend_weighted); a gain or a negative weight: obmc.hip
   if (j.w1 < 0 || j.w2 < 0 || j.wbits < 0 || j.wbits > 6 || j.w1 + j.w2 != (1 << j.wbits))
-    return 0;
+    return {};
   // rows of up to 16 bytes are one run; 24-byte rows (the 24 / 16 and 24 / 12 block sets) two segments of 12, 32-byte rows
   // (32 / 16: what the reference's encoder makes of 1080p and larger pictures by default, schroengine.c:411-453) two of 16;
   // 20 and 28 bytes (block lengths the syntax allows and no preset uses, schroparams.c:255-270) two of 10 and 14 in the
@@ -198,54 +174,43 @@ obmc_row_form (const ObmcJob & j, bool uv, int *ns)
   int seg_bytes = j.xblen << ps;
   if (seg_bytes > 16) {
     if (seg_bytes > 32 || (seg_bytes & 3))      // (halves of whole pixel pairs: luma lengths are multiples of 4)
-      return 0;
-    *ns = 2;
+      return {};
+    ns = 2;
     seg_bytes /= 2;
   }
   // rim blocks keep their clamped fetch origins (get_block: at most (size + 32) << prec) in 16 bits
   if (((std::max (j.w, j.h) + 32) << j.prec) > 32767)
-    return 0;
+    return {};
   if (j.prec == 0) {
     // plain planes: dword-aligned runs from a buffer of whole dwords
     if (((((uintptr_t) j.ref[0]) | ((uintptr_t) j.ref[1])) & 3) || ((j.ref_stride[0] | j.ref_stride[1]) & 3) || j.ref_stride[0] < j.w
         || j.ref_stride[1] < j.w || j.w < 4)
-      return 0;
+      return {};
     if (uv && (!j.ref_b[0] || !j.ref_b[1] || ((((uintptr_t) j.ref_b[0]) | ((uintptr_t) j.ref_b[1])) & 3)))
-      return 0;
+      return {};
   } else {
     if ((((uintptr_t) j.ref[0]) | ((uintptr_t) j.ref[1])) & 127)
-      return 0;
+      return {};
     if (((j.ref_stride[0] | j.ref_stride[1]) & 511) || j.ref_stride[0] < hp_chunks (j.w, ps) * 512 || j.ref_stride[1] < hp_chunks (j.w, ps) * 512)
-      return 0;
+      return {};
   }
   const int need = (seg_bytes + 3) / 4, nd = need <= 2 ? 2 : need;      // 2, 3 or 4
-  if (!obmc_row_has_kernel (j.prec, nd, uv ? 3 : 1, *ns, j.w1 != 1 || j.wbits != 1))
-    return 0;
+  const RowForm form = { j.prec == 0 ? 0 : j.prec == 3 ? 3 : 1, nd, uv ? 3 : 1, ns, nores, j.w1 != 1 || j.wbits != 1 };
+  if (!row_kernel (form))
+    return {};
   // the blocks (segments) that can meet a tile and their rows inside it fit the kernel's tables
-  const int tw = uv ? RowGeo < 3, true >::kTW : RowGeo < 3, false >::kTW;
+  const RowCaps caps = row_caps (nd, ns, uv);
   // (a launch's order table names a tile in 16 bits -- plane_obmc.cpp: obmc_tile_order --: larger planes go to obmc.hip
   // instead of failing there)
-  if ((long long) ((j.w + tw - 1) / tw) * ((j.h + kRTH - 1) / kRTH) > 0xffff)
-    return 0;
-  const int nbi = ((tw - 1 + j.xblen - 1) / j.xbsep + 1) * *ns, nbj = (kRTH - 1 + j.yblen - 1) / j.ybsep + 1;
-  int blk_cap, item_cap;
-  if (*ns == 2) {
-    blk_cap = uv ? RowGeo < 3, true, 2 >::kBlk : RowGeo < 3, false, 2 >::kBlk;
-    item_cap = uv ? RowGeo < 3, true, 2 >::kItem : RowGeo < 3, false, 2 >::kItem;
-  } else if (nd == 4) {
-    blk_cap = uv ? RowGeo < 4, true >::kBlk : RowGeo < 4, false >::kBlk;
-    item_cap = uv ? RowGeo < 4, true >::kItem : RowGeo < 4, false >::kItem;
-  } else {
-    blk_cap = uv ? (nd <= 2 ? RowGeo < 2, true >::kBlk : RowGeo < 3, true >::kBlk) : (nd <= 2 ? RowGeo < 2, false >::kBlk : RowGeo < 3, false >::kBlk);
-    item_cap = uv ? (nd <= 2 ? RowGeo < 2, true >::kItem : RowGeo < 3, true >::kItem)
-        : (nd <= 2 ? RowGeo < 2, false >::kItem : RowGeo < 3, false >::kItem);
-  }
+  if ((long long) ((j.w + caps.tw - 1) / caps.tw) * ((j.h + kRTH - 1) / kRTH) > 0xffff)
+    return {};
+  const int nbi = ((caps.tw - 1 + j.xblen - 1) / j.xbsep + 1) * ns, nbj = (kRTH - 1 + j.yblen - 1) / j.ybsep + 1;
   // the rows of one column of blocks (segments) inside a tile: the tile's rows, each under at most ceil (yblen / ybsep)
   // blocks -- or, for small overlaps the tighter count, the rows plus the overlaps of the block rows that meet it
   const int rows_col = std::min (kRTH * ((j.yblen + j.ybsep - 1) / j.ybsep), kRTH + (kRTH / j.ybsep + 2) * 2 * j.yoff);
-  if (nbi > 255 || nbi * nbj > blk_cap || nbi * rows_col > item_cap)
-    return 0;
-  return nd;
+  if (nbi > 255 || nbi * nbj > caps.blk || nbi * rows_col > caps.item)
+    return {};
+  return form;
 }
 
 // r05: the weight table a row kernel of `nd` dwords per row and `ns` segments copies into LDS for a job of this block
@@ -339,7 +304,7 @@ obmc_row_weight_table (const ObmcJob & j, int nd, int ns, bool uv, uint32_t * ou
 void
 obmc_row_tile_record (const ObmcJob & j, bool uv, int ns, int tx, int ty, uint32_t * rec)
 {
-  const int tw = uv ? RowGeo < 3, true >::kTW : RowGeo < 3, false >::kTW;
+  const int tw = obmc_row_tile_width (uv);
   const int x_lo = tx * tw, y_lo = ty * kRTH, x_hi = std::min (x_lo + tw, j.w), y_hi = std::min (y_lo + kRTH, j.h);
   const int i_lo = std::max (0, (x_lo + j.xoff - j.xblen + 2 * j.xbsep) / j.xbsep - 1);
   const int i_hi = std::min (j.nbx - 1, (x_hi - 1 + j.xoff) / j.xbsep);
@@ -362,7 +327,7 @@ obmc_row_tile_height ()
 int
 obmc_row_tile_width (bool uv)
 {
-  return uv ? RowGeo < 3, true >::kTW : RowGeo < 3, false >::kTW;
+  return row_caps (3, 1, uv).tw;
 }
 
 }                               // namespace schro

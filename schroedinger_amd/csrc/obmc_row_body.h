@@ -1498,15 +1498,64 @@ obmc_row_body (const ObmcJob * __restrict__ jobs, int njobs, const uint32_t * __
 #undef RSTAMP
 }
 
+// the form of obmc_row_body's instantiation <ND, NP, UV, TH, NORES, RK, NS, WP, PAD> (schro_hip_internal.h: RowForm)
+template < int ND, int NP, bool UV = false, int TH = kRTH, bool NORES = false, int RK = 1, int NS = 1, bool WP = false, bool PAD = false >
+constexpr RowForm
+row_form ()
+{
+  return RowForm { RK, ND, UV ? 3 : NP, NS, NORES, WP };
+}
+
+// a kernel and, as name##_form, its form
 #define SCHRO_ROW_KERNEL(name, waves, ...) \
 __global__ __launch_bounds__ (kRThreads) __attribute__ ((amdgpu_waves_per_eu (waves, waves))) \
 void name (const ObmcJob * __restrict__ jobs, int njobs, const uint32_t * __restrict__ order, uint32_t * __restrict__ overflow, \
     const uint32_t * __restrict__ wtabs) \
 { \
   obmc_row_body < __VA_ARGS__ > (jobs, njobs, order, overflow, wtabs); \
-}
+} \
+constexpr RowForm name##_form = row_form < __VA_ARGS__ > ();
+
+}                               // namespace
 
 typedef void (*RowKernel) (const ObmcJob *, int, const uint32_t *, uint32_t *, const uint32_t *);
 
-}                               // namespace
+// The kernels of one reference kind (obmc_row.hip, obmc_row_plain.hip, obmc_row_eighth.hip: a table at the end of each,
+// ROW_ENTRY (kernel) after kernel) and the one rule by which a launch finds its kernel: the entry of its form, else -- for
+// a prediction_only launch -- the entry of the same form with the residual (it serves both)
+struct RowEntry {
+  RowForm form;
+  RowKernel kernel;
+};
+#define ROW_ENTRY(name) RowEntry { name##_form, name }
+struct RowTable {
+  const RowEntry *e;
+  int n;
+};
+// (host functions rather than variables: the device code stays the kernels alone)
+RowTable obmc_row_table_half (), obmc_row_table_plain (), obmc_row_table_eighth ();
+
+constexpr RowKernel
+row_find (const RowTable & t, const RowForm & f)
+{
+  for (int i = 0; i < t.n; i++)
+    if (t.e[i].form == f)
+      return t.e[i].kernel;
+  return f.nores ? row_find (t, RowForm { f.kind, f.nd, f.np, f.ns, false, f.weighted }) : nullptr;
+}
+
+// (compile-time checks of a table: its forms differ, its entries are of its kind)
+constexpr bool
+row_table_ok (const RowTable & t, int kind)
+{
+  for (int i = 0; i < t.n; i++) {
+    if (t.e[i].form.kind != kind)
+      return false;
+    for (int k = 0; k < i; k++)
+      if (t.e[k].form == t.e[i].form)
+        return false;
+  }
+  return true;
+}
+
 }                               // namespace schro

@@ -35,37 +35,25 @@ SCHRO_ROW_KERNEL (obmc_row_eighth_w_h2_uv_3, 6, 3, 1, true, kRTH, false, 3, 2, t
 SCHRO_ROW_KERNEL (obmc_row_eighth_w_h2_4_1, 5, 4, 1, false, kRTH, false, 3, 2, true)
 SCHRO_ROW_KERNEL (obmc_row_eighth_w_h2_uv_4, 5, 4, 1, true, kRTH, false, 3, 2, true)
 
+constexpr RowEntry kEighth[] = {
+  ROW_ENTRY (obmc_row_eighth_2_1), ROW_ENTRY (obmc_row_eighth_3_1), ROW_ENTRY (obmc_row_eighth_4_1), ROW_ENTRY (obmc_row_eighth_uv_2),
+  ROW_ENTRY (obmc_row_eighth_uv_3), ROW_ENTRY (obmc_row_eighth_uv_4), ROW_ENTRY (obmc_row_eighth_p_3_1), ROW_ENTRY (obmc_row_eighth_p_uv_3),
+  ROW_ENTRY (obmc_row_eighth_h2_3_1), ROW_ENTRY (obmc_row_eighth_h2_uv_3), ROW_ENTRY (obmc_row_eighth_h2_4_1), ROW_ENTRY (obmc_row_eighth_h2_uv_4),
+  ROW_ENTRY (obmc_row_eighth_w_3_1), ROW_ENTRY (obmc_row_eighth_w_uv_3), ROW_ENTRY (obmc_row_eighth_w_p_3_1), ROW_ENTRY (obmc_row_eighth_w_p_uv_3),
+  ROW_ENTRY (obmc_row_eighth_w_2_1), ROW_ENTRY (obmc_row_eighth_w_4_1), ROW_ENTRY (obmc_row_eighth_w_uv_2), ROW_ENTRY (obmc_row_eighth_w_uv_4),
+  ROW_ENTRY (obmc_row_eighth_w_h2_3_1), ROW_ENTRY (obmc_row_eighth_w_h2_uv_3), ROW_ENTRY (obmc_row_eighth_w_h2_4_1),
+  ROW_ENTRY (obmc_row_eighth_w_h2_uv_4),
+};
+constexpr RowTable kEighthTable = { kEighth, (int) std::size (kEighth) };
+static_assert (row_table_ok (kEighthTable, 3), "obmc_row_eighth.hip: one kernel per form");
+static_assert (row_find (kEighthTable, RowForm { 3, 2, 1, 1, true, false }) == obmc_row_eighth_2_1, "obmc_row_eighth.hip: a prediction_only launch without a kernel of its form takes the residual form's");
+
 }                               // namespace
 
-RowKernel
-obmc_row_kernel_eighth (int nd, int np, int ns, bool nores, bool weighted)
+RowTable
+obmc_row_table_eighth ()
 {
-  if (weighted) {
-    if (np != 1 && np != 3)
-      return nullptr;
-    const bool uv = np == 3;
-    if (ns == 2)
-      return nd == 3 ? (uv ? obmc_row_eighth_w_h2_uv_3 : obmc_row_eighth_w_h2_3_1) : nd == 4 ? (uv ? obmc_row_eighth_w_h2_uv_4 : obmc_row_eighth_w_h2_4_1) : nullptr;
-    if (nd == 3)
-      return uv ? (nores ? obmc_row_eighth_w_p_uv_3 : obmc_row_eighth_w_uv_3) : (nores ? obmc_row_eighth_w_p_3_1 : obmc_row_eighth_w_3_1);
-    return nd == 2 ? (uv ? obmc_row_eighth_w_uv_2 : obmc_row_eighth_w_2_1) : nd == 4 ? (uv ? obmc_row_eighth_w_uv_4 : obmc_row_eighth_w_4_1) : nullptr;
-  }
-  if (ns == 2)
-    return nd == 3 && np == 1 ? obmc_row_eighth_h2_3_1 : nd == 3 && np == 3 ? obmc_row_eighth_h2_uv_3
-        : nd == 4 && np == 1 ? obmc_row_eighth_h2_4_1 : nd == 4 && np == 3 ? obmc_row_eighth_h2_uv_4 : nullptr;
-  if (nores && nd == 3 && np == 1)
-    return obmc_row_eighth_p_3_1;
-  if (nores && nd == 3 && np == 3)
-    return obmc_row_eighth_p_uv_3;
-  switch (nd * 10 + np) {
-    case 21: return obmc_row_eighth_2_1;
-    case 31: return obmc_row_eighth_3_1;
-    case 41: return obmc_row_eighth_4_1;
-    case 23: return obmc_row_eighth_uv_2;
-    case 33: return obmc_row_eighth_uv_3;
-    case 43: return obmc_row_eighth_uv_4;
-  }
-  return nullptr;
+  return kEighthTable;
 }
 
 }                               // namespace schro

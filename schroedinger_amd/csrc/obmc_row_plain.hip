@@ -58,50 +58,28 @@ SCHRO_ROW_KERNEL (obmc_row_plain_w_h2_uv_3, 6, 3, 1, true, kRTH, false, 0, 2, tr
 SCHRO_ROW_KERNEL (obmc_row_plain_w_h2_4_1, 6, 4, 1, false, kRTH, false, 0, 2, true)
 SCHRO_ROW_KERNEL (obmc_row_plain_w_h2_uv_4, 6, 4, 1, true, kRTH, false, 0, 2, true)
 
+constexpr RowEntry kPlain[] = {
+  ROW_ENTRY (obmc_row_plain_2_1), ROW_ENTRY (obmc_row_plain_2_2), ROW_ENTRY (obmc_row_plain_3_1), ROW_ENTRY (obmc_row_plain_3_2),
+  ROW_ENTRY (obmc_row_plain_4_1), ROW_ENTRY (obmc_row_plain_4_2), ROW_ENTRY (obmc_row_plain_p_2_1), ROW_ENTRY (obmc_row_plain_p_2_2),
+  ROW_ENTRY (obmc_row_plain_p_3_1), ROW_ENTRY (obmc_row_plain_p_4_1), ROW_ENTRY (obmc_row_plain_uv_2), ROW_ENTRY (obmc_row_plain_uv_3),
+  ROW_ENTRY (obmc_row_plain_uv_4), ROW_ENTRY (obmc_row_plain_p_uv_2), ROW_ENTRY (obmc_row_plain_p_uv_3), ROW_ENTRY (obmc_row_plain_p_uv_4),
+  ROW_ENTRY (obmc_row_plain_h2_3_1), ROW_ENTRY (obmc_row_plain_p_h2_3_1), ROW_ENTRY (obmc_row_plain_h2_uv_3), ROW_ENTRY (obmc_row_plain_p_h2_uv_3),
+  ROW_ENTRY (obmc_row_plain_h2_4_1), ROW_ENTRY (obmc_row_plain_h2_uv_4), ROW_ENTRY (obmc_row_plain_p_h2_4_1), ROW_ENTRY (obmc_row_plain_p_h2_uv_4),
+  ROW_ENTRY (obmc_row_plain_w_3_1), ROW_ENTRY (obmc_row_plain_w_uv_3), ROW_ENTRY (obmc_row_plain_w_p_3_1), ROW_ENTRY (obmc_row_plain_w_p_uv_3),
+  ROW_ENTRY (obmc_row_plain_w_2_1), ROW_ENTRY (obmc_row_plain_w_4_1), ROW_ENTRY (obmc_row_plain_w_uv_2), ROW_ENTRY (obmc_row_plain_w_uv_4),
+  ROW_ENTRY (obmc_row_plain_w_h2_3_1), ROW_ENTRY (obmc_row_plain_w_h2_uv_3), ROW_ENTRY (obmc_row_plain_w_h2_4_1),
+  ROW_ENTRY (obmc_row_plain_w_h2_uv_4),
+};
+constexpr RowTable kPlainTable = { kPlain, (int) std::size (kPlain) };
+static_assert (row_table_ok (kPlainTable, 0), "obmc_row_plain.hip: one kernel per form");
+static_assert (row_find (kPlainTable, RowForm { 0, 3, 2, 1, true, false }) == obmc_row_plain_3_2, "obmc_row_plain.hip: a prediction_only launch without a kernel of its form takes the residual form's");
+
 }                               // namespace
 
-RowKernel
-obmc_row_kernel_plain (int nd, int np, int ns, bool nores, bool weighted)
+RowTable
+obmc_row_table_plain ()
 {
-  if (weighted) {
-    if (np != 1 && np != 3)
-      return nullptr;
-    const bool uv = np == 3;
-    if (ns == 2)
-      return nd == 3 ? (uv ? obmc_row_plain_w_h2_uv_3 : obmc_row_plain_w_h2_3_1) : nd == 4 ? (uv ? obmc_row_plain_w_h2_uv_4 : obmc_row_plain_w_h2_4_1) : nullptr;
-    if (nd == 3)
-      return uv ? (nores ? obmc_row_plain_w_p_uv_3 : obmc_row_plain_w_uv_3) : (nores ? obmc_row_plain_w_p_3_1 : obmc_row_plain_w_3_1);
-    return nd == 2 ? (uv ? obmc_row_plain_w_uv_2 : obmc_row_plain_w_2_1) : nd == 4 ? (uv ? obmc_row_plain_w_uv_4 : obmc_row_plain_w_4_1) : nullptr;
-  }
-  if (ns == 2) {
-    if (nd == 3)
-      return np == 1 ? (nores ? obmc_row_plain_p_h2_3_1 : obmc_row_plain_h2_3_1) : np == 3 ? (nores ? obmc_row_plain_p_h2_uv_3 : obmc_row_plain_h2_uv_3) : nullptr;
-    if (nd == 4)
-      return np == 1 ? (nores ? obmc_row_plain_p_h2_4_1 : obmc_row_plain_h2_4_1) : np == 3 ? (nores ? obmc_row_plain_p_h2_uv_4 : obmc_row_plain_h2_uv_4) : nullptr;
-    return nullptr;
-  }
-  if (nores)
-    switch (nd * 10 + np) {
-      case 23: return obmc_row_plain_p_uv_2;
-      case 33: return obmc_row_plain_p_uv_3;
-      case 43: return obmc_row_plain_p_uv_4;
-      case 21: return obmc_row_plain_p_2_1;
-      case 22: return obmc_row_plain_p_2_2;
-      case 31: return obmc_row_plain_p_3_1;
-      case 41: return obmc_row_plain_p_4_1;
-    }
-  switch (nd * 10 + np) {
-    case 23: return obmc_row_plain_uv_2;
-    case 33: return obmc_row_plain_uv_3;
-    case 43: return obmc_row_plain_uv_4;
-    case 21: return obmc_row_plain_2_1;
-    case 22: return obmc_row_plain_2_2;
-    case 31: return obmc_row_plain_3_1;
-    case 32: return obmc_row_plain_3_2;
-    case 41: return obmc_row_plain_4_1;
-    case 42: return obmc_row_plain_4_2;
-  }
-  return nullptr;
+  return kPlainTable;
 }
 
 }                               // namespace schro

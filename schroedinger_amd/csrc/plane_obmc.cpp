@@ -307,7 +307,19 @@ schro_hip_obmc_batch (SchroHipContext * ctx, const SchroHipObmcPlane * planes, i
   // item kernel (A/B runs: the second formulation the parity tests compare)
   static const bool use_row = !SCHRO_ENV ("SCHRO_HIP_OBMC_KERNEL") || strcmp (SCHRO_ENV ("SCHRO_HIP_OBMC_KERNEL"), "row") == 0;
   std::vector < ObmcJob > all (nplanes);
-  std::vector < int >key (nplanes), row_nd (nplanes), row_ns (nplanes, 1);
+  // what makes a launch: the planes of one key go out together, in plane order.  Row launches: one per kernel form (the
+  // kernels differ in registers and so in workgroups per CU, and in the weights they blend), at one precision
+  struct LaunchKey {
+    int prec;
+    int variant;                // obmc_tiles' and the general kernel's (obmc.hip); row launches 3, (U, V) pairs 4
+    RowForm form;               // row launches: the kernel's form; false: the general kernel
+    bool pred_only, out_s16;
+    bool operator== (const LaunchKey & o) const
+    {
+      return prec == o.prec && variant == o.variant && form == o.form && pred_only == o.pred_only && out_s16 == o.out_s16;
+    }
+  };
+  std::vector < LaunchKey > key (nplanes);
   uint32_t pred_epoch = 0;      // (r05: this call's number among the context's prediction_only calls, once it has one)
   // r06: however the call ends, its ring word's event goes onto the queue behind whatever it has launched
   struct OvfDone {
@@ -396,13 +408,10 @@ schro_hip_obmc_batch (SchroHipContext * ctx, const SchroHipObmcPlane * planes, i
             "obmc_batch: plane %d: reference %d is not a half-pel image of this component (128-byte aligned, stride from "
             "schro_hip_upsampled_bytes / _pair_bytes)", p, r + 1);
     j.out_s16 = pl.prediction_only == 2;
-    const int variant = variant_of (pl);
+    const bool pred_only = pl.prediction_only == 1;
     // (obmc_row_form looks at the weights itself: 1, 1 / 2 and, r06, every non-negative pair that adds up to 1 << bits)
-    const int nd_row = (use_row && !j.out_s16) ? obmc_row_form (j, false, &row_ns[p]) : 0;
-    // (a launch per row length: the kernels differ in registers and so in workgroups per CU)
-    key[p] = pl.mv_precision | (variant << 4) | (nd_row << 8) | (nd_row ? 1 << 16 : 0) | (pl.prediction_only == 1 ? 1 << 19 : 0)
-        | (nd_row ? row_ns[p] << 20 : 0) | (j.out_s16 ? 1 << 22 : 0);
-    row_nd[p] = nd_row;
+    const RowForm form = (use_row && !j.out_s16) ? obmc_row_form (j, false, pred_only) : RowForm {};
+    key[p] = LaunchKey { pl.mv_precision, form ? 3 : variant_of (pl), form, pred_only, (bool) j.out_s16 };
   }
   // row kernel: the U and V planes of a picture (same vectors, blocks and sample windows) become
   // ONE job whose tile workgroups decode the blocks once; such pairs form their own launch
@@ -411,7 +420,7 @@ schro_hip_obmc_batch (SchroHipContext * ctx, const SchroHipObmcPlane * planes, i
   // 2160p picture: 510 pair tiles against 1536 slots)
   long pair_tiles = 0;
   for (int p = 0; p < nplanes; p++)
-    if (row_nd[p] && all[p].comp != 0)
+    if (key[p].form && all[p].comp != 0)
       pair_tiles += (long) ((all[p].w + 127) / 128) * ((all[p].h + 31) / 32);
   const bool pairs_pay = obmc_row_merge_mode () == 2 || (obmc_row_merge_mode () == 1 && pair_tiles > 6L * ctx->cus);
   auto same_blocks = [](const ObmcJob & a, const ObmcJob & b) {
@@ -432,26 +441,25 @@ schro_hip_obmc_batch (SchroHipContext * ctx, const SchroHipObmcPlane * planes, i
     if (((a.ref_ps && b.ref_ps && a.ref[0] == b.ref[0] && a.ref[1] == b.ref[1]) || uv_plain)
         && use_row && same_blocks (a, b)
         && planes[p].prediction_only == planes[p + 1].prediction_only && !a.out_s16 && !b.out_s16) {
-      int ns;
       ObmcJob au = a;
       au.ref_b[0] = b.ref[0];
       au.ref_b[1] = b.ref[1];
-      const int nd = obmc_row_form (au, true, &ns);
-      if (nd) {
-        row_nd[p] = row_nd[p + 1] = nd;
-        row_ns[p] = row_ns[p + 1] = ns;
-        key[p] = key[p + 1] = a.prec | (1 << 4) | (nd << 8) | (1 << 16) | (1 << 18) | (planes[p].prediction_only == 1 ? 1 << 19 : 0) | (ns << 20);
+      const RowForm uv = obmc_row_form (au, true, key[p].pred_only);
+      if (uv) {
+        key[p] = key[p + 1] = LaunchKey { a.prec, 4, uv, key[p].pred_only, false };
         p++;
         continue;
       }
       if (!uv_plain)            // (pair images outside the row kernels' case: obmc.hip reads the components out of them)
         continue;
     }
-    if (pairs_pay && row_nd[p] && row_nd[p + 1] && key[p] == key[p + 1] && same_blocks (a, b)
-        && obmc_row_has_kernel (a.prec, row_nd[p], 2, row_ns[p], a.w1 != 1 || a.wbits != 1)) {
-      key[p] |= 1 << 17;
-      key[p + 1] |= 1 << 17;
-      p++;
+    if (pairs_pay && key[p].form && key[p] == key[p + 1] && same_blocks (a, b)) {
+      LaunchKey two = key[p];
+      two.form.np = 2;
+      if (obmc_row_has_kernel (two.form)) {
+        key[p] = key[p + 1] = two;
+        p++;
+      }
     }
   }
   // one launch per (precision class, kernel) group, keeping plane order
@@ -459,22 +467,11 @@ schro_hip_obmc_batch (SchroHipContext * ctx, const SchroHipObmcPlane * planes, i
   for (int first = 0; first < nplanes; first++) {
     if (done[first])
       continue;
-    const int prec = planes[first].mv_precision;
-    int nd = (key[first] >> 8) & 0xff;
-    const bool row = (key[first] >> 16) & 1;
-    if (row)
-      for (int p = first; p < nplanes; p++)
-        if (!done[p] && key[p] == key[first])
-          nd = std::max (nd, row_nd[p]);
-    const bool paired = (key[first] >> 17) & 1, uv = (key[first] >> 18) & 1, pred_only = (key[first] >> 19) & 1;
-    const int ns = row ? std::max (1, (key[first] >> 20) & 3) : 1;
-    // (two planes per job: every row length of the group needs the kernel)
-    // (a launch group's planes have one kind of weights: the key carries the variant)
-    const bool weighted = row && (all[first].w1 != 1 || all[first].wbits != 1);
-    SCHRO_HIP_REQUIRE (!row || obmc_row_has_kernel (prec, nd, uv ? 3 : paired ? 2 : 1, ns, weighted),
-        "obmc_batch: no row kernel for precision %d, %d dwords x %d segments per row, %s", prec, nd, ns, uv ? "(U, V) pairs" : paired ? "two planes per job" : "one plane per job");
+    const LaunchKey & group = key[first];
+    const RowForm & form = group.form;
+    const bool row = (bool) form, paired = form.np == 2, uv = form.np == 3;
     uint32_t *overflow = nullptr;
-    if (pred_only) {
+    if (group.pred_only) {
       if (!ctx->dc_gave_up) {
         SCHRO_HIP_CHECK (hipHostMalloc ((void **) &ctx->dc_gave_up, 64, hipHostMallocDefault));
         memset (ctx->dc_gave_up, 0, 64);
@@ -492,16 +489,15 @@ schro_hip_obmc_batch (SchroHipContext * ctx, const SchroHipObmcPlane * planes, i
       }
       overflow = ctx->dc_gave_up + 4 + pred_epoch % SchroHipContext::kOvfRing;
     }
-    const int variant = uv ? 4 : nd ? 3 : ((key[first] >> 4) & 15);
     std::vector < ObmcJob > jobs;
     int tile_base = 0;
     for (int p = first; p < nplanes; p++) {
-      if (done[p] || key[p] != key[first])
+      if (done[p] || !(key[p] == group))
         continue;
       done[p] = 1;
       ObmcJob j = all[p];
       int tiles_y;
-      obmc_tiles (variant, j.w, j.h, j.xoff, &j.tiles_x, &tiles_y);
+      obmc_tiles (group.variant, j.w, j.h, j.xoff, &j.tiles_x, &tiles_y);
       j.tile_base = tile_base;
       obmc_item_geometry (&j);
       j.stamps = obmc_stamp_buffer ();
@@ -527,7 +523,7 @@ schro_hip_obmc_batch (SchroHipContext * ctx, const SchroHipObmcPlane * planes, i
     // LDS tile); its waves take strips of 15 block columns x segments of 8 block rows
 #ifdef SCHRO_HIP_EXPERIMENTS
     static const bool use_strip = SCHRO_ENV ("SCHRO_HIP_OBMC_STRIP") && atoi (SCHRO_ENV ("SCHRO_HIP_OBMC_STRIP")) != 0;
-    bool strip = use_strip && row && !paired && !uv && nd == 3 && ns == 1;
+    bool strip = use_strip && row && form.np == 1 && form.nd == 3 && form.ns == 1;
     for (size_t k = 0; strip && k < jobs.size (); k++)
       strip = obmc_strip_ok (jobs[k]);
     if (strip) {
@@ -545,7 +541,7 @@ schro_hip_obmc_batch (SchroHipContext * ctx, const SchroHipObmcPlane * planes, i
       if (rs)
         return rs;
       ProfileScope ps (ctx, SCHRO_HIP_KERNEL_OBMC);
-      rs = launch_obmc_strip (ctx->stream, (const ObmcJob *) d_sjobs, (int) jobs.size (), wave_base, seg_rows, pred_only, overflow, ctx->cus);
+      rs = launch_obmc_strip (ctx->stream, (const ObmcJob *) d_sjobs, (int) jobs.size (), wave_base, seg_rows, group.pred_only, overflow, ctx->cus);
       if (rs)
         return rs;
       continue;
@@ -563,11 +559,11 @@ schro_hip_obmc_batch (SchroHipContext * ctx, const SchroHipObmcPlane * planes, i
       size_t end_job = all_jobs.size ();
       std::vector < uint32_t > tabs;
       if (row) {
-        const size_t words = (size_t) obmc_row_weight_words (nd, ns);
+        const size_t words = (size_t) obmc_row_weight_words (form.nd, form.ns);
         std::vector < uint32_t > one (words);
         for (size_t n = first_job; n < end_job; n++) {
           ObmcJob & j = all_jobs[n];
-          obmc_row_weight_table (j, nd, ns, uv, one.data ());
+          obmc_row_weight_table (j, form.nd, form.ns, uv, one.data ());
           size_t k = 0;
           while (k * words < tabs.size () && memcmp (&tabs[k * words], one.data (), words * 4))
             k++;
@@ -596,7 +592,7 @@ schro_hip_obmc_batch (SchroHipContext * ctx, const SchroHipObmcPlane * planes, i
       if (r)
         return r;
       const uint32_t *d_order;
-      r = obmc_tile_order (ctx, jobs, variant, tile_base, &d_order, row ? (uv ? 1 : 0) : -1, ns);
+      r = obmc_tile_order (ctx, jobs, group.variant, tile_base, &d_order, row ? (uv ? 1 : 0) : -1, form.ns);
       if (r)
         return r;
 #ifndef SCHRO_HIP_EXPERIMENTS
@@ -609,8 +605,8 @@ schro_hip_obmc_batch (SchroHipContext * ctx, const SchroHipObmcPlane * planes, i
         (void) hipMemsetAsync (g_stamps, 0, 16384 * 16 * 8, ctx->stream);
       {
         ProfileScope ps (ctx, SCHRO_HIP_KERNEL_OBMC);
-        r = row ? launch_obmc_row (ctx->stream, (const ObmcJob *) d_jobs, (int) jobs.size (), tile_base, prec, nd, ns, uv ? 3 : paired ? 2 : 1, d_order, overflow, (const uint32_t *) d_wtabs, weighted)
-            : launch_obmc (ctx->stream, (const ObmcJob *) d_jobs, (int) jobs.size (), tile_base, prec, variant, d_order, overflow);
+        r = row ? launch_obmc_row (ctx->stream, (const ObmcJob *) d_jobs, (int) jobs.size (), tile_base, form, d_order, overflow, (const uint32_t *) d_wtabs)
+            : launch_obmc (ctx->stream, (const ObmcJob *) d_jobs, (int) jobs.size (), tile_base, group.prec, group.variant, d_order, overflow);
       }
     }
     if (r)

@@ -493,11 +493,23 @@ void dequant_tables (int quant_index, int is_intra, uint32_t * factor, uint32_t 
 // overflow: NULL, or (prediction_only launches) the word a prediction that does not fit 8 bits is reported in
 int launch_obmc (hipStream_t stream, const ObmcJob * d_jobs, int njobs,
     int total_tiles, int prec, int variant, const uint32_t * d_order, uint32_t * overflow);
-// row kernels (obmc_row*.hip): prediction dwords per block row and segment, *ns = segments per block row (1, 2);
-// 0 = not their case
-int obmc_row_form (const ObmcJob & job, bool uv, int *ns);
-// is there a kernel of `np` planes per job (1, 2; 3: (U, V) pairs from pair images) for this precision and form?
-bool obmc_row_has_kernel (int prec, int nd, int np, int ns, bool weighted);
+// The form of a row kernel (obmc_row*.hip) and of a launch that wants one: the reference kind (0 plain planes, 1 half-pel
+// images read at half / quarter pel, 3 at eighth pel), nd prediction dwords per block row and segment (2 .. 4), np planes
+// per job (1, 2; 3: (U, V) pairs), ns segments per block row (1, 2); nores: a prediction_only launch; weighted: picture
+// weights other than 1, 1 / 2.  nd 0: not the row kernels' case (obmc.hip).
+struct RowForm {
+  int kind, nd, np, ns;
+  bool nores, weighted;
+  constexpr explicit operator bool () const { return nd != 0; }
+  constexpr bool operator== (const RowForm & o) const
+  {
+    return kind == o.kind && nd == o.nd && np == o.np && ns == o.ns && nores == o.nores && weighted == o.weighted;
+  }
+};
+// row kernels: the form a plane takes as one job (uv: the U plane of a (U, V) job, ref_b the V planes); nores: of a
+// prediction_only launch.  False: not their case
+RowForm obmc_row_form (const ObmcJob & job, bool uv, bool nores);
+bool obmc_row_has_kernel (const RowForm & form);
 // obmc_strip.hip (r05): the register-accumulator form for the 12 / 8 block set
 bool obmc_strip_ok (const ObmcJob & j);
 void obmc_strip_tiles (const ObmcJob & j, int seg_rows, int *strips, int *segs);
@@ -505,8 +517,8 @@ int launch_obmc_strip (hipStream_t stream, const ObmcJob * d_jobs, int njobs, in
     int cus);
 int obmc_row_tile_width (bool uv);
 int obmc_row_tile_height ();
-int launch_obmc_row (hipStream_t stream, const ObmcJob * d_jobs, int njobs, int total_tiles, int prec, int nd, int ns,
-    int planes_per_job, const uint32_t * d_order, uint32_t * overflow, const uint32_t * d_wtabs, bool weighted);
+int launch_obmc_row (hipStream_t stream, const ObmcJob * d_jobs, int njobs, int total_tiles, const RowForm & form,
+    const uint32_t * d_order, uint32_t * overflow, const uint32_t * d_wtabs);
 // the weight table of a job's block geometry as the row kernels copy it into LDS (ObmcJob::ipw: its index in d_wtabs)
 // words 1 .. 3 of tile (tx, ty)'s record in a row launch's order table (word 0: job << 16 | tile)
 void obmc_row_tile_record (const ObmcJob & job, bool uv, int ns, int tx, int ty, uint32_t * rec);

@@ -23,11 +23,19 @@ def comp_size(w, h, k, chroma):
     return -(-w // (1 << chroma[0])), -(-h // (1 << chroma[1]))
 
 
-def run_case(ctx, w, h, xblen, xbsep, prec, weights, chroma, mv_range, seed, res_dtype=np.int16,
-             modes=(0.05, 0.45, 0.15, 0.35), edit_mv=None, pair=False, only=None, yblen=None, ybsep=None):
+def run_case(ctx, *args, **kw):
+    """One picture's planes in one call, each checked against the oracle (make_case's arguments)."""
+    jobs, want, keep = make_case(ctx, *args, **kw)
+    ctx.obmc_batch(jobs)
+    check_case(want, keep)
+
+
+def make_case(ctx, w, h, xblen, xbsep, prec, weights, chroma, mv_range, seed, res_dtype=np.int16,
+              modes=(0.05, 0.45, 0.15, 0.35), edit_mv=None, pair=False, only=None, yblen=None, ybsep=None):
     """pair: the chroma references are (U, V) PAIR images (include/schro_hip.h, r04) -- sub-pel precisions
     of horizontally subsampled chroma only; only: the components whose planes are rendered (default all);
-    yblen, ybsep: blocks that are not square (default: as wide as high)."""
+    yblen, ybsep: blocks that are not square (default: as wide as high).  Returns the batch's jobs, (oracle,
+    output plane, component) per plane and the device buffers to free."""
     P = synth.motion_params(w, h, xblen, xbsep, prec, weights, chroma, yblen=yblen, ybsep=ybsep)
     mv = synth.motion_field(P["x_num_blocks"], P["y_num_blocks"], mv_range, seed, modes)
     if edit_mv is not None:
@@ -70,14 +78,17 @@ def run_case(ctx, w, h, xblen, xbsep, prec, weights, chroma, mv_range, seed, res
         jobs.append(sa.obmc_plane(d_mv, P, k, g1, g2, d_res, out))
         keep += [d_res, out]
         want[-1] = (want[-1], out, k)
-    ctx.obmc_batch(jobs)
+    return jobs, want, keep + [d_mv]
+
+
+def check_case(want, keep):
     for ref, out, k in want:
         got = out.download()
         if not np.array_equal(got, ref):
             bad = np.argwhere(got != ref)
             raise AssertionError("component %d: %d mismatches, first at (y,x)=%s got %d want %d" % (
                 k, len(bad), tuple(bad[0]), got[tuple(bad[0])], ref[tuple(bad[0])]))
-    for p in keep + [d_mv]:
+    for p in keep:
         p.free()
 
 
@@ -409,6 +420,20 @@ def test_fades_on_every_row_form(ctx):
             for prec in (0, 1, 2, 3):
                 for chroma in ((1, 1), (0, 0)):
                     run_case(ctx, 136, 72, blk[0], blk[1], prec, weights, chroma, 40 << prec, 17, pair=True)
+
+
+@pytest.mark.parametrize("fade_first", [False, True])
+@pytest.mark.parametrize("prec", [0, 1, 2, 3])
+def test_default_weights_and_a_fade_in_one_batch(ctx, prec, fade_first):
+    """Two pictures in ONE call, one with the default weights and one a fade: their (U, V) jobs -- from pair images, or at
+    full pel the two plain planes of each reference -- must go out in launches of their own, each on its own kernel."""
+    cases = [make_case(ctx, 96, 64, 12, 8, prec, weights, (1, 1), 24 << prec, seed, pair=True)
+             for weights, seed in (((1, 1, 1), 5), ((3, 5, 3), 6))]
+    if fade_first:
+        cases.reverse()
+    ctx.obmc_batch(cases[0][0] + cases[1][0])
+    for _, want, keep in cases:
+        check_case(want, keep)
 
 
 def test_the_reference_encoders_default_block_sets_at_size(ctx):
