@@ -84,29 +84,52 @@ def test_obmc_geometries(ctx):
 
 def test_obmc_batches_of_unlike_pictures(ctx):
     """Eight pictures of one geometry and a few others in ONE call (launch groups, tile orders over several references,
-    the weight-table dedupe, job tables near the slot's size)."""
+    the weight-table dedupe, job tables near the slot's size) -- and the dimensions tests/test_gpu_mixed_batches.py mixes:
+    weights (fades, gains), prediction_only 0 / 1 / 2, s16 / s32 / no residual, blocks drawn apart in x and y, pair or
+    plain references shared between pictures, one reference, the planes shuffled."""
     rng = np.random.default_rng(9)
-    for rnd in range(6 * SCALE):
-        jobs, keep = [], []
+    weight_sets = [(1, 1, 1), (1, 1, 1), (3, 5, 3), (1, 3, 2), (2, 3, 1), (3, -1, 1)]
+    for rnd in range(12 * SCALE):
+        jobs, keep, pool = [], [], []
         for pic in range(int(rng.integers(2, 12))):
-            w, h = [(640, 360), (352, 288), (1920, 1080)][int(rng.integers(0, 3))]
-            blen, sep = [(12, 8), (8, 4), (24, 16), (16, 12)][int(rng.integers(0, 4))]
+            w, h = [(640, 360), (352, 288), (1920, 1080), (200, 120)][int(rng.integers(0, 4))]
+            xblen, xbsep = [(12, 8), (8, 4), (24, 16), (16, 12), (32, 16), (20, 12), (64, 32)][int(rng.integers(0, 7))]
+            yblen, ybsep = (xblen, xbsep) if rng.integers(0, 2) else [(12, 8), (16, 12), (8, 8), (28, 16)][int(rng.integers(0, 4))]
+            chroma = [(1, 1), (1, 1), (1, 0), (0, 0)][int(rng.integers(0, 4))]
             prec = int(rng.integers(0, 4))
-            P = synth.motion_params(w, h, blen, sep, prec, (1, 1, 1), (1, 1))
+            pred = int(rng.integers(0, 3))
+            weights = weight_sets[int(rng.integers(0, len(weight_sets)))]
+            if pred == 1 and (weights[1] < 0 or weights[0] + weights[1] > (1 << weights[2])):
+                weights = (1, 1, 1)
+            res_dt = [np.int16, np.int32, None][int(rng.integers(0, 3))]
+            pair_ok = prec > 0 and chroma[0] == 1
+            # references: the pool's, where one of this size, chroma format and layout exists (shared), else new
+            kind = (w, h, chroma, prec > 0, pair_ok and bool(rng.integers(0, 2)))
+            refs = next((r for k, r in pool if k == kind), None) if rng.integers(0, 2) else None
+            if refs is None:
+                refs = []
+                for _ in range(2):
+                    comps = []
+                    pairimg = ctx.hp_plane(*comp_size(w, h, 1, chroma)[::-1], pair=True) if kind[4] else None
+                    for k in range(3):
+                        cw, ch = comp_size(w, h, k, chroma)
+                        comps.append(pairimg if k and pairimg is not None else
+                                     ctx.hp_plane(ch, cw) if prec else ctx.plane(ch, cw, np.uint8))
+                    refs.append(comps)
+                    keep += comps
+                pool.append((kind, refs))
+            one_ref = rng.integers(0, 5) == 0
+            P = synth.motion_params(w, h, xblen, xbsep, prec, weights, chroma, yblen=yblen, ybsep=ybsep)
             d_mv = ctx.upload_bytes(synth.motion_field(P["x_num_blocks"], P["y_num_blocks"], 16 << prec, seed=pic))
             keep.append(d_mv)
-            pair = [ctx.hp_plane(h // 2, w // 2, pair=True) for _ in range(2)] if prec else None
             for k in range(3):
-                cw, ch = comp_size(w, h, k, (1, 1))
-                if prec == 0:
-                    g = [ctx.plane(ch, cw, np.uint8) for _ in range(2)]
-                elif k:
-                    g = pair
-                else:
-                    g = [ctx.hp_plane(ch, cw) for _ in range(2)]
-                out = ctx.plane(ch, cw, np.uint8)
-                keep += list(g) + [out]
-                jobs.append(sa.obmc_plane(d_mv, P, k, g[0], g[1], None, out, prediction_only=1))
+                cw, ch = comp_size(w, h, k, chroma)
+                out = ctx.plane(ch, cw, np.int16 if pred == 2 else np.uint8)
+                res = ctx.plane(ch + 8, cw + 16, res_dt) if pred == 0 and res_dt is not None else None
+                keep += [out] + ([res] if res is not None else [])
+                jobs.append(sa.obmc_plane(d_mv, P, k, refs[0][k], None if one_ref else refs[1][k], res, out, prediction_only=pred))
+        if rnd % 2:
+            jobs = [jobs[i] for i in rng.permutation(len(jobs))]
         ctx.obmc_batch(jobs)
         for p in set(keep):
             p.free()

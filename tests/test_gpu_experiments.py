@@ -9,8 +9,10 @@ with the same oracle on the whole case matrix of its test file:
   * no switch: the tests of test_gpu_iiwt.py / test_gpu_lowdelay.py that set switches themselves (fused levels,
     small / large register tiles, LDS kernel instead of the register kernel, per-level Haar, slice_kernel instead of
     slice_run_kernel, dc_predict_kernel instead of dc_skew_kernel) -- in the product library those switches are inert;
-  * SCHRO_HIP_OBMC_KERNEL=item: obmc.hip's item kernel for every default-weight case (also out of pair images);
-  * SCHRO_HIP_OBMC_MERGE=2: U + V planes of one-component images as one job (obmc_row_kernel_*_2) always;
+  * SCHRO_HIP_OBMC_KERNEL=item: obmc.hip's item kernel for every default-weight case (also out of pair images), and
+    for every plane of test_gpu_mixed_batches.py;
+  * SCHRO_HIP_OBMC_MERGE=2: U + V planes of one-component images as one job (obmc_row_kernel_*_2) always, also in the
+    calls of unlike pictures of test_gpu_mixed_batches.py;
   * SCHRO_HIP_IIWT_CHAIN=1: every level of the register wavelet in one launch (r04, iiwt_reg.hip);
   * SCHRO_HIP_OBMC_STRIP=1: the 12 / 8 block set's luma planes by the strip kernel (r05, obmc_strip.hip: accumulator in
     registers, no LDS tile -- a third formulation of the same arithmetic; measured 2.5 x slower);
@@ -47,11 +49,14 @@ def test_switch_driven_tests_with_live_switches():
 def test_item_kernel_takes_every_default_weight_case():
     run(["test_gpu_obmc.py"], env={"SCHRO_HIP_OBMC_KERNEL": "item"},
         k="test_default_weights or test_dc_values or test_rotating or test_pair_images_default or test_pair_images_edges")
+    run(["test_gpu_mixed_batches.py"], env={"SCHRO_HIP_OBMC_KERNEL": "item"})
 
 
 def test_u_and_v_planes_always_one_job():
     run(["test_gpu_obmc.py"], env={"SCHRO_HIP_OBMC_MERGE": "2"},
         k="test_default_weights or test_dc_values or test_rotating or test_ragged")
+    # (and the mixed batches: every call's half-pel U + V planes as two-plane jobs, beside the other keys' planes)
+    run(["test_gpu_mixed_batches.py"], env={"SCHRO_HIP_OBMC_MERGE": "2"})
 
 
 def test_register_wavelet_chain_form():

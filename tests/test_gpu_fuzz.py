@@ -12,7 +12,7 @@ import oracle_lib as O
 import schroedinger_amd as sa
 import synth
 from test_gpu_lowdelay import compare, decode_cpu, decode_gpu
-from test_gpu_obmc import run_case
+from test_gpu_obmc import Ref, check_case, make_case, run_case
 
 
 # SCHRO_FUZZ_SCALE multiplies the number of draws, SCHRO_FUZZ_SEED shifts the seeds (a long campaign
@@ -149,6 +149,75 @@ def test_obmc_random_geometry_pair_images(ctx):
         weights = [(1, 1, 1), (1, 1, 1), (1, 1, 1), (2, 3, 1), (1, 2, 2)][int(rng.integers(0, 5))]
         run_case(ctx, w, h, blen, sep, prec, weights, chroma, int(rng.integers(1, 120)) << prec, seed=int(rng.integers(1, 1 << 16)),
                  res_dtype=[np.int16, np.int32][rnd & 1], modes=tuple(rng.dirichlet([1, 2, 1, 2])), pair=True)
+
+
+def test_obmc_random_unlike_batches(ctx):
+    """Calls of 2 - 8 unlike pictures: each its own size, block set (x and y drawn apart), precision, weights, chroma format,
+    pair or plain references, residual (s16, s32, none), prediction_only 0 / 1 / 2 and one or two references -- some
+    sharing the references of a picture before them --, the planes shuffled in every other call.  Half the pictures of a
+    call are a variation of one base picture (a stream's geometry, references and precision; their own weights, residual,
+    prediction_only, references), so that unlike pictures meet on one launch key.  Every plane against the oracle's
+    render of that plane alone (tests/test_gpu_mixed_batches.py: the hand-made cases)."""
+    rng = np.random.default_rng(1111 + SEED)
+    seps = [4, 8, 12, 16, 24, 32]
+    presets = [(8, 4), (12, 8), (16, 12), (24, 16), (16, 8), (24, 12), (32, 16), (20, 12), (28, 16), (64, 32)]
+    all_weights = [(1, 1, 1), (1, 1, 1), (1, 1, 1), (3, 5, 3), (1, 3, 2), (1, 2, 2), (2, 3, 1), (3, -1, 1)]
+
+    def axis():
+        sep = seps[int(rng.integers(0, len(seps)))]
+        return min(sep + 4 * int(rng.integers(0, sep // 4 + 1)), 2 * sep, 64), sep
+
+    def geometry():
+        if rng.integers(0, 2):
+            (xblen, xbsep), (yblen, ybsep) = axis(), axis()
+        else:
+            (xblen, xbsep) = (yblen, ybsep) = presets[int(rng.integers(0, len(presets)))]
+        w, h = int(rng.integers(xblen, 200 * BIG)), int(rng.integers(yblen, 120 * BIG))
+        return dict(w=w, h=h, xblen=xblen, xbsep=xbsep, yblen=yblen, ybsep=ybsep, prec=int(rng.integers(0, 4)),
+                    chroma=[(0, 0), (1, 0), (1, 1)][int(rng.integers(0, 3))], pair=bool(rng.integers(0, 2)), refs=None)
+    for rnd in range(200 * SCALE):
+        cases, shared = [], []
+        base = geometry()
+        for _ in range(int(rng.integers(2, 9))):
+            from_base = bool(rng.integers(0, 2))
+            g = dict(base) if from_base else geometry()
+            if g["refs"] is not None and rng.integers(0, 2):
+                g["refs"] = None                    # (the base's geometry with references of its own)
+            if g["refs"] is None:
+                g["refs"] = [Ref(ctx, g["w"], g["h"], g["chroma"], g["prec"] > 0, g["pair"], int(rng.integers(1, 1 << 16)))
+                             for _ in range(2)]
+                shared += g["refs"]
+                if from_base and base["refs"] is None:
+                    base["refs"] = g["refs"]       # (later variations of the base may share them)
+            refs = list(g["refs"])
+            if rng.integers(0, 2):
+                refs.reverse()
+            prec = g["prec"] if g["prec"] == 0 else int(rng.integers(1, 4))      # (half-pel images serve every sub-pel precision)
+            pred = int(rng.integers(0, 3))
+            weights = all_weights[int(rng.integers(0, len(all_weights)))]
+            if pred == 1:       # (a u8 prediction: weights >= 0 that add up to at most 1 << bits)
+                while weights[1] < 0 or weights[0] + weights[1] > (1 << weights[2]):
+                    weights = all_weights[int(rng.integers(0, len(all_weights)))]
+            res = [np.int16, np.int32, None][int(rng.integers(0, 3))]
+            args = (g["w"], g["h"], g["xblen"], g["xbsep"], prec, weights, g["chroma"], int(rng.integers(1, 100)) << prec)
+            kw = dict(res_dtype=res or np.int16, residual=res is not None or pred != 0, prediction_only=pred,
+                      one_ref=bool(rng.integers(0, 5) == 0), refs=refs, yblen=g["yblen"], ybsep=g["ybsep"],
+                      modes=tuple(rng.dirichlet([1, 2, 1, 2])))
+            cases.append((make_case(ctx, *args, seed=int(rng.integers(1, 1 << 16)), **kw), args, kw))
+        jobs = [j for c in cases for j in c[0][0]]
+        shuffled = rnd % 2 == 1
+        if shuffled:
+            jobs = [jobs[i] for i in rng.permutation(len(jobs))]
+        ctx.obmc_batch(jobs)
+        for n, ((_, want, keep), args, kw) in enumerate(cases):
+            try:
+                check_case(want, keep)
+            except AssertionError as e:
+                raise AssertionError("call %d (%s) picture %d of %d: %r %r" % (
+                    rnd, "shuffled" if shuffled else "in order", n, len(cases), args,
+                    {k: v for k, v in kw.items() if k not in ("refs", "modes")})) from e
+        for r in shared:
+            r.free()
 
 
 def test_combine_random_geometry(ctx):

@@ -30,55 +30,100 @@ def run_case(ctx, *args, **kw):
     check_case(want, keep)
 
 
+class Ref:
+    """One reference picture as the library reads it: per component the oracle's picture (`np`, `up`) and the device
+    buffer (`dev`) -- the plane itself (full pel), its half-pel image, or for the chroma of `pair` references ONE (U, V)
+    pair image that serves both components.  Pictures of one size, chroma format and reference layout can share it."""
+
+    def __init__(self, ctx, w, h, chroma, upsampled, pair, seed):
+        self.w, self.h, self.chroma, self.upsampled = w, h, chroma, upsampled
+        self.pair = pair = pair and upsampled and chroma[0] == 1
+        self.np = [synth.picture_u8(*comp_size(w, h, k, chroma)[::-1], seed=seed + k) for k in range(3)]
+        self.up = [O.UpComp(p, upsample=upsampled) for p in self.np]
+        self.dev, self.keep = [], []
+        if pair:
+            cw, ch = comp_size(w, h, 1, chroma)
+            pu, pv, g = ctx.upload(self.np[1]), ctx.upload(self.np[2]), ctx.hp_plane(ch, cw, pair=True)
+            ctx.upsample_batch([((pu, pv), g)])
+            self.keep += [pu, pv, g]
+        for k in range(3):
+            if pair and k:
+                self.dev.append(g)
+                continue
+            p = ctx.upload(self.np[k])
+            self.keep.append(p)
+            if upsampled:
+                cw, ch = comp_size(w, h, k, chroma)
+                hp = ctx.hp_plane(ch, cw)
+                ctx.upsample_batch([(p, hp)])
+                self.keep.append(hp)
+                p = hp
+            self.dev.append(p)
+
+    def free(self):
+        for p in self.keep:
+            p.free()
+
+
 def make_case(ctx, w, h, xblen, xbsep, prec, weights, chroma, mv_range, seed, res_dtype=np.int16,
-              modes=(0.05, 0.45, 0.15, 0.35), edit_mv=None, pair=False, only=None, yblen=None, ybsep=None):
+              modes=(0.05, 0.45, 0.15, 0.35), edit_mv=None, pair=False, only=None, yblen=None, ybsep=None,
+              prediction_only=0, residual=True, one_ref=False, refs=None, mv=None):
     """pair: the chroma references are (U, V) PAIR images (include/schro_hip.h, r04) -- sub-pel precisions
     of horizontally subsampled chroma only; only: the components whose planes are rendered (default all);
-    yblen, ybsep: blocks that are not square (default: as wide as high).  Returns the batch's jobs, (oracle,
-    output plane, component) per plane and the device buffers to free."""
+    yblen, ybsep: blocks that are not square (default: as wide as high);
+    prediction_only: 1 the u8 prediction alone (the combine form), 2 the prediction - 128 into an s16 plane -- both
+    without a residual; residual False: a zero-residual picture (residual NULL, prediction_only 0);
+    one_ref: ref2 NULL, the vectors use reference 1 and DC only; refs: the caller's references [Ref, Ref or None]
+    (shared with other pictures; the caller frees them); mv: the caller's vectors (host records, device copy) for this
+    geometry (pictures that share them).
+    Returns the batch's jobs, (oracle, output plane, component) per plane and the device buffers to free."""
+    assert not (prediction_only and not residual)
     P = synth.motion_params(w, h, xblen, xbsep, prec, weights, chroma, yblen=yblen, ybsep=ybsep)
-    mv = synth.motion_field(P["x_num_blocks"], P["y_num_blocks"], mv_range, seed, modes)
-    if edit_mv is not None:
-        edit_mv(mv, P)
+    if one_ref:
+        modes = (modes[0], sum(modes[1:]), 0, 0)
+    if mv is None:
+        mv = synth.motion_field(P["x_num_blocks"], P["y_num_blocks"], mv_range, seed, modes)
+        if edit_mv is not None:
+            edit_mv(mv, P)
+        d_mv = ctx.upload_bytes(mv)
+        keep = [d_mv]
+    else:
+        mv, d_mv = mv
+        keep = []
     op = O.MotionParams(**P)
-    d_mv = ctx.upload_bytes(mv)
-    pair = pair and prec > 0 and chroma[0] == 1
-    jobs, keep, want = [], [], []
-    refs_np = [[synth.picture_u8(*comp_size(w, h, k, chroma)[::-1], seed=seed + 10 * (r + 1) + k) for k in range(3)]
-               for r in range(2)]
-    pair_hp = []
-    if pair:
-        cw, ch = comp_size(w, h, 1, chroma)
-        for r in range(2):
-            pu, pv, g = ctx.upload(refs_np[r][1]), ctx.upload(refs_np[r][2]), ctx.hp_plane(ch, cw, pair=True)
-            ctx.upsample_batch([((pu, pv), g)])
-            pair_hp.append(g)
-            keep += [pu, pv, g]
+    if refs is None:
+        refs = [Ref(ctx, w, h, chroma, prec > 0, pair, seed + 10 * (r + 1)) for r in range(2)]
+        keep += refs[0].keep + refs[1].keep
+    if one_ref:
+        refs = [refs[0], None]
+    for r in refs:
+        assert r is None or ((r.w, r.h, r.chroma, r.upsampled) == (w, h, chroma, prec > 0)), "references of another picture"
+    assert refs[1] is None or refs[1].pair == refs[0].pair
+    jobs, want = [], []
     for k in range(3):
         cw, ch = comp_size(w, h, k, chroma)
-        r1, r2 = refs_np[0][k], refs_np[1][k]
         res = (synth.image_s(ch + 8, cw + 16, res_dtype, seed=seed + 30 + k).astype(np.int64) * 2
                ).astype(res_dtype)       # residual lives in the iwt-padded frame
         if only is not None and k not in only:
             continue
-        u1, u2 = O.UpComp(r1, upsample=prec > 0), O.UpComp(r2, upsample=prec > 0)
-        want.append(O.motion_render(mv, op, k, u1, u2, res, cw, ch))
-        if prec == 0:
-            g1, g2 = ctx.upload(r1), ctx.upload(r2)
-            keep += [g1, g2]
-        elif pair and k:
-            g1, g2 = pair_hp
+        u1, u2 = refs[0].up[k], refs[1].up[k] if refs[1] is not None else None
+        if prediction_only or not residual:
+            zero = np.zeros((ch, cw), np.int16)
+            if prediction_only == 2:
+                want.append(O.rrshift6_s16(O.motion_render(mv, op, k, u1, u2, zero, cw, ch, return_acc=True)[1]))
+            else:
+                want.append(O.motion_render(mv, op, k, u1, u2, zero, cw, ch))
+            d_res = None
         else:
-            p1, p2 = ctx.upload(r1), ctx.upload(r2)
-            g1, g2 = ctx.hp_plane(ch, cw), ctx.hp_plane(ch, cw)
-            ctx.upsample_batch([(p1, g1), (p2, g2)])
-            keep += [p1, p2, g1, g2]
-        d_res = ctx.upload(res)
-        out = ctx.plane(ch, cw, np.uint8).fill(0x33)
-        jobs.append(sa.obmc_plane(d_mv, P, k, g1, g2, d_res, out))
-        keep += [d_res, out]
+            want.append(O.motion_render(mv, op, k, u1, u2, res, cw, ch))
+            d_res = ctx.upload(res)
+            keep.append(d_res)
+        g1, g2 = refs[0].dev[k], refs[1].dev[k] if refs[1] is not None else None
+        out = ctx.plane(ch, cw, np.int16 if prediction_only == 2 else np.uint8).fill(0x33)
+        jobs.append(sa.obmc_plane(d_mv, P, k, g1, g2, d_res, out, prediction_only=prediction_only))
+        keep.append(out)
         want[-1] = (want[-1], out, k)
-    return jobs, want, keep + [d_mv]
+    return jobs, want, keep
 
 
 def check_case(want, keep):
