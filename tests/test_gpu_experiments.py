@@ -18,6 +18,9 @@ with the same oracle on the whole case matrix of its test file:
     registers, no LDS tile -- a third formulation of the same arithmetic; measured 2.5 x slower);
   * SCHRO_HIP_UPSAMPLE_PERSIST=n: the upsample as n persistent workgroups per CU that prefetch the next tile (r06);
   * SCHRO_HIP_OBMC_PAD=1: the prediction-only 12-pixel-row OBMC kernel with line-aligned quads of lanes (r06).
+
+Every one of these runs also takes test_gpu_footprint.py (or its parts that reach the forced kernel): the slower forms
+must write their output region and nothing else, as the product's do.
 """
 import os
 import subprocess
@@ -43,13 +46,14 @@ def run(files, env=None, k=None, timeout=900):
 
 
 def test_switch_driven_tests_with_live_switches():
-    run(["test_gpu_iiwt.py", "test_gpu_lowdelay.py"])
+    run(["test_gpu_iiwt.py", "test_gpu_lowdelay.py", "test_gpu_footprint.py"])
 
 
 def test_item_kernel_takes_every_default_weight_case():
     run(["test_gpu_obmc.py"], env={"SCHRO_HIP_OBMC_KERNEL": "item"},
         k="test_default_weights or test_dc_values or test_rotating or test_pair_images_default or test_pair_images_edges")
     run(["test_gpu_mixed_batches.py"], env={"SCHRO_HIP_OBMC_KERNEL": "item"})
+    run(["test_gpu_footprint.py"], env={"SCHRO_HIP_OBMC_KERNEL": "item"}, k="obmc or frame_layer or random")
 
 
 def test_u_and_v_planes_always_one_job():
@@ -57,15 +61,17 @@ def test_u_and_v_planes_always_one_job():
         k="test_default_weights or test_dc_values or test_rotating or test_ragged")
     # (and the mixed batches: every call's half-pel U + V planes as two-plane jobs, beside the other keys' planes)
     run(["test_gpu_mixed_batches.py"], env={"SCHRO_HIP_OBMC_MERGE": "2"})
+    run(["test_gpu_footprint.py"], env={"SCHRO_HIP_OBMC_MERGE": "2"}, k="obmc or frame_layer or random")
 
 
 def test_register_wavelet_chain_form():
-    out = run(["test_gpu_iiwt.py", "test_gpu_stream.py", "test_gpu_fuzz.py"], env={"SCHRO_HIP_IIWT_CHAIN": "1"})
+    out = run(["test_gpu_iiwt.py", "test_gpu_stream.py", "test_gpu_fuzz.py", "test_gpu_footprint.py"], env={"SCHRO_HIP_IIWT_CHAIN": "1"})
     assert "passed" in out
 
 
 def test_strip_kernel_takes_the_12_8_luma_planes():
-    out = run(["test_gpu_obmc.py", "test_gpu_combine.py", "test_gpu_stream.py", "test_gpu_fuzz.py"], env={"SCHRO_HIP_OBMC_STRIP": "1"})
+    out = run(["test_gpu_obmc.py", "test_gpu_combine.py", "test_gpu_stream.py", "test_gpu_fuzz.py", "test_gpu_footprint.py"],
+              env={"SCHRO_HIP_OBMC_STRIP": "1"})
     assert "passed" in out
 
 
@@ -74,11 +80,13 @@ def test_persistent_prefetching_upsample():
     tiles and asks for the next tile's source before it filters and stores the current one -- the same planes."""
     out = run(["test_gpu_frameops.py", "test_gpu_stream.py"], env={"SCHRO_HIP_UPSAMPLE_PERSIST": "1"})
     assert "passed" in out
+    out = run(["test_gpu_footprint.py"], env={"SCHRO_HIP_UPSAMPLE_PERSIST": "1"}, k="upsample or obmc or frame_layer")
+    assert "passed" in out
 
 
 def test_line_aligned_quads_in_the_obmc_passes():
     """r06 (measured slower, HISTORY 9): the prediction-only 12-pixel-row kernel with every block's lanes laid out as whole
     128-byte lines of its reference (masked lanes in front of and behind the window's rows) -- the same pictures."""
-    out = run(["test_gpu_combine.py", "test_gpu_stages.py", "test_gpu_fuzz.py"], env={"SCHRO_HIP_OBMC_PAD": "1"})
+    out = run(["test_gpu_combine.py", "test_gpu_stages.py", "test_gpu_fuzz.py", "test_gpu_footprint.py"], env={"SCHRO_HIP_OBMC_PAD": "1"})
     assert "passed" in out
 

@@ -67,7 +67,7 @@ class Ref:
 
 def make_case(ctx, w, h, xblen, xbsep, prec, weights, chroma, mv_range, seed, res_dtype=np.int16,
               modes=(0.05, 0.45, 0.15, 0.35), edit_mv=None, pair=False, only=None, yblen=None, ybsep=None,
-              prediction_only=0, residual=True, one_ref=False, refs=None, mv=None):
+              prediction_only=0, residual=True, one_ref=False, refs=None, mv=None, alloc=None):
     """pair: the chroma references are (U, V) PAIR images (include/schro_hip.h, r04) -- sub-pel precisions
     of horizontally subsampled chroma only; only: the components whose planes are rendered (default all);
     yblen, ybsep: blocks that are not square (default: as wide as high);
@@ -75,7 +75,8 @@ def make_case(ctx, w, h, xblen, xbsep, prec, weights, chroma, mv_range, seed, re
     without a residual; residual False: a zero-residual picture (residual NULL, prediction_only 0);
     one_ref: ref2 NULL, the vectors use reference 1 and DC only; refs: the caller's references [Ref, Ref or None]
     (shared with other pictures; the caller frees them); mv: the caller's vectors (host records, device copy) for this
-    geometry (pictures that share them).
+    geometry (pictures that share them); alloc: alloc (role, height, width, dtype) -> a plane of the caller's for the
+    "residual" (uploaded here) and the "out" plane (left as it is) instead of ctx.upload / ctx.plane.
     Returns the batch's jobs, (oracle, output plane, component) per plane and the device buffers to free."""
     assert not (prediction_only and not residual)
     P = synth.motion_params(w, h, xblen, xbsep, prec, weights, chroma, yblen=yblen, ybsep=ybsep)
@@ -116,12 +117,18 @@ def make_case(ctx, w, h, xblen, xbsep, prec, weights, chroma, mv_range, seed, re
             d_res = None
         else:
             want.append(O.motion_render(mv, op, k, u1, u2, res, cw, ch))
-            d_res = ctx.upload(res)
-            keep.append(d_res)
+            if alloc is None:
+                d_res = ctx.upload(res)
+                keep.append(d_res)
+            else:
+                d_res = alloc("residual", res.shape[0], res.shape[1], res_dtype).upload(res)
         g1, g2 = refs[0].dev[k], refs[1].dev[k] if refs[1] is not None else None
-        out = ctx.plane(ch, cw, np.int16 if prediction_only == 2 else np.uint8).fill(0x33)
+        if alloc is None:
+            out = ctx.plane(ch, cw, np.int16 if prediction_only == 2 else np.uint8).fill(0x33)
+            keep.append(out)
+        else:
+            out = alloc("out", ch, cw, np.int16 if prediction_only == 2 else np.uint8)
         jobs.append(sa.obmc_plane(d_mv, P, k, g1, g2, d_res, out, prediction_only=prediction_only))
-        keep.append(out)
         want[-1] = (want[-1], out, k)
     return jobs, want, keep
 
