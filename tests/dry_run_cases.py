@@ -8,8 +8,10 @@ UndefinedBehaviorSanitizer and ThreadSanitizer see the index arithmetic a GPU bo
 
 Not collected by a plain `pytest tests/` (the name): the product library has no dry mode."""
 import ctypes as C
+import json
 import os
 import threading
+import types
 
 import numpy as np
 import pytest
@@ -359,3 +361,53 @@ def test_scheduler_with_contexts_and_moving_references():
     sched.close()
     for plain, up in keep.values():
         pass                                            # (the scheduler released the published frames; the plain ones go with their contexts)
+
+
+def test_obmc_row_form_limits(ctx, tmp_path):
+    """tests/test_gpu_row_forms.py's pictures at both sides of every obmc_row_form limit -- rim origins at 16 bits, yblen and
+    row lengths, weights, full-pel alignment, plane width, and the geometries closest to each row-kernel table's capacity
+    (tables built full) -- less the 2^28-sample tile-limit pictures.  tests/test_sanitizers.py works the list out before
+    the sanitizer runtime is preloaded and names its file in SCHRO_DRY_ROW_CASES."""
+    if os.environ.get("SCHRO_DRY_ROW_CASES"):
+        with open(os.environ["SCHRO_DRY_ROW_CASES"]) as f:
+            cases = json.load(f)
+    else:
+        import row_forms as R
+        recs, _, _ = R.enumerate_geometries(R.admission_program(str(tmp_path)))
+        cases = R.limit_cases() + R.capacity_cases(R.limit_geometries(recs))
+    for name, side, spec in cases:
+        if spec.get("big"):
+            continue
+        s = dict(spec)
+        w, h, prec, chroma = s["w"], s["h"], s["prec"], s["chroma"]
+        P = synth.motion_params(w, h, s["xblen"], s["xbsep"], prec, s["weights"], chroma, yblen=s.get("yblen"),
+                                ybsep=s.get("ybsep"))
+        d_mv = ctx.upload_bytes(synth.motion_field(P["x_num_blocks"], P["y_num_blocks"], s["mv_range"], seed=w + h))
+        keep, jobs = [d_mv], []
+        pair = s.get("pair", False)
+        pair_hp = [ctx.hp_plane(*comp_size(w, h, 1, chroma)[::-1], pair=True) for _ in range(2)] if pair else None
+        off, pad = s.get("ref_offset", 0), s.get("ref_stride_pad", 0)
+        pred = s.get("prediction_only", 0)
+        for k in s.get("only", (0, 1, 2)):
+            cw, ch = comp_size(w, h, k, chroma)
+            if prec == 0:
+                stride = (cw + off + 3) // 4 * 4 + pad
+                bufs = [ctx.plane(ch + 1, stride, np.uint8, stride=stride) for _ in range(2)]
+                keep += bufs
+                g1, g2 = [types.SimpleNamespace(ptr=b.ptr + off, stride=stride) for b in bufs]
+            elif pair and k:
+                g1, g2 = pair_hp
+            else:
+                g1, g2 = ctx.hp_plane(ch, cw), ctx.hp_plane(ch, cw)
+                keep += [g1, g2]
+            out = ctx.plane(ch, cw, np.uint8)
+            res = None if pred or not s.get("residual", True) else ctx.plane(ch + 8, cw + 16, np.int16)
+            jobs.append(sa.obmc_plane(d_mv, P, k, g1, g2, res, out, prediction_only=pred))
+            keep += [out] + ([res] if res is not None else [])
+        if side == "error":
+            with pytest.raises(sa.SchroHipError, match="picture_weight_bits"):
+                ctx.obmc_batch(jobs)
+        else:
+            ctx.obmc_batch(jobs)
+        for p in set(keep) | set(pair_hp or []):
+            p.free()
