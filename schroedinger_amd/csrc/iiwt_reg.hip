@@ -178,10 +178,11 @@ load_rows (int which)
   return need[which];
 }
 
-// one vertical lifting step on the register tile: E = even rows (LL | HL), O = odd rows
-template < int F, int K, int RP, int LO, int HI >
+// one vertical lifting step on the register tile: E = even rows (LL | HL), O = odd rows; NW dwords per row
+// (4: a level-0 lane's four columns of each half, 2: the level-1 phase's two)
+template < int F, int K, int RP, int LO, int HI, int NW >
 __device__ __forceinline__ void
-vstep (P (&E)[RP][4], P (&O)[RP][4])
+vstep (P (&E)[RP][NW], P (&O)[RP][NW])
 {
   constexpr Step st = filter_step (F, K);
   constexpr int NT = kind_ntaps (st.kind);
@@ -191,7 +192,7 @@ vstep (P (&E)[RP][4], P (&O)[RP][4])
     if (i < rg.lo || i > rg.hi)
       continue;
 #pragma unroll
-    for (int j = 0; j < 4; j++) {
+    for (int j = 0; j < NW; j++) {
       P s[NT];
 #pragma unroll
       for (int t = 0; t < NT; t++) {
@@ -350,6 +351,113 @@ finish_row (P (&row)[4], bool is_first, bool is_last, bool store_lane, char *dst
   }
 }
 
+// ---- level 1 inside level 0 (MODE bit 8) ------------------------------------------------------------------
+// Level 1 wrote its output -- the LL band of level 0 -- for one reader, and level 0 read it straight back; with
+// 3264 tiles for 8 x 2160p level 1 was one round of about three waves per SIMD, bound by latency, not bytes.  Here the
+// level-0 tile synthesises the LL rows it reads itself.  Lane l holds the level-0 LL columns 4 l .. 4 l + 3 of the
+// tile, which level 1 makes of its sub-band columns 2 l, 2 l + 1: the lane loads those two columns of the four
+// level-1 sub-bands (4-byte loads) for the RP / 2 level-1 row pairs under the tile's RP LL rows plus H row pairs of
+// halo above and below (r0 is even for the filters built: H even), lifts them with the same steps, clamps and wrap
+// points as a level-1 launch, and ends with exactly the LL dwords level 0's lifting expects.  The column halo grows:
+// lanes 0 and 63 are halo at level 1, and so the level-0 lanes next to them (l1_lane_halo).
+constexpr int
+l1_lane_halo (int f)
+{
+  return f == 2 ? 3 : 2;
+}
+
+// The filters this form is built for: DD(9,7) and Daub(9,7).  LeGall(5,3) and DD(13,7) have an odd halo -- their tiles
+// start on odd rows, which level 1 would split across a row pair -- and the Haar filters' plain tile (MODE 8) spills
+// at three waves (168 registers); they keep a launch per level.
+constexpr bool
+l1_built (int f)
+{
+  return f == 0 || f == 6;
+}
+
+// one horizontal lifting step of a level-1 row: row[0] = low half samples 0, 1 of this lane, row[1] = high half
+template < int F, int K, bool HEDGE >
+__device__ __forceinline__ void
+hstep2 (P (&row)[2], bool is_first, bool is_last)
+{
+  constexpr Step st = filter_step (F, K);
+  constexpr int NT = kind_ntaps (st.kind);
+  const P y = st.target ? row[0] : row[1];
+  P p = lane_prev (y), n = lane_next (y);
+  if constexpr (HEDGE) {
+    p = is_first ? __builtin_amdgcn_perm (y, y, 0x01000100u) : p;
+    n = is_last ? __builtin_amdgcn_perm (y, y, 0x03020302u) : n;
+  }
+  // (the window of pair_at: dwords of samples -4 .. 7; the level-1 taps reach samples -2 .. 3)
+  const P W[6] = { 0u, p, y, n, 0u, 0u };
+  P s[NT];
+  gather_taps < F, K, 0, 0, NT > (W, s);
+  if (st.target)
+    row[1] = lift_apply_pk < F, K > (row[1], s);
+  else
+    row[0] = lift_apply_pk < F, K > (row[0], s);
+}
+
+// all horizontal steps of one level-1 row, rounded and interleaved: the lane's four LL samples of level 0
+template < int F, bool HEDGE >
+__device__ __forceinline__ void
+l1_row (P (&row)[2], bool is_first, bool is_last, P & o0, P & o1)
+{
+  hstep2 < F, 0, HEDGE > (row, is_first, is_last);
+  hstep2 < F, 1, HEDGE > (row, is_first, is_last);
+  if constexpr (filter_nsteps (F) == 4) {
+    hstep2 < F, 2, HEDGE > (row, is_first, is_last);
+    hstep2 < F, 3, HEDGE > (row, is_first, is_last);
+  }
+  constexpr int SH = filter_shift (F);
+  const P a = out_round_pk < SH > (row[0]), b = out_round_pk < SH > (row[1]);
+  o0 = __builtin_amdgcn_perm (b, a, 0x05040100u);
+  o1 = __builtin_amdgcn_perm (b, a, 0x07060302u);
+}
+
+// the level-0 tile's LL rows (E[k][0..1] for the rows k that level 0 reads) from level 1's sub-bands.
+// LO1..HI1: the level-1 region row pairs that exist (compile-time, as LO..HI at level 0)
+template < int F, int RP, int LO, int HI, int LO1, int HI1, bool HEDGE >
+__device__ __forceinline__ void
+l1_phase (const IwtJob & job, int r0, int c0, int lane, bool is_first, bool is_last, P (&E)[RP][4])
+{
+  constexpr int H = filter_halo (F), RP1 = RP / 2 + 2 * H;
+  static_assert (H % 2 == 0, "level 1 inside level 0 needs an even tile origin");
+  P E1[RP1][2], O1[RP1][2];
+  const int nr1 = job.h >> 2, nc1 = job.w >> 2;
+  const int q0 = (r0 >> 1) - H;
+  const uint32_t voff = (uint32_t) clampi ((c0 >> 1) + 2 * lane, 0, nc1 - 2) * 2u;
+  constexpr Rng le = load_rows < F, RP1, LO1, HI1 > (0), lo = load_rows < F, RP1, LO1, HI1 > (1);
+#pragma unroll
+  for (int k = 0; k < RP1; k++) {
+    const int r = clampi (q0 + k, 0, nr1 - 1);
+    if (k >= le.lo && k <= le.hi) {
+      E1[k][0] = gload < uint32_t > ((const char *) job.l1_sb[0] + (size_t) r * job.l1_sb_stride[0] + voff);
+      E1[k][1] = gload < uint32_t > ((const char *) job.l1_sb[1] + (size_t) r * job.l1_sb_stride[1] + voff);
+    }
+    if (k >= lo.lo && k <= lo.hi) {
+      O1[k][0] = gload < uint32_t > ((const char *) job.l1_sb[2] + (size_t) r * job.l1_sb_stride[2] + voff);
+      O1[k][1] = gload < uint32_t > ((const char *) job.l1_sb[3] + (size_t) r * job.l1_sb_stride[3] + voff);
+    }
+  }
+  vstep < F, 0, RP1, LO1, HI1 > (E1, O1);
+  vstep < F, 1, RP1, LO1, HI1 > (E1, O1);
+  if constexpr (filter_nsteps (F) == 4) {
+    vstep < F, 2, RP1, LO1, HI1 > (E1, O1);
+    vstep < F, 3, RP1, LO1, HI1 > (E1, O1);
+  }
+  // level-1 row pair i makes LL rows 2 (i - H) and 2 (i - H) + 1 of the level-0 tile
+  constexpr Rng need = load_rows < F, RP, LO, HI > (0);
+#pragma unroll
+  for (int i = H; i < RP1 - H; i++) {
+    const int k = 2 * (i - H);
+    if (k >= need.lo && k <= need.hi)
+      l1_row < F, HEDGE > (E1[i], is_first, is_last, E[k][0], E[k][1]);
+    if (k + 1 >= need.lo && k + 1 <= need.hi)
+      l1_row < F, HEDGE > (O1[i], is_first, is_last, E[k + 1][0], E[k + 1][1]);
+  }
+}
+
 // LO..HI: region row pairs that exist in the picture (compile-time: see the header)
 // COH (chain form): bit 0 the LL band is another tile's output of this launch, bit 1 so is this tile's output
 struct NoWait {
@@ -358,7 +466,8 @@ struct NoWait {
   __device__ __forceinline__ void settle (Seen) const { }
 };
 
-template < int F, int RP, int LO, int HI, bool HEDGE, int COH = 0, typename WAIT = NoWait >
+// COH bit 3: level 1 inside level 0 (l1_phase makes the LL band; LO1..HI1 its level-1 region row pairs that exist)
+template < int F, int RP, int LO, int HI, bool HEDGE, int COH = 0, typename WAIT = NoWait, int LO1 = 0, int HI1 = -1 >
 __device__ __forceinline__ void
 reg_tile (const IwtJob & job, int r0, int c0, int nr, int nc, int lane, WAIT wait = WAIT ())
 {
@@ -371,6 +480,15 @@ reg_tile (const IwtJob & job, int r0, int c0, int nr, int nc, int lane, WAIT wai
   // (chain form) ask how far the tiles that produce this tile's LL rows are, then load the detail bands -- they
   // come from the coefficient frame whatever the level above is doing --, then look at the answer (loads return
   // in order: it is there while the ~36 detail loads are still in flight), then load LL
+  // lanes inside the picture: first / last substitute their edge sample for the neighbour (the same lanes at level 1:
+  // c0 and the sub-band width are multiples of 4)
+  const int l_lo = (max (0, -c0) + 3) >> 2, l_hi = min (63, ((nc - c0) >> 2) - 1);
+  const bool is_first = lane == l_lo, is_last = lane == l_hi;
+  if constexpr ((COH & 8) != 0) {
+    // level 1 first: its 40 registers are free again before the detail bands' 72 are loaded into
+    l1_phase < F, RP, LO, HI, LO1, HI1, HEDGE > (job, r0, c0, lane, is_first, is_last, E);
+    __builtin_amdgcn_sched_barrier (0);
+  }
   const auto seen = wait.ask ();
 #pragma unroll
   for (int k = 0; k < RP; k++) {
@@ -390,13 +508,15 @@ reg_tile (const IwtJob & job, int r0, int c0, int nr, int nc, int lane, WAIT wai
     }
   }
   wait.settle (seen);
+  if constexpr ((COH & 8) == 0) {
 #pragma unroll
-  for (int k = 0; k < RP; k++) {
-    const int r = clampi (r0 + k, 0, nr - 1);
-    if (k >= le.lo && k <= le.hi) {
-      const u32x2 ll = IWT_LOAD8 ((const char *) job.sb[0] + (size_t) r * job.sb_stride[0] + voff);
-      E[k][0] = ll.x;
-      E[k][1] = ll.y;
+    for (int k = 0; k < RP; k++) {
+      const int r = clampi (r0 + k, 0, nr - 1);
+      if (k >= le.lo && k <= le.hi) {
+        const u32x2 ll = IWT_LOAD8 ((const char *) job.sb[0] + (size_t) r * job.sb_stride[0] + voff);
+        E[k][0] = ll.x;
+        E[k][1] = ll.y;
+      }
     }
   }
 
@@ -407,10 +527,8 @@ reg_tile (const IwtJob & job, int r0, int c0, int nr, int nc, int lane, WAIT wai
     vstep < F, 3, RP, LO, HI > (E, O);
   }
 
-  // lanes inside the picture: first / last substitute their edge sample for the neighbour
-  const int l_lo = (max (0, -c0) + 3) >> 2, l_hi = min (63, ((nc - c0) >> 2) - 1);
-  const bool is_first = lane == l_lo, is_last = lane == l_hi;
-  const bool store_lane = lane >= max (l_lo, 1) && lane <= min (l_hi, 62);
+  constexpr int LH = (COH & 8) != 0 ? l1_lane_halo (F) : 1;     // halo lanes on either side
+  const bool store_lane = lane >= max (l_lo, LH) && lane <= min (l_hi, 63 - LH);
   if constexpr ((COH & 4) != 0) {
     // combine form: the destination is the u8 picture (out_w x out_h inside the iwt-padded w x h).  The lane's 8
     // prediction bytes of a row are ONE aligned load (the host keeps rows of the prediction plane 8-byte aligned and
@@ -532,6 +650,65 @@ reg_tile_at (const IwtJob & job, int tx, int ty, int lane, WAIT wait = WAIT ())
   }
 }
 
+// ---- level 1 inside level 0: tile placement.  The level-1 region of a tile is row pairs q0 .. q0 + RP1 - 1,
+// q0 = r0 / 2 - H.  Only the top tile reaches above the picture at level 1 (the host asks for nr >= RP + 2 H, so the
+// second tile row starts at level-1 row pair RP / 2 - 3 H / 2 >= H for H <= 2); the tiles of the last rows reach
+// n1 = 0 .. H (nout = 0) or H + nout / 2 (nout even: r0, RP and nr are) row pairs below it.
+template < int F, int RP, int LO, int HI, bool HEDGE, int COH, int N1 >
+__device__ __forceinline__ void
+reg_tile_l1_n1 (int n1, const IwtJob & job, int r0, int c0, int nr, int nc, int lane)
+{
+  constexpr int RP1 = RP / 2 + 2 * filter_halo (F);
+  if constexpr (N1 >= 1) {
+    if (n1 == N1)
+      reg_tile < F, RP, LO, HI, HEDGE, COH, NoWait, 0, RP1 - 1 - N1 > (job, r0, c0, nr, nc, lane);
+    else
+      reg_tile_l1_n1 < F, RP, LO, HI, HEDGE, COH, N1 - 1 > (n1, job, r0, c0, nr, nc, lane);
+  } else {
+    reg_tile < F, RP, LO, HI, HEDGE, COH, NoWait, 0, RP1 - 1 > (job, r0, c0, nr, nc, lane);
+  }
+}
+
+template < int F, int RP, int COH, int N >
+__device__ __forceinline__ void
+reg_tile_l1_bottom (int nout, const IwtJob & job, int r0, int c0, int nr, int nc, int lane)
+{
+  constexpr int H = filter_halo (F), RP1 = RP / 2 + 2 * H;
+  if constexpr (N >= 1) {
+    if constexpr (N % 2 == 0) {
+      if (nout == N) {
+        reg_tile < F, RP, 0, RP - 1 - N, true, COH, NoWait, 0, RP1 - 1 - H - N / 2 > (job, r0, c0, nr, nc, lane);
+        return;
+      }
+    }
+    reg_tile_l1_bottom < F, RP, COH, N - 1 > (nout, job, r0, c0, nr, nc, lane);
+  }
+}
+
+template < int F, int RP, int COH >
+__device__ __forceinline__ void
+reg_tile_l1_at (const IwtJob & job, int tx, int ty, int lane)
+{
+  constexpr int H = filter_halo (F), RP1 = RP / 2 + 2 * H, LH = l1_lane_halo (F);
+  const int nr = job.h >> 1, nc = job.w >> 1;
+  const int r0 = reg_tile_r0 < F, RP > (ty, nr);
+  const int nout = max (0, r0 + RP - nr);
+  const int c0 = tx * (4 * (64 - 2 * LH)) - 4 * LH;
+  const bool hedge = c0 < 0 || c0 + 256 > nc;
+  if (r0 < 0) {
+    // r0 = -H: level-1 row pairs from -3 H / 2
+    reg_tile < F, RP, H, RP - 1, true, COH, NoWait, H + H / 2, RP1 - 1 > (job, r0, c0, nr, nc, lane);
+  } else if (nout == 0) {
+    const int n1 = max (0, (r0 + RP - nr) / 2 + H);
+    if (!hedge)
+      reg_tile_l1_n1 < F, RP, 0, RP - 1, false, COH, H > (n1, job, r0, c0, nr, nc, lane);
+    else
+      reg_tile_l1_n1 < F, RP, 0, RP - 1, true, COH, H > (n1, job, r0, c0, nr, nc, lane);
+  } else {
+    reg_tile_l1_bottom < F, RP, COH, H > (nout, job, r0, c0, nr, nc, lane);
+  }
+}
+
 // Register budget: four waves per SIMD (128 registers; DD(9,7) with 12 row pairs takes 106 -- left to itself the
 // compiler spreads to 144, three waves).  Alone the kernel runs the same either way; beside the other batch's
 // OBMC (seven waves of 69 registers on every SIMD) the smaller waves find room: finest level 0.0722 -> 0.0703 ms,
@@ -540,7 +717,9 @@ reg_tile_at (const IwtJob & job, int tx, int ty, int lane, WAIT wait = WAIT ())
 #define IIWT_REG_WAVES(F, RP) (((F) == 3 || (F) == 4) && (RP) == 12 ? 3 : 4)
 // (the combine form of the 12-pair tiles: 4 waves spill ~40 registers of the epilogue and are still the faster
 // launch -- 8 x 2160p finest level 0.081 ms against 0.086 ms at 3 waves without a spill, r04)
-#define IIWT_REG_WAVES_M(F, RP, MODE) ((MODE) == 4 && (RP) == 12 ? 4 : IIWT_REG_WAVES (F, RP))
+// (level 1 inside level 0, MODE bit 8: at four waves the 12-pair tile spills 30 (MODE 8) / 121 (MODE 12) registers
+// of the level-0 phase; at three it takes 130 / 150 and none)
+#define IIWT_REG_WAVES_M(F, RP, MODE) (((MODE) & 8) != 0 ? 3 : (MODE) == 4 && (RP) == 12 ? 4 : IIWT_REG_WAVES (F, RP))
 template < int F, int RP, int MODE >
 __global__ __launch_bounds__ (kRegThreads) __attribute__ ((amdgpu_waves_per_eu (IIWT_REG_WAVES_M (F, RP, MODE), IIWT_REG_WAVES_M (F, RP, MODE))))
 void iiwt_reg_kernel (const IwtJob * __restrict__ jobs, int njobs, int total_tiles)
@@ -554,7 +733,10 @@ void iiwt_reg_kernel (const IwtJob * __restrict__ jobs, int njobs, int total_til
   const int lane = threadIdx.x & 63;
   const IwtJob job = jobs[find_job (jobs, njobs, tile)];
   const int t = tile - job.tile_base;
-  reg_tile_at < F, RP, MODE > (job, t % job.tiles_x, t / job.tiles_x, lane);
+  if constexpr ((MODE & 8) != 0)
+    reg_tile_l1_at < F, RP, MODE > (job, t % job.tiles_x, t / job.tiles_x, lane);
+  else
+    reg_tile_at < F, RP, MODE > (job, t % job.tiles_x, t / job.tiles_x, lane);
 }
 
 // rows per wave of the small form: 4 useful row pairs whatever the halo
@@ -687,9 +869,27 @@ launch_chain (hipStream_t stream, const IwtJob * d_jobs, const uint32_t * d_orde
 
 template < int F >
 int
-launch_reg (hipStream_t stream, const IwtJob * d_jobs, int njobs, int total_tiles, bool small, bool combine)
+launch_reg (hipStream_t stream, const IwtJob * d_jobs, int njobs, int total_tiles, bool small, bool combine, bool l1)
 {
   const int wgs = (total_tiles + kRegThreads / 64 - 1) / (kRegThreads / 64);
+  if constexpr (l1_built (F)) {
+    if (l1) {
+      if (small)
+        return set_error (SCHRO_HIP_EINVAL, "iiwt (register form): level 1 inside level 0 takes the large tile only");
+      if (combine)
+        SCHRO_LAUNCH ((iiwt_reg_kernel < F, kRegRP, 12 >), dim3 (wgs), dim3 (kRegThreads), 0, stream, d_jobs, njobs,
+            total_tiles);
+      else
+        SCHRO_LAUNCH ((iiwt_reg_kernel < F, kRegRP, 8 >), dim3 (wgs), dim3 (kRegThreads), 0, stream, d_jobs, njobs,
+            total_tiles);
+      hipError_t e = hipGetLastError ();
+      if (e != hipSuccess)
+        return set_error (SCHRO_HIP_EDEVICE, "iiwt (register form, level 1 inside) launch: %s", hipGetErrorString (e));
+      return 0;
+    }
+  } else if (l1) {
+    return set_error (SCHRO_HIP_EINVAL, "iiwt (register form): level 1 inside level 0 is not built for filter %d", F);
+  }
   if (small && combine)
     SCHRO_LAUNCH ((iiwt_reg_kernel < F, small_rp (F), 4 >), dim3 (wgs), dim3 (kRegThreads), 0, stream,
         d_jobs, njobs, total_tiles);
@@ -730,6 +930,23 @@ iiwt_reg_geometry (int filter, int small, int *useful_cols, int *useful_row_pair
   *min_row_pairs = rp - filter_halo (filter);
 }
 
+// level 1 inside level 0: the filters built (l1_built)
+bool
+iiwt_reg_l1_supported (int filter)
+{
+  return iiwt_reg_supported (filter, 2) && l1_built (filter);
+}
+
+// its tile: 12 row pairs, 4 (64 - 2 l1_lane_halo) useful columns; a plane needs RP + 2 H sub-band rows (only the top
+// tile reaches above the picture at level 1, and it does not reach below it)
+void
+iiwt_reg_l1_geometry (int filter, int *useful_cols, int *useful_row_pairs, int *min_row_pairs)
+{
+  *useful_cols = 4 * (64 - 2 * l1_lane_halo (filter));
+  *useful_row_pairs = kRegRP - 2 * filter_halo (filter);
+  *min_row_pairs = kRegRP + 2 * filter_halo (filter);
+}
+
 // (the chain form is a measured-slower form: built into the experiments library only, schro_hip_internal.h)
 int
 launch_iiwt_chain (hipStream_t stream, const IwtJob * d_jobs, const uint32_t * d_order, int n_tiles, uint32_t * ctrl,
@@ -753,15 +970,15 @@ launch_iiwt_chain (hipStream_t stream, const IwtJob * d_jobs, const uint32_t * d
 
 int
 launch_iiwt_reg (hipStream_t stream, const IwtJob * d_jobs, int njobs, int total_tiles, int filter,
-    int small, int combine)
+    int small, int combine, int l1_inline)
 {
   switch (filter) {
-    case 0: return launch_reg < 0 > (stream, d_jobs, njobs, total_tiles, small, combine);
-    case 1: return launch_reg < 1 > (stream, d_jobs, njobs, total_tiles, small, combine);
-    case 2: return launch_reg < 2 > (stream, d_jobs, njobs, total_tiles, small, combine);
-    case 3: return launch_reg < 3 > (stream, d_jobs, njobs, total_tiles, small, combine);
-    case 4: return launch_reg < 4 > (stream, d_jobs, njobs, total_tiles, small, combine);
-    case 6: return launch_reg < 6 > (stream, d_jobs, njobs, total_tiles, small, combine);
+    case 0: return launch_reg < 0 > (stream, d_jobs, njobs, total_tiles, small, combine, l1_inline);
+    case 1: return launch_reg < 1 > (stream, d_jobs, njobs, total_tiles, small, combine, l1_inline);
+    case 2: return launch_reg < 2 > (stream, d_jobs, njobs, total_tiles, small, combine, l1_inline);
+    case 3: return launch_reg < 3 > (stream, d_jobs, njobs, total_tiles, small, combine, l1_inline);
+    case 4: return launch_reg < 4 > (stream, d_jobs, njobs, total_tiles, small, combine, l1_inline);
+    case 6: return launch_reg < 6 > (stream, d_jobs, njobs, total_tiles, small, combine, l1_inline);
   }
   return set_error (SCHRO_HIP_EINVAL, "iiwt (register form): filter %d not built", filter);
 }

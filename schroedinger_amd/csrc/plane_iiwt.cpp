@@ -332,9 +332,108 @@ schro_hip_iiwt_batch (SchroHipContext * ctx, const SchroHipIwtPlane * planes, in
     rmin_any = std::max (rmin, srmin);  // (whichever tile form the level loop picks for level 0)
   }
 
-  // scratch for the intermediate LL images: levels depth-1 .. 1 of every plane
+  // scratch for the intermediate LL images: levels depth-1 .. 1 of every plane (level 1: where it is not synthesised
+  // inside level 0)
   std::vector < size_t > scratch_off ((size_t) nplanes * depth, 0);
   std::vector < int >scratch_stride ((size_t) nplanes * depth, 0);
+
+  // the job of (plane, level): the level view of the coefficient frame {w, h, stride << level}
+  // (schrodecoder.c:1834-1845), sub-band positions schroparams.c:319-352, LL from / output to the scratch
+  auto level_job = [&](int p, int level, bool * src_al_out, bool * dst_al_out) {
+    const SchroHipIwtPlane & pl = planes[p];
+    IwtJob j;
+    memset (&j, 0, sizeof (j));
+    int w = pl.width >> level, h = pl.height >> level;
+    const char *base = (const char *) pl.src;
+    int vstride = pl.src_stride << level;
+    const char *ll = base;
+    int ll_stride = vstride * 2;
+    if (level < depth - 1) {
+      ll = (const char *) ctx->scratch_ref () + scratch_off[(size_t) p * depth + level + 1];
+      ll_stride = scratch_stride[(size_t) p * depth + level + 1];
+    } else if (pl.ll) {         // (r04: the coarser levels ran in a call of their own)
+      ll = (const char *) pl.ll;
+      ll_stride = pl.ll_stride;
+    }
+    j.sb[0] = ll;
+    j.sb_stride[0] = ll_stride;
+    j.sb[1] = base + (size_t) (w / 2) * bpp;
+    j.sb_stride[1] = vstride * 2;
+    j.sb[2] = base + vstride;
+    j.sb_stride[2] = vstride * 2;
+    j.sb[3] = base + vstride + (size_t) (w / 2) * bpp;
+    j.sb_stride[3] = vstride * 2;
+    if (level == 0 && pl.combine && scratch_stride[(size_t) p * depth]) {
+      // (combine through a residual plane in the scratch: see above)
+      j.dst = (char *) ctx->scratch_ref () + scratch_off[(size_t) p * depth];
+      j.dst_stride = scratch_stride[(size_t) p * depth];
+    } else if (level == 0) {
+      j.dst = pl.dst;
+      j.dst_stride = pl.dst_stride;
+      if (pl.combine) {
+        j.pred = pl.combine == 1 ? pl.pred : nullptr;
+        j.pred_stride = pl.pred_stride;
+        j.out_w = pl.out_width;
+        j.out_h = pl.out_height;
+        j.pad2 = 1;             // (combine form)
+      }
+    } else {
+      j.dst = (char *) ctx->scratch_ref () + scratch_off[(size_t) p * depth + level];
+      j.dst_stride = scratch_stride[(size_t) p * depth + level];
+    }
+    j.w = w;
+    j.h = h;
+    int nc = w / 2;
+    int vl = 8 / bpp;
+    bool src_al = (nc % vl) == 0 && nc >= vl;
+    for (int s = 0; s < 4; s++)
+      src_al = src_al && (((uintptr_t) j.sb[s] | (uintptr_t) j.sb_stride[s]) & 7) == 0;
+    bool dst_al = (((uintptr_t) j.dst | (uintptr_t) j.dst_stride) & (j.pad2 ? 7 : 15)) == 0;
+    j.flags = (src_al ? 1 : 0) | (dst_al ? 2 : 0);
+    j.ctr = -1;
+    *src_al_out = src_al;
+    *dst_al_out = dst_al;
+    return j;
+  };
+  // which tile form a level takes in the register kernels: a level of fewer tiles than the chip has SIMDs
+  // twice over is latency, not bandwidth -- the small form (4 useful row pairs per wave)
+  auto level_is_small = [&](int level) {
+    long tiles = 0;
+    for (int p = 0; p < nplanes; p++)
+      tiles += (long) div_up ((planes[p].width >> level) / 2, ruc) * div_up ((planes[p].height >> level) / 2, rur);
+    const char *env = SCHRO_ENV ("SCHRO_HIP_IIWT_SMALL");
+    const char *envb = SCHRO_ENV ("SCHRO_HIP_IIWT_SMALL_BELOW");
+    // (r03, SCHRO_HIP_IIWT_SMALL_BELOW: with 4096 the 3264-tile level -- 8 x 1080p's finest, 8 x 2160p's
+    // middle one -- takes the small form: alone 0.0381 -> 0.0351 ms, but 0.0263 -> 0.0322 with two batches in
+    // flight, and 0.002 ms of a 2160p step: left at 2048)
+    return env ? atoi (env) != 0 : tiles < (envb ? atol (envb) : 2048);
+  };
+
+  // Level 1 inside level 0 (iiwt_reg.hip, MODE bit 8): a plane of depth >= 2 whose levels 1 and 0 both take the
+  // register form, and level 0 its large tile, runs level 1 in the level-0 launch -- no level-1 launch, no level-1
+  // image in the scratch.  Not for the residual-and-convert route of the combine form, nor beside the chain form or a
+  // fused LDS group (experiments build).  8 x 2160p 4:2:0, combine form: see DESIGN 4.1.
+  // (experiments: SCHRO_HIP_IIWT_L1_INLINE=0 keeps a launch per level, for A/B runs)
+  const bool chain_on = SCHRO_ENV ("SCHRO_HIP_IIWT_CHAIN") && atoi (SCHRO_ENV ("SCHRO_HIP_IIWT_CHAIN")) != 0;
+  const bool l1_on = use_reg && depth >= 2 && iiwt_reg_l1_supported (filter) && !chain_on
+      && !(SCHRO_ENV ("SCHRO_HIP_IIWT_FUSE") && atoi (SCHRO_ENV ("SCHRO_HIP_IIWT_FUSE")) != 0)
+      && !(SCHRO_ENV ("SCHRO_HIP_IIWT_L1_INLINE") && atoi (SCHRO_ENV ("SCHRO_HIP_IIWT_L1_INLINE")) == 0)
+      && !level_is_small (0);
+  int l1uc = 0, l1ur = 0, l1rmin = 0;
+  if (l1_on)
+    iiwt_reg_l1_geometry (filter, &l1uc, &l1ur, &l1rmin);
+  std::vector < char >l1_inline (nplanes, 0);
+  // (called once the plane's level-0 scratch, if any, is decided: level_job (p, 0) looks at it)
+  auto plane_l1_inline = [&](int p) {
+    if (!l1_on)
+      return false;
+    bool a0, d0, a1, d1;
+    const IwtJob j0 = level_job (p, 0, &a0, &d0), j1 = level_job (p, 1, &a1, &d1);
+    int uc1, ur1, rmin1;
+    iiwt_reg_geometry (filter, level_is_small (1), &uc1, &ur1, &rmin1);
+    return (!planes[p].combine || j0.pad2) && a0 && d0 && (j0.w / 2) % 4 == 0 && j0.h / 2 >= l1rmin
+        && a1 && (j1.w / 2) % 4 == 0 && j1.h / 2 >= rmin1;
+  };
   size_t total = 0;
   bool any_ll = false;
   for (int p = 0; p < nplanes; p++) {
@@ -376,7 +475,8 @@ schro_hip_iiwt_batch (SchroHipContext * ctx, const SchroHipIwtPlane * planes, in
         total += round_up ((size_t) stride * pl.height, 256);
       }
     }
-    for (int l = 1; l < depth; l++) {
+    l1_inline[p] = plane_l1_inline (p);
+    for (int l = l1_inline[p] ? 2 : 1; l < depth; l++) {
       int w = pl.width >> l, h = pl.height >> l;
       // (whole 128-byte lines per row: in the chain form of the register kernels a consumer tile must never bring a
       // line into its XCD's L2 that also holds samples of a row its producer has not written yet)
@@ -473,78 +573,6 @@ schro_hip_iiwt_batch (SchroHipContext * ctx, const SchroHipIwtPlane * planes, in
     }
   }
 
-  // the job of (plane, level): the level view of the coefficient frame {w, h, stride << level}
-  // (schrodecoder.c:1834-1845), sub-band positions schroparams.c:319-352, LL from / output to the scratch
-  auto level_job = [&](int p, int level, bool * src_al_out, bool * dst_al_out) {
-    const SchroHipIwtPlane & pl = planes[p];
-    IwtJob j;
-    memset (&j, 0, sizeof (j));
-    int w = pl.width >> level, h = pl.height >> level;
-    const char *base = (const char *) pl.src;
-    int vstride = pl.src_stride << level;
-    const char *ll = base;
-    int ll_stride = vstride * 2;
-    if (level < depth - 1) {
-      ll = (const char *) ctx->scratch_ref () + scratch_off[(size_t) p * depth + level + 1];
-      ll_stride = scratch_stride[(size_t) p * depth + level + 1];
-    } else if (pl.ll) {         // (r04: the coarser levels ran in a call of their own)
-      ll = (const char *) pl.ll;
-      ll_stride = pl.ll_stride;
-    }
-    j.sb[0] = ll;
-    j.sb_stride[0] = ll_stride;
-    j.sb[1] = base + (size_t) (w / 2) * bpp;
-    j.sb_stride[1] = vstride * 2;
-    j.sb[2] = base + vstride;
-    j.sb_stride[2] = vstride * 2;
-    j.sb[3] = base + vstride + (size_t) (w / 2) * bpp;
-    j.sb_stride[3] = vstride * 2;
-    if (level == 0 && pl.combine && scratch_stride[(size_t) p * depth]) {
-      // (combine through a residual plane in the scratch: see above)
-      j.dst = (char *) ctx->scratch_ref () + scratch_off[(size_t) p * depth];
-      j.dst_stride = scratch_stride[(size_t) p * depth];
-    } else if (level == 0) {
-      j.dst = pl.dst;
-      j.dst_stride = pl.dst_stride;
-      if (pl.combine) {
-        j.pred = pl.combine == 1 ? pl.pred : nullptr;
-        j.pred_stride = pl.pred_stride;
-        j.out_w = pl.out_width;
-        j.out_h = pl.out_height;
-        j.pad2 = 1;             // (combine form)
-      }
-    } else {
-      j.dst = (char *) ctx->scratch_ref () + scratch_off[(size_t) p * depth + level];
-      j.dst_stride = scratch_stride[(size_t) p * depth + level];
-    }
-    j.w = w;
-    j.h = h;
-    int nc = w / 2;
-    int vl = 8 / bpp;
-    bool src_al = (nc % vl) == 0 && nc >= vl;
-    for (int s = 0; s < 4; s++)
-      src_al = src_al && (((uintptr_t) j.sb[s] | (uintptr_t) j.sb_stride[s]) & 7) == 0;
-    bool dst_al = (((uintptr_t) j.dst | (uintptr_t) j.dst_stride) & (j.pad2 ? 7 : 15)) == 0;
-    j.flags = (src_al ? 1 : 0) | (dst_al ? 2 : 0);
-    j.ctr = -1;
-    *src_al_out = src_al;
-    *dst_al_out = dst_al;
-    return j;
-  };
-  // which tile form a level takes in the register kernels: a level of fewer tiles than the chip has SIMDs
-  // twice over is latency, not bandwidth -- the small form (4 useful row pairs per wave)
-  auto level_is_small = [&](int level) {
-    long tiles = 0;
-    for (int p = 0; p < nplanes; p++)
-      tiles += (long) div_up ((planes[p].width >> level) / 2, ruc) * div_up ((planes[p].height >> level) / 2, rur);
-    const char *env = SCHRO_ENV ("SCHRO_HIP_IIWT_SMALL");
-    const char *envb = SCHRO_ENV ("SCHRO_HIP_IIWT_SMALL_BELOW");
-    // (r03, SCHRO_HIP_IIWT_SMALL_BELOW: with 4096 the 3264-tile level -- 8 x 1080p's finest, 8 x 2160p's
-    // middle one -- takes the small form: alone 0.0381 -> 0.0351 ms, but 0.0263 -> 0.0322 with two batches in
-    // flight, and 0.002 ms of a 2160p step: left at 2048)
-    return env ? atoi (env) != 0 : tiles < (envb ? atol (envb) : 2048);
-  };
-
   // r04: every level in ONE launch where all of them can take the register form (iiwt_reg.hip, chain form).
   // Built as VERDICT r03 asked and measured: 8 x 2160p 0.135 ms against 0.103 for a launch per level (8 x 1080p
   // 0.058 against 0.038) -- a tile's extra round trip to its producers' counters and the written-through LL
@@ -552,14 +580,14 @@ schro_hip_iiwt_batch (SchroHipContext * ctx, const SchroHipIwtPlane * planes, in
   bool any_combine = false;
   for (int p = 0; p < nplanes; p++)
     any_combine |= planes[p].combine != 0;
-  if (use_reg && depth >= 2 && !nl && !any_combine && !any_ll && SCHRO_ENV ("SCHRO_HIP_IIWT_CHAIN") && atoi (SCHRO_ENV ("SCHRO_HIP_IIWT_CHAIN")) != 0) {
+  if (use_reg && depth >= 2 && !nl && !any_combine && !any_ll && chain_on) {
     int done = 0;
     const int r = iiwt_chain (ctx, nplanes, depth, filter, level_job, level_is_small, &done);
     if (r || done)
       return r;
   }
 
-  std::vector < IwtJob > jobs, rjobs, hjobs, cjobs;
+  std::vector < IwtJob > jobs, rjobs, hjobs, cjobs, r1jobs, c1jobs;
   for (int level = depth - 1; level >= 0; level--) {
     if (nl && level >= fb && level < fb + nl) {
       if (level == fb + nl - 1) {
@@ -569,11 +597,13 @@ schro_hip_iiwt_batch (SchroHipContext * ctx, const SchroHipIwtPlane * planes, in
       }
       continue;
     }
-    int tile_base = 0, rtile_base = 0, htile_base = 0, ctile_base = 0;
+    int tile_base = 0, rtile_base = 0, htile_base = 0, ctile_base = 0, r1tile_base = 0, c1tile_base = 0;
     jobs.clear ();
     rjobs.clear ();
     hjobs.clear ();
     cjobs.clear ();
+    r1jobs.clear ();
+    c1jobs.clear ();
     int lruc = ruc, lrur = rur, lrmin = rmin, small = 0;
     if (use_reg) {
       small = level_is_small (level);
@@ -581,9 +611,26 @@ schro_hip_iiwt_batch (SchroHipContext * ctx, const SchroHipIwtPlane * planes, in
         iiwt_reg_geometry (filter, 1, &lruc, &lrur, &lrmin);
     }
     for (int p = 0; p < nplanes; p++) {
+      if (level == 1 && l1_inline[p])
+        continue;               // (its level-0 tiles synthesise it)
       bool src_al, dst_al;
       IwtJob j = level_job (p, level, &src_al, &dst_al);
       const int nc = j.w / 2, nr = j.h / 2;
+      if (level == 0 && l1_inline[p]) {
+        bool a1, d1;
+        const IwtJob j1 = level_job (p, 1, &a1, &d1);
+        for (int s = 0; s < 4; s++) {
+          j.l1_sb[s] = j1.sb[s];
+          j.l1_sb_stride[s] = j1.sb_stride[s];
+        }
+        j.tiles_x = div_up (nc, l1uc);
+        std::vector < IwtJob > &list = j.pad2 ? c1jobs : r1jobs;
+        int &base = j.pad2 ? c1tile_base : r1tile_base;
+        j.tile_base = base;
+        base += j.tiles_x * div_up (nr, l1ur);
+        list.push_back (j);
+        continue;
+      }
       if (use_haar && iiwt_haar_job_ok (j)) {
         j.tiles_x = div_up (nc, hcols);
         j.tile_base = htile_base;
@@ -609,10 +656,14 @@ schro_hip_iiwt_batch (SchroHipContext * ctx, const SchroHipIwtPlane * planes, in
         jobs.push_back (j);
       }
     }
-    void *d_rjobs = nullptr, *d_jobs = nullptr, *d_hjobs = nullptr, *d_cjobs = nullptr;
+    void *d_rjobs = nullptr, *d_jobs = nullptr, *d_hjobs = nullptr, *d_cjobs = nullptr, *d_r1jobs = nullptr, *d_c1jobs = nullptr;
     int r = 0;
     if (!rjobs.empty ())
       r = push_args (ctx, rjobs.data (), sizeof (IwtJob) * rjobs.size (), &d_rjobs);
+    if (!r && !r1jobs.empty ())
+      r = push_args (ctx, r1jobs.data (), sizeof (IwtJob) * r1jobs.size (), &d_r1jobs);
+    if (!r && !c1jobs.empty ())
+      r = push_args (ctx, c1jobs.data (), sizeof (IwtJob) * c1jobs.size (), &d_c1jobs);
     if (!r && !cjobs.empty ())
       r = push_args (ctx, cjobs.data (), sizeof (IwtJob) * cjobs.size (), &d_cjobs);
     if (!r && !hjobs.empty ())
@@ -626,6 +677,10 @@ schro_hip_iiwt_batch (SchroHipContext * ctx, const SchroHipIwtPlane * planes, in
       r = launch_iiwt_reg (ctx->stream, (const IwtJob *) d_rjobs, (int) rjobs.size (), rtile_base, filter, small, 0);
     if (!r && d_cjobs)
       r = launch_iiwt_reg (ctx->stream, (const IwtJob *) d_cjobs, (int) cjobs.size (), ctile_base, filter, small, 1);
+    if (!r && d_r1jobs)
+      r = launch_iiwt_reg (ctx->stream, (const IwtJob *) d_r1jobs, (int) r1jobs.size (), r1tile_base, filter, 0, 0, 1);
+    if (!r && d_c1jobs)
+      r = launch_iiwt_reg (ctx->stream, (const IwtJob *) d_c1jobs, (int) c1jobs.size (), c1tile_base, filter, 0, 1, 1);
     if (!r && d_hjobs)
       r = launch_iiwt_haar (ctx->stream, (const IwtJob *) d_hjobs, (int) hjobs.size (), htile_base, filter);
     if (!r && d_jobs)

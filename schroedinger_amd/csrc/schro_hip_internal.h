@@ -106,6 +106,11 @@ struct IwtJob {
   int pred_stride;
   int out_w, out_h;
   int pad2;
+  // level 1 inside level 0 (iiwt_reg.hip, MODE bit 8): this job is level 0 and synthesises its LL band itself from
+  // level 1's sub-bands -- LL (level 2's output, or the coefficient frame / the caller's LL plane), HL, LH, HH of the
+  // coefficient frame's level-1 view; sb[0] is unused
+  const void *l1_sb[4];
+  int l1_sb_stride[4];
 };
 
 // r05: the three-level s32 Haar transform of a 4:2:2 picture with the v210 copy-out as its epilogue (iiwt_haar.hip)
@@ -440,7 +445,10 @@ bool iiwt_reg_supported (int filter, int bpp);
 void iiwt_reg_geometry (int filter, int small, int *useful_cols, int *useful_row_pairs,
     int *min_row_pairs);
 int launch_iiwt_reg (hipStream_t stream, const IwtJob * d_jobs, int njobs, int total_tiles,
-    int filter, int small, int combine);
+    int filter, int small, int combine, int l1_inline = 0);
+// ... level 1 synthesised inside the level-0 tile (large tiles only): the filters built, the tile geometry
+bool iiwt_reg_l1_supported (int filter);
+void iiwt_reg_l1_geometry (int filter, int *useful_cols, int *useful_row_pairs, int *min_row_pairs);
 int launch_iiwt_chain (hipStream_t stream, const IwtJob * d_jobs, const uint32_t * d_order, int n_tiles, uint32_t * ctrl,
     uint32_t run, uint32_t * gave_up, uint32_t epoch, int filter);
 void iiwt_tile_geometry (int filter, int bpp, int *useful_cols,
