@@ -197,6 +197,20 @@ int schro_hip_profile_reset (SchroHipContext * ctx);
 int schro_hip_profile_read (SchroHipContext * ctx, int kernel_class,
     double *total_ms, int *launches);
 
+/* Which OBMC formulation a plane ran on.  schro_hip_obmc_routes copies, per
+ * route, the number of planes this context's schro_hip_obmc_batch calls (and
+ * so schro_motion_render_hip) have handed to launches of that route since the
+ * context was created or last reset (reset != 0 clears them after the copy).
+ * A (U, V) job counts two planes; a call that fails validation counts
+ * nothing.  Counted on the host as the launches are enqueued: no
+ * synchronisation, and profiling need not be on.  Returns 0 or an error. */
+#define SCHRO_HIP_OBMC_ROUTE_ROW 0      /* obmc_row*.hip */
+#define SCHRO_HIP_OBMC_ROUTE_ITEM 1     /* obmc.hip, item kernel */
+#define SCHRO_HIP_OBMC_ROUTE_GENERAL 2  /* obmc.hip, per-pixel kernel */
+#define SCHRO_HIP_OBMC_ROUTE_STRIP 3    /* obmc_strip.hip (experiments library only) */
+#define SCHRO_HIP_OBMC_ROUTES 4
+int schro_hip_obmc_routes (SchroHipContext * ctx, long long counts[SCHRO_HIP_OBMC_ROUTES], int reset);
+
 /* ---- plane layer: batched launches --------------------------------------- */
 
 /* One component of one picture for the inverse wavelet.

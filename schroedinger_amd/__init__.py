@@ -289,6 +289,16 @@ class Context:
             out[name] = (ms.value, n.value)
         return out
 
+    OBMC_ROUTES = ("row", "item", "general", "strip")       # SCHRO_HIP_OBMC_ROUTE_* (include/schro_hip.h)
+
+    def obmc_routes(self, reset=False):
+        """{route: planes} this context's OBMC calls have handed to the launches of each route (schro_hip_obmc_routes):
+        "row" obmc_row*.hip, "item" / "general" obmc.hip's item / per-pixel kernel, "strip" obmc_strip.hip; reset: start
+        the counts again from zero after reading them."""
+        counts = (C.c_longlong * len(self.OBMC_ROUTES))()
+        check(self.lib.schro_hip_obmc_routes(self.h, counts, 1 if reset else 0))
+        return dict(zip(self.OBMC_ROUTES, (int(n) for n in counts)))
+
     def plane(self, height, width, dtype, stride=None):
         return DevicePlane(self, height, width, dtype, stride)
 

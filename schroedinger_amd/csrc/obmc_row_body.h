@@ -957,6 +957,109 @@ row_finish_uv (const PlaneIO & iou, const PlaneIO & iov, const uint32_t * acc, i
   }
 }
 
+// r07, s16 planes (prediction_only 2: schro_motion_render_hip's mc_tmp_frame) on the residual-form kernels: no residual,
+// `out` receives (int16) ((int16) ((int16) acc - 8160) >> 6) = the prediction - 128 (orc_rrshift6_s16_ip_2d, as obmc.hip):
+// no clamp, the reference's 16-bit wrap kept.  The fast finish stores 8 samples (16 bytes) per lane and row
+template < typename G >
+__device__ __forceinline__ bool
+row_finish_s16_is_fast (const PlaneIO & io, int x_lo, int x_hi)
+{
+  return x_hi - x_lo == G::kTW && ((((uintptr_t) io.out) | (uintptr_t) io.out_stride) & 15) == 0;
+}
+
+// ... and a pixel per lane and step (any alignment, any tile width); UV: component cb of the pixels' words
+template < int TH, typename G, bool UV >
+__device__ __forceinline__ void
+row_finish_s16_plain (const PlaneIO & io, int cb, const uint32_t * acc, int par, int tid, int x_lo, int y_lo, int x_hi, int y_hi)
+{
+  for (int it = tid; it < TH * G::kTW; it += kRThreads) {
+    const int xx = it & (G::kTW - 1), yy = it / G::kTW;
+    const int x = x_lo + xx, y = y_lo + yy;
+    if (y >= y_hi || x >= x_hi)
+      continue;
+    int half;
+    const uint32_t *aw = acc_word < G, UV > (const_cast < uint32_t * >(acc), par, xx, yy, &half);
+    if constexpr (UV)
+      half = cb;
+    const int16_t a = (int16_t) (*aw >> (16 * half));
+    gstore < int16_t > ((int16_t *) (io.out + (size_t) y * io.out_stride) + x, (int16_t) ((int16_t) ((int16_t) a - 8160) >> 6));
+  }
+}
+
+template < int TH, typename G >
+__device__ __forceinline__ void
+row_finish_s16 (const PlaneIO & io, const uint32_t * acc, int par, int tid, int x_lo, int y_lo, int x_hi, int y_hi, bool fast)
+{
+  constexpr int kG = G::kTW / 8;
+  if (fast) {
+#pragma unroll
+    for (int n = 0; n < kRFinishRounds < TH, G >; n++) {
+      const int it = tid + n * kRThreads;
+      const int g = it & (kG - 1), yy = it / kG;
+      const int y = y_lo + yy;
+      if (y >= y_hi || it >= TH * kG)
+        continue;
+      const uint32_t *ap = acc + yy * G::kAccW + (G::kMargin / 2 + 4 * g);
+      uint32_t av[4];
+      if (par) {                // (as row_finish)
+        const uint32_t w0 = ap[0], w1 = ap[1], w2 = ap[2], w3 = ap[3], w4 = ap[4];
+        av[0] = __builtin_amdgcn_alignbit (w1, w0, 16);
+        av[1] = __builtin_amdgcn_alignbit (w2, w1, 16);
+        av[2] = __builtin_amdgcn_alignbit (w3, w2, 16);
+        av[3] = __builtin_amdgcn_alignbit (w4, w3, 16);
+      } else {
+        av[0] = ap[0];
+        av[1] = ap[1];
+        av[2] = ap[2];
+        av[3] = ap[3];
+      }
+      uint32_t t[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++)
+        t[k] = __builtin_bit_cast (uint32_t, (s16x2) ((__builtin_bit_cast (s16x2, av[k]) - (short) 8160) >> 6));
+      const int x = x_lo + 8 * g;
+      __builtin_nontemporal_store ((u32x4) { t[0], t[1], t[2], t[3] },
+          (SCHRO_GLOBAL u32x4 *) (io.out + (size_t) y * io.out_stride + 2 * x));
+    }
+    return;
+  }
+  row_finish_s16_plain < TH, G, false > (io, 0, acc, par, tid, x_lo, y_lo, x_hi, y_hi);
+}
+
+// UV: 8 pixels of one row of BOTH planes per lane (U sum low, V sum high), 16 bytes into each plane
+template < int TH, typename G >
+__device__ __forceinline__ void
+row_finish_s16_uv (const PlaneIO & iou, const PlaneIO & iov, const uint32_t * acc, int tid, int x_lo, int y_lo, int y_hi)
+{
+  constexpr int kG = G::kTW / 8;
+#pragma unroll
+  for (int n = 0; n < kRFinishRounds < TH, G >; n++) {
+    const int it = tid + n * kRThreads;
+    const int g = it & (kG - 1), yy = it / kG;
+    const int y = y_lo + yy;
+    if (y >= y_hi || it >= TH * kG)
+      continue;
+    const uint32_t *ap = acc + yy * G::kAccW + (G::kMargin + 8 * g);
+    uint32_t t[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++)
+      t[k] = __builtin_bit_cast (uint32_t, (s16x2) ((__builtin_bit_cast (s16x2, ap[k]) - (short) 8160) >> 6));
+    // t[k] = (U_k, V_k) -> U_k U_k+1 | V_k V_k+1
+    u32x4 ou, ov;
+    ou.x = __builtin_amdgcn_perm (t[1], t[0], 0x05040100u);
+    ou.y = __builtin_amdgcn_perm (t[3], t[2], 0x05040100u);
+    ou.z = __builtin_amdgcn_perm (t[5], t[4], 0x05040100u);
+    ou.w = __builtin_amdgcn_perm (t[7], t[6], 0x05040100u);
+    ov.x = __builtin_amdgcn_perm (t[1], t[0], 0x07060302u);
+    ov.y = __builtin_amdgcn_perm (t[3], t[2], 0x07060302u);
+    ov.z = __builtin_amdgcn_perm (t[5], t[4], 0x07060302u);
+    ov.w = __builtin_amdgcn_perm (t[7], t[6], 0x07060302u);
+    const int x = x_lo + 8 * g;
+    __builtin_nontemporal_store (ou, (SCHRO_GLOBAL u32x4 *) (iou.out + (size_t) y * iou.out_stride + 2 * x));
+    __builtin_nontemporal_store (ov, (SCHRO_GLOBAL u32x4 *) (iov.out + (size_t) y * iov.out_stride + 2 * x));
+  }
+}
+
 // NORES (r05): every job of the launch is a prediction_only job (no residual to add: the combine form's launches,
 // bench.py's headline).  The eight registers that carry the prefetched residual through the passes are not held at all.
 // RK, NS (r06): the reference kind and the segments of a block row, see the head of the file.
@@ -1373,7 +1476,10 @@ obmc_row_body (const ObmcJob * __restrict__ jobs, int njobs, const uint32_t * __
     // (8 per lane, held through the passes): it streams from HBM, and fetched after the passes
     // its latency was the tile's to wait for.
     constexpr bool kEarlyRes = ND >= 3 && NP == 1 && !NORES;
-    const bool fast = row_finish_is_fast < G > (job, io, x_lo, x_hi) && (!UV || row_finish_is_fast < G > (job, iov, x_lo, x_hi));
+    // r07: an s16 plane (residual NULL: the prefetch below only clears `res`) takes the s16 finish and its own alignment test
+    const bool s16 = !NORES && job.out_s16;
+    const bool fast = s16 ? row_finish_s16_is_fast < G > (io, x_lo, x_hi) && (!UV || row_finish_s16_is_fast < G > (iov, x_lo, x_hi))
+        : row_finish_is_fast < G > (job, io, x_lo, x_hi) && (!UV || row_finish_is_fast < G > (job, iov, x_lo, x_hi));
     constexpr int kRounds = kRFinishRounds < TH, G >;
     u32x4 res[UV ? 2 * kRounds : kRounds];
 #define SCHRO_ROW_PREFETCH() do { \
@@ -1461,7 +1567,18 @@ obmc_row_body (const ObmcJob * __restrict__ jobs, int njobs, const uint32_t * __
     RSTAMP (6);
 #pragma unroll
     for (int rep_ = 0; rep_ < kRepFinish; rep_++)
-    if constexpr (UV) {
+    if (s16) {
+      if constexpr (UV) {
+        if (fast) {
+          row_finish_s16_uv < TH, G > (io, iov, acc, tid, x_lo, y_lo, y_hi);
+        } else {
+          row_finish_s16_plain < TH, G, true > (io, 0, acc, par, tid, x_lo, y_lo, x_hi, y_hi);
+          row_finish_s16_plain < TH, G, true > (iov, 1, acc, par, tid, x_lo, y_lo, x_hi, y_hi);
+        }
+      } else {
+        row_finish_s16 < TH, G > (io, acc, par, tid, x_lo, y_lo, x_hi, y_hi, fast);
+      }
+    } else if constexpr (UV) {
       if (fast) {
         if (NORES && !exact)
           row_finish_uv < TH, G, NORES > (io, iov, acc, tid, x_lo, y_lo, y_hi, res);

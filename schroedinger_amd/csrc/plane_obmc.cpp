@@ -410,7 +410,9 @@ schro_hip_obmc_batch (SchroHipContext * ctx, const SchroHipObmcPlane * planes, i
     j.out_s16 = pl.prediction_only == 2;
     const bool pred_only = pl.prediction_only == 1;
     // (obmc_row_form looks at the weights itself: 1, 1 / 2 and, r06, every non-negative pair that adds up to 1 << bits)
-    const RowForm form = (use_row && !j.out_s16) ? obmc_row_form (j, false, pred_only) : RowForm {};
+    // r07: an s16 plane takes the residual form of its geometry wherever a u8 plane would (obmc_row_body.h: row_finish_s16;
+    // its residual is NULL and its launches claim no overflow word)
+    const RowForm form = use_row ? obmc_row_form (j, false, pred_only) : RowForm {};
     key[p] = LaunchKey { pl.mv_precision, form ? 3 : variant_of (pl), form, pred_only, (bool) j.out_s16 };
   }
   // row kernel: the U and V planes of a picture (same vectors, blocks and sample windows) become
@@ -440,13 +442,13 @@ schro_hip_obmc_batch (SchroHipContext * ctx, const SchroHipObmcPlane * planes, i
     const bool uv_plain = a.prec == 0 && b.prec == 0 && !a.ref_ps && !b.ref_ps;
     if (((a.ref_ps && b.ref_ps && a.ref[0] == b.ref[0] && a.ref[1] == b.ref[1]) || uv_plain)
         && use_row && same_blocks (a, b)
-        && planes[p].prediction_only == planes[p + 1].prediction_only && !a.out_s16 && !b.out_s16) {
+        && planes[p].prediction_only == planes[p + 1].prediction_only) {     // (r07: s16 with s16 too)
       ObmcJob au = a;
       au.ref_b[0] = b.ref[0];
       au.ref_b[1] = b.ref[1];
       const RowForm uv = obmc_row_form (au, true, key[p].pred_only);
       if (uv) {
-        key[p] = key[p + 1] = LaunchKey { a.prec, 4, uv, key[p].pred_only, false };
+        key[p] = key[p + 1] = LaunchKey { a.prec, 4, uv, key[p].pred_only, (bool) a.out_s16 };
         p++;
         continue;
       }
@@ -491,10 +493,12 @@ schro_hip_obmc_batch (SchroHipContext * ctx, const SchroHipObmcPlane * planes, i
     }
     std::vector < ObmcJob > jobs;
     int tile_base = 0;
+    long long group_planes = 0;         // (schro_hip_obmc_routes)
     for (int p = first; p < nplanes; p++) {
       if (done[p] || !(key[p] == group))
         continue;
       done[p] = 1;
+      group_planes++;
       ObmcJob j = all[p];
       int tiles_y;
       obmc_tiles (group.variant, j.w, j.h, j.xoff, &j.tiles_x, &tiles_y);
@@ -544,6 +548,7 @@ schro_hip_obmc_batch (SchroHipContext * ctx, const SchroHipObmcPlane * planes, i
       rs = launch_obmc_strip (ctx->stream, (const ObmcJob *) d_sjobs, (int) jobs.size (), wave_base, seg_rows, group.pred_only, overflow, ctx->cus);
       if (rs)
         return rs;
+      ctx->obmc_routes[SCHRO_HIP_OBMC_ROUTE_STRIP] += group_planes;
       continue;
     }
 #endif
@@ -611,6 +616,7 @@ schro_hip_obmc_batch (SchroHipContext * ctx, const SchroHipObmcPlane * planes, i
     }
     if (r)
       return r;
+    ctx->obmc_routes[row ? SCHRO_HIP_OBMC_ROUTE_ROW : group.variant == 1 ? SCHRO_HIP_OBMC_ROUTE_ITEM : SCHRO_HIP_OBMC_ROUTE_GENERAL] += group_planes;
   }
   return 0;
 }
@@ -626,6 +632,20 @@ unsigned int
 schro_hip_obmc_prediction_epoch (SchroHipContext * ctx)
 {
   return ctx ? ctx->pred_epoch : 0u;
+}
+
+// r07: the planes this context's schro_hip_obmc_batch calls have handed to the launches of each route (counted on the host
+// as the launches are enqueued: no synchronisation, profiling on or off)
+int
+schro_hip_obmc_routes (SchroHipContext * ctx, long long counts[SCHRO_HIP_OBMC_ROUTES], int reset)
+{
+  SCHRO_HIP_REQUIRE (ctx && counts, "obmc_routes: bad arguments");
+  for (int k = 0; k < SCHRO_HIP_OBMC_ROUTES; k++) {
+    counts[k] = ctx->obmc_routes[k];
+    if (reset)
+      ctx->obmc_routes[k] = 0;
+  }
+  return 0;
 }
 
 }                               // extern "C"

@@ -194,7 +194,7 @@ struct ObmcJob {
   uint32_t m_xramp, m_yramp;    // ceil (2^32 / (2 * offset - 1)): get_ramp's division (schromotion.c:40-49)
   int out_s16;                  // r06: `out` is an s16 plane that receives (acc - 8160) >> 6 = the prediction - 128
                                 // (orc_rrshift6_s16_ip_2d: schro_motion_render's add = FALSE, schro_motion_render_cuda's dest);
-                                // no residual.  obmc.hip's kernels only
+                                // no residual.  r07: the row kernels' residual forms too (obmc_row_body.h: row_finish_s16)
   unsigned long long *stamps;   // scratch runs only (SCHRO_HIP_OBMC_STAMPS): per-workgroup phase stamps
   // row kernel: the second plane of a job.  The U and V planes of a picture have the same
   // blocks, vectors and sample windows, so one workgroup decodes a tile's blocks once and
@@ -669,6 +669,8 @@ struct SchroHipContext {
   // r06: batches found raised, oldest first -- not yet named by a synchronising call's status / not yet fetched by
   // schro_hip_obmc_overflowed (nothing is dropped: a word is cleared only into these lists)
   std::vector < uint32_t > ovf_unannounced, ovf_unfetched;
+  // r07: planes handed to the OBMC launches of each route (schro_hip_obmc_routes)
+  long long obmc_routes[SCHRO_HIP_OBMC_ROUTES] = {};
   int cus;                      // compute units of the device (launch shaping)
 };
 
