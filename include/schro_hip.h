@@ -211,6 +211,18 @@ int schro_hip_profile_read (SchroHipContext * ctx, int kernel_class,
 #define SCHRO_HIP_OBMC_ROUTES 4
 int schro_hip_obmc_routes (SchroHipContext * ctx, long long counts[SCHRO_HIP_OBMC_ROUTES], int reset);
 
+/* Which route a picture of schro_hip_iiwt_pack_v210_batch (and so of
+ * schro_frame_inverse_iwt_transform_convert_hip) took.  schro_hip_v210_routes
+ * copies, per route, the number of pictures this context's calls have handed
+ * to it since the context was created or last reset (reset != 0 clears them
+ * after the copy).  A call that fails validation counts nothing.  Counted on
+ * the host as the launches are enqueued.  Returns 0 or an error. */
+#define SCHRO_HIP_V210_ROUTE_HAAR3 0    /* iiwt_haar.hip: three s32 Haar levels + v210 in one kernel */
+#define SCHRO_HIP_V210_ROUTE_LEVEL 1    /* iiwt.hip: the finest level writes v210, coarser levels by the level loop */
+#define SCHRO_HIP_V210_ROUTE_TWO_PASS 2 /* the pixel frame in a scratch block, then the v210 pack */
+#define SCHRO_HIP_V210_ROUTES 3
+int schro_hip_v210_routes (SchroHipContext * ctx, long long counts[SCHRO_HIP_V210_ROUTES], int reset);
+
 /* ---- plane layer: batched launches --------------------------------------- */
 
 /* One component of one picture for the inverse wavelet.
@@ -334,7 +346,13 @@ int schro_hip_pack_v210_batch (SchroHipContext * ctx,
  * schrovirtframe.c:1438-1537, :943-991).  dst receives exactly the bytes of schro_hip_iiwt_batch into a pixel frame followed by
  * schro_hip_pack_v210_batch from it.  Where the transform is the three-level s32 Haar (filters 3, 4) of a 4:2:2 picture whose
  * size is a multiple of 192 x 8 (v210 groups of 6 pixels x whole strips of the kernel; BASELINE config 5: 7680 x 4320) the copy-out is the transform kernel's epilogue and the pixel
- * frame never exists (per 8K picture 353 MB of memory traffic instead of 883 MB); every other case runs the two passes. */
+ * frame never exists (per 8K picture 353 MB of memory traffic instead of 883 MB).  Every other picture -- any filter, depth,
+ * s16 / s32, a picture smaller than its transform -- runs levels depth-1 .. 1 into a quarter-size LL plane and then one
+ * launch whose finest level writes the v210 bytes (no pixel frame, no pack launch; per 8K s32 DD(9,7) picture about 520 MB
+ * instead of 880 MB).  Only a dst or dst_stride that is not a multiple of 16 bytes, coefficient planes not aligned to
+ * their sample size, or a dst that overlaps a coefficient plane still take the two passes.  schro_hip_v210_routes reports
+ * which.  Every component must be a multiple of 2^depth in both directions (chroma: width / 2) and each src_stride must
+ * hold its component's row, as schro_hip_iiwt_batch asks; a picture that is not is refused. */
 typedef struct {
   const void *src[3];           /* the coefficient planes Y, U, V (device, s16 or s32), in-place sub-band layout */
   int src_stride[3];

@@ -299,6 +299,16 @@ class Context:
         check(self.lib.schro_hip_obmc_routes(self.h, counts, 1 if reset else 0))
         return dict(zip(self.OBMC_ROUTES, (int(n) for n in counts)))
 
+    V210_ROUTES = ("haar3", "level", "two_pass")             # SCHRO_HIP_V210_ROUTE_* (include/schro_hip.h)
+
+    def v210_routes(self, reset=False):
+        """{route: pictures} this context's iiwt_pack_v210 calls have handed to each route (schro_hip_v210_routes): "haar3"
+        the three-level s32 Haar kernel with the copy-out, "level" the finest level writing v210 (iiwt_v210_kernel), "two_pass"
+        the pixel frame in a scratch block and the pack; reset: start the counts again from zero after reading them."""
+        counts = (C.c_longlong * len(self.V210_ROUTES))()
+        check(self.lib.schro_hip_v210_routes(self.h, counts, 1 if reset else 0))
+        return dict(zip(self.V210_ROUTES, (int(n) for n in counts)))
+
     def plane(self, height, width, dtype, stride=None):
         return DevicePlane(self, height, width, dtype, stride)
 

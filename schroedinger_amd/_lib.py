@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "schro_hip_queue_mark", "schro_hip_queue_wait_mark",
     "schro_hip_timer_begin", "schro_hip_timer_end",
     "schro_hip_profile_enable", "schro_hip_profile_reset", "schro_hip_profile_read", "schro_hip_obmc_routes",
+    "schro_hip_v210_routes",
     "schro_hip_iiwt_batch", "schro_hip_convert_u8_batch", "schro_hip_upsample_batch",
     "schro_hip_upsampled_bytes", "schro_hip_upsampled_download", "schro_hip_upsampled_pair_bytes",
     "schro_hip_upsampled_pair_download", "schro_hip_pack_u8_batch",
@@ -338,6 +339,8 @@ def load():
     L.schro_hip_profile_read.restype = i
     L.schro_hip_obmc_routes.argtypes = [vp, C.POINTER(C.c_longlong), i]
     L.schro_hip_obmc_routes.restype = i
+    L.schro_hip_v210_routes.argtypes = [vp, C.POINTER(C.c_longlong), i]
+    L.schro_hip_v210_routes.restype = i
     L.schro_hip_iiwt_batch.argtypes = [vp, C.POINTER(IwtPlane), i, i, i, i]
     L.schro_hip_iiwt_batch.restype = i
     L.schro_hip_convert_u8_batch.argtypes = [vp, C.POINTER(ConvertPlane), i, i]

@@ -663,6 +663,217 @@ void iiwt_fused_kernel (const IwtFusedJob * __restrict__ jobs, int njobs)
   lift_region < T, F, G0::RP, G0::RC, HC0 / 4, (G0::RC - HC0) / 4 - 1 > (lds0, tid, r00, c00, nr0, nc0, sink);
 }
 
+// ---- the finest level with the v210 copy-out as its sink -------------------------
+// One workgroup owns 2 * UR picture rows x PX picture columns of ALL THREE components of a 4:2:2 picture: the Y region
+// (PX / 2 sub-band columns) and the U and V regions (PX / 4 each) are staged and lifted one after the other in the same
+// LDS tile, and the last lifting step of each hands its interleaved samples to V210Sink -- the sample pack_v210_s16
+// sees (s32 truncated to 16 bits as convert_s16_s32 does, then clamp (x + 512, 0, 1023), schrovirtframe.c:943-991,
+// :1438-1537) as u16 in a staging area.  After one barrier the lanes pack whole v210 groups (6 pixels, 16 bytes) from
+// it.  PX is a multiple of 48: whole v210 groups, whole chroma pairs, whole 128-byte lines of output per tile row.
+// LDS (s32 DD(9,7)): 28 KB tile + 21 KB staging, three workgroups per CU.
+template < typename T, int F > struct VGeo {
+  static constexpr int PX = 96;                         // picture columns per workgroup
+  static constexpr int RP = 32;
+  static constexpr int H = filter_halo (F);
+  static constexpr int HC = (H + 3) & ~3;
+  static constexpr int UR = RP - 2 * H;
+  static constexpr int ROWS = 2 * UR;                   // picture rows per workgroup
+  static constexpr int UCY = PX / 2, UCC = PX / 4;      // useful sub-band columns, Y / U, V
+  static constexpr int RCY = UCY + 2 * HC, RCC = UCC + 2 * HC;
+  static_assert (PX % 48 == 0 && UCC % 4 == 0, "whole v210 groups and sample quads");
+};
+
+template < typename T > struct V210Sink {
+  uint16_t *row0;               // staging row of tile row 0
+  int pitch;                    // u16 per staging row
+  int hc;                       // region column of staging column 0
+
+  __device__ __forceinline__ void store (int yy, int i, const T * out) const
+  {
+    uint32_t q[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const int a = clampi ((int) (int16_t) out[2 * k] + 512, 0, 1023), b = clampi ((int) (int16_t) out[2 * k + 1] + 512, 0, 1023);
+      q[k] = (uint32_t) a | ((uint32_t) b << 16);
+    }
+    // (i and hc are multiples of 4: 16-byte aligned)
+    *reinterpret_cast < u32x4 * >(row0 + yy * pitch + 2 * (i - hc)) = (u32x4) { q[0], q[1], q[2], q[3] };
+  }
+};
+
+// component C's four bands: LL from job.ll[C], HL / LH / HH from the coefficient plane
+template < typename T, int C >
+__device__ __forceinline__ void
+v210_bands (const V210Job & job, const void **sb, int *ss, int *nc)
+{
+  const int w = C ? job.w >> 1 : job.w;
+  *nc = w >> 1;
+  const char *plane = (const char *) job.src[C];
+  const int S = job.src_stride[C];
+  sb[0] = job.ll[C];
+  sb[1] = plane + (size_t) *nc * sizeof (T);
+  sb[2] = plane + S;
+  sb[3] = plane + S + (size_t) *nc * sizeof (T);
+  ss[0] = job.ll_stride[C];
+  ss[1] = ss[2] = ss[3] = 2 * S;
+}
+
+// issue the 8-byte loads of component C's region (where its bands allow them): the kernel issues a component's loads
+// before the previous component is lifted
+template < typename T, int F, int C, int RC, int UC, int NPS >
+__device__ __forceinline__ void
+v210_load (uint2 (&v)[4][NPS], const V210Job & job, int tid, int r0, int tx)
+{
+  typedef VGeo < T, F > G;
+  if (!(job.flags & (1 << C)))
+    return;
+  const void *sb[4];
+  int ss[4], nc;
+  v210_bands < T, C > (job, sb, ss, &nc);
+#pragma unroll
+  for (int b = 0; b < 4; b++)
+    band_load < T, G::RP, RC, NPS > (v[b], sb[b], ss[b], tid, r0, tx * UC - G::HC, job.h >> 1, nc);
+}
+
+// stage component C's region in LDS (from the loads above, or sample by sample) and lift it into the staging area
+template < typename T, int F, int C, int RC, int UC, int NPS >
+__device__ __forceinline__ void
+v210_lift (T (*lds)[2 * RC], const uint2 (&v)[4][NPS], const V210Job & job, int tid, int r0, int tx, uint16_t * stage, int pitch)
+{
+  typedef VGeo < T, F > G;
+  constexpr int RP = G::RP, HC = G::HC;
+  const int nr = job.h >> 1, c0 = tx * UC - HC;
+  const void *sb[4];
+  int ss[4], nc;
+  v210_bands < T, C > (job, sb, ss, &nc);
+  if (job.flags & (1 << C)) {
+#pragma unroll
+    for (int b = 0; b < 4; b++)
+      band_store < T, RP, RC, NPS > (lds, v[b], b, tid);
+  } else {
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+      const char *base = (const char *) sb[b];
+      for (int it = tid; it < RP * RC; it += kThreads) {
+        const int c = it % RC, rp = it / RC;
+        const int r = r0 + rp, cc = c0 + c;
+        if (r >= 0 && r < nr && cc >= 0 && cc < nc)
+          lds[2 * rp + (b >> 1)][(b & 1) * RC + c] = gload < T > ((const T *) (base + (size_t) r * ss[b]) + cc);
+      }
+    }
+  }
+  __syncthreads ();
+  V210Sink < T > sink;
+  sink.row0 = stage;
+  sink.pitch = pitch;
+  sink.hc = HC;
+  lift_region < T, F, RP, RC, HC / 4, (RC - HC) / 4 - 1 > (lds, tid, r0, c0, nr, nc, sink);
+}
+
+template < typename T, int F >
+__global__ __launch_bounds__ (kThreads)
+void iiwt_v210_kernel (const V210Job * __restrict__ jobs, int njobs)
+{
+  typedef VGeo < T, F > G;
+  constexpr int RP = G::RP, H = G::H, UR = G::UR, ROWS = G::ROWS, PX = G::PX;
+  __shared__ __attribute__ ((aligned (16))) T lds[2 * RP][2 * G::RCY];
+  __shared__ __attribute__ ((aligned (16))) uint16_t s_y[ROWS][PX];
+  __shared__ __attribute__ ((aligned (16))) uint16_t s_c[2][ROWS][PX / 2];
+
+  const int tid = threadIdx.x;
+  const int bid = xcd_tile_id (blockIdx.x, gridDim.x);
+  const V210Job job = jobs[find_job (jobs, njobs, bid)];
+  const int t = bid - job.tile_base;
+  const int ty = t / job.tiles_x, tx = t - ty * job.tiles_x;
+  const int r0 = ty * UR - H;   // sub-band row of region row pair 0 (all three components: 4:2:2)
+  T (*ldsc)[2 * G::RCC] = reinterpret_cast < T (*)[2 * G::RCC] > (&lds[0][0]);
+
+  constexpr int NPSY = band_nps < T, RP, G::RCY > (), NPSC = band_nps < T, RP, G::RCC > ();
+  uint2 vy[4][NPSY], vu[4][NPSC], vv[4][NPSC];
+  v210_load < T, F, 0, G::RCY, G::UCY, NPSY > (vy, job, tid, r0, tx);
+  v210_load < T, F, 1, G::RCC, G::UCC, NPSC > (vu, job, tid, r0, tx);
+  v210_lift < T, F, 0, G::RCY, G::UCY, NPSY > (lds, vy, job, tid, r0, tx, &s_y[0][0], PX);
+  __syncthreads ();
+  v210_load < T, F, 2, G::RCC, G::UCC, NPSC > (vv, job, tid, r0, tx);
+  v210_lift < T, F, 1, G::RCC, G::UCC, NPSC > (ldsc, vu, job, tid, r0, tx, &s_c[0][0][0], PX / 2);
+  __syncthreads ();
+  v210_lift < T, F, 2, G::RCC, G::UCC, NPSC > (ldsc, vv, job, tid, r0, tx, &s_c[1][0][0], PX / 2);
+  __syncthreads ();
+
+  // ---- pack: a task = one v210 group (6 pixels, 16 bytes) of one row ----
+  constexpr int GPR = PX / 6;
+  const int y0 = ty * ROWS, x0 = tx * PX;
+  const int rows = min (ROWS, job.out_h - y0);
+  const int ng = min (GPR, (job.out_w - x0 + 5) / 6);   // groups that hold a pixel of the picture
+  for (int task = tid; task < rows * GPR; task += kThreads) {
+    const int y = task / GPR, g = task - y * GPR;
+    if (g >= ng)
+      continue;
+    const int lim = job.out_w - (x0 + 6 * g);           // pixels of the picture in this group (pack_v210_s16 zero-pads the rest)
+    const uint32_t *yp = reinterpret_cast < const uint32_t * >(&s_y[y][6 * g]);
+    const uint32_t ya = yp[0], yb = yp[1], yc = yp[2];
+    uint32_t yv[6] = { ya & 0xffffu, ya >> 16, yb & 0xffffu, yb >> 16, yc & 0xffffu, yc >> 16 };
+    uint32_t cb[3], cr[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      cb[k] = 2 * k < lim ? (uint32_t) s_c[0][y][3 * g + k] : 0u;
+      cr[k] = 2 * k < lim ? (uint32_t) s_c[1][y][3 * g + k] : 0u;
+    }
+#pragma unroll
+    for (int k = 0; k < 6; k++)
+      yv[k] = k < lim ? yv[k] : 0u;
+    u32x4 o;
+    o.x = (cr[0] << 20) | (yv[0] << 10) | cb[0];        // schrovirtframe.c:956-977 (pack_v210_s16)
+    o.y = (yv[2] << 20) | (cb[1] << 10) | yv[1];
+    o.z = (cb[2] << 20) | (yv[3] << 10) | cr[1];
+    o.w = (yv[5] << 20) | (cr[2] << 10) | yv[4];
+    char *d = (char *) job.dst + (size_t) (y0 + y) * job.dst_stride + (size_t) (x0 / 6 + g) * 16;
+    __builtin_nontemporal_store (o, (SCHRO_GLOBAL u32x4 *) d);
+  }
+}
+
+template < typename T, int F >
+int
+launch_v210_one (hipStream_t stream, const V210Job * d_jobs, int njobs, int total_tiles)
+{
+  SCHRO_LAUNCH ((iiwt_v210_kernel < T, F >), dim3 (total_tiles), dim3 (kThreads), 0, stream, d_jobs, njobs);
+  hipError_t e = hipGetLastError ();
+  if (e != hipSuccess)
+    return set_error (SCHRO_HIP_EDEVICE, "iiwt + v210 launch: %s", hipGetErrorString (e));
+  return 0;
+}
+
+template < typename T >
+int
+launch_v210_filter (hipStream_t stream, const V210Job * d_jobs, int njobs, int total_tiles, int filter)
+{
+  switch (filter) {
+    case 0: return launch_v210_one < T, 0 > (stream, d_jobs, njobs, total_tiles);
+    case 1: return launch_v210_one < T, 1 > (stream, d_jobs, njobs, total_tiles);
+    case 2: return launch_v210_one < T, 2 > (stream, d_jobs, njobs, total_tiles);
+    case 3: return launch_v210_one < T, 3 > (stream, d_jobs, njobs, total_tiles);
+    case 4: return launch_v210_one < T, 4 > (stream, d_jobs, njobs, total_tiles);
+    case 5: return launch_v210_one < T, 5 > (stream, d_jobs, njobs, total_tiles);
+    case 6: return launch_v210_one < T, 6 > (stream, d_jobs, njobs, total_tiles);
+  }
+  return set_error (SCHRO_HIP_EINVAL, "wavelet filter index %d out of range", filter);
+}
+
+template < typename T >
+void
+v210_geometry (int filter, int *cols, int *rows)
+{
+  switch (filter) {
+    case 0: *cols = VGeo < T, 0 >::PX; *rows = VGeo < T, 0 >::ROWS; break;
+    case 1: *cols = VGeo < T, 1 >::PX; *rows = VGeo < T, 1 >::ROWS; break;
+    case 2: *cols = VGeo < T, 2 >::PX; *rows = VGeo < T, 2 >::ROWS; break;
+    case 3: *cols = VGeo < T, 3 >::PX; *rows = VGeo < T, 3 >::ROWS; break;
+    case 4: *cols = VGeo < T, 4 >::PX; *rows = VGeo < T, 4 >::ROWS; break;
+    case 5: *cols = VGeo < T, 5 >::PX; *rows = VGeo < T, 5 >::ROWS; break;
+    default: *cols = VGeo < T, 6 >::PX; *rows = VGeo < T, 6 >::ROWS; break;
+  }
+}
+
 template < typename T, int F >
 int
 launch_one (hipStream_t stream, const IwtJob * d_jobs, int njobs, int total_tiles)
@@ -810,6 +1021,23 @@ launch_iiwt_level (hipStream_t stream, const IwtJob * d_jobs, int njobs, int tot
   if (bpp == 2)
     return launch_filter < int16_t > (stream, d_jobs, njobs, total_tiles, filter);
   return launch_filter < int32_t > (stream, d_jobs, njobs, total_tiles, filter);
+}
+
+void
+iiwt_v210_geometry (int filter, int bpp, int *cols, int *rows)
+{
+  if (bpp == 2)
+    v210_geometry < int16_t > (filter, cols, rows);
+  else
+    v210_geometry < int32_t > (filter, cols, rows);
+}
+
+int
+launch_iiwt_v210 (hipStream_t stream, const V210Job * d_jobs, int njobs, int total_tiles, int filter, int bpp)
+{
+  if (bpp == 2)
+    return launch_v210_filter < int16_t > (stream, d_jobs, njobs, total_tiles, filter);
+  return launch_v210_filter < int32_t > (stream, d_jobs, njobs, total_tiles, filter);
 }
 
 size_t

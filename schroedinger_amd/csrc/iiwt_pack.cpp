@@ -5,11 +5,27 @@
 // 10-bit 4:2:2): x_wavelet_transform writes the pixel frame (s32 for > 8-bit streams, schrodecoder.c:1855-1886), x_combine
 // converts it into the application's picture (schro_frame_convert, :2011-2052 -> schrovirtframe.c:1438-1537 convert_s16_s32,
 // :1823-1895 crop / edge extend, :943-991 pack_v210_s16).  On the device that was two launches with the 4-byte pixel frame
-// written and read back between them: per 8K picture 265 MB out + 265 MB in around 88 MB of v210.  Where the transform is the
-// three-level s32 Haar of a 4:2:2 picture (iiwt_haar.hip: an 8 x 8 block of samples depends on 64 coefficients of its own 8
-// frame rows) the copy-out is the transform kernel's epilogue; every other picture takes the two passes, with the same bytes out.
+// written and read back between them: per 8K picture 265 MB out + 265 MB in around 88 MB of v210.  The routes now
+// (schro_hip_v210_routes counts the pictures of each):
+//   HAAR3     the three-level s32 Haar of a 4:2:2 picture whose size is the transform's and a multiple of 192 x 8 (iiwt_haar.hip:
+//             an 8 x 8 block of samples depends on 64 coefficients of its own 8 frame rows): the copy-out is the transform
+//             kernel's epilogue.  Every picture of the call must allow it.
+//   LEVEL     every other picture, every filter, depth and sample type: levels depth-1 .. 1 run through the level loop
+//             (schro_hip_iiwt_batch on the frame's level-1 view) into compact LL planes -- a quarter of each component -- in
+//             the queue's grow-only block, then ONE launch of iiwt_v210_kernel (iiwt.hip) for all pictures of the call lifts
+//             the finest level of Y, U and V per tile and packs the v210 groups: the pixel frame is never written.  Depth 1
+//             reads the LL band from the frame's LL quadrant.  Per 8K s32 DD(9,7) picture 0.173 against 0.266 ms.
+//   TWO_PASS  the pixel frame in that block, then the pack, only where the level kernel cannot apply:
+//               * dst or dst_stride not a multiple of 16 bytes (its stores are whole 16-byte v210 groups);
+//               * a coefficient plane or stride not aligned to the sample size;
+//               * dst overlapping a coefficient plane (the two passes read every coefficient before the pack writes);
+//               * experiments library: SCHRO_HIP_V210_TWO_PASS=1 (A/B runs).
+//             Every filter measured faster on LEVEL than on two passes (Fidelity too: 0.291 against 0.336 ms per 8K picture),
+//             so no filter is sent to two passes; nor is a plane narrower than one tile (the tile clamps to the picture).
+// The bytes out are the same on every route.
 #include "schro_hip_internal.h"
 
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -33,6 +49,14 @@ schro_hip_iiwt_pack_v210_batch (SchroHipContext * ctx, const SchroHipIwtPackPict
         && pic.dst_stride >= 16 * ((pic.out_width + 5) / 6), "iiwt_pack_v210_batch: picture %d: bad geometry", p);
     // (convert_4xx_422 of s16 / s32 frames is not on the reference's path either: schro_frame_convert finds no match, schroframe.c:869-979)
     SCHRO_HIP_REQUIRE (pic.h_shift == 1 && pic.v_shift == 0, "iiwt_pack_v210_batch: picture %d: v210 from s16 / s32 frames needs a 4:2:2 frame", p);
+    // (what schro_hip_iiwt_batch asks of every component: whole transform levels, rows that hold the component)
+    for (int c = 0; c < 3; c++) {
+      const int w = c ? pic.width >> pic.h_shift : pic.width, h = c ? pic.height >> pic.v_shift : pic.height;
+      SCHRO_HIP_REQUIRE (w % (1 << depth) == 0 && h % (1 << depth) == 0 && w > 0 && h > 0,
+          "iiwt_pack_v210_batch: picture %d component %d: size %dx%d is not a multiple of 2^depth", p, c, w, h);
+      SCHRO_HIP_REQUIRE (pic.src_stride[c] >= w * bytes_per_sample,
+          "iiwt_pack_v210_batch: picture %d component %d: stride %d does not hold %d samples", p, c, pic.src_stride[c], w);
+    }
     HaarPackJob & j = jobs[(size_t) p];
     for (int c = 0; c < 3; c++) {
       j.src[c] = pic.src[c];
@@ -54,19 +78,44 @@ schro_hip_iiwt_pack_v210_batch (SchroHipContext * ctx, const SchroHipIwtPackPict
     if (r)
       return r;
     ProfileScope ps (ctx, SCHRO_HIP_KERNEL_IIWT_FINEST);
-    return launch_iiwt_haar3_v210 (ctx->stream, (const HaarPackJob *) d_jobs, npictures, tile_base, filter);
+    r = launch_iiwt_haar3_v210 (ctx->stream, (const HaarPackJob *) d_jobs, npictures, tile_base, filter);
+    if (!r)
+      ctx->v210_routes[SCHRO_HIP_V210_ROUTE_HAAR3] += npictures;
+    return r;
   }
-  // the two passes (the general form): transform into pixel planes, then the pack
-  std::vector < SchroHipIwtPlane > planes ((size_t) 3 * npictures);
-  std::vector < SchroHipPackPlane > packs ((size_t) npictures);
-  // r06: the pixel planes live in the queue's own grow-only block -- nothing is allocated, freed or waited
-  // for per call; a block that must grow waits for the queue once
+  // which pictures the finest level's v210 kernel takes (the rest: the two passes); a 16-byte aligned destination (its
+  // stores are whole v210 groups), sample-aligned coefficient rows
+  // (experiments: SCHRO_HIP_V210_TWO_PASS=1 sends every picture the Haar kernel does not take to the two passes, for A/B runs)
+  const bool level_on = !(SCHRO_ENV ("SCHRO_HIP_V210_TWO_PASS") && atoi (SCHRO_ENV ("SCHRO_HIP_V210_TWO_PASS")) != 0);
+  std::vector < char >level ((size_t) npictures, 0);
+  int nlevel = 0;
+  for (int p = 0; p < npictures; p++) {
+    const SchroHipIwtPackPicture & pic = pictures[p];
+    uintptr_t src_bits = 0;
+    bool apart = true;          // (the two passes read every coefficient before the pack writes dst; one launch does not)
+    const char *d0 = (const char *) pic.dst, *d1 = d0 + (size_t) pic.dst_stride * pic.out_height;
+    for (int c = 0; c < 3; c++) {
+      src_bits |= (uintptr_t) pic.src[c] | (uintptr_t) pic.src_stride[c];
+      const char *s0 = (const char *) pic.src[c], *s1 = s0 + (size_t) pic.src_stride[c] * (c ? pic.height >> pic.v_shift : pic.height);
+      apart = apart && (s1 <= d0 || d1 <= s0);
+    }
+    level[(size_t) p] = level_on && ((((uintptr_t) pic.dst | (uintptr_t) pic.dst_stride) & 15) == 0)
+        && (src_bits & (bytes_per_sample - 1)) == 0 && apart;
+    nlevel += level[(size_t) p];
+  }
+  // the queue's grow-only block: per level picture the three compact LL planes of level 0 (depth > 1: the coarser levels'
+  // output, a quarter of the component), per two-pass picture its three pixel planes
+  // r06: nothing is allocated, freed or waited for per call; a block that must grow waits for the queue once
+  auto ll_stride = [&](int w) { return (int) round_up ((size_t) (w >> 1) * bytes_per_sample, 128); };
   size_t need = 0;
   for (int p = 0; p < npictures; p++)
     for (int c = 0; c < 3; c++) {
       const SchroHipIwtPackPicture & pic = pictures[p];
       const int w = c ? pic.width >> pic.h_shift : pic.width, h = c ? pic.height >> pic.v_shift : pic.height;
-      need += round_up (round_up ((size_t) w * bytes_per_sample, 64) * (size_t) h, 256);
+      if (!level[(size_t) p])
+        need += round_up (round_up ((size_t) w * bytes_per_sample, 64) * (size_t) h, 256);
+      else if (depth > 1)
+        need += round_up ((size_t) ll_stride (w) * (size_t) (h >> 1), 256);
     }
   const int q = ctx->cur;
   if (ctx->pack_tmp_size_q[q] < need) {
@@ -80,16 +129,96 @@ schro_hip_iiwt_pack_v210_batch (SchroHipContext * ctx, const SchroHipIwtPackPict
     ctx->pack_tmp_size_q[q] = need;
   }
   size_t at = 0;
+  int r = 0;
+
+  // ---- the level route: levels depth-1 .. 1 by the level loop into the LL planes, then the finest level + v210 ----
+  if (nlevel) {
+    std::vector < SchroHipIwtPlane > coarse;
+    std::vector < V210Job > vj;
+    int cols, rows;
+    iiwt_v210_geometry (filter, bytes_per_sample, &cols, &rows);
+    const int vl = 8 / bytes_per_sample;
+    int vtiles = 0;
+    for (int p = 0; p < npictures; p++) {
+      if (!level[(size_t) p])
+        continue;
+      const SchroHipIwtPackPicture & pic = pictures[p];
+      V210Job j;
+      memset (&j, 0, sizeof (j));
+      for (int c = 0; c < 3; c++) {
+        const int w = c ? pic.width >> pic.h_shift : pic.width, h = pic.height;
+        j.src[c] = pic.src[c];
+        j.src_stride[c] = pic.src_stride[c];
+        if (depth > 1) {
+          // the level-1 view of the coefficient frame {w / 2, h / 2, stride x 2} (schroparams.c:319-352), depth - 1 levels
+          void *t = (char *) ctx->pack_tmp_q[q] + at;
+          at += round_up ((size_t) ll_stride (w) * (size_t) (h >> 1), 256);
+          SchroHipIwtPlane pl;
+          memset (&pl, 0, sizeof (pl));
+          pl.src = pic.src[c];
+          pl.src_stride = 2 * pic.src_stride[c];
+          pl.dst = t;
+          pl.dst_stride = ll_stride (w);
+          pl.width = w >> 1;
+          pl.height = h >> 1;
+          coarse.push_back (pl);
+          j.ll[c] = t;
+          j.ll_stride[c] = ll_stride (w);
+        } else {
+          j.ll[c] = pic.src[c];             // (the frame's LL quadrant)
+          j.ll_stride[c] = 2 * pic.src_stride[c];
+        }
+        // 8-byte loads of the four bands: whole groups of samples per row, 8-byte aligned rows and band origins
+        const int nc = w >> 1;
+        const uintptr_t bits = (uintptr_t) j.ll[c] | (uintptr_t) j.ll_stride[c] | (uintptr_t) pic.src[c] | (uintptr_t) pic.src_stride[c]
+            | (uintptr_t) nc * bytes_per_sample;
+        if (nc % vl == 0 && nc >= vl && (bits & 7) == 0)
+          j.flags |= 1 << c;
+      }
+      j.w = pic.width;
+      j.h = pic.height;
+      j.out_w = pic.out_width;
+      j.out_h = pic.out_height;
+      j.dst = pic.dst;
+      j.dst_stride = pic.dst_stride;
+      j.tiles_x = div_up (pic.out_width, cols);
+      j.tile_base = vtiles;
+      vtiles += j.tiles_x * div_up (pic.out_height, rows);
+      vj.push_back (j);
+    }
+    if (!coarse.empty ())
+      r = schro_hip_iiwt_batch (ctx, coarse.data (), (int) coarse.size (), depth - 1, filter, bytes_per_sample);
+    void *d_vj = nullptr;
+    if (!r)
+      r = push_args (ctx, vj.data (), sizeof (V210Job) * vj.size (), &d_vj);
+    if (r)
+      return r;
+    {
+      ProfileScope ps (ctx, SCHRO_HIP_KERNEL_IIWT_FINEST);
+      r = launch_iiwt_v210 (ctx->stream, (const V210Job *) d_vj, (int) vj.size (), vtiles, filter, bytes_per_sample);
+    }
+    if (r)
+      return r;
+    ctx->v210_routes[SCHRO_HIP_V210_ROUTE_LEVEL] += nlevel;
+    if (nlevel == npictures)
+      return 0;
+  }
+
+  // ---- the two passes (the general form): transform into pixel planes, then the pack ----
+  std::vector < SchroHipIwtPlane > planes;
+  std::vector < SchroHipPackPlane > packs;
   for (int p = 0; p < npictures; p++) {
+    if (level[(size_t) p])
+      continue;
     const SchroHipIwtPackPicture & pic = pictures[p];
-    SchroHipPackPlane & pk = packs[(size_t) p];
+    SchroHipPackPlane pk;
     memset (&pk, 0, sizeof (pk));
     for (int c = 0; c < 3; c++) {
       const int w = c ? pic.width >> pic.h_shift : pic.width, h = c ? pic.height >> pic.v_shift : pic.height;
       const int stride = (int) round_up ((size_t) w * bytes_per_sample, 64);
       void *t = (char *) ctx->pack_tmp_q[q] + at;
       at += round_up ((size_t) stride * (size_t) h, 256);
-      SchroHipIwtPlane & pl = planes[(size_t) 3 * p + c];
+      SchroHipIwtPlane pl;
       memset (&pl, 0, sizeof (pl));
       pl.src = pic.src[c];
       pl.src_stride = pic.src_stride[c];
@@ -97,6 +226,7 @@ schro_hip_iiwt_pack_v210_batch (SchroHipContext * ctx, const SchroHipIwtPackPict
       pl.dst_stride = stride;
       pl.width = w;
       pl.height = h;
+      planes.push_back (pl);
       pk.src[c] = (const uint8_t *) t;
       pk.src_stride[c] = stride;
     }
@@ -109,9 +239,24 @@ schro_hip_iiwt_pack_v210_batch (SchroHipContext * ctx, const SchroHipIwtPackPict
     pk.width = pic.out_width;
     pk.height = pic.out_height;
     pk.format = SCHRO_HIP_FORMAT_v210;
+    packs.push_back (pk);
   }
-  int r = schro_hip_iiwt_batch (ctx, planes.data (), 3 * npictures, depth, filter, bytes_per_sample);
+  r = schro_hip_iiwt_batch (ctx, planes.data (), (int) planes.size (), depth, filter, bytes_per_sample);
   if (!r)
-    r = schro_hip_pack_v210_batch (ctx, packs.data (), npictures, bytes_per_sample);
+    r = schro_hip_pack_v210_batch (ctx, packs.data (), (int) packs.size (), bytes_per_sample);
+  if (!r)
+    ctx->v210_routes[SCHRO_HIP_V210_ROUTE_TWO_PASS] += (long long) packs.size ();
   return r;
+}
+
+extern "C" int
+schro_hip_v210_routes (SchroHipContext * ctx, long long counts[SCHRO_HIP_V210_ROUTES], int reset)
+{
+  SCHRO_HIP_REQUIRE (ctx && counts, "v210_routes: bad arguments");
+  for (int k = 0; k < SCHRO_HIP_V210_ROUTES; k++) {
+    counts[k] = ctx->v210_routes[k];
+    if (reset)
+      ctx->v210_routes[k] = 0;
+  }
+  return 0;
 }

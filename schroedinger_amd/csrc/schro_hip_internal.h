@@ -124,6 +124,21 @@ struct HaarPackJob {
   int tile_base;
 };
 
+// The finest level of a 4:2:2 picture's inverse wavelet with the v210 copy-out as its sink (iiwt.hip, iiwt_v210_kernel)
+struct V210Job {
+  const void *src[3];           // the coefficient planes (Y, U, V), in-place sub-band layout
+  int src_stride[3];
+  const void *ll[3];            // each component's level-0 LL band: the frame's LL quadrant (depth 1) or a compact plane
+  int ll_stride[3];
+  int w, h;                     // luma transform size (chroma: w / 2 x h)
+  int out_w, out_h;             // the picture inside it
+  uint8_t *dst;                 // v210 rows: 16 bytes per 6 pixels; dst and dst_stride 16-byte aligned
+  int dst_stride;
+  int tiles_x;
+  int tile_base;
+  int flags;                    // bit c: component c's four bands take 8-byte loads
+};
+
 struct ConvertJob {
   const void *src;
   uint8_t *dst;
@@ -491,6 +506,9 @@ namespace schro {
 bool iiwt_haar3_v210_ok (const HaarPackJob & j);
 int iiwt_haar3_v210_strip_width ();
 int launch_iiwt_haar3_v210 (hipStream_t stream, const HaarPackJob * d_jobs, int njobs, int total_tiles, int filter);
+// iiwt.hip: the finest level + v210 copy-out of every filter (picture columns / rows per workgroup)
+void iiwt_v210_geometry (int filter, int bpp, int *cols, int *rows);
+int launch_iiwt_v210 (hipStream_t stream, const V210Job * d_jobs, int njobs, int total_tiles, int filter, int bpp);
 int launch_dequant (hipStream_t stream, const DequantJob * d_jobs, int njobs, int total_tiles, int bpp, int arith);
 int launch_dequant_plan (hipStream_t stream, const DequantGeo * d_geo, int njobs, int total_tiles,
     const SchroHipCodeblock * d_recs, const DequantPlaneDyn * d_planes, int bpp, int arith);
@@ -671,6 +689,8 @@ struct SchroHipContext {
   std::vector < uint32_t > ovf_unannounced, ovf_unfetched;
   // r07: planes handed to the OBMC launches of each route (schro_hip_obmc_routes)
   long long obmc_routes[SCHRO_HIP_OBMC_ROUTES] = {};
+  // pictures handed to each route of schro_hip_iiwt_pack_v210_batch (schro_hip_v210_routes)
+  long long v210_routes[SCHRO_HIP_V210_ROUTES] = {};
   int cus;                      // compute units of the device (launch shaping)
 };
 
