@@ -223,6 +223,14 @@ int schro_hip_obmc_routes (SchroHipContext * ctx, long long counts[SCHRO_HIP_OBM
 #define SCHRO_HIP_V210_ROUTES 3
 int schro_hip_v210_routes (SchroHipContext * ctx, long long counts[SCHRO_HIP_V210_ROUTES], int reset);
 
+/* The same for schro_hip_iiwt_pack_u8_batch (and so for schro_frame_inverse_iwt_transform_convert_hip /
+ * _combine_convert_hip with a YUYV, UYVY or AYUV frame): pictures per route, counted on the host as the launches
+ * are enqueued, nothing for a call that fails validation. */
+#define SCHRO_HIP_PACK8_ROUTE_LEVEL 0   /* iiwt.hip: the finest level writes the packed rows, coarser levels by the level loop */
+#define SCHRO_HIP_PACK8_ROUTE_TWO_PASS 1        /* the planar u8 picture in a scratch block, then schro_hip_pack_u8_batch's kernel */
+#define SCHRO_HIP_PACK8_ROUTES 2
+int schro_hip_pack8_routes (SchroHipContext * ctx, long long counts[SCHRO_HIP_PACK8_ROUTES], int reset);
+
 /* ---- plane layer: batched launches --------------------------------------- */
 
 /* One component of one picture for the inverse wavelet.
@@ -363,6 +371,54 @@ typedef struct {
   int out_width, out_height;    /* the picture inside the transform's size */
 } SchroHipIwtPackPicture;
 int schro_hip_iiwt_pack_v210_batch (SchroHipContext * ctx, const SchroHipIwtPackPicture * pictures, int npictures, int depth,
+    int filter, int bytes_per_sample);
+
+/* The inverse wavelet of a picture, its last step -- + 128 (a picture without references) or + the u8 prediction
+ * schro_hip_obmc_batch wrote with prediction_only = 1 -- and the YUYV / UYVY / AYUV copy-out as one call: x_wavelet_transform,
+ * the add and schro_frame_convert (&output_picture, ...) of x_combine (schrodecoder.c:1969-2021) for a picture that is not a
+ * reference, whose planar picture has no other reader.  dst receives exactly the bytes of schro_hip_iiwt_batch (combine 1 or
+ * 2, the same pred: the 16-bit wrapping add and the u8 clamp described at SchroHipIwtPlane) into planar u8 planes followed by
+ * schro_hip_pack_u8_batch from them: YUYV / UYVY rows of out_width / 2 four-byte groups, AYUV rows of out_width.
+ * Routes, chosen per picture and mixed freely in a call (schro_hip_pack8_routes counts them):
+ *   LEVEL     levels depth-1 .. 1 run into quarter-size LL planes in the queue's scratch, then ONE launch lifts the finest
+ *             level of Y, U and V per tile, adds and clamps, and writes whole packed groups: no planar picture, no pack
+ *             launch (about 6 bytes of memory traffic per 4:2:2 pixel with a prediction instead of 10).  Every filter and
+ *             depth.  Taken when ALL of these hold:
+ *               - bytes_per_sample is 2;
+ *               - the filter measured faster on this route than on the two passes by more than the spread of the rounds,
+ *                 with and without a prediction (8 x 2160p per call, profiles/r09_pack8_fused.txt; ms per call with a
+ *                 prediction): YUYV / UYVY: filters 3, 4 (Haar: 0.163 against 0.199) and 5 (Fidelity: 0.423 against
+ *                 0.719); AYUV: filters 1 (LeGall: 0.277 against 0.384), 3, 4 (0.245 against 0.382) and 5 (0.582 against
+ *                 1.127).  Filters 0, 1, 2, 6 into YUYV / UYVY and 0, 2, 6 into AYUV keep the two passes, whose transform
+ *                 ends in the register kernel (Daub(9,7) into YUYV: 0.304 against 0.227; DD(9,7) into AYUV: 0.294
+ *                 against 0.364, a gain inside the 21 % spread of its rounds);
+ *               - the source's chroma format is the packed format's own: h_shift 1, v_shift 0 for YUYV / UYVY, 0, 0 for AYUV;
+ *               - dst and dst_stride are multiples of 16 bytes;
+ *               - every src and src_stride is a multiple of 2 bytes;
+ *               - with a prediction: every pred and pred_stride is a multiple of 8 bytes and pred_stride is at least the
+ *                 component's out width rounded up to 8 (rows are read in 8-byte words, as the combine form reads them);
+ *               - dst overlaps no coefficient plane and no prediction plane.
+ *   TWO_PASS  everything else -- 4:2:0 sources (chroma rows repeated, schrovirtframe.c:1438-1537), a source whose chroma
+ *             format is not the destination's, s32 sources, other alignments, an overlapping dst: the planar picture in
+ *             the queue's scratch, then the pack kernel.
+ * Refused (SCHRO_HIP_EINVAL, nothing launched or counted): what schro_hip_iiwt_batch refuses (a component that is not a
+ * multiple of 2^depth, a src_stride shorter than a row), pred set for some components only, a pred_stride below the
+ * component's out width, out_width x out_height outside the transform, a dst_stride below the packed row, another format,
+ * bytes_per_sample other than 2 or 4. */
+typedef struct {
+  const void *src[3];           /* the coefficient planes Y, U, V (device, s16 or s32), in-place sub-band layout */
+  int src_stride[3];
+  int width, height;            /* luma transform size (a multiple of 2^depth); chroma: >> h_shift, >> v_shift */
+  int h_shift, v_shift;         /* chroma format of the SOURCE picture: 0, 0 / 1, 0 / 1, 1 */
+  const uint8_t *pred[3];       /* all NULL: sat_u8 (x + 128) (combine 2); all set: sat_u8 (x + pred) (combine 1); component c is
+                                 * out_width x out_height, chroma rounded up after the shifts */
+  int pred_stride[3];
+  uint8_t *dst;                 /* packed rows */
+  int dst_stride;
+  int out_width, out_height;    /* the picture inside the transform's size (crop only) */
+  int format;                   /* SCHRO_HIP_FORMAT_YUYV / _UYVY / _AYUV */
+} SchroHipIwtPack8Picture;
+int schro_hip_iiwt_pack_u8_batch (SchroHipContext * ctx, const SchroHipIwtPack8Picture * pictures, int npictures, int depth,
     int filter, int bytes_per_sample);
 
 /* The remaining packed destinations of schro_frame_convert (schroframe.c:886-895, 957-968),
@@ -903,6 +959,15 @@ int schro_frame_inverse_iwt_transform_combine_hip (SchroHipFrame * output_frame,
  * schro_frame_inverse_iwt_transform_hip + schro_hipframe_convert; the pixel frame is not written where
  * schro_hip_iiwt_pack_v210_batch's fused kernel applies. */
 int schro_frame_inverse_iwt_transform_convert_hip (SchroHipFrame * packed, SchroHipFrame * transform_frame, SchroHipParams * params);
+/* `packed` may also be a YUYV, UYVY or AYUV device frame (s16 or s32 transform frame of any chroma format the pack takes):
+ * schro_hip_iiwt_pack_u8_batch.  And the same with a prediction: x_wavelet_transform, the add and x_combine's convert of
+ * an inter picture that is not a reference (schrodecoder.c:1908-1921, :1969-2021) in one stage call -- prediction = the u8
+ * frame schro_motion_render_hip (motion, dest, NULL, FALSE, NULL) rendered, as for
+ * schro_frame_inverse_iwt_transform_combine_hip, with its domain and size checks; prediction == NULL is the call above.
+ * Same bytes as schro_frame_inverse_iwt_transform_combine_hip + schro_hipframe_convert; a v210 `packed` takes no
+ * prediction. */
+int schro_frame_inverse_iwt_transform_combine_convert_hip (SchroHipFrame * packed, SchroHipFrame * transform_frame,
+    SchroHipParams * params, SchroHipFrame * prediction);
 
 /* schro_decoder_decode_lowdelay_transform_data (picture), schrolowdelay.c:746-762, with
  * picture->transform_frame on the device: `slices` is picture->lowdelay_buffer->data (host),

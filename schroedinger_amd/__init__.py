@@ -309,6 +309,16 @@ class Context:
         check(self.lib.schro_hip_v210_routes(self.h, counts, 1 if reset else 0))
         return dict(zip(self.V210_ROUTES, (int(n) for n in counts)))
 
+    PACK8_ROUTES = ("level", "two_pass")                     # SCHRO_HIP_PACK8_ROUTE_* (include/schro_hip.h)
+
+    def pack8_routes(self, reset=False):
+        """{route: pictures} this context's iiwt_pack_u8 calls have handed to each route (schro_hip_pack8_routes): "level" the
+        finest level writing the packed rows (iiwt_pack8_kernel), "two_pass" the planar picture in a scratch block and the
+        pack; reset: start the counts again from zero after reading them."""
+        counts = (C.c_longlong * len(self.PACK8_ROUTES))()
+        check(self.lib.schro_hip_pack8_routes(self.h, counts, 1 if reset else 0))
+        return dict(zip(self.PACK8_ROUTES, (int(n) for n in counts)))
+
     def plane(self, height, width, dtype, stride=None):
         return DevicePlane(self, height, width, dtype, stride)
 
@@ -403,6 +413,29 @@ class Context:
             a.dst, a.dst_stride = dst.ptr, dst.stride
             a.out_width, a.out_height = w, h
         check(self.lib.schro_hip_iiwt_pack_v210_batch(self.h, arr, n, depth, filt, bpp))
+
+    def iiwt_pack_u8_batch(self, jobs, depth, filt):
+        """The inverse wavelet, the add of the prediction (or of 128) and the YUYV / UYVY / AYUV copy-out in one call.  jobs:
+        (coefficient planes [Y, U, V] of one dtype, h_shift, v_shift, predictions [Y, U, V] u8 planes or None (a picture
+        without references), dst plane of bytes, picture width, picture height, format) per picture; planes: DevicePlanes
+        or SubPlanes."""
+        n = len(jobs)
+        arr = (_lib.IwtPack8Picture * n)()
+        bpp = jobs[0][0][0].dtype.itemsize
+        for a, (planes, hs, vs, preds, dst, w, h, fmt) in zip(arr, jobs):
+            for k in range(3):
+                assert planes[k].dtype.itemsize == bpp
+                a.src[k] = planes[k].ptr
+                a.src_stride[k] = planes[k].stride
+                if preds is not None:
+                    assert preds[k].dtype == np.uint8
+                    a.pred[k] = preds[k].ptr
+                    a.pred_stride[k] = preds[k].stride
+            a.width, a.height = planes[0].width, planes[0].height
+            a.h_shift, a.v_shift = hs, vs
+            a.dst, a.dst_stride = dst.ptr, dst.stride
+            a.out_width, a.out_height, a.format = w, h, fmt
+        check(self.lib.schro_hip_iiwt_pack_u8_batch(self.h, arr, n, depth, filt, bpp))
 
     def pack_wide_batch(self, jobs):
         """jobs: (planes [Y, U, V] DevicePlanes of one dtype, h_shift, v_shift, dst DevicePlane of

@@ -425,13 +425,60 @@ schro_frame_inverse_iwt_transform_combine_hip (SchroHipFrame * output_frame, Sch
 // without references (schrodecoder.c:1855-1886 + :2011-2052; the > 8-bit shift of :2013-2019 is 0 when the stream's depth
 // is the output's): `packed` is a DEVICE frame of format v210, the transform frame a device s16 / s32 4:2:2 frame.  The
 // pixel frame (picture->frame) is not written where the fused kernel applies (schro_hip_iiwt_pack_v210_batch).
+// ... and into a YUYV, UYVY or AYUV output picture, with the prediction of an inter picture that is not a reference
+// (prediction != NULL: the u8 frame schro_motion_render_hip (add = FALSE) wrote; x_combine's add, :1908-1921) or + 128:
+// schro_hip_iiwt_pack_u8_batch.  The planar picture is not written where its fused kernel applies.
+static int
+inverse_iwt_transform_pack8 (SchroHipFrame * packed, SchroHipFrame * transform_frame, SchroHipParams * params, SchroHipFrame * prediction)
+{
+  SchroHipContext *ctx = frame_ctx (packed);
+  const int bpp = format_bpp (transform_frame->format);
+  SCHRO_HIP_REQUIRE (bpp == 2 || bpp == 4, "inverse_iwt_transform_convert: the transform frame must be s16 or s32");
+  SCHRO_HIP_REQUIRE (!prediction || (prediction->domain == packed->domain && format_bpp (prediction->format) == 1),
+      "inverse_iwt_transform_combine_convert: the prediction must be the u8 frame of schro_motion_render_hip (add = FALSE) in the same domain");
+  SchroHipIwtPack8Picture pic;
+  memset (&pic, 0, sizeof (pic));
+  pic.width = params->iwt_luma_width;
+  pic.height = params->iwt_luma_height;
+  pic.h_shift = SCHRO_HIP_FORMAT_H_SHIFT (transform_frame->format);
+  pic.v_shift = SCHRO_HIP_FORMAT_V_SHIFT (transform_frame->format);
+  SCHRO_HIP_REQUIRE ((params->iwt_chroma_width << pic.h_shift) == pic.width && (params->iwt_chroma_height << pic.v_shift) == pic.height,
+      "inverse_iwt_transform_convert: params' chroma transform size is not the luma size shifted by the frame's chroma format");
+  pic.out_width = std::min (packed->width, pic.width);
+  pic.out_height = std::min (packed->height, pic.height);
+  SCHRO_HIP_REQUIRE (pic.out_width == packed->width && pic.out_height == packed->height,
+      "inverse_iwt_transform_convert: the packed frame is larger than the transform");
+  for (int k = 0; k < 3; k++) {
+    pic.src[k] = transform_frame->components[k].data;
+    pic.src_stride[k] = transform_frame->components[k].stride;
+    const int w = k ? params->iwt_chroma_width : params->iwt_luma_width, h = k ? params->iwt_chroma_height : params->iwt_luma_height;
+    SCHRO_HIP_REQUIRE (w <= transform_frame->components[k].width && h <= transform_frame->components[k].height,
+        "inverse_iwt_transform_convert: component %d smaller than the iwt size", k);
+    if (prediction) {
+      const int ow = k ? (pic.out_width + pic.h_shift) >> pic.h_shift : pic.out_width;
+      const int oh = k ? (pic.out_height + pic.v_shift) >> pic.v_shift : pic.out_height;
+      SCHRO_HIP_REQUIRE (prediction->components[k].width >= ow && prediction->components[k].height >= oh,
+          "inverse_iwt_transform_combine_convert: component %d of the prediction is smaller than the picture", k);
+      pic.pred[k] = (const uint8_t *) prediction->components[k].data;
+      pic.pred_stride[k] = prediction->components[k].stride;
+    }
+  }
+  pic.dst = (uint8_t *) packed->components[0].data;
+  pic.dst_stride = packed->components[0].stride;
+  pic.format = packed->format;
+  return stage_done (ctx, schro_hip_iiwt_pack_u8_batch (ctx, &pic, 1, params->transform_depth, params->wavelet_filter_index, bpp));
+}
+
 int
-schro_frame_inverse_iwt_transform_convert_hip (SchroHipFrame * packed, SchroHipFrame * transform_frame, SchroHipParams * params)
+schro_frame_inverse_iwt_transform_combine_convert_hip (SchroHipFrame * packed, SchroHipFrame * transform_frame, SchroHipParams * params,
+    SchroHipFrame * prediction)
 {
   SCHRO_HIP_REQUIRE (packed && transform_frame && params && frame_ctx (packed) && transform_frame->domain == packed->domain,
       "inverse_iwt_transform_convert: the packed frame and the transform frame must live in the same device domain");
-  SCHRO_HIP_REQUIRE (packed->format == SCHRO_HIP_FORMAT_v210, "inverse_iwt_transform_convert: the destination must be a v210 frame "
-      "(other formats: schro_frame_inverse_iwt_transform_hip + schro_hipframe_convert)");
+  if (packed->format == SCHRO_HIP_FORMAT_YUYV || packed->format == SCHRO_HIP_FORMAT_UYVY || packed->format == SCHRO_HIP_FORMAT_AYUV)
+    return inverse_iwt_transform_pack8 (packed, transform_frame, params, prediction);
+  SCHRO_HIP_REQUIRE (packed->format == SCHRO_HIP_FORMAT_v210 && !prediction, "inverse_iwt_transform_convert: the destination must be a "
+      "YUYV, UYVY, AYUV or (without a prediction) v210 frame (other formats: schro_frame_inverse_iwt_transform_hip + schro_hipframe_convert)");
   SchroHipContext *ctx = frame_ctx (packed);
   const int bpp = format_bpp (transform_frame->format);
   SCHRO_HIP_REQUIRE (bpp == 2 || bpp == 4, "inverse_iwt_transform_convert: the transform frame must be s16 or s32");
@@ -452,6 +499,12 @@ schro_frame_inverse_iwt_transform_convert_hip (SchroHipFrame * packed, SchroHipF
   pic.out_width = packed->width;
   pic.out_height = packed->height;
   return stage_done (ctx, schro_hip_iiwt_pack_v210_batch (ctx, &pic, 1, params->transform_depth, params->wavelet_filter_index, bpp));
+}
+
+int
+schro_frame_inverse_iwt_transform_convert_hip (SchroHipFrame * packed, SchroHipFrame * transform_frame, SchroHipParams * params)
+{
+  return schro_frame_inverse_iwt_transform_combine_convert_hip (packed, transform_frame, params, nullptr);
 }
 
 int

@@ -33,16 +33,7 @@ clampi (int x, int lo, int hi)
 
 constexpr int kCvtTW = 512, kCvtTH = 4;
 
-// the last steps of orc_rrshift6_add_s16_2d / _s32_2d with the prediction p = (acc + 32) >> 6 already there:
-// convlw (s32), addw (wraps), convsuswb
-template < typename T >
-__device__ __forceinline__ uint8_t
-combine_pred (T s, uint32_t p)
-{
-  const int v = (int16_t) ((int16_t) s + (int16_t) p);
-  return (uint8_t) clampi (v, 0, 255);
-}
-
+// (combine_pred: schro_hip_internal.h, shared with the packed sink of iiwt.hip)
 template < typename T >
 __device__ __forceinline__ uint8_t
 offsetconvert (T s)

@@ -874,6 +874,282 @@ v210_geometry (int filter, int *cols, int *rows)
   }
 }
 
+// ---- the finest level with the YUYV / UYVY / AYUV copy-out as its sink ------------------------------------------
+// The 8-bit twin of iiwt_v210_kernel, s16 only: one workgroup owns 2 * UR picture rows x PX picture columns of all three
+// components.  Each component's tile of the PREDICTION is staged first (8-byte coalesced loads, read once) in the byte
+// area its samples will occupy; the last lifting step hands its interleaved samples to Pack8Sink, which replaces those
+// bytes by sat_u8 (sample + prediction) -- combine_pred, the combine form's 16-bit wrapping add and clamp -- or by
+// sat_u8 (sample + 128) where the picture has no prediction.  After one barrier the lanes write whole 16-byte groups:
+// 8 pixels of YUYV / UYVY (AYUV 0: a 4:2:2 source, chroma regions half as wide, the byte order a run-time flag) or 4
+// pixels of AYUV (AYUV 1: a 4:4:4 source, three full-width regions).  The planar picture never exists.
+// PX: whole 128-byte lines of output per tile row, and tile + staging stay below 40 KB: four workgroups per CU.
+template < int F, int AYUV > struct P8Geo {
+  static constexpr int PX = AYUV ? 96 : 128;            // picture columns per workgroup
+  static constexpr int CS = AYUV ? 0 : 1;               // chroma columns = luma columns >> CS
+  static constexpr int RP = 32;
+  static constexpr int H = filter_halo (F);
+  static constexpr int HC = (H + 3) & ~3;
+  static constexpr int UR = RP - 2 * H;
+  static constexpr int ROWS = 2 * UR;                   // picture rows per workgroup
+  static constexpr int PXC = PX >> CS;                  // chroma samples per tile row
+  static constexpr int UCY = PX / 2, UCC = PXC / 2;     // useful sub-band columns, Y / U, V
+  static constexpr int RCY = UCY + 2 * HC, RCC = UCC + 2 * HC;
+  static_assert (PX % 32 == 0 && UCC % 4 == 0 && PXC % 8 == 0, "whole 16-byte groups, sample quads and 8-byte staging words");
+};
+
+struct Pack8Sink {
+  uint8_t *row0;                // staging row of tile row 0: the prediction's bytes on entry (has_pred)
+  int pitch;                    // bytes per staging row (a multiple of 8)
+  int hc;                       // region column of staging column 0
+  bool has_pred;                // (uniform: a picture without references adds 128 instead)
+
+  __device__ __forceinline__ void store (int yy, int i, const int16_t * out) const
+  {
+    // (i and hc are multiples of 4: 8-byte aligned)
+    u32x2 *p = reinterpret_cast < u32x2 * >(row0 + yy * pitch + 2 * (i - hc));
+    const u32x2 pr = has_pred ? *p : (u32x2) { 0x80808080u, 0x80808080u };
+    u32x2 b = { 0u, 0u };
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      b.x |= (uint32_t) combine_pred < int16_t > (out[k], (pr.x >> (8 * k)) & 0xffu) << (8 * k);
+      b.y |= (uint32_t) combine_pred < int16_t > (out[4 + k], (pr.y >> (8 * k)) & 0xffu) << (8 * k);
+    }
+    *p = b;
+  }
+};
+
+// component C's four bands: LL from job.ll[C], HL / LH / HH from the coefficient plane
+template < int C, int CS >
+__device__ __forceinline__ void
+pack8_bands (const Pack8Job & job, const void **sb, int *ss, int *nc)
+{
+  const int w = C ? job.w >> CS : job.w;
+  *nc = w >> 1;
+  const char *plane = (const char *) job.src[C];
+  const int S = job.src_stride[C];
+  sb[0] = job.ll[C];
+  sb[1] = plane + (size_t) *nc * sizeof (int16_t);
+  sb[2] = plane + S;
+  sb[3] = plane + S + (size_t) *nc * sizeof (int16_t);
+  ss[0] = job.ll_stride[C];
+  ss[1] = ss[2] = ss[3] = 2 * S;
+}
+
+// issue the 8-byte loads of component C's region (where its bands allow them)
+template < int F, int AYUV, int C, int RC, int UC, int NPS >
+__device__ __forceinline__ void
+pack8_load (uint2 (&v)[4][NPS], const Pack8Job & job, int tid, int r0, int tx)
+{
+  typedef P8Geo < F, AYUV > G;
+  if (!(job.flags & (1 << C)))
+    return;
+  const void *sb[4];
+  int ss[4], nc;
+  pack8_bands < C, G::CS > (job, sb, ss, &nc);
+#pragma unroll
+  for (int b = 0; b < 4; b++)
+    band_load < int16_t, G::RP, RC, NPS > (v[b], sb[b], ss[b], tid, r0, tx * UC - G::HC, job.h >> 1, nc);
+}
+
+// the tile of component C's prediction into its staging area: W bytes per row, (x0, y0) the tile's first sample, cw x ch
+// the component's picture.  Rows are 8-byte aligned and readable up to a multiple of 8 columns (the host's route test);
+// words outside the picture are left alone (nothing reads them back into the packed rows).
+template < int ROWS, int W >
+__device__ __forceinline__ void
+pack8_stage_pred (uint8_t * stage, const uint8_t * pred, int pred_stride, int tid, int x0, int y0, int cw, int ch)
+{
+  constexpr int WPR = W / 8, N = (ROWS * WPR + kThreads - 1) / kThreads;
+  u32x2 v[N];
+#pragma unroll
+  for (int n = 0; n < N; n++) {
+    const int it = tid + n * kThreads, y = it / WPR, x = 8 * (it - y * WPR);
+    // (clamped, not skipped: every load is issued before the first LDS write)
+    const int gy = min (y0 + y, ch - 1), gx = min (x0 + x, (cw - 1) & ~7);
+    v[n] = gload < u32x2 > (pred + (size_t) gy * pred_stride + gx);
+  }
+#pragma unroll
+  for (int n = 0; n < N; n++) {
+    const int it = tid + n * kThreads, y = it / WPR, x = 8 * (it - y * WPR);
+    if (y < ROWS)
+      *reinterpret_cast < u32x2 * >(stage + y * W + x) = v[n];
+  }
+}
+
+// stage component C's region in LDS (from the loads above, or sample by sample) and lift it into the staging area
+template < int F, int AYUV, int C, int RC, int UC, int NPS >
+__device__ __forceinline__ void
+pack8_lift (int16_t (*lds)[2 * RC], const uint2 (&v)[4][NPS], const Pack8Job & job, int tid, int r0, int tx, uint8_t * stage, int pitch)
+{
+  typedef P8Geo < F, AYUV > G;
+  constexpr int RP = G::RP, HC = G::HC;
+  const int nr = job.h >> 1, c0 = tx * UC - HC;
+  const void *sb[4];
+  int ss[4], nc;
+  pack8_bands < C, G::CS > (job, sb, ss, &nc);
+  if (job.flags & (1 << C)) {
+#pragma unroll
+    for (int b = 0; b < 4; b++)
+      band_store < int16_t, RP, RC, NPS > (lds, v[b], b, tid);
+  } else {
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+      const char *base = (const char *) sb[b];
+      for (int it = tid; it < RP * RC; it += kThreads) {
+        const int c = it % RC, rp = it / RC;
+        const int r = r0 + rp, cc = c0 + c;
+        if (r >= 0 && r < nr && cc >= 0 && cc < nc)
+          lds[2 * rp + (b >> 1)][(b & 1) * RC + c] = gload < int16_t > ((const int16_t *) (base + (size_t) r * ss[b]) + cc);
+      }
+    }
+  }
+  __syncthreads ();             // (also: the prediction's bytes are in the staging area)
+  Pack8Sink sink;
+  sink.row0 = stage;
+  sink.pitch = pitch;
+  sink.hc = HC;
+  sink.has_pred = job.pred[0] != nullptr;
+  lift_region < int16_t, F, RP, RC, HC / 4, (RC - HC) / 4 - 1 > (lds, tid, r0, c0, nr, nc, sink);
+}
+
+template < int F, int AYUV >
+__global__ __launch_bounds__ (kThreads)
+void iiwt_pack8_kernel (const Pack8Job * __restrict__ jobs, int njobs)
+{
+  typedef P8Geo < F, AYUV > G;
+  typedef int16_t T;
+  constexpr int RP = G::RP, H = G::H, UR = G::UR, ROWS = G::ROWS, PX = G::PX, PXC = G::PXC, CS = G::CS;
+  __shared__ __attribute__ ((aligned (16))) T lds[2 * RP][2 * G::RCY];
+  __shared__ __attribute__ ((aligned (16))) uint8_t s_y[ROWS][PX];
+  __shared__ __attribute__ ((aligned (16))) uint8_t s_c[2][ROWS][PXC];
+
+  const int tid = threadIdx.x;
+  const int bid = xcd_tile_id (blockIdx.x, gridDim.x);
+  const Pack8Job job = jobs[find_job (jobs, njobs, bid)];
+  const int t = bid - job.tile_base;
+  const int ty = t / job.tiles_x, tx = t - ty * job.tiles_x;
+  const int r0 = ty * UR - H;   // sub-band row of region row pair 0 (all three components: no vertical subsampling)
+  const int y0 = ty * ROWS, x0 = tx * PX;
+  T (*ldsc)[2 * G::RCC] = reinterpret_cast < T (*)[2 * G::RCC] > (&lds[0][0]);
+
+  constexpr int NPSY = band_nps < T, RP, G::RCY > (), NPSC = band_nps < T, RP, G::RCC > ();
+  uint2 vy[4][NPSY], vu[4][NPSC], vv[4][NPSC];
+  pack8_load < F, AYUV, 0, G::RCY, G::UCY, NPSY > (vy, job, tid, r0, tx);
+  if (job.pred[0]) {
+    const int cw = (job.out_w + CS) >> CS;
+    pack8_stage_pred < ROWS, PX > (&s_y[0][0], job.pred[0], job.pred_stride[0], tid, x0, y0, job.out_w, job.out_h);
+    pack8_stage_pred < ROWS, PXC > (&s_c[0][0][0], job.pred[1], job.pred_stride[1], tid, x0 >> CS, y0, cw, job.out_h);
+    pack8_stage_pred < ROWS, PXC > (&s_c[1][0][0], job.pred[2], job.pred_stride[2], tid, x0 >> CS, y0, cw, job.out_h);
+  }
+  pack8_load < F, AYUV, 1, G::RCC, G::UCC, NPSC > (vu, job, tid, r0, tx);
+  pack8_lift < F, AYUV, 0, G::RCY, G::UCY, NPSY > (lds, vy, job, tid, r0, tx, &s_y[0][0], PX);
+  __syncthreads ();
+  pack8_load < F, AYUV, 2, G::RCC, G::UCC, NPSC > (vv, job, tid, r0, tx);
+  pack8_lift < F, AYUV, 1, G::RCC, G::UCC, NPSC > (ldsc, vu, job, tid, r0, tx, &s_c[0][0][0], PXC);
+  __syncthreads ();
+  pack8_lift < F, AYUV, 2, G::RCC, G::UCC, NPSC > (ldsc, vv, job, tid, r0, tx, &s_c[1][0][0], PXC);
+  __syncthreads ();
+
+  // ---- pack: a task = one 16-byte group of one row (pack_yuyv / _uyvy / _ayuv, schrovirtframe.c:943-991, :1230-1247) ----
+  const int rows = min (ROWS, job.out_h - y0);
+  if constexpr (AYUV) {
+    constexpr int GPR = PX / 4;         // 4 pixels per group
+    for (int task = tid; task < rows * GPR; task += kThreads) {
+      const int y = task / GPR, g = task - y * GPR;
+      const int n = min (4, job.out_w - (x0 + 4 * g));  // pixels of the picture in this group
+      if (n <= 0)
+        continue;
+      const uint32_t yy = *reinterpret_cast < const uint32_t * >(&s_y[y][4 * g]);
+      const uint32_t uu = *reinterpret_cast < const uint32_t * >(&s_c[0][y][4 * g]);
+      const uint32_t vv4 = *reinterpret_cast < const uint32_t * >(&s_c[1][y][4 * g]);
+      uint32_t o[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++)
+        o[k] = 0xffu | (((yy >> (8 * k)) & 0xffu) << 8) | (((uu >> (8 * k)) & 0xffu) << 16) | (((vv4 >> (8 * k)) & 0xffu) << 24);
+      char *d = (char *) job.dst + (size_t) (y0 + y) * job.dst_stride + (size_t) (x0 + 4 * g) * 4;
+      if (n == 4) {
+        __builtin_nontemporal_store ((u32x4) { o[0], o[1], o[2], o[3] }, (SCHRO_GLOBAL u32x4 *) d);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+          if (k < n)
+            gstore < uint32_t > (d + 4 * k, o[k]);
+      }
+    }
+  } else {
+    constexpr int GPR = PX / 8;         // 4 pixel pairs per group
+    const bool yuyv = !(job.flags & 8);
+    const int pairs = job.out_w >> 1;   // (an odd width's last column is not packed, as pack_u8 leaves it)
+    for (int task = tid; task < rows * GPR; task += kThreads) {
+      const int y = task / GPR, g = task - y * GPR;
+      const int n = min (4, pairs - (x0 / 2 + 4 * g));
+      if (n <= 0)
+        continue;
+      const u32x2 yy = *reinterpret_cast < const u32x2 * >(&s_y[y][8 * g]);
+      const uint32_t uu = *reinterpret_cast < const uint32_t * >(&s_c[0][y][4 * g]);
+      const uint32_t vv4 = *reinterpret_cast < const uint32_t * >(&s_c[1][y][4 * g]);
+      // (Y0 U Y1 V) or (U Y0 V Y1) per pair, as pack_kernel (frameops.hip) builds them
+      const uint32_t uv01 = __builtin_amdgcn_perm (vv4, uu, 0x05010400u);       // u0 v0 u1 v1
+      const uint32_t uv23 = __builtin_amdgcn_perm (vv4, uu, 0x07030602u);       // u2 v2 u3 v3
+      uint32_t o[4];
+      if (yuyv) {
+        o[0] = __builtin_amdgcn_perm (uv01, yy.x, 0x05010400u);
+        o[1] = __builtin_amdgcn_perm (uv01, yy.x, 0x07030602u);
+        o[2] = __builtin_amdgcn_perm (uv23, yy.y, 0x05010400u);
+        o[3] = __builtin_amdgcn_perm (uv23, yy.y, 0x07030602u);
+      } else {
+        o[0] = __builtin_amdgcn_perm (yy.x, uv01, 0x05010400u);
+        o[1] = __builtin_amdgcn_perm (yy.x, uv01, 0x07030602u);
+        o[2] = __builtin_amdgcn_perm (yy.y, uv23, 0x05010400u);
+        o[3] = __builtin_amdgcn_perm (yy.y, uv23, 0x07030602u);
+      }
+      char *d = (char *) job.dst + (size_t) (y0 + y) * job.dst_stride + (size_t) (x0 / 8 + g) * 16;
+      if (n == 4) {
+        __builtin_nontemporal_store ((u32x4) { o[0], o[1], o[2], o[3] }, (SCHRO_GLOBAL u32x4 *) d);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+          if (k < n)
+            gstore < uint32_t > (d + 4 * k, o[k]);
+      }
+    }
+  }
+}
+
+template < int F, int AYUV >
+int
+launch_pack8_one (hipStream_t stream, const Pack8Job * d_jobs, int njobs, int total_tiles)
+{
+  SCHRO_LAUNCH ((iiwt_pack8_kernel < F, AYUV >), dim3 (total_tiles), dim3 (kThreads), 0, stream, d_jobs, njobs);
+  hipError_t e = hipGetLastError ();
+  if (e != hipSuccess)
+    return set_error (SCHRO_HIP_EDEVICE, "iiwt + packed u8 launch: %s", hipGetErrorString (e));
+  return 0;
+}
+
+template < int AYUV >
+int
+launch_pack8_filter (hipStream_t stream, const Pack8Job * d_jobs, int njobs, int total_tiles, int filter)
+{
+  switch (filter) {
+    case 0: return launch_pack8_one < 0, AYUV > (stream, d_jobs, njobs, total_tiles);
+    case 1: return launch_pack8_one < 1, AYUV > (stream, d_jobs, njobs, total_tiles);
+    case 2: return launch_pack8_one < 2, AYUV > (stream, d_jobs, njobs, total_tiles);
+    case 3: return launch_pack8_one < 3, AYUV > (stream, d_jobs, njobs, total_tiles);
+    case 4: return launch_pack8_one < 4, AYUV > (stream, d_jobs, njobs, total_tiles);
+    case 5: return launch_pack8_one < 5, AYUV > (stream, d_jobs, njobs, total_tiles);
+    case 6: return launch_pack8_one < 6, AYUV > (stream, d_jobs, njobs, total_tiles);
+  }
+  return set_error (SCHRO_HIP_EINVAL, "wavelet filter index %d out of range", filter);
+}
+
+template < int AYUV >
+void
+pack8_geometry (int filter, int *cols, int *rows)
+{
+  *cols = P8Geo < 0, AYUV >::PX;
+  *rows = 2 * (P8Geo < 0, AYUV >::RP - 2 * filter_halo (filter));
+}
+
 template < typename T, int F >
 int
 launch_one (hipStream_t stream, const IwtJob * d_jobs, int njobs, int total_tiles)
@@ -1038,6 +1314,23 @@ launch_iiwt_v210 (hipStream_t stream, const V210Job * d_jobs, int njobs, int tot
   if (bpp == 2)
     return launch_v210_filter < int16_t > (stream, d_jobs, njobs, total_tiles, filter);
   return launch_v210_filter < int32_t > (stream, d_jobs, njobs, total_tiles, filter);
+}
+
+void
+iiwt_pack8_geometry (int filter, int ayuv, int *cols, int *rows)
+{
+  if (ayuv)
+    pack8_geometry < 1 > (filter, cols, rows);
+  else
+    pack8_geometry < 0 > (filter, cols, rows);
+}
+
+int
+launch_iiwt_pack8 (hipStream_t stream, const Pack8Job * d_jobs, int njobs, int total_tiles, int filter, int ayuv)
+{
+  if (ayuv)
+    return launch_pack8_filter < 1 > (stream, d_jobs, njobs, total_tiles, filter);
+  return launch_pack8_filter < 0 > (stream, d_jobs, njobs, total_tiles, filter);
 }
 
 size_t

@@ -260,3 +260,252 @@ schro_hip_v210_routes (SchroHipContext * ctx, long long counts[SCHRO_HIP_V210_RO
   }
   return 0;
 }
+
+// ---- 8-bit packed output: YUYV / UYVY / AYUV (schro_hip.h: schro_hip_iiwt_pack_u8_batch) ---------------------------
+// The chain the call replaces for a picture that is not a reference: schro_hip_iiwt_batch in its combine form (the planar u8
+// picture: + 128, or + the prediction), then schro_hip_pack_u8_batch -- 10 bytes per 4:2:2 pixel with a prediction where
+// the coefficients, the prediction and the packed rows are 6.  Routes, per picture (schro_hip_pack8_routes):
+//   LEVEL     s16, the source's chroma format the packed format's own, the alignments of the header: levels depth-1 .. 1
+//             into compact LL planes in the queue's block, then ONE launch of iiwt_pack8_kernel (iiwt.hip) for all
+//             such YUYV / UYVY pictures of the call and one for its AYUV pictures.
+//   TWO_PASS  every other picture: the planar picture in the queue's block (one combine-form transform call for all of
+//             them), then one pack launch.
+//             Also the filters for which 8 x 2160p per call did NOT measure faster on LEVEL than on the chain by more
+//             than the round-to-round spread, with and without a prediction (profiles/r09_pack8_fused.txt; below ms per
+//             call with a prediction, level / chain): their chain ends in the register kernel's combine form, the level
+//             route in the LDS tile.  4:2:2 -> YUYV / UYVY: DD(9,7) 0.216 / 0.193, LeGall 0.204 / 0.203, DD(13,7)
+//             0.235 / 0.223, Daub(9,7) 0.304 / 0.227 keep the two passes (Haar 0.163 / 0.199 and Fidelity 0.423 / 0.719
+//             take LEVEL); 4:4:4 -> AYUV: DD(9,7) 0.294 / 0.364 and DD(13,7) 0.339 / 0.403 (gains of 19 % and 16 %
+//             inside the 20 % spread of their rounds) and Daub(9,7) 0.421 / 0.412 keep them (LeGall 0.277 / 0.384,
+//             Haar 0.245 / 0.382, Fidelity 0.582 / 1.127 take LEVEL).
+//             (experiments library: SCHRO_HIP_PACK8_TWO_PASS=1 sends every picture here, SCHRO_HIP_PACK8_LEVEL=1 lets
+//             every filter take LEVEL, for A/B runs and the tests of those kernels.)
+static bool
+pack8_level_filter (int filter, bool ayuv)
+{
+  return ayuv ? (filter == 1 || (filter >= 3 && filter <= 5)) : (filter >= 3 && filter <= 5);
+}
+
+static bool
+pack8_apart (const void *a, size_t an, const void *b, size_t bn)
+{
+  const char *a0 = (const char *) a, *b0 = (const char *) b;
+  return a0 + an <= b0 || b0 + bn <= a0;
+}
+
+extern "C" int
+schro_hip_iiwt_pack_u8_batch (SchroHipContext * ctx, const SchroHipIwtPack8Picture * pictures, int npictures, int depth, int filter,
+    int bytes_per_sample)
+{
+  SCHRO_HIP_REQUIRE (ctx && pictures && npictures > 0 && 3 * npictures <= kMaxJobs, "iiwt_pack_u8_batch: bad arguments");
+  SCHRO_HIP_REQUIRE (depth >= 1 && depth <= 6 && filter >= 0 && filter <= 6 && (bytes_per_sample == 2 || bytes_per_sample == 4),
+      "iiwt_pack_u8_batch: depth %d, filter %d, %d bytes per sample", depth, filter, bytes_per_sample);
+  (void) hipSetDevice (ctx->device);
+  const int bps = bytes_per_sample;
+  const bool level_on = !(SCHRO_ENV ("SCHRO_HIP_PACK8_TWO_PASS") && atoi (SCHRO_ENV ("SCHRO_HIP_PACK8_TWO_PASS")) != 0);
+  const bool level_all = SCHRO_ENV ("SCHRO_HIP_PACK8_LEVEL") && atoi (SCHRO_ENV ("SCHRO_HIP_PACK8_LEVEL")) != 0;
+  auto comp_w = [](const SchroHipIwtPack8Picture & pic, int c, int w) { return c ? (w + pic.h_shift) >> pic.h_shift : w; };
+  auto comp_h = [](const SchroHipIwtPack8Picture & pic, int c, int h) { return c ? (h + pic.v_shift) >> pic.v_shift : h; };
+  std::vector < char >level ((size_t) npictures, 0);
+  int nlevel = 0;
+  for (int p = 0; p < npictures; p++) {
+    const SchroHipIwtPack8Picture & pic = pictures[p];
+    SCHRO_HIP_REQUIRE (pic.format == SCHRO_HIP_FORMAT_YUYV || pic.format == SCHRO_HIP_FORMAT_UYVY || pic.format == SCHRO_HIP_FORMAT_AYUV,
+        "iiwt_pack_u8_batch: picture %d: format 0x%x is not YUYV / UYVY / AYUV", p, pic.format);
+    const bool ayuv = pic.format == SCHRO_HIP_FORMAT_AYUV;
+    SCHRO_HIP_REQUIRE (pic.src[0] && pic.src[1] && pic.src[2] && pic.dst && pic.width > 0 && pic.height > 0
+        && pic.out_width > 0 && pic.out_height > 0 && pic.out_width <= pic.width && pic.out_height <= pic.height
+        && pic.dst_stride >= (ayuv ? 4 * pic.out_width : 4 * (pic.out_width / 2)), "iiwt_pack_u8_batch: picture %d: bad geometry", p);
+    SCHRO_HIP_REQUIRE ((pic.h_shift == 0 || pic.h_shift == 1) && (pic.v_shift == 0 || pic.v_shift == 1) && !(pic.v_shift && !pic.h_shift),
+        "iiwt_pack_u8_batch: picture %d: chroma format not 4:4:4 / 4:2:2 / 4:2:0", p);
+    const bool has_pred = pic.pred[0] != nullptr;
+    SCHRO_HIP_REQUIRE ((pic.pred[1] != nullptr) == has_pred && (pic.pred[2] != nullptr) == has_pred,
+        "iiwt_pack_u8_batch: picture %d: a prediction for some components and not for others", p);
+    bool fits = bps == 2 && level_on && (level_all || pack8_level_filter (filter, ayuv)) && pic.v_shift == 0 && pic.h_shift == (ayuv ? 0 : 1)
+        && ((((uintptr_t) pic.dst | (uintptr_t) pic.dst_stride) & 15) == 0);
+    const size_t dst_bytes = (size_t) pic.dst_stride * pic.out_height;
+    for (int c = 0; c < 3; c++) {
+      // (what schro_hip_iiwt_batch asks of every component: whole transform levels, rows that hold the component)
+      const int w = c ? pic.width >> pic.h_shift : pic.width, h = c ? pic.height >> pic.v_shift : pic.height;
+      SCHRO_HIP_REQUIRE (w % (1 << depth) == 0 && h % (1 << depth) == 0 && w > 0 && h > 0 && (w << (c ? pic.h_shift : 0)) == pic.width
+          && (h << (c ? pic.v_shift : 0)) == pic.height,
+          "iiwt_pack_u8_batch: picture %d component %d: size %dx%d is not a multiple of 2^depth", p, c, w, h);
+      SCHRO_HIP_REQUIRE (pic.src_stride[c] >= w * bps,
+          "iiwt_pack_u8_batch: picture %d component %d: stride %d does not hold %d samples", p, c, pic.src_stride[c], w);
+      const int ow = comp_w (pic, c, pic.out_width), oh = comp_h (pic, c, pic.out_height);
+      SCHRO_HIP_REQUIRE (!has_pred || pic.pred_stride[c] >= ow,
+          "iiwt_pack_u8_batch: picture %d component %d: prediction stride %d does not hold %d samples", p, c, pic.pred_stride[c], ow);
+      fits = fits && ((((uintptr_t) pic.src[c] | (uintptr_t) pic.src_stride[c]) & (bps - 1)) == 0)
+          && pack8_apart (pic.dst, dst_bytes, pic.src[c], (size_t) pic.src_stride[c] * h);
+      if (has_pred)
+        fits = fits && ((((uintptr_t) pic.pred[c] | (uintptr_t) pic.pred_stride[c]) & 7) == 0) && pic.pred_stride[c] >= ((ow + 7) & ~7)
+            && pack8_apart (pic.dst, dst_bytes, pic.pred[c], (size_t) pic.pred_stride[c] * oh);
+    }
+    level[(size_t) p] = fits;
+    nlevel += fits;
+  }
+  // the queue's grow-only block (shared with the v210 call: in-order reuse on the queue): per level picture the three
+  // compact LL planes of level 0 (depth > 1), per two-pass picture its three u8 planes
+  auto ll_stride = [&](int w) { return (int) round_up ((size_t) (w >> 1) * bps, 128); };
+  size_t need = 0;
+  for (int p = 0; p < npictures; p++)
+    for (int c = 0; c < 3; c++) {
+      const SchroHipIwtPack8Picture & pic = pictures[p];
+      if (!level[(size_t) p])
+        need += round_up (round_up ((size_t) comp_w (pic, c, pic.out_width), 64) * (size_t) comp_h (pic, c, pic.out_height), 256);
+      else if (depth > 1)
+        need += round_up ((size_t) ll_stride (c ? pic.width >> pic.h_shift : pic.width) * (size_t) (pic.height >> 1), 256);
+    }
+  const int q = ctx->cur;
+  if (ctx->pack_tmp_size_q[q] < need) {
+    if (ctx->pack_tmp_q[q]) {
+      SCHRO_HIP_CHECK (hipStreamSynchronize (ctx->stream));
+      SCHRO_HIP_CHECK (hipFree (ctx->pack_tmp_q[q]));
+      ctx->pack_tmp_q[q] = nullptr;
+      ctx->pack_tmp_size_q[q] = 0;
+    }
+    SCHRO_HIP_CHECK (hipMalloc (&ctx->pack_tmp_q[q], need));
+    ctx->pack_tmp_size_q[q] = need;
+  }
+  size_t at = 0;
+  int r = 0;
+
+  // ---- the level route: levels depth-1 .. 1 by the level loop into the LL planes, then the finest level + pack ----
+  if (nlevel) {
+    std::vector < SchroHipIwtPlane > coarse;
+    std::vector < Pack8Job > pj[2];     // [0] YUYV / UYVY, [1] AYUV: one launch each
+    int tiles[2] = { 0, 0 };
+    for (int p = 0; p < npictures; p++) {
+      if (!level[(size_t) p])
+        continue;
+      const SchroHipIwtPack8Picture & pic = pictures[p];
+      const int ayuv = pic.format == SCHRO_HIP_FORMAT_AYUV;
+      int cols, rows;
+      iiwt_pack8_geometry (filter, ayuv, &cols, &rows);
+      Pack8Job j;
+      memset (&j, 0, sizeof (j));
+      for (int c = 0; c < 3; c++) {
+        const int w = c ? pic.width >> pic.h_shift : pic.width, h = pic.height;
+        j.src[c] = pic.src[c];
+        j.src_stride[c] = pic.src_stride[c];
+        j.pred[c] = pic.pred[c];
+        j.pred_stride[c] = pic.pred_stride[c];
+        if (depth > 1) {
+          // the level-1 view of the coefficient frame {w / 2, h / 2, stride x 2} (schroparams.c:319-352), depth - 1 levels
+          void *t = (char *) ctx->pack_tmp_q[q] + at;
+          at += round_up ((size_t) ll_stride (w) * (size_t) (h >> 1), 256);
+          SchroHipIwtPlane pl;
+          memset (&pl, 0, sizeof (pl));
+          pl.src = pic.src[c];
+          pl.src_stride = 2 * pic.src_stride[c];
+          pl.dst = t;
+          pl.dst_stride = ll_stride (w);
+          pl.width = w >> 1;
+          pl.height = h >> 1;
+          coarse.push_back (pl);
+          j.ll[c] = t;
+          j.ll_stride[c] = ll_stride (w);
+        } else {
+          j.ll[c] = pic.src[c];             // (the frame's LL quadrant)
+          j.ll_stride[c] = 2 * pic.src_stride[c];
+        }
+        // 8-byte loads of the four bands: whole groups of samples per row, 8-byte aligned rows and band origins
+        const int nc = w >> 1, vl = 8 / bps;
+        const uintptr_t bits = (uintptr_t) j.ll[c] | (uintptr_t) j.ll_stride[c] | (uintptr_t) pic.src[c] | (uintptr_t) pic.src_stride[c]
+            | (uintptr_t) nc * bps;
+        if (nc % vl == 0 && nc >= vl && (bits & 7) == 0)
+          j.flags |= 1 << c;
+      }
+      if (pic.format == SCHRO_HIP_FORMAT_UYVY)
+        j.flags |= 8;
+      j.w = pic.width;
+      j.h = pic.height;
+      j.out_w = pic.out_width;
+      j.out_h = pic.out_height;
+      j.dst = pic.dst;
+      j.dst_stride = pic.dst_stride;
+      j.tiles_x = div_up (pic.out_width, cols);
+      j.tile_base = tiles[ayuv];
+      tiles[ayuv] += j.tiles_x * div_up (pic.out_height, rows);
+      pj[ayuv].push_back (j);
+    }
+    if (!coarse.empty ())
+      r = schro_hip_iiwt_batch (ctx, coarse.data (), (int) coarse.size (), depth - 1, filter, bps);
+    for (int ayuv = 0; ayuv < 2 && !r; ayuv++) {
+      if (pj[ayuv].empty ())
+        continue;
+      void *d_pj = nullptr;
+      r = push_args (ctx, pj[ayuv].data (), sizeof (Pack8Job) * pj[ayuv].size (), &d_pj);
+      if (r)
+        break;
+      ProfileScope ps (ctx, SCHRO_HIP_KERNEL_IIWT_FINEST);
+      r = launch_iiwt_pack8 (ctx->stream, (const Pack8Job *) d_pj, (int) pj[ayuv].size (), tiles[ayuv], filter, ayuv);
+    }
+    if (r)
+      return r;
+    ctx->pack8_routes[SCHRO_HIP_PACK8_ROUTE_LEVEL] += nlevel;
+    if (nlevel == npictures)
+      return 0;
+  }
+
+  // ---- the two passes (the general form): the combine form into planar u8 planes, then the pack ----
+  std::vector < SchroHipIwtPlane > planes;
+  std::vector < SchroHipPackPlane > packs;
+  for (int p = 0; p < npictures; p++) {
+    if (level[(size_t) p])
+      continue;
+    const SchroHipIwtPack8Picture & pic = pictures[p];
+    SchroHipPackPlane pk;
+    memset (&pk, 0, sizeof (pk));
+    for (int c = 0; c < 3; c++) {
+      const int ow = comp_w (pic, c, pic.out_width), oh = comp_h (pic, c, pic.out_height);
+      const int stride = (int) round_up ((size_t) ow, 64);
+      void *t = (char *) ctx->pack_tmp_q[q] + at;
+      at += round_up ((size_t) stride * (size_t) oh, 256);
+      SchroHipIwtPlane pl;
+      memset (&pl, 0, sizeof (pl));
+      pl.src = pic.src[c];
+      pl.src_stride = pic.src_stride[c];
+      pl.dst = t;
+      pl.dst_stride = stride;
+      pl.width = c ? pic.width >> pic.h_shift : pic.width;
+      pl.height = c ? pic.height >> pic.v_shift : pic.height;
+      pl.combine = pic.pred[0] ? 1 : 2;
+      pl.pred = pic.pred[c];
+      pl.pred_stride = pic.pred_stride[c];
+      pl.out_width = ow;
+      pl.out_height = oh;
+      planes.push_back (pl);
+      pk.src[c] = (const uint8_t *) t;
+      pk.src_stride[c] = stride;
+    }
+    pk.src_width = pic.out_width;
+    pk.src_height = pic.out_height;
+    pk.src_h_shift = pic.h_shift;
+    pk.src_v_shift = pic.v_shift;
+    pk.dst = pic.dst;
+    pk.dst_stride = pic.dst_stride;
+    pk.width = pic.out_width;
+    pk.height = pic.out_height;
+    pk.format = pic.format;
+    packs.push_back (pk);
+  }
+  r = schro_hip_iiwt_batch (ctx, planes.data (), (int) planes.size (), depth, filter, bps);
+  if (!r)
+    r = schro_hip_pack_u8_batch (ctx, packs.data (), (int) packs.size ());
+  if (!r)
+    ctx->pack8_routes[SCHRO_HIP_PACK8_ROUTE_TWO_PASS] += (long long) packs.size ();
+  return r;
+}
+
+extern "C" int
+schro_hip_pack8_routes (SchroHipContext * ctx, long long counts[SCHRO_HIP_PACK8_ROUTES], int reset)
+{
+  SCHRO_HIP_REQUIRE (ctx && counts, "pack8_routes: bad arguments");
+  for (int k = 0; k < SCHRO_HIP_PACK8_ROUTES; k++) {
+    counts[k] = ctx->pack8_routes[k];
+    if (reset)
+      ctx->pack8_routes[k] = 0;
+  }
+  return 0;
+}

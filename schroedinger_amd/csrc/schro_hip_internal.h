@@ -139,6 +139,24 @@ struct V210Job {
   int flags;                    // bit c: component c's four bands take 8-byte loads
 };
 
+// The finest level of a 4:2:2 / 4:4:4 s16 picture's inverse wavelet with the YUYV / UYVY / AYUV copy-out as its sink (iiwt.hip,
+// iiwt_pack8_kernel)
+struct Pack8Job {
+  const void *src[3];           // the coefficient planes (Y, U, V), in-place sub-band layout
+  int src_stride[3];
+  const void *ll[3];            // each component's level-0 LL band: the frame's LL quadrant (depth 1) or a compact plane
+  int ll_stride[3];
+  const uint8_t *pred[3];       // the prediction to add (rows 8-byte aligned, readable up to a multiple of 8 columns);
+  int pred_stride[3];           // pred[0] NULL: + 128 (a picture without references)
+  int w, h;                     // luma transform size (chroma: w / 2 x h for YUYV / UYVY, w x h for AYUV)
+  int out_w, out_h;             // the picture inside it
+  uint8_t *dst;                 // packed rows; dst and dst_stride 16-byte aligned
+  int dst_stride;
+  int tiles_x;
+  int tile_base;
+  int flags;                    // bit c: component c's four bands take 8-byte loads; bit 3: UYVY byte order
+};
+
 struct ConvertJob {
   const void *src;
   uint8_t *dst;
@@ -312,6 +330,16 @@ template < typename V, typename P > __device__ __forceinline__ void
 gstore (P * p, V v)
 {
   *(SCHRO_GLOBAL V *) p = v;
+}
+
+// the last steps of orc_rrshift6_add_s16_2d / _s32_2d with the prediction p = (acc + 32) >> 6 already there:
+// convlw (s32), addw (wraps), convsuswb; p = 128: orc_offsetconvert_u8_s16 / _s32 (a picture without references)
+template < typename T >
+__device__ __forceinline__ uint8_t
+combine_pred (T s, uint32_t p)
+{
+  const int v = (int16_t) ((int16_t) s + (int16_t) p);
+  return (uint8_t) min (max (v, 0), 255);
 }
 
 // n / d for 1 <= d <= 1024 and 0 <= n < 2^22 without the ~35-instruction integer division
@@ -509,6 +537,9 @@ int launch_iiwt_haar3_v210 (hipStream_t stream, const HaarPackJob * d_jobs, int 
 // iiwt.hip: the finest level + v210 copy-out of every filter (picture columns / rows per workgroup)
 void iiwt_v210_geometry (int filter, int bpp, int *cols, int *rows);
 int launch_iiwt_v210 (hipStream_t stream, const V210Job * d_jobs, int njobs, int total_tiles, int filter, int bpp);
+// iiwt.hip: the finest level + YUYV / UYVY (ayuv 0) or AYUV (ayuv 1) copy-out of every filter, s16
+void iiwt_pack8_geometry (int filter, int ayuv, int *cols, int *rows);
+int launch_iiwt_pack8 (hipStream_t stream, const Pack8Job * d_jobs, int njobs, int total_tiles, int filter, int ayuv);
 int launch_dequant (hipStream_t stream, const DequantJob * d_jobs, int njobs, int total_tiles, int bpp, int arith);
 int launch_dequant_plan (hipStream_t stream, const DequantGeo * d_geo, int njobs, int total_tiles,
     const SchroHipCodeblock * d_recs, const DequantPlaneDyn * d_planes, int bpp, int arith);
@@ -691,6 +722,8 @@ struct SchroHipContext {
   long long obmc_routes[SCHRO_HIP_OBMC_ROUTES] = {};
   // pictures handed to each route of schro_hip_iiwt_pack_v210_batch (schro_hip_v210_routes)
   long long v210_routes[SCHRO_HIP_V210_ROUTES] = {};
+  // ... of schro_hip_iiwt_pack_u8_batch (schro_hip_pack8_routes)
+  long long pack8_routes[SCHRO_HIP_PACK8_ROUTES] = {};
   int cus;                      // compute units of the device (launch shaping)
 };
 
