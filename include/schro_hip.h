@@ -231,6 +231,14 @@ int schro_hip_v210_routes (SchroHipContext * ctx, long long counts[SCHRO_HIP_V21
 #define SCHRO_HIP_PACK8_ROUTES 2
 int schro_hip_pack8_routes (SchroHipContext * ctx, long long counts[SCHRO_HIP_PACK8_ROUTES], int reset);
 
+/* The same for schro_hip_iiwt_pack_wide_batch (and so for schro_frame_inverse_iwt_transform_convert_hip /
+ * _shift_convert_hip with a v216, ARGB or AY64 frame): pictures per route, counted on the host as the launches are
+ * enqueued, nothing for a call that fails validation. */
+#define SCHRO_HIP_WIDE_ROUTE_LEVEL 0    /* iiwt.hip: the finest level shifts, converts and writes the packed rows */
+#define SCHRO_HIP_WIDE_ROUTE_TWO_PASS 1 /* the pixel frame in a scratch block, the shift, then schro_hip_pack_wide_batch's kernel */
+#define SCHRO_HIP_WIDE_ROUTES 2
+int schro_hip_wide_routes (SchroHipContext * ctx, long long counts[SCHRO_HIP_WIDE_ROUTES], int reset);
+
 /* ---- plane layer: batched launches --------------------------------------- */
 
 /* One component of one picture for the inverse wavelet.
@@ -436,6 +444,51 @@ int schro_hip_iiwt_pack_u8_batch (SchroHipContext * ctx, const SchroHipIwtPack8P
  * format must already be the destination's (the reference resamples u8 frames only). */
 int schro_hip_pack_wide_batch (SchroHipContext * ctx, const SchroHipPackPlane * planes, int nplanes,
     int src_bpp);
+
+/* The inverse wavelet of an intra picture that is not a reference, x_combine's schro_frame_shift_right (schrodecoder.c:2013-2019:
+ * the stream's bit depth above the output picture's) and the v216 / ARGB / AY64 copy-out as one call -- the formats the > 8-bit
+ * pictures go out in, whose frames are s32 (schrodecoder.c:350-352).  dst receives exactly the bytes of schro_hip_iiwt_batch into
+ * s16 / s32 pixel planes, schro_hip_shift_right_batch on them where shift != 0, then schro_hip_pack_wide_batch from them, for
+ * every input: the shift's add wraps at the sample's width, s32 is truncated to 16 bits for v216 / ARGB, s16 sign-extended
+ * for AY64, and v216 reads its s16 lines through byte pointers as pack_v216 does (rows of out_width / 2 eight-byte pairs from
+ * luma columns [0, out_width / 2) and chroma columns [0, out_width / 4)).
+ * Routes, chosen per picture and mixed freely in a call -- formats, sizes and shifts too -- (schro_hip_wide_routes counts them):
+ *   LEVEL     levels depth-1 .. 1 run into quarter-size LL planes in the queue's scratch, then ONE launch per kernel family
+ *             (v216; ARGB / AY64) lifts the finest level of Y, U and V per tile, shifts, converts and writes whole 16-byte
+ *             groups: no pixel frame, no shift launch, no pack launch.  Every filter, depth and sample type.  Taken when ALL
+ *             of these hold:
+ *               - the format x filter x sample type measured faster on this route than on the chain by more than the larger
+ *                 spread of the two forms' rounds, without a shift and with one (depth 3, 8 x 2160p per call;
+ *                 profiles/r10_wide_fused.txt; ms per call without a shift): every s32 combination (v216 DD(9,7) 0.226 against
+ *                 0.474, ARGB 0.492 against 0.728, AY64 0.508 against 0.727), every s16 filter into v216 (DD(9,7) 0.143
+ *                 against 0.250), s16 filters 0, 1, 3, 4 into ARGB (DD(9,7) 0.292 against 0.359) and 0 - 5 into AY64 (0.319
+ *                 against 0.452).  s16 filters 2, 5, 6 into ARGB and 6 into AY64 keep the two passes, whose transform ends
+ *                 in the register kernel (Daub(9,7) into ARGB: 0.430 against 0.401; into AY64 0.436 against 0.490, a gain
+ *                 inside the 21 % spread of its rounds);
+ *               - dst and dst_stride are multiples of 16 bytes;
+ *               - every src and src_stride is a multiple of bytes_per_sample;
+ *               - dst overlaps no coefficient plane;
+ *               - a v216 row holds at least one pixel pair.
+ *   TWO_PASS  everything else: the pixel planes in the queue's scratch, one shift launch per distinct non-zero shift, then the
+ *             pack kernel.
+ * Refused (SCHRO_HIP_EINVAL, nothing launched or counted): what schro_hip_iiwt_batch refuses (a component that is not a
+ * multiple of 2^depth, a src_stride shorter than a row), a chroma format that is not the packed format's own (v216: h_shift 1,
+ * v_shift 0; ARGB / AY64: 0, 0 -- as schro_hip_pack_wide_batch), out_width x out_height outside the transform, a dst_stride
+ * below the packed row (v216 8 * (out_width / 2), ARGB 4 * out_width, AY64 8 * out_width), another format, shift < 0 or
+ * >= 8 * bytes_per_sample, bytes_per_sample other than 2 or 4. */
+typedef struct {
+  const void *src[3];           /* the coefficient planes Y, U, V (device, s16 or s32), in-place sub-band layout */
+  int src_stride[3];
+  int width, height;            /* luma transform size (a multiple of 2^depth); chroma: >> h_shift, >> v_shift */
+  int h_shift, v_shift;         /* the packed format's own chroma format: 1, 0 for v216; 0, 0 for ARGB / AY64 */
+  uint8_t *dst;                 /* packed rows */
+  int dst_stride;
+  int out_width, out_height;    /* the picture inside the transform's size (crop only) */
+  int format;                   /* SCHRO_HIP_FORMAT_v216 / _ARGB / _AY64 */
+  int shift;                    /* x_combine's schro_frame_shift_right before the convert; 0: none */
+} SchroHipIwtPackWidePicture;
+int schro_hip_iiwt_pack_wide_batch (SchroHipContext * ctx, const SchroHipIwtPackWidePicture * pictures, int npictures, int depth,
+    int filter, int bytes_per_sample);
 
 
 
@@ -968,6 +1021,17 @@ int schro_frame_inverse_iwt_transform_convert_hip (SchroHipFrame * packed, Schro
  * prediction. */
 int schro_frame_inverse_iwt_transform_combine_convert_hip (SchroHipFrame * packed, SchroHipFrame * transform_frame,
     SchroHipParams * params, SchroHipFrame * prediction);
+/* `packed` may also be a v216, ARGB or AY64 device frame -- the formats of the > 8-bit pictures -- from an s16 / s32 transform
+ * frame of the format's own chroma format (4:2:2 for v216, 4:4:4 for ARGB / AY64): schro_hip_iiwt_pack_wide_batch, same bytes as
+ * schro_frame_inverse_iwt_transform_hip + schro_hipframe_convert.  With a prediction these formats are refused, like v210
+ * (the reference has no > 8-bit inter path).
+ * schro_frame_inverse_iwt_transform_shift_convert_hip is the whole non-reference intra tail of x_combine in one stage call:
+ * x_wavelet_transform, schro_frame_shift_right (frame, shift) where the stream's bit depth exceeds the output picture's
+ * (schrodecoder.c:2013-2019) and the convert -- same bytes as schro_frame_inverse_iwt_transform_hip +
+ * schro_hipframe_shift_right + schro_hipframe_convert.  v216 / ARGB / AY64 take any shift in [0, 8 * bytes per sample); for
+ * the other packed formats shift 0 is schro_frame_inverse_iwt_transform_convert_hip and another shift SCHRO_HIP_EINVAL. */
+int schro_frame_inverse_iwt_transform_shift_convert_hip (SchroHipFrame * packed, SchroHipFrame * transform_frame,
+    SchroHipParams * params, int shift);
 
 /* schro_decoder_decode_lowdelay_transform_data (picture), schrolowdelay.c:746-762, with
  * picture->transform_frame on the device: `slices` is picture->lowdelay_buffer->data (host),

@@ -319,6 +319,16 @@ class Context:
         check(self.lib.schro_hip_pack8_routes(self.h, counts, 1 if reset else 0))
         return dict(zip(self.PACK8_ROUTES, (int(n) for n in counts)))
 
+    WIDE_ROUTES = ("level", "two_pass")                      # SCHRO_HIP_WIDE_ROUTE_* (include/schro_hip.h)
+
+    def wide_routes(self, reset=False):
+        """{route: pictures} this context's iiwt_pack_wide calls have handed to each route (schro_hip_wide_routes): "level" the
+        finest level shifting, converting and writing the packed rows (iiwt_wide_kernel), "two_pass" the pixel frame in a
+        scratch block, the shift and the pack; reset: start the counts again from zero after reading them."""
+        counts = (C.c_longlong * len(self.WIDE_ROUTES))()
+        check(self.lib.schro_hip_wide_routes(self.h, counts, 1 if reset else 0))
+        return dict(zip(self.WIDE_ROUTES, (int(n) for n in counts)))
+
     def plane(self, height, width, dtype, stride=None):
         return DevicePlane(self, height, width, dtype, stride)
 
@@ -436,6 +446,24 @@ class Context:
             a.dst, a.dst_stride = dst.ptr, dst.stride
             a.out_width, a.out_height, a.format = w, h, fmt
         check(self.lib.schro_hip_iiwt_pack_u8_batch(self.h, arr, n, depth, filt, bpp))
+
+    def iiwt_pack_wide_batch(self, jobs, depth, filt):
+        """The inverse wavelet, schro_frame_shift_right and the v216 / ARGB / AY64 copy-out in one call.  jobs: (coefficient
+        planes [Y, U, V] of one dtype (s16 / s32), h_shift, v_shift, dst plane of bytes, picture width, picture height, format,
+        shift) per picture; planes: DevicePlanes or SubPlanes."""
+        n = len(jobs)
+        arr = (_lib.IwtPackWidePicture * n)()
+        bpp = jobs[0][0][0].dtype.itemsize
+        for a, (planes, hs, vs, dst, w, h, fmt, shift) in zip(arr, jobs):
+            for k in range(3):
+                assert planes[k].dtype.itemsize == bpp
+                a.src[k] = planes[k].ptr
+                a.src_stride[k] = planes[k].stride
+            a.width, a.height = planes[0].width, planes[0].height
+            a.h_shift, a.v_shift = hs, vs
+            a.dst, a.dst_stride = dst.ptr, dst.stride
+            a.out_width, a.out_height, a.format, a.shift = w, h, fmt, shift
+        check(self.lib.schro_hip_iiwt_pack_wide_batch(self.h, arr, n, depth, filt, bpp))
 
     def pack_wide_batch(self, jobs):
         """jobs: (planes [Y, U, V] DevicePlanes of one dtype, h_shift, v_shift, dst DevicePlane of

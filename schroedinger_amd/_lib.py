@@ -33,11 +33,12 @@ EXPORTED_SYMBOLS = [
     "schro_hip_queue_mark", "schro_hip_queue_wait_mark",
     "schro_hip_timer_begin", "schro_hip_timer_end",
     "schro_hip_profile_enable", "schro_hip_profile_reset", "schro_hip_profile_read", "schro_hip_obmc_routes",
-    "schro_hip_v210_routes", "schro_hip_pack8_routes",
+    "schro_hip_v210_routes", "schro_hip_pack8_routes", "schro_hip_wide_routes",
     "schro_hip_iiwt_batch", "schro_hip_convert_u8_batch", "schro_hip_upsample_batch",
     "schro_hip_upsampled_bytes", "schro_hip_upsampled_download", "schro_hip_upsampled_pair_bytes",
     "schro_hip_upsampled_pair_download", "schro_hip_pack_u8_batch",
     "schro_hip_pack_v210_batch", "schro_hip_iiwt_pack_v210_batch", "schro_hip_iiwt_pack_u8_batch", "schro_hip_pack_wide_batch", "schro_hip_shift_right_batch",
+    "schro_hip_iiwt_pack_wide_batch",
     "schro_hipframe_shift_right", "schro_hip_add_batch", "schro_hipframe_add",
     "schro_hip_lowdelay_arith", "schro_hip_lowdelay_batch", "schro_hip_dc_predict_batch",
     "schro_hip_dequant_batch",
@@ -46,7 +47,8 @@ EXPORTED_SYMBOLS = [
     "schro_hip_frame_new_and_alloc", "schro_hip_frame_ref", "schro_hip_frame_unref",
     "schro_frame_to_hip", "schro_hipframe_to_cpu",
     "schro_frame_inverse_iwt_transform_hip", "schro_frame_inverse_iwt_transform_combine_hip", "schro_frame_inverse_iwt_transform_convert_hip",
-    "schro_frame_inverse_iwt_transform_combine_convert_hip", "schro_upsampled_hipframe_upsample",
+    "schro_frame_inverse_iwt_transform_combine_convert_hip", "schro_frame_inverse_iwt_transform_shift_convert_hip",
+    "schro_upsampled_hipframe_upsample",
     "schro_motion_render_hip", "schro_hipframe_convert",
 ]
 
@@ -85,6 +87,12 @@ class IwtPack8Picture(C.Structure):
                 ("h_shift", C.c_int), ("v_shift", C.c_int), ("pred", C.c_void_p * 3), ("pred_stride", C.c_int * 3),
                 ("dst", C.c_void_p), ("dst_stride", C.c_int), ("out_width", C.c_int), ("out_height", C.c_int),
                 ("format", C.c_int)]
+
+
+class IwtPackWidePicture(C.Structure):
+    _fields_ = [("src", C.c_void_p * 3), ("src_stride", C.c_int * 3), ("width", C.c_int), ("height", C.c_int),
+                ("h_shift", C.c_int), ("v_shift", C.c_int), ("dst", C.c_void_p), ("dst_stride", C.c_int),
+                ("out_width", C.c_int), ("out_height", C.c_int), ("format", C.c_int), ("shift", C.c_int)]
 
 
 class LowDelayParams(C.Structure):
@@ -351,6 +359,8 @@ def load():
     L.schro_hip_v210_routes.restype = i
     L.schro_hip_pack8_routes.argtypes = [vp, C.POINTER(C.c_longlong), i]
     L.schro_hip_pack8_routes.restype = i
+    L.schro_hip_wide_routes.argtypes = [vp, C.POINTER(C.c_longlong), i]
+    L.schro_hip_wide_routes.restype = i
     L.schro_hip_iiwt_batch.argtypes = [vp, C.POINTER(IwtPlane), i, i, i, i]
     L.schro_hip_iiwt_batch.restype = i
     L.schro_hip_convert_u8_batch.argtypes = [vp, C.POINTER(ConvertPlane), i, i]
@@ -365,6 +375,8 @@ def load():
     L.schro_hip_iiwt_pack_v210_batch.restype = i
     L.schro_hip_iiwt_pack_u8_batch.argtypes = [vp, C.POINTER(IwtPack8Picture), i, i, i, i]
     L.schro_hip_iiwt_pack_u8_batch.restype = i
+    L.schro_hip_iiwt_pack_wide_batch.argtypes = [vp, C.POINTER(IwtPackWidePicture), i, i, i, i]
+    L.schro_hip_iiwt_pack_wide_batch.restype = i
     L.schro_hip_lowdelay_arith.argtypes = [C.POINTER(LowDelayParams), i]
     L.schro_hip_lowdelay_arith.restype = i
     L.schro_hip_lowdelay_batch.argtypes = [vp, C.POINTER(LowDelayPicture), i, C.POINTER(LowDelayParams), i]
@@ -422,6 +434,8 @@ def load():
     L.schro_frame_inverse_iwt_transform_combine_convert_hip.argtypes = [C.POINTER(Frame), C.POINTER(Frame), C.POINTER(Params),
                                                                         C.POINTER(Frame)]
     L.schro_frame_inverse_iwt_transform_combine_convert_hip.restype = i
+    L.schro_frame_inverse_iwt_transform_shift_convert_hip.argtypes = [C.POINTER(Frame), C.POINTER(Frame), C.POINTER(Params), i]
+    L.schro_frame_inverse_iwt_transform_shift_convert_hip.restype = i
     L.schro_upsampled_hipframe_upsample.argtypes = [C.POINTER(Frame), C.POINTER(Frame)]
     L.schro_upsampled_hipframe_upsample.restype = i
     L.schro_motion_render_hip.argtypes = [C.POINTER(Motion), C.POINTER(Frame), C.POINTER(Frame), i,

@@ -469,6 +469,40 @@ inverse_iwt_transform_pack8 (SchroHipFrame * packed, SchroHipFrame * transform_f
   return stage_done (ctx, schro_hip_iiwt_pack_u8_batch (ctx, &pic, 1, params->transform_depth, params->wavelet_filter_index, bpp));
 }
 
+// ... and into a v216, ARGB or AY64 output picture -- the > 8-bit formats, no prediction (the reference has no > 8-bit inter
+// path) --, with x_combine's schro_frame_shift_right (schrodecoder.c:2013-2019) in the same call: schro_hip_iiwt_pack_wide_batch.
+static int
+inverse_iwt_transform_wide (SchroHipFrame * packed, SchroHipFrame * transform_frame, SchroHipParams * params, int shift)
+{
+  SchroHipContext *ctx = frame_ctx (packed);
+  const int bpp = format_bpp (transform_frame->format);
+  SCHRO_HIP_REQUIRE (bpp == 2 || bpp == 4, "inverse_iwt_transform_convert: the transform frame must be s16 or s32");
+  SchroHipIwtPackWidePicture pic;
+  memset (&pic, 0, sizeof (pic));
+  pic.width = params->iwt_luma_width;
+  pic.height = params->iwt_luma_height;
+  pic.h_shift = SCHRO_HIP_FORMAT_H_SHIFT (transform_frame->format);
+  pic.v_shift = SCHRO_HIP_FORMAT_V_SHIFT (transform_frame->format);
+  SCHRO_HIP_REQUIRE ((params->iwt_chroma_width << pic.h_shift) == pic.width && (params->iwt_chroma_height << pic.v_shift) == pic.height,
+      "inverse_iwt_transform_convert: params' chroma transform size is not the luma size shifted by the frame's chroma format");
+  SCHRO_HIP_REQUIRE (packed->width <= pic.width && packed->height <= pic.height,
+      "inverse_iwt_transform_convert: the packed frame is larger than the transform");
+  for (int k = 0; k < 3; k++) {
+    pic.src[k] = transform_frame->components[k].data;
+    pic.src_stride[k] = transform_frame->components[k].stride;
+    const int w = k ? params->iwt_chroma_width : params->iwt_luma_width, h = k ? params->iwt_chroma_height : params->iwt_luma_height;
+    SCHRO_HIP_REQUIRE (w <= transform_frame->components[k].width && h <= transform_frame->components[k].height,
+        "inverse_iwt_transform_convert: component %d smaller than the iwt size", k);
+  }
+  pic.dst = (uint8_t *) packed->components[0].data;
+  pic.dst_stride = packed->components[0].stride;
+  pic.out_width = packed->width;
+  pic.out_height = packed->height;
+  pic.format = packed->format;
+  pic.shift = shift;
+  return stage_done (ctx, schro_hip_iiwt_pack_wide_batch (ctx, &pic, 1, params->transform_depth, params->wavelet_filter_index, bpp));
+}
+
 int
 schro_frame_inverse_iwt_transform_combine_convert_hip (SchroHipFrame * packed, SchroHipFrame * transform_frame, SchroHipParams * params,
     SchroHipFrame * prediction)
@@ -477,8 +511,11 @@ schro_frame_inverse_iwt_transform_combine_convert_hip (SchroHipFrame * packed, S
       "inverse_iwt_transform_convert: the packed frame and the transform frame must live in the same device domain");
   if (packed->format == SCHRO_HIP_FORMAT_YUYV || packed->format == SCHRO_HIP_FORMAT_UYVY || packed->format == SCHRO_HIP_FORMAT_AYUV)
     return inverse_iwt_transform_pack8 (packed, transform_frame, params, prediction);
-  SCHRO_HIP_REQUIRE (packed->format == SCHRO_HIP_FORMAT_v210 && !prediction, "inverse_iwt_transform_convert: the destination must be a "
-      "YUYV, UYVY, AYUV or (without a prediction) v210 frame (other formats: schro_frame_inverse_iwt_transform_hip + schro_hipframe_convert)");
+  SCHRO_HIP_REQUIRE ((packed->format == SCHRO_HIP_FORMAT_v210 || is_wide_format (packed->format)) && !prediction,
+      "inverse_iwt_transform_convert: the destination must be a YUYV, UYVY, AYUV or (without a prediction: the reference has no "
+      "> 8-bit inter path) v210, v216, ARGB or AY64 frame");
+  if (is_wide_format (packed->format))
+    return inverse_iwt_transform_wide (packed, transform_frame, params, 0);
   SchroHipContext *ctx = frame_ctx (packed);
   const int bpp = format_bpp (transform_frame->format);
   SCHRO_HIP_REQUIRE (bpp == 2 || bpp == 4, "inverse_iwt_transform_convert: the transform frame must be s16 or s32");
@@ -504,6 +541,20 @@ schro_frame_inverse_iwt_transform_combine_convert_hip (SchroHipFrame * packed, S
 int
 schro_frame_inverse_iwt_transform_convert_hip (SchroHipFrame * packed, SchroHipFrame * transform_frame, SchroHipParams * params)
 {
+  return schro_frame_inverse_iwt_transform_combine_convert_hip (packed, transform_frame, params, nullptr);
+}
+
+// the whole non-reference intra tail of x_combine (schrodecoder.c:2009-2021: schro_frame_shift_right where the stream's bit
+// depth exceeds the output picture's, then schro_frame_convert) behind x_wavelet_transform, in one stage call
+int
+schro_frame_inverse_iwt_transform_shift_convert_hip (SchroHipFrame * packed, SchroHipFrame * transform_frame, SchroHipParams * params, int shift)
+{
+  SCHRO_HIP_REQUIRE (packed && transform_frame && params && frame_ctx (packed) && transform_frame->domain == packed->domain,
+      "inverse_iwt_transform_shift_convert: the packed frame and the transform frame must live in the same device domain");
+  if (is_wide_format (packed->format))
+    return inverse_iwt_transform_wide (packed, transform_frame, params, shift);
+  SCHRO_HIP_REQUIRE (shift == 0, "inverse_iwt_transform_shift_convert: a shift of %d with a format other than v216 / ARGB / AY64 "
+      "(schro_frame_inverse_iwt_transform_hip + schro_hipframe_shift_right + schro_hipframe_convert)", shift);
   return schro_frame_inverse_iwt_transform_combine_convert_hip (packed, transform_frame, params, nullptr);
 }
 

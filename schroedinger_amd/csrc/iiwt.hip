@@ -1150,6 +1150,262 @@ pack8_geometry (int filter, int *cols, int *rows)
   *rows = 2 * (P8Geo < 0, AYUV >::RP - 2 * filter_halo (filter));
 }
 
+// ---- the finest level with the v216 / ARGB / AY64 copy-out as its sink --------------------------------------------
+// The > 8-bit twin of the two kernels above, s16 and s32: one workgroup owns 2 * UR picture rows x PX luma columns of all
+// three components, staged and lifted one after the other in the same LDS tile.  WideSink applies x_combine's
+// schro_frame_shift_right (at the sample's width) and brings each sample to the 16 bits the packer reads: truncated
+// (convert_s16_s32) for v216 / ARGB, clamp (x + 0x8000, 0, 0xffff) for AY64 (pack_ayuv64 on the sign-extended sample).
+// After one barrier the lanes write whole 16-byte groups (frameops.hip, pack_kernel, is the arithmetic):
+//   V216 1  a 4:2:2 source.  pack_v216 walks the s16 lines through byte pointers (schrovirtframe.c:1007-1028): output pair
+//           j takes the two bytes of Y SAMPLE j and byte j & 1 of chroma sample j >> 1, so a tile of PX pairs lifts PX luma
+//           and PX / 2 chroma columns -- the 2 : 1 tile of the v210 kernel indexed by pair -- and the luma columns from
+//           out_width / 2 on are never lifted at this level.  A group is two pairs.
+//   V216 0  a 4:4:4 source, three full-width regions; ARGB (YCoCg-R, four pixels per group) or AY64 (two), a run-time flag.
+// PX: whole 128-byte lines of output per tile row; s32 DD(9,7): 28 KB tile + 21 KB staging (v216), 20 + 21 KB (4:4:4),
+// three workgroups per CU.
+template < typename T, int F, int V216 > struct WGeo {
+  static constexpr int PX = V216 ? 96 : 64;             // luma columns per workgroup (v216: output pairs)
+  static constexpr int CS = V216 ? 1 : 0;               // chroma columns = luma columns >> CS
+  static constexpr int RP = 32;
+  static constexpr int H = filter_halo (F);
+  static constexpr int HC = (H + 3) & ~3;
+  static constexpr int UR = RP - 2 * H;
+  static constexpr int ROWS = 2 * UR;                   // picture rows per workgroup
+  static constexpr int PXC = PX >> CS;                  // chroma samples per tile row
+  static constexpr int UCY = PX / 2, UCC = PXC / 2;     // useful sub-band columns, Y / U, V
+  static constexpr int RCY = UCY + 2 * HC, RCC = UCC + 2 * HC;
+  static_assert (PX % 32 == 0 && UCC % 4 == 0 && PXC % 8 == 0, "whole 128-byte lines of every format, sample quads, 16-byte staging words");
+};
+
+template < typename T > struct WideSink {
+  uint16_t *row0;               // staging row of tile row 0
+  int pitch;                    // u16 per staging row
+  int hc;                       // region column of staging column 0
+  int shift;                    // (uniform) schro_frame_shift_right before the convert; 0: none
+  bool ay64;                    // (uniform)
+
+  __device__ __forceinline__ uint32_t word (T v) const
+  {
+    typedef typename std::make_unsigned < T >::type U;
+    // orc_add_const_rshift_s16 / _s32: the add wraps at the sample's width, arithmetic shift
+    const T x = (T) ((T) ((U) v + (U) ((1u << shift) >> 1)) >> shift);
+    return ay64 ? (uint32_t) (clampi ((int) x, -0x8000, 0x7fff) + 0x8000) : (uint32_t) (uint16_t) x;
+  }
+
+  __device__ __forceinline__ void store (int yy, int i, const T * out) const
+  {
+    uint32_t q[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      q[k] = word (out[2 * k]) | (word (out[2 * k + 1]) << 16);
+    // (i and hc are multiples of 4: 16-byte aligned)
+    *reinterpret_cast < u32x4 * >(row0 + yy * pitch + 2 * (i - hc)) = (u32x4) { q[0], q[1], q[2], q[3] };
+  }
+};
+
+// component C's four bands: LL from job.ll[C], HL / LH / HH from the coefficient plane
+template < typename T, int C, int CS >
+__device__ __forceinline__ void
+wide_bands (const WideJob & job, const void **sb, int *ss, int *nc)
+{
+  const int w = C ? job.w >> CS : job.w;
+  *nc = w >> 1;
+  const char *plane = (const char *) job.src[C];
+  const int S = job.src_stride[C];
+  sb[0] = job.ll[C];
+  sb[1] = plane + (size_t) *nc * sizeof (T);
+  sb[2] = plane + S;
+  sb[3] = plane + S + (size_t) *nc * sizeof (T);
+  ss[0] = job.ll_stride[C];
+  ss[1] = ss[2] = ss[3] = 2 * S;
+}
+
+// issue the 8-byte loads of component C's region (where its bands allow them)
+template < typename G, typename T, int C, int RC, int UC, int NPS >
+__device__ __forceinline__ void
+wide_load (uint2 (&v)[4][NPS], const WideJob & job, int tid, int r0, int tx)
+{
+  if (!(job.flags & (1 << C)))
+    return;
+  const void *sb[4];
+  int ss[4], nc;
+  wide_bands < T, C, G::CS > (job, sb, ss, &nc);
+#pragma unroll
+  for (int b = 0; b < 4; b++)
+    band_load < T, G::RP, RC, NPS > (v[b], sb[b], ss[b], tid, r0, tx * UC - G::HC, job.h >> 1, nc);
+}
+
+// stage component C's region in LDS (from the loads above, or sample by sample) and lift it into the staging area
+template < typename G, typename T, int F, int C, int RC, int UC, int NPS >
+__device__ __forceinline__ void
+wide_lift (T (*lds)[2 * RC], const uint2 (&v)[4][NPS], const WideJob & job, int tid, int r0, int tx, uint16_t * stage, int pitch)
+{
+  constexpr int RP = G::RP, HC = G::HC;
+  const int nr = job.h >> 1, c0 = tx * UC - HC;
+  const void *sb[4];
+  int ss[4], nc;
+  wide_bands < T, C, G::CS > (job, sb, ss, &nc);
+  if (job.flags & (1 << C)) {
+#pragma unroll
+    for (int b = 0; b < 4; b++)
+      band_store < T, RP, RC, NPS > (lds, v[b], b, tid);
+  } else {
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+      const char *base = (const char *) sb[b];
+      for (int it = tid; it < RP * RC; it += kThreads) {
+        const int c = it % RC, rp = it / RC;
+        const int r = r0 + rp, cc = c0 + c;
+        if (r >= 0 && r < nr && cc >= 0 && cc < nc)
+          lds[2 * rp + (b >> 1)][(b & 1) * RC + c] = gload < T > ((const T *) (base + (size_t) r * ss[b]) + cc);
+      }
+    }
+  }
+  __syncthreads ();
+  WideSink < T > sink;
+  sink.row0 = stage;
+  sink.pitch = pitch;
+  sink.hc = HC;
+  sink.shift = job.shift;
+  sink.ay64 = (job.flags & 8) != 0;
+  lift_region < T, F, RP, RC, HC / 4, (RC - HC) / 4 - 1 > (lds, tid, r0, c0, nr, nc, sink);
+}
+
+template < typename T, int F, int V216 >
+__global__ __launch_bounds__ (kThreads)
+void iiwt_wide_kernel (const WideJob * __restrict__ jobs, int njobs)
+{
+  typedef WGeo < T, F, V216 > G;
+  constexpr int RP = G::RP, H = G::H, UR = G::UR, ROWS = G::ROWS, PX = G::PX, PXC = G::PXC;
+  __shared__ __attribute__ ((aligned (16))) T lds[2 * RP][2 * G::RCY];
+  __shared__ __attribute__ ((aligned (16))) uint16_t s_y[ROWS][PX];
+  __shared__ __attribute__ ((aligned (16))) uint16_t s_c[2][ROWS][PXC];
+
+  const int tid = threadIdx.x;
+  const int bid = xcd_tile_id (blockIdx.x, gridDim.x);
+  const WideJob job = jobs[find_job (jobs, njobs, bid)];
+  const int t = bid - job.tile_base;
+  const int ty = t / job.tiles_x, tx = t - ty * job.tiles_x;
+  const int r0 = ty * UR - H;   // sub-band row of region row pair 0 (all three components: no vertical subsampling)
+  const int y0 = ty * ROWS, x0 = tx * PX;
+  T (*ldsc)[2 * G::RCC] = reinterpret_cast < T (*)[2 * G::RCC] > (&lds[0][0]);
+
+  constexpr int NPSY = band_nps < T, RP, G::RCY > (), NPSC = band_nps < T, RP, G::RCC > ();
+  uint2 vy[4][NPSY], vu[4][NPSC], vv[4][NPSC];
+  wide_load < G, T, 0, G::RCY, G::UCY, NPSY > (vy, job, tid, r0, tx);
+  wide_load < G, T, 1, G::RCC, G::UCC, NPSC > (vu, job, tid, r0, tx);
+  wide_lift < G, T, F, 0, G::RCY, G::UCY, NPSY > (lds, vy, job, tid, r0, tx, &s_y[0][0], PX);
+  __syncthreads ();
+  wide_load < G, T, 2, G::RCC, G::UCC, NPSC > (vv, job, tid, r0, tx);
+  wide_lift < G, T, F, 1, G::RCC, G::UCC, NPSC > (ldsc, vu, job, tid, r0, tx, &s_c[0][0][0], PXC);
+  __syncthreads ();
+  wide_lift < G, T, F, 2, G::RCC, G::UCC, NPSC > (ldsc, vv, job, tid, r0, tx, &s_c[1][0][0], PXC);
+  __syncthreads ();
+
+  // ---- pack: a task = one 16-byte group of one row (pack_v216 / pack_argb / pack_ayuv64, schrovirtframe.c:1007-1028, :1265-1322) ----
+  const int rows = min (ROWS, job.out_h - y0);
+  if constexpr (V216) {
+    constexpr int GPR = PX / 2;         // two pairs per group: luma samples 2g, 2g + 1, chroma sample g
+    const int pairs = job.out_w >> 1;
+    for (int task = tid; task < rows * GPR; task += kThreads) {
+      const int y = task / GPR, g = task - y * GPR;
+      const int n = min (2, pairs - (x0 + 2 * g));      // pairs of the picture in this group
+      if (n <= 0)
+        continue;
+      const uint32_t yy = *reinterpret_cast < const uint32_t * >(&s_y[y][2 * g]);
+      const uint32_t u = s_c[0][y][g], v = s_c[1][y][g];
+      // pair j: (U byte, U byte, Y lo, Y lo), (V byte, V byte, Y hi, Y hi) with byte j & 1 of the chroma samples
+      u32x4 o;
+      o.x = (u & 0xffu) * 0x0101u | ((yy & 0xffu) * 0x01010000u);
+      o.y = (v & 0xffu) * 0x0101u | (((yy >> 8) & 0xffu) * 0x01010000u);
+      o.z = (u >> 8) * 0x0101u | (((yy >> 16) & 0xffu) * 0x01010000u);
+      o.w = (v >> 8) * 0x0101u | ((yy >> 24) * 0x01010000u);
+      char *d = (char *) job.dst + (size_t) (y0 + y) * job.dst_stride + (size_t) (x0 + 2 * g) * 8;
+      if (n == 2)
+        __builtin_nontemporal_store (o, (SCHRO_GLOBAL u32x4 *) d);
+      else
+        gstore < u32x2 > (d, (u32x2) { o.x, o.y });
+    }
+  } else if (job.flags & 8) {
+    constexpr int GPR = PX / 2;         // AY64: two pixels per group
+    for (int task = tid; task < rows * GPR; task += kThreads) {
+      const int y = task / GPR, g = task - y * GPR;
+      const int n = min (2, job.out_w - (x0 + 2 * g));
+      if (n <= 0)
+        continue;
+      const uint32_t yy = *reinterpret_cast < const uint32_t * >(&s_y[y][2 * g]);
+      const uint32_t uu = *reinterpret_cast < const uint32_t * >(&s_c[0][y][2 * g]);
+      const uint32_t vv2 = *reinterpret_cast < const uint32_t * >(&s_c[1][y][2 * g]);
+      u32x4 o;
+      o.x = 0xffffu | (yy << 16);
+      o.y = (uu & 0xffffu) | (vv2 << 16);
+      o.z = 0xffffu | (yy & 0xffff0000u);
+      o.w = (uu >> 16) | (vv2 & 0xffff0000u);
+      char *d = (char *) job.dst + (size_t) (y0 + y) * job.dst_stride + (size_t) (x0 + 2 * g) * 8;
+      if (n == 2)
+        __builtin_nontemporal_store (o, (SCHRO_GLOBAL u32x4 *) d);
+      else
+        gstore < u32x2 > (d, (u32x2) { o.x, o.y });
+    }
+  } else {
+    constexpr int GPR = PX / 4;         // ARGB: four pixels per group
+    for (int task = tid; task < rows * GPR; task += kThreads) {
+      const int y = task / GPR, g = task - y * GPR;
+      const int n = min (4, job.out_w - (x0 + 4 * g));
+      if (n <= 0)
+        continue;
+      const u32x2 yy = *reinterpret_cast < const u32x2 * >(&s_y[y][4 * g]);
+      const u32x2 oo = *reinterpret_cast < const u32x2 * >(&s_c[0][y][4 * g]);   // component 1: Co
+      const u32x2 gg = *reinterpret_cast < const u32x2 * >(&s_c[1][y][4 * g]);   // component 2: Cg
+      uint32_t o[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const int sh = 16 * (k & 1);
+        const int yv = (int16_t) ((k < 2 ? yy.x : yy.y) >> sh), co = (int16_t) ((k < 2 ? oo.x : oo.y) >> sh);
+        const int cg = (int16_t) ((k < 2 ? gg.x : gg.y) >> sh);
+        const int tt = yv + (cg >> 1), b = tt - (co >> 1);      // YCoCg-R, schrovirtframe.c:1281-1286
+        o[k] = 0xffu | ((uint32_t) ((b + co) & 0xff) << 8) | ((uint32_t) ((tt + cg) & 0xff) << 16) | ((uint32_t) (b & 0xff) << 24);
+      }
+      char *d = (char *) job.dst + (size_t) (y0 + y) * job.dst_stride + (size_t) (x0 + 4 * g) * 4;
+      if (n == 4) {
+        __builtin_nontemporal_store ((u32x4) { o[0], o[1], o[2], o[3] }, (SCHRO_GLOBAL u32x4 *) d);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 3; k++)
+          if (k < n)
+            gstore < uint32_t > (d + 4 * k, o[k]);
+      }
+    }
+  }
+}
+
+template < typename T, int F, int V216 >
+int
+launch_wide_one (hipStream_t stream, const WideJob * d_jobs, int njobs, int total_tiles)
+{
+  SCHRO_LAUNCH ((iiwt_wide_kernel < T, F, V216 >), dim3 (total_tiles), dim3 (kThreads), 0, stream, d_jobs, njobs);
+  hipError_t e = hipGetLastError ();
+  if (e != hipSuccess)
+    return set_error (SCHRO_HIP_EDEVICE, "iiwt + v216 / ARGB / AY64 launch: %s", hipGetErrorString (e));
+  return 0;
+}
+
+template < typename T, int V216 >
+int
+launch_wide_filter (hipStream_t stream, const WideJob * d_jobs, int njobs, int total_tiles, int filter)
+{
+  switch (filter) {
+    case 0: return launch_wide_one < T, 0, V216 > (stream, d_jobs, njobs, total_tiles);
+    case 1: return launch_wide_one < T, 1, V216 > (stream, d_jobs, njobs, total_tiles);
+    case 2: return launch_wide_one < T, 2, V216 > (stream, d_jobs, njobs, total_tiles);
+    case 3: return launch_wide_one < T, 3, V216 > (stream, d_jobs, njobs, total_tiles);
+    case 4: return launch_wide_one < T, 4, V216 > (stream, d_jobs, njobs, total_tiles);
+    case 5: return launch_wide_one < T, 5, V216 > (stream, d_jobs, njobs, total_tiles);
+    case 6: return launch_wide_one < T, 6, V216 > (stream, d_jobs, njobs, total_tiles);
+  }
+  return set_error (SCHRO_HIP_EINVAL, "wavelet filter index %d out of range", filter);
+}
+
 template < typename T, int F >
 int
 launch_one (hipStream_t stream, const IwtJob * d_jobs, int njobs, int total_tiles)
@@ -1331,6 +1587,23 @@ launch_iiwt_pack8 (hipStream_t stream, const Pack8Job * d_jobs, int njobs, int t
   if (ayuv)
     return launch_pack8_filter < 1 > (stream, d_jobs, njobs, total_tiles, filter);
   return launch_pack8_filter < 0 > (stream, d_jobs, njobs, total_tiles, filter);
+}
+
+void
+iiwt_wide_geometry (int filter, int v216, int *cols, int *rows)
+{
+  *cols = v216 ? WGeo < int16_t, 0, 1 >::PX : WGeo < int16_t, 0, 0 >::PX;
+  *rows = 2 * (WGeo < int16_t, 0, 0 >::RP - 2 * filter_halo (filter));
+}
+
+int
+launch_iiwt_wide (hipStream_t stream, const WideJob * d_jobs, int njobs, int total_tiles, int filter, int bpp, int v216)
+{
+  if (bpp == 2)
+    return v216 ? launch_wide_filter < int16_t, 1 > (stream, d_jobs, njobs, total_tiles, filter)
+        : launch_wide_filter < int16_t, 0 > (stream, d_jobs, njobs, total_tiles, filter);
+  return v216 ? launch_wide_filter < int32_t, 1 > (stream, d_jobs, njobs, total_tiles, filter)
+      : launch_wide_filter < int32_t, 0 > (stream, d_jobs, njobs, total_tiles, filter);
 }
 
 size_t

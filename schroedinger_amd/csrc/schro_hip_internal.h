@@ -157,6 +157,23 @@ struct Pack8Job {
   int flags;                    // bit c: component c's four bands take 8-byte loads; bit 3: UYVY byte order
 };
 
+// The finest level of a 4:2:2 / 4:4:4 s16 / s32 picture's inverse wavelet with the v216 / ARGB / AY64 copy-out as its sink
+// (iiwt.hip, iiwt_wide_kernel)
+struct WideJob {
+  const void *src[3];           // the coefficient planes (Y, U, V), in-place sub-band layout
+  int src_stride[3];
+  const void *ll[3];            // each component's level-0 LL band: the frame's LL quadrant (depth 1) or a compact plane
+  int ll_stride[3];
+  int w, h;                     // luma transform size (chroma: w / 2 x h for v216, w x h for ARGB / AY64)
+  int out_w, out_h;             // the picture inside it
+  uint8_t *dst;                 // packed rows; dst and dst_stride 16-byte aligned
+  int dst_stride;
+  int tiles_x;
+  int tile_base;
+  int flags;                    // bit c: component c's four bands take 8-byte loads; bit 3: AY64 (4:4:4 kernel: else ARGB)
+  int shift;                    // schro_frame_shift_right before the convert; 0: none
+};
+
 struct ConvertJob {
   const void *src;
   uint8_t *dst;
@@ -540,6 +557,9 @@ int launch_iiwt_v210 (hipStream_t stream, const V210Job * d_jobs, int njobs, int
 // iiwt.hip: the finest level + YUYV / UYVY (ayuv 0) or AYUV (ayuv 1) copy-out of every filter, s16
 void iiwt_pack8_geometry (int filter, int ayuv, int *cols, int *rows);
 int launch_iiwt_pack8 (hipStream_t stream, const Pack8Job * d_jobs, int njobs, int total_tiles, int filter, int ayuv);
+// iiwt.hip: the finest level + v216 (v216 1: columns = output pairs) or ARGB / AY64 (v216 0) copy-out of every filter, s16 / s32
+void iiwt_wide_geometry (int filter, int v216, int *cols, int *rows);
+int launch_iiwt_wide (hipStream_t stream, const WideJob * d_jobs, int njobs, int total_tiles, int filter, int bpp, int v216);
 int launch_dequant (hipStream_t stream, const DequantJob * d_jobs, int njobs, int total_tiles, int bpp, int arith);
 int launch_dequant_plan (hipStream_t stream, const DequantGeo * d_geo, int njobs, int total_tiles,
     const SchroHipCodeblock * d_recs, const DequantPlaneDyn * d_planes, int bpp, int arith);
@@ -724,6 +744,8 @@ struct SchroHipContext {
   long long v210_routes[SCHRO_HIP_V210_ROUTES] = {};
   // ... of schro_hip_iiwt_pack_u8_batch (schro_hip_pack8_routes)
   long long pack8_routes[SCHRO_HIP_PACK8_ROUTES] = {};
+  // ... of schro_hip_iiwt_pack_wide_batch (schro_hip_wide_routes)
+  long long wide_routes[SCHRO_HIP_WIDE_ROUTES] = {};
   int cus;                      // compute units of the device (launch shaping)
 };
 
