@@ -290,6 +290,28 @@ int schro_hip_iiwt_batch (SchroHipContext * ctx,
     const SchroHipIwtPlane * planes, int nplanes, int depth, int filter,
     int bpp);
 
+/* One component of one picture for the FORWARD wavelet: the level loop of schro_frame_iwt_transform /
+ * schro_gpuframe_iwt_transform (schrogpuframe.h:13-31), schro_wavelet_transform_2d per level, finest level first.
+ * `src` holds width x height pixels or residuals; `dst` receives the coefficients in the reference's in-place
+ * sub-band layout (level view {w>>l, h>>l, stride<<l}; even rows = [LL|HL], odd rows = [LH|HH]) -- what
+ * schro_hip_iiwt_batch takes as its src.  src and dst must not overlap (the transform is tiled, not in place); src is
+ * left untouched, and nothing outside dst's width x height samples is written. */
+typedef struct {
+  const void *src;
+  int src_stride;               /* bytes */
+  void *dst;
+  int dst_stride;               /* bytes */
+  int width;                    /* iwt_{luma,chroma}_width: a multiple of 1 << depth */
+  int height;                   /* iwt_{luma,chroma}_height: a multiple of 1 << depth */
+} SchroHipIwtFwdPlane;
+
+/* depth levels (1 .. 6), Dirac filter index 0..6 (schrobitstream.h:124-132), bytes_per_sample 2 (s16) or 4 (s32).
+ * Enqueues `depth` launches (fine to coarse), each covering all planes; planes of unlike sizes mix freely.
+ * Refused (SCHRO_HIP_EINVAL, nothing launched): a size that is not a multiple of 1 << depth, a stride shorter than
+ * a row or not a multiple of the sample size, dst overlapping src, a filter, depth or sample size out of range. */
+int schro_hip_iwt_batch (SchroHipContext * ctx, const SchroHipIwtFwdPlane * planes, int nplanes, int depth, int filter,
+    int bytes_per_sample);
+
 /* intra pictures: dst_u8 = sat_u8 (src + 128), cropped to width x height;
  * replaces schro_frame_convert (ref_output_frame, frame)
  * (schrodecoder.c:1788-1790) / schro_gpuframe_convert. */
@@ -994,6 +1016,11 @@ SchroHipFrame *schro_hip_frame_copy_to (SchroHipContext * dst_ctx, SchroHipFrame
  * orders them with marks (0.58 ms per 2160p picture, host hand-over included, against 0.98 ms
  * under the contract). */
 int schro_hip_context_set_stage_completion (SchroHipContext * ctx, int complete_on_return);
+
+/* schro_gpuframe_iwt_transform (schrogpuframe.h:13-31) replacement: the forward wavelet of all three components of
+ * `frame` (device, s16 or s32) IN PLACE, with params->wavelet_filter_index and transform_depth over iwt_luma_* /
+ * iwt_chroma_*: the source planes are copied into the queue's scratch first, then schro_hip_iwt_batch's launches. */
+int schro_hipframe_iwt_transform (SchroHipContext * ctx, SchroHipFrame * frame, const SchroHipParams * params);
 
 /* schro_frame_inverse_iwt_transform_cuda (schrocuda.h:13-14) replacement, same arguments:
  * upload transform_frame (host) or use it where it is (device), run the multi-level inverse

@@ -375,6 +375,17 @@ class Context:
                 arr[k].ll, arr[k].ll_stride = q.ptr, q.stride
         check(self.lib.schro_hip_iiwt_batch(self.h, arr, n, depth, filt, bpp))
 
+    def iwt_batch(self, pairs, depth, filt):
+        """The forward wavelet.  pairs: [(src, dst DevicePlane)], all s16 or all s32 -- src: pixels or residuals, dst: the
+        coefficient plane in the in-place sub-band layout (what iiwt_batch takes as its src); sizes may differ."""
+        n = len(pairs)
+        arr = (_lib.IwtFwdPlane * n)()
+        bpp = pairs[0][0].dtype.itemsize
+        for k, (s, d) in enumerate(pairs):
+            assert s.dtype == d.dtype and s.dtype.itemsize == bpp and (s.height, s.width) == (d.height, d.width)
+            arr[k] = _lib.IwtFwdPlane(s.ptr, s.stride, d.ptr, d.stride, s.width, s.height)
+        check(self.lib.schro_hip_iwt_batch(self.h, arr, n, depth, filt, bpp))
+
     def pack_u8_batch(self, jobs):
         """jobs: (planes [Y, U, V] DevicePlanes, h_shift, v_shift, dst DevicePlane of 4-byte
         groups, width, height, format) per picture."""

@@ -34,7 +34,7 @@ EXPORTED_SYMBOLS = [
     "schro_hip_timer_begin", "schro_hip_timer_end",
     "schro_hip_profile_enable", "schro_hip_profile_reset", "schro_hip_profile_read", "schro_hip_obmc_routes",
     "schro_hip_v210_routes", "schro_hip_pack8_routes", "schro_hip_wide_routes",
-    "schro_hip_iiwt_batch", "schro_hip_convert_u8_batch", "schro_hip_upsample_batch",
+    "schro_hip_iiwt_batch", "schro_hip_iwt_batch", "schro_hipframe_iwt_transform", "schro_hip_convert_u8_batch", "schro_hip_upsample_batch",
     "schro_hip_upsampled_bytes", "schro_hip_upsampled_download", "schro_hip_upsampled_pair_bytes",
     "schro_hip_upsampled_pair_download", "schro_hip_pack_u8_batch",
     "schro_hip_pack_v210_batch", "schro_hip_iiwt_pack_v210_batch", "schro_hip_iiwt_pack_u8_batch", "schro_hip_pack_wide_batch", "schro_hip_shift_right_batch",
@@ -60,6 +60,12 @@ class IwtPlane(C.Structure):
                 ("pred", C.c_void_p), ("pred_stride", C.c_int),
                 ("out_width", C.c_int), ("out_height", C.c_int), ("combine", C.c_int),
                 ("ll", C.c_void_p), ("ll_stride", C.c_int), ("reserved", C.c_int)]
+
+
+class IwtFwdPlane(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("src_stride", C.c_int),
+                ("dst", C.c_void_p), ("dst_stride", C.c_int),
+                ("width", C.c_int), ("height", C.c_int)]
 
 
 class ConvertPlane(C.Structure):
@@ -363,6 +369,10 @@ def load():
     L.schro_hip_wide_routes.restype = i
     L.schro_hip_iiwt_batch.argtypes = [vp, C.POINTER(IwtPlane), i, i, i, i]
     L.schro_hip_iiwt_batch.restype = i
+    L.schro_hip_iwt_batch.argtypes = [vp, C.POINTER(IwtFwdPlane), i, i, i, i]
+    L.schro_hip_iwt_batch.restype = i
+    L.schro_hipframe_iwt_transform.argtypes = [vp, C.POINTER(Frame), C.POINTER(Params)]
+    L.schro_hipframe_iwt_transform.restype = i
     L.schro_hip_convert_u8_batch.argtypes = [vp, C.POINTER(ConvertPlane), i, i]
     L.schro_hip_convert_u8_batch.restype = i
     L.schro_hip_upsample_batch.argtypes = [vp, C.POINTER(UpsamplePlane), i]

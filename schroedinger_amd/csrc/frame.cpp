@@ -332,6 +332,27 @@ schro_hip_frame_copy_to (SchroHipContext * dst_ctx, SchroHipFrame * src)
   return dst;
 }
 
+// schro_gpuframe_iwt_transform (schrogpuframe.h:13-31): the forward transform of a device frame in place.  The level
+// kernels are out of place, so the plane layer copies the source planes into the queue's scratch first.
+int
+schro_hipframe_iwt_transform (SchroHipContext * ctx, SchroHipFrame * frame, const SchroHipParams * params)
+{
+  SCHRO_HIP_REQUIRE (ctx && frame && params && frame_ctx (frame) == ctx, "hipframe_iwt_transform: the frame must be in the context's domain");
+  const int bpp = format_bpp (frame->format);
+  SCHRO_HIP_REQUIRE (bpp == 2 || bpp == 4, "hipframe_iwt_transform: the frame must be s16 or s32");
+  SchroHipIwtFwdPlane planes[3];
+  memset (planes, 0, sizeof (planes));
+  for (int k = 0; k < 3; k++) {
+    planes[k].src = planes[k].dst = frame->components[k].data;
+    planes[k].src_stride = planes[k].dst_stride = frame->components[k].stride;
+    planes[k].width = k ? params->iwt_chroma_width : params->iwt_luma_width;
+    planes[k].height = k ? params->iwt_chroma_height : params->iwt_luma_height;
+    SCHRO_HIP_REQUIRE (planes[k].width <= frame->components[k].width && planes[k].height <= frame->components[k].height,
+        "hipframe_iwt_transform: component %d smaller than the iwt size", k);
+  }
+  return stage_done (ctx, iwt_batch_run (ctx, planes, 3, params->transform_depth, params->wavelet_filter_index, bpp, true));
+}
+
 // frame: the residual frame (s16 / s32, combine 0) or the u8 picture (combine 1: + prediction, 2: + 128)
 static int
 inverse_iwt_transform (SchroHipFrame * frame, SchroHipFrame * transform_frame, SchroHipParams * params, int combine,

@@ -113,6 +113,20 @@ struct IwtJob {
   int l1_sb_stride[4];
 };
 
+// One (plane, level) of the forward wavelet (iwt_fwd.hip).
+struct IwtFwdJob {
+  const void *src;              // the level's compact input image: the source plane, or the LL image of the level before
+  int src_stride;               // bytes
+  int flags;                    // bit0: src takes 8-byte loads, bit1: the bands take 4-sample stores
+  void *band[4];                // LL, HL, LH, HH: element (0,0) of each sub-band this level writes
+  int band_stride[4];           // bytes between sub-band rows
+  int w, h;                     // input size of this level (sub-bands are w/2 x h/2)
+  int tiles_x;
+  int tile_base;                // first block id of this job
+  uint32_t m_tiles_x;           // div_magic (tiles_x)
+  int pad;
+};
+
 // r05: the three-level s32 Haar transform of a 4:2:2 picture with the v210 copy-out as its epilogue (iiwt_haar.hip)
 struct HaarPackJob {
   const void *src[3];           // the coefficient planes (Y, U, V), in-place sub-band layout
@@ -513,6 +527,9 @@ int launch_iiwt_chain (hipStream_t stream, const IwtJob * d_jobs, const uint32_t
     uint32_t run, uint32_t * gave_up, uint32_t epoch, int filter);
 void iiwt_tile_geometry (int filter, int bpp, int *useful_cols,
     int *useful_row_pairs);
+// one level of the forward wavelet (iwt_fwd.hip)
+void iwt_fwd_tile_geometry (int filter, int bpp, int *useful_cols, int *useful_row_pairs);
+int launch_iwt_fwd_level (hipStream_t stream, const IwtFwdJob * d_jobs, int njobs, int total_tiles, int filter, int bpp);
 int launch_convert (hipStream_t stream, const ConvertJob * d_jobs, int njobs,
     int total_tiles, int bpp);
 void convert_tile_geometry (int *tw, int *th);
@@ -764,6 +781,10 @@ int big_table_commit (SchroHipContext * ctx, size_t bytes);
 // rows of row_bytes bytes, host <-> device or device -> device, enqueued on the selected queue (context.cpp)
 int copy_2d_async (SchroHipContext * ctx, void *dst, int dst_stride, const void *src, int src_stride, int row_bytes,
     int height, hipMemcpyKind kind);
+// schro_hip_iwt_batch with src == dst allowed (plane_iwt.cpp): the source planes are copied into the queue's scratch
+// first, as the frame layer's in-place schro_hipframe_iwt_transform needs
+int iwt_batch_run (SchroHipContext * ctx, const SchroHipIwtFwdPlane * planes, int nplanes, int depth, int filter, int bpp,
+    bool in_place);
 // v216 / ARGB / AY64 (plane_frameops.cpp)
 bool is_wide_format (int format);
 // the launches made while a scope is open are timed under its kernel class (when profiling is on)
