@@ -312,6 +312,70 @@ typedef struct {
 int schro_hip_iwt_batch (SchroHipContext * ctx, const SchroHipIwtFwdPlane * planes, int nplanes, int depth, int filter,
     int bytes_per_sample);
 
+/* ---- encoder analysis: the downsample pyramid and the SAD scan (schroanalysis.c:8-28, schrometric.c:31-214) ----
+ *
+ * One u8 component for schro_frame_downsample (schroframe.c:1449-1505): the 6, 26, 26, 6 filter down the columns,
+ * rounded to u8, then along the rows, rounded again, source coordinates clamped to the picture.  dst_extension > 0 also
+ * writes the apron schro_frame_mc_edgeextend (schroframe.c:1940-1997) would add -- every apron sample is computed at
+ * its clamped coordinate inside the same launch, no sample another workgroup wrote is read. */
+typedef struct {
+  const uint8_t *src;
+  int src_stride;
+  int src_width, src_height;
+  uint8_t *dst;                 /* pixel (0,0) of the (src_width + 1) / 2 x (src_height + 1) / 2 picture */
+  int dst_stride;
+  int dst_extension;            /* > 0: also write the apron of that many samples on all four sides */
+} SchroHipDownsamplePlane;
+
+/* One launch for all planes; planes of unlike sizes mix freely; a pyramid is one call per level on the same queue.
+ * Nothing outside the dst picture plus its apron is written.  Refused (SCHRO_HIP_EINVAL, nothing launched):
+ * non-positive sizes, a stride shorter than a row plus its aprons, dst overlapping src, a negative extension. */
+int schro_hip_downsample_batch (SchroHipContext * ctx, const SchroHipDownsamplePlane * planes, int nplanes);
+
+#define SCHRO_HIP_LIMIT_METRIC_SCAN 42  /* SCHRO_LIMIT_METRIC_SCAN, schrometric.h:16 */
+
+/* The input members of SchroMetricScan (schrometric.h:38-53), luma only. */
+typedef struct {
+  int x, y, block_width, block_height;
+  int ref_x, ref_y, scan_width, scan_height;    /* 1 .. SCHRO_HIP_LIMIT_METRIC_SCAN */
+  int gravity_x, gravity_y;
+  int dx, dy;                   /* the caller's initial vector, returned when nothing beats the gravity position */
+} SchroHipMetricScan;
+
+typedef struct {
+  int dx, dy;
+  uint32_t metric;
+  uint32_t reserved;
+} SchroHipMetricScanResult;
+
+/* The scans of one (frame, reference) pair of u8 planes: schro_metric_scan_do_scan + schro_metric_scan_get_min of every
+ * descriptor.  metrics[i * scan_height + j] = SAD (block at (x, y) of frame, block at (ref_x + i, ref_y + j) of ref); a
+ * block of non-positive width or height has SAD 0.  The minimum starts at the gravity position i = gravity_x + x - ref_x,
+ * j = gravity_y + y - ref_y and is replaced only by a strictly smaller metric, i outer, j inner; dx, dy change only on
+ * replacement.  Samples outside a picture are its edge-extended apron: the kernel clamps coordinates. */
+typedef struct {
+  const uint8_t *frame;
+  int frame_stride;
+  const uint8_t *ref;
+  int ref_stride;
+  int width, height;            /* both planes */
+  int extension;                /* the apron the reference frame WOULD have; the kernel clamps coordinates instead */
+  const SchroHipMetricScan *scans;      /* HOST array, copied by the call, reusable on return */
+  int nscans;
+  SchroHipMetricScanResult *results;    /* device, nscans records */
+  uint32_t *metrics;            /* device or NULL: scan k's table at metrics + k * 42 * 42, entry i * scan_height + j */
+} SchroHipMetricScanPicture;
+
+/* host only: schro_metric_scan_setup (schrometric.c:174-214) taken literally on scan->x, y, block_width, block_height --
+ * sets ref_x, ref_y, scan_width, scan_height (which may come out <= 0: such a scan is not handed to the batch).
+ * SCHRO_HIP_EINVAL where the reference asserts (dist <= 0, a window over the limit). */
+int schro_hip_metric_scan_setup (SchroHipMetricScan * scan, int frame_width, int frame_height, int extension,
+    int dx, int dy, int dist);
+/* One launch for all scans of all pictures, one wave per scan.  Every descriptor is validated on the host first with the
+ * assertions of schrometric.c:38-45; also refused: a gravity position outside the window, a window over 42, a block over
+ * 64 x 64.  A refusal (SCHRO_HIP_EINVAL, nothing launched) names the picture and the scan. */
+int schro_hip_metric_scan_batch (SchroHipContext * ctx, const SchroHipMetricScanPicture * pictures, int npictures);
+
 /* intra pictures: dst_u8 = sat_u8 (src + 128), cropped to width x height;
  * replaces schro_frame_convert (ref_output_frame, frame)
  * (schrodecoder.c:1788-1790) / schro_gpuframe_convert. */
@@ -1021,6 +1085,19 @@ int schro_hip_context_set_stage_completion (SchroHipContext * ctx, int complete_
  * `frame` (device, s16 or s32) IN PLACE, with params->wavelet_filter_index and transform_depth over iwt_luma_* /
  * iwt_chroma_*: the source planes are copied into the queue's scratch first, then schro_hip_iwt_batch's launches. */
 int schro_hipframe_iwt_transform (SchroHipContext * ctx, SchroHipFrame * frame, const SchroHipParams * params);
+
+/* One pyramid level of schro_encoder_frame_downsample (schroanalysis.c:24-25): schro_frame_downsample (dest, src) plus,
+ * when dest->extension > 0, schro_frame_mc_edgeextend (dest), all three components in one launch.  Both frames are u8
+ * device frames of one domain; every component of dest is (w + 1) / 2 x (h + 1) / 2 of src's, its data pointer at pixel
+ * (0, 0) with dest->extension samples of apron around it (schro_frame_new_and_alloc_extended's layout). */
+int schro_hipframe_downsample (SchroHipFrame * dest, SchroHipFrame * src);
+/* schro_rough_me_heirarchical_scan_nohint (schroroughmotion.c:64-141; the spelling is the reference's) over the luma
+ * planes of two u8 device frames that are both ALREADY at pyramid level `shift`.  motion_vectors: a HOST array of
+ * params->x_num_blocks x params->y_num_blocks SchroMotionVector records; every record is set as schro_motion_field_set
+ * (mf, 0, 1) leaves it, the blocks at multiples of 1 << shift receive dx << shift, dy << shift in dx[ref], dy[ref] and
+ * the metric (a scan of no width or height: 0, 0, INT_MAX).  Synchronises: the array is complete on return. */
+int schro_rough_me_heirarchical_scan_nohint_hip (SchroHipFrame * frame, SchroHipFrame * ref_frame,
+    const SchroHipParams * params, int shift, int distance, int ref, void *motion_vectors);
 
 /* schro_frame_inverse_iwt_transform_cuda (schrocuda.h:13-14) replacement, same arguments:
  * upload transform_frame (host) or use it where it is (device), run the multi-level inverse

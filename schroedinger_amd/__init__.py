@@ -27,6 +27,21 @@ MV_DTYPE = np.dtype([("flags", "<u4"), ("metric", "<u4"), ("chroma_metric", "<u4
                      ("v", "<i2", (4,))])
 
 
+# SchroHipMetricScan / SchroHipMetricScanResult (include/schro_hip.h) as numpy records
+SCAN_DTYPE = np.dtype([(n, "<i4") for n in ("x", "y", "block_width", "block_height", "ref_x", "ref_y", "scan_width", "scan_height",
+                                            "gravity_x", "gravity_y", "dx", "dy")])
+SCAN_RESULT_DTYPE = np.dtype([("dx", "<i4"), ("dy", "<i4"), ("metric", "<u4"), ("reserved", "<u4")])
+LIMIT_METRIC_SCAN = 42
+
+
+def metric_scan_setup(x, y, block_width, block_height, frame_width, frame_height, extension, dx, dy, dist):
+    """schro_metric_scan_setup (schrometric.c:174-214) on the host: (ref_x, ref_y, scan_width, scan_height) of the window
+    of `dist` around (x + dx, y + dy); the sizes may come out <= 0.  Raises where the reference asserts."""
+    s = _lib.MetricScan(x=x, y=y, block_width=block_width, block_height=block_height)
+    check(_lib.load().schro_hip_metric_scan_setup(C.byref(s), frame_width, frame_height, extension, dx, dy, dist))
+    return s.ref_x, s.ref_y, s.scan_width, s.scan_height
+
+
 def device_count():
     return _lib.load().schro_hip_device_count()
 
@@ -385,6 +400,60 @@ class Context:
             assert s.dtype == d.dtype and s.dtype.itemsize == bpp and (s.height, s.width) == (d.height, d.width)
             arr[k] = _lib.IwtFwdPlane(s.ptr, s.stride, d.ptr, d.stride, s.width, s.height)
         check(self.lib.schro_hip_iwt_batch(self.h, arr, n, depth, filt, bpp))
+
+    def downsample_batch(self, jobs):
+        """One pyramid level (schro_frame_downsample + schro_frame_mc_edgeextend).  jobs: [(src, dst)] or [(src, dst, ext)],
+        u8 DevicePlanes -- dst holds the (h + 1) // 2 x (w + 1) // 2 picture with `ext` samples of apron on every side:
+        (h + 1) // 2 + 2 * ext rows of (w + 1) // 2 + 2 * ext samples; sizes may differ."""
+        n = len(jobs)
+        arr = (_lib.DownsamplePlane * n)()
+        for k, t in enumerate(jobs):
+            s, d, ext = t[0], t[1], (t[2] if len(t) > 2 else 0)
+            assert s.dtype == d.dtype == np.uint8
+            assert (d.height, d.width) == ((s.height + 1) // 2 + 2 * ext, (s.width + 1) // 2 + 2 * ext), (d.height, d.width)
+            arr[k] = _lib.DownsamplePlane(s.ptr, s.stride, s.width, s.height, d.ptr + ext * d.stride + ext, d.stride, ext)
+        check(self.lib.schro_hip_downsample_batch(self.h, arr, n))
+
+    def metric_scan_batch(self, pictures, tables=True):
+        """The SAD scans of schro_metric_scan_do_scan + schro_metric_scan_get_min.  pictures: [(frame, ref, extension,
+        scans)] -- frame, ref: u8 DevicePlanes of one size, scans: a SCAN_DTYPE array.  Returns [(results, metrics)] per
+        picture, DevicePlanes to download: results nscans x 4 int32 (dx, dy, metric, 0), metrics nscans x 42 * 42 uint32
+        (entry i * scan_height + j of each scan; None without `tables`)."""
+        n = len(pictures)
+        arr = (_lib.MetricScanPicture * n)()
+        out, keep = [], []
+        for k, (f, r, ext, scans) in enumerate(pictures):
+            assert f.dtype == r.dtype == np.uint8 and (f.height, f.width) == (r.height, r.width)
+            scans = np.ascontiguousarray(scans, dtype=SCAN_DTYPE)
+            keep.append(scans)
+            res = DevicePlane(self, max(len(scans), 1), 4, np.int32, stride=16)
+            met = DevicePlane(self, max(len(scans), 1), LIMIT_METRIC_SCAN ** 2, np.uint32, stride=4 * LIMIT_METRIC_SCAN ** 2) if tables else None
+            arr[k] = _lib.MetricScanPicture(f.ptr, f.stride, r.ptr, r.stride, f.width, f.height, ext,
+                                            scans.ctypes.data_as(C.POINTER(_lib.MetricScan)), len(scans), res.ptr,
+                                            met.ptr if met is not None else None)
+            out.append((res, met))
+        try:
+            check(self.lib.schro_hip_metric_scan_batch(self.h, arr, n))
+        except SchroHipError:
+            for res, met in out:
+                res.free()
+                if met is not None:
+                    met.free()
+            raise
+        return out
+
+    def rough_scan_nohint(self, frame, ref, params, shift, distance, ref_index, extension=0):
+        """schro_rough_me_heirarchical_scan_nohint over two u8 luma DevicePlanes that are already at pyramid level `shift`
+        (schro_rough_me_heirarchical_scan_nohint_hip on frames made of them).  params: a dict with x_num_blocks,
+        y_num_blocks, xbsep_luma, ybsep_luma (or a _lib.Params).  Returns the MV_DTYPE array, complete."""
+        from . import frames
+        if not isinstance(params, _lib.Params):
+            params = frames.make_params(**{k: params[k] for k in ("x_num_blocks", "y_num_blocks", "xbsep_luma", "ybsep_luma")})
+        fa, fb = frames.PlaneFrame(self, [frame] * 3, extension), frames.PlaneFrame(self, [ref] * 3, extension)
+        mvs = np.zeros(params.x_num_blocks * params.y_num_blocks, MV_DTYPE)
+        check(self.lib.schro_rough_me_heirarchical_scan_nohint_hip(fa.ptr(), fb.ptr(), C.byref(params), shift, distance, ref_index,
+                                                                   mvs.ctypes.data_as(C.c_void_p)))
+        return mvs
 
     def pack_u8_batch(self, jobs):
         """jobs: (planes [Y, U, V] DevicePlanes, h_shift, v_shift, dst DevicePlane of 4-byte

@@ -35,6 +35,8 @@ EXPORTED_SYMBOLS = [
     "schro_hip_profile_enable", "schro_hip_profile_reset", "schro_hip_profile_read", "schro_hip_obmc_routes",
     "schro_hip_v210_routes", "schro_hip_pack8_routes", "schro_hip_wide_routes",
     "schro_hip_iiwt_batch", "schro_hip_iwt_batch", "schro_hipframe_iwt_transform", "schro_hip_convert_u8_batch", "schro_hip_upsample_batch",
+    "schro_hip_downsample_batch", "schro_hip_metric_scan_setup", "schro_hip_metric_scan_batch", "schro_hipframe_downsample",
+    "schro_rough_me_heirarchical_scan_nohint_hip",
     "schro_hip_upsampled_bytes", "schro_hip_upsampled_download", "schro_hip_upsampled_pair_bytes",
     "schro_hip_upsampled_pair_download", "schro_hip_pack_u8_batch",
     "schro_hip_pack_v210_batch", "schro_hip_iiwt_pack_v210_batch", "schro_hip_iiwt_pack_u8_batch", "schro_hip_pack_wide_batch", "schro_hip_shift_right_batch",
@@ -66,6 +68,28 @@ class IwtFwdPlane(C.Structure):
     _fields_ = [("src", C.c_void_p), ("src_stride", C.c_int),
                 ("dst", C.c_void_p), ("dst_stride", C.c_int),
                 ("width", C.c_int), ("height", C.c_int)]
+
+
+class DownsamplePlane(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("src_stride", C.c_int), ("src_width", C.c_int), ("src_height", C.c_int),
+                ("dst", C.c_void_p), ("dst_stride", C.c_int), ("dst_extension", C.c_int)]
+
+
+class MetricScan(C.Structure):
+    """The input members of SchroMetricScan (schrometric.h:38-53)."""
+    _fields_ = [(n, C.c_int) for n in ("x", "y", "block_width", "block_height", "ref_x", "ref_y", "scan_width", "scan_height",
+                                       "gravity_x", "gravity_y", "dx", "dy")]
+
+
+class MetricScanResult(C.Structure):
+    _fields_ = [("dx", C.c_int), ("dy", C.c_int), ("metric", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class MetricScanPicture(C.Structure):
+    _fields_ = [("frame", C.c_void_p), ("frame_stride", C.c_int), ("ref", C.c_void_p), ("ref_stride", C.c_int),
+                ("width", C.c_int), ("height", C.c_int), ("extension", C.c_int),
+                ("scans", C.POINTER(MetricScan)), ("nscans", C.c_int),
+                ("results", C.c_void_p), ("metrics", C.c_void_p)]
 
 
 class ConvertPlane(C.Structure):
@@ -373,6 +397,16 @@ def load():
     L.schro_hip_iwt_batch.restype = i
     L.schro_hipframe_iwt_transform.argtypes = [vp, C.POINTER(Frame), C.POINTER(Params)]
     L.schro_hipframe_iwt_transform.restype = i
+    L.schro_hip_downsample_batch.argtypes = [vp, C.POINTER(DownsamplePlane), i]
+    L.schro_hip_downsample_batch.restype = i
+    L.schro_hip_metric_scan_setup.argtypes = [C.POINTER(MetricScan), i, i, i, i, i, i]
+    L.schro_hip_metric_scan_setup.restype = i
+    L.schro_hip_metric_scan_batch.argtypes = [vp, C.POINTER(MetricScanPicture), i]
+    L.schro_hip_metric_scan_batch.restype = i
+    L.schro_hipframe_downsample.argtypes = [C.POINTER(Frame), C.POINTER(Frame)]
+    L.schro_hipframe_downsample.restype = i
+    L.schro_rough_me_heirarchical_scan_nohint_hip.argtypes = [C.POINTER(Frame), C.POINTER(Frame), C.POINTER(Params), i, i, i, vp]
+    L.schro_rough_me_heirarchical_scan_nohint_hip.restype = i
     L.schro_hip_convert_u8_batch.argtypes = [vp, C.POINTER(ConvertPlane), i, i]
     L.schro_hip_convert_u8_batch.restype = i
     L.schro_hip_upsample_batch.argtypes = [vp, C.POINTER(UpsamplePlane), i]

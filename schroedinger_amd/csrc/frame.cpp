@@ -982,4 +982,49 @@ schro_hipframe_shift_right (SchroHipFrame * frame, int shift)
   return stage_done (frame_ctx (frame), schro_hip_shift_right_batch (frame_ctx (frame), planes, 3, format_bpp (frame->format), shift));
 }
 
+// schro_frame_downsample (dest, src) + schro_frame_mc_edgeextend (dest): one level of schro_encoder_frame_downsample
+// (schroanalysis.c:24-25), the three components in one launch
+int
+schro_hipframe_downsample (SchroHipFrame * dest, SchroHipFrame * src)
+{
+  SCHRO_HIP_REQUIRE (dest && src && frame_ctx (dest) && dest->domain == src->domain, "hipframe_downsample: needs two device frames of one domain");
+  SCHRO_HIP_REQUIRE (!(dest->format & 0x100) && !(src->format & 0x100) && format_bpp (dest->format) == 1 && dest->format == src->format
+      && !src->is_upsampled && !dest->is_upsampled, "hipframe_downsample: needs two planar u8 frames of one chroma format");
+  SCHRO_HIP_REQUIRE (dest->extension >= 0, "hipframe_downsample: negative extension %d", dest->extension);
+  SchroHipDownsamplePlane planes[3];
+  memset (planes, 0, sizeof (planes));
+  for (int k = 0; k < 3; k++) {
+    const SchroHipFrameData & s = src->components[k], &d = dest->components[k];
+    SCHRO_HIP_REQUIRE (s.width > 0 && s.height > 0 && d.width == (s.width + 1) / 2 && d.height == (s.height + 1) / 2,
+        "hipframe_downsample: component %d is %dx%d, half of %dx%d is %dx%d", k, d.width, d.height, s.width, s.height, (s.width + 1) / 2,
+        (s.height + 1) / 2);
+    planes[k].src = (const uint8_t *) s.data;
+    planes[k].src_stride = s.stride;
+    planes[k].src_width = s.width;
+    planes[k].src_height = s.height;
+    planes[k].dst = (uint8_t *) d.data;
+    planes[k].dst_stride = d.stride;
+    planes[k].dst_extension = dest->extension;
+  }
+  return stage_done (frame_ctx (dest), schro_hip_downsample_batch (frame_ctx (dest), planes, 3));
+}
+
+int
+schro_rough_me_heirarchical_scan_nohint_hip (SchroHipFrame * frame, SchroHipFrame * ref_frame, const SchroHipParams * params, int shift,
+    int distance, int ref, void *motion_vectors)
+{
+  SCHRO_HIP_REQUIRE (frame && ref_frame && params && motion_vectors && frame_ctx (frame) && frame->domain == ref_frame->domain,
+      "rough_me_heirarchical_scan_nohint_hip: needs two device frames of one domain, the parameters and the vectors");
+  SCHRO_HIP_REQUIRE (!(frame->format & 0x100) && !(ref_frame->format & 0x100) && format_bpp (frame->format) == 1
+      && format_bpp (ref_frame->format) == 1 && !frame->is_upsampled && !ref_frame->is_upsampled,
+      "rough_me_heirarchical_scan_nohint_hip: needs planar u8 frames");
+  SCHRO_HIP_REQUIRE (frame->width == ref_frame->width && frame->height == ref_frame->height && frame->components[0].width == frame->width
+      && frame->components[0].height == frame->height && ref_frame->components[0].width == frame->width
+      && ref_frame->components[0].height == frame->height, "rough_me_heirarchical_scan_nohint_hip: the frames differ in size");
+  // (complete on return whatever the stage-completion setting: the vectors are host memory)
+  return rough_scan_nohint_run (frame_ctx (frame), (const uint8_t *) frame->components[0].data, frame->components[0].stride,
+      (const uint8_t *) ref_frame->components[0].data, ref_frame->components[0].stride, frame->width, frame->height, frame->extension,
+      params, shift, distance, ref, motion_vectors);
+}
+
 }                               // extern "C"

@@ -127,6 +127,44 @@ struct IwtFwdJob {
   int pad;
 };
 
+// One plane of the downsample (analysis.hip).  A tile is kDownTileCols x kDownTileRows samples of the destination
+// INCLUDING its apron: column xorg + 4 * group, row -ext + row.
+struct DownsampleJob {
+  const uint8_t *src;
+  uint8_t *dst;                 // pixel (0, 0)
+  int src_stride, dst_stride;
+  int sw, sh;                   // source size
+  int dw, dh;                   // destination size, (sw + 1) / 2 x (sh + 1) / 2
+  int ext;                      // apron samples on every side
+  int xorg;                     // column of the first group: -ext, lowered so that the groups' stores are 4-byte aligned
+  int tiles_x;
+  int tile_base;                // first block id of this job
+  uint32_t m_tiles_x;           // div_magic (tiles_x)
+  int pad;
+};
+
+// One picture of the SAD scan (analysis.hip), and one scan as the kernel reads it
+struct ScanPicture {
+  const uint8_t *frame;
+  const uint8_t *ref;
+  SchroHipMetricScanResult *results;
+  uint32_t *metrics;            // NULL: no tables
+  int frame_stride, ref_stride;
+  int width, height;
+  int scan_base;                // index of the picture's first scan in the launch
+  int pad[3];
+};
+struct ScanJob {
+  int x, y, bw, bh;
+  int ref_x, ref_y, sw, sh;
+  int gi, gj;                   // the gravity position inside the window
+  int dx, dy;                   // the caller's vector
+  int pic;
+  uint32_t m_sh;                // div_magic (sh)
+  int pad[2];
+};
+static_assert (sizeof (ScanJob) == 64 && sizeof (ScanPicture) == 64, "scan tables: 64-byte records");
+
 // r05: the three-level s32 Haar transform of a 4:2:2 picture with the v210 copy-out as its epilogue (iiwt_haar.hip)
 struct HaarPackJob {
   const void *src[3];           // the coefficient planes (Y, U, V), in-place sub-band layout
@@ -530,6 +568,13 @@ void iiwt_tile_geometry (int filter, int bpp, int *useful_cols,
 // one level of the forward wavelet (iwt_fwd.hip)
 void iwt_fwd_tile_geometry (int filter, int bpp, int *useful_cols, int *useful_row_pairs);
 int launch_iwt_fwd_level (hipStream_t stream, const IwtFwdJob * d_jobs, int njobs, int total_tiles, int filter, int bpp);
+// the downsample and the SAD scan (analysis.hip)
+void downsample_tile_geometry (int *cols, int *rows);
+int launch_downsample (hipStream_t stream, const DownsampleJob * d_jobs, int njobs, int total_tiles);
+// LDS bytes one wave needs for a bw x bh block scanned over sw x sh positions (0: an empty block), and the most a launch gives
+size_t scan_lds_bytes (int bw, int bh, int sw, int sh);
+size_t scan_lds_limit ();
+int launch_metric_scan (hipStream_t stream, const ScanPicture * d_pics, const ScanJob * d_scans, int nscans, size_t lds_per_wave);
 int launch_convert (hipStream_t stream, const ConvertJob * d_jobs, int njobs,
     int total_tiles, int bpp);
 void convert_tile_geometry (int *tw, int *th);
@@ -785,6 +830,11 @@ int copy_2d_async (SchroHipContext * ctx, void *dst, int dst_stride, const void 
 // first, as the frame layer's in-place schro_hipframe_iwt_transform needs
 int iwt_batch_run (SchroHipContext * ctx, const SchroHipIwtFwdPlane * planes, int nplanes, int depth, int filter, int bpp,
     bool in_place);
+// the loop of schro_rough_me_heirarchical_scan_nohint over schro_hip_metric_scan_batch (plane_analysis.cpp): fills the
+// host SchroMotionVector array and waits for the queue
+int rough_scan_nohint_run (SchroHipContext * ctx, const uint8_t * frame, int frame_stride, const uint8_t * ref, int ref_stride,
+    int width, int height, int extension, const SchroHipParams * params, int shift, int distance, int ref_index,
+    void *motion_vectors);
 // v216 / ARGB / AY64 (plane_frameops.cpp)
 bool is_wide_format (int format);
 // the launches made while a scope is open are timed under its kernel class (when profiling is on)

@@ -110,6 +110,30 @@ class DeviceFrame:
             self.p = None
 
 
+class PlaneFrame:
+    """A device frame over DevicePlanes that exist already (not owned): three u8 / s16 / s32 planes of the context, each
+    holding its component with `extension` samples of apron on every side -- (h + 2 * extension) x (w + 2 * extension)
+    samples, the component's data pointer at pixel (0, 0): schro_frame_new_and_alloc_extended's layout."""
+
+    def __init__(self, ctx, planes, extension=0, h_shift=0, v_shift=0):
+        self.planes = list(planes)
+        self.c = _lib.Frame()
+        f, e = self.c, int(extension)
+        f.refcount, f.domain, f.extension = 1, ctx.lib.schro_hip_context_domain(ctx.h), e
+        f.format = frame_format(self.planes[0].dtype, h_shift, v_shift)
+        f.height, f.width = self.planes[0].height - 2 * e, self.planes[0].width - 2 * e
+        for k, p in enumerate(self.planes):
+            d = f.components[k]
+            d.format, d.stride = f.format, p.stride
+            d.data = p.ptr + e * p.stride + e * p.dtype.itemsize
+            d.height, d.width = p.height - 2 * e, p.width - 2 * e
+            d.length = p.stride * p.height
+            d.h_shift, d.v_shift = (h_shift, v_shift) if k else (0, 0)
+
+    def ptr(self):
+        return C.byref(self.c)
+
+
 def make_params(**kw):
     p = _lib.Params()
     for k, v in kw.items():
