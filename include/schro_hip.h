@@ -352,7 +352,8 @@ typedef struct {
  * descriptor.  metrics[i * scan_height + j] = SAD (block at (x, y) of frame, block at (ref_x + i, ref_y + j) of ref); a
  * block of non-positive width or height has SAD 0.  The minimum starts at the gravity position i = gravity_x + x - ref_x,
  * j = gravity_y + y - ref_y and is replaced only by a strictly smaller metric, i outer, j inner; dx, dy change only on
- * replacement.  Samples outside a picture are its edge-extended apron: the kernel clamps coordinates. */
+ * replacement.  Samples outside a picture are its edge-extended apron: the kernel clamps coordinates.  The entries of a
+ * scan's table from scan_width * scan_height on are left as they were. */
 typedef struct {
   const uint8_t *frame;
   int frame_stride;

@@ -1000,3 +1000,67 @@ def test_random_footprints(ctx):
                 finish()
         except AssertionError as e:
             raise AssertionError("%s: %s" % (where, e)) from e
+
+
+# ---- the SAD scan ---------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("tables", [True, False], ids=["tables", "no_tables"])
+@pytest.mark.parametrize("skew", [0, 1, 2, 3])
+def test_metric_scan(ctx, skew, tables):
+    """schro_hip_metric_scan_batch through the C ABI, `results` and `metrics` the test's own memory: 16 bytes per scan, and of
+    a scan's table of 42 * 42 entries only the first scan_width * scan_height (include/schro_hip.h); nothing else, also
+    with metrics = NULL.  Two pictures with 1 and 7 scans (no multiples of the four scans per workgroup: the last
+    workgroup's idle waves), planes at every byte alignment with strides that are no multiple of 4."""
+    import analysis_ref as A
+    T = sa.LIMIT_METRIC_SCAN ** 2
+    ext = 8
+    pics = [(37, 29, [dict(x=8, y=8, block_width=8, block_height=8, ref_x=6, ref_y=5, scan_width=5, scan_height=7, gi=4, gj=0)]),
+            (70, 50, [dict(x=0, y=0, block_width=16, block_height=16, ref_x=-8, ref_y=-8, scan_width=17, scan_height=17, gi=8, gj=8),
+                      dict(x=20, y=10, block_width=0, block_height=4, ref_x=18, ref_y=8, scan_width=5, scan_height=5, gi=2, gj=2),
+                      dict(x=6, y=2, block_width=64, block_height=48, ref_x=-6, ref_y=-8, scan_width=19, scan_height=17, gi=0, gj=16),
+                      dict(x=33, y=21, block_width=5, block_height=3, ref_x=13, ref_y=20, scan_width=42, scan_height=1, gi=41, gj=0),
+                      dict(x=12, y=1, block_width=1, block_height=1, ref_x=12, ref_y=1, scan_width=1, scan_height=1, gi=0, gj=0),
+                      dict(x=40, y=30, block_width=13, block_height=9, ref_x=30, ref_y=8, scan_width=1, scan_height=42, gi=0, gj=21),
+                      dict(x=3, y=4, block_width=7, block_height=64 - 18, ref_x=-7, ref_y=-8, scan_width=42, scan_height=20, gi=10, gj=12)])]
+    L, todo = G.Layout(), []
+    for n, (w, h, dicts) in enumerate(pics):
+        scans = np.zeros(len(dicts), sa.SCAN_DTYPE)
+        for k, (s, d) in enumerate(zip(scans, dicts)):
+            for key in ("x", "y", "block_width", "block_height", "ref_x", "ref_y", "scan_width", "scan_height"):
+                s[key] = d[key]
+            s["gravity_x"], s["gravity_y"] = d["ref_x"] + d["gi"] - d["x"], d["ref_y"] + d["gj"] - d["y"]
+            s["dx"], s["dy"] = 100 + k, -100 - k
+        f = L.plane(h, w, np.uint8, stride=w + 5 + 2 * n, align=64, skew=skew, footprint=None, name="frame%d" % n)
+        r = L.plane(h, w, np.uint8, stride=w + 1 + 2 * n, align=64, skew=(skew + 1 + n) & 3, footprint=None, name="ref%d" % n)
+        res = L.span(16 * len(scans), align=16, footprint=("bytes", 16 * len(scans)), name="results%d" % n)
+        met = L.span(4 * T * len(scans), align=4, name="metrics%d" % n,
+                     footprint=[(k * T * 4, 0, 4 * int(s["scan_width"]) * int(s["scan_height"]), 1) for k, s in enumerate(scans)]) if tables else None
+        todo.append((f, r, res, met, scans, A.picture(w, h, 80 + n + skew), A.picture(w, h, 90 + n + skew)))
+        assert (w + 5 + 2 * n) % 4 and (w + 1 + 2 * n) % 4
+    B = G.GuardedBlock(ctx, L, seed=31 + skew)
+    try:
+        arr = (_lib.MetricScanPicture * len(todo))()
+        for a, (f, r, res, met, scans, frame, ref) in zip(arr, todo):
+            B[f].upload(frame)
+            B[r].upload(ref)
+            a.frame, a.frame_stride, a.ref, a.ref_stride = B[f].ptr, f.stride, B[r].ptr, r.stride
+            a.width, a.height, a.extension = f.width, f.height, ext
+            a.scans, a.nscans = scans.ctypes.data_as(C.POINTER(_lib.MetricScan)), len(scans)
+            a.results, a.metrics = B[res].ptr, B[met].ptr if met is not None else None
+        sa.check(ctx.lib.schro_hip_metric_scan_batch(ctx.h, arr, len(todo)))
+        ctx.synchronize()
+        want = {}
+        for (f, r, res, met, scans, frame, ref) in todo:
+            want_r = np.zeros(len(scans), sa.SCAN_RESULT_DTYPE)
+            want_m = B[met].initial().copy().view(np.uint32).reshape(len(scans), T) if met is not None else None
+            for k, s in enumerate(scans):
+                m = A.do_scan(frame, ref, s)
+                want_r[k] = A.get_min(m, s) + (0,)
+                if want_m is not None:
+                    want_m[k, :m.size] = m
+            want[res] = want_r.view(np.uint8).reshape(1, -1)
+            if met is not None:
+                want[met] = want_m.view(np.uint8).reshape(1, -1)
+        B.check(want)
+    finally:
+        B.free()

@@ -1,9 +1,16 @@
 """GPU parity: the forward wavelet (schro_hip_iwt_batch, schro_hipframe_iwt_transform) vs the CPU oracle.
 
 Every comparison is bit-exact (np.array_equal) against oracle_forward_iwt_component, which tests/test_oracle_wavelet.py
-pins on the reference's compiled Orc kernels for filters 0 - 4 and 6.  The oracle's Fidelity filter (5) is unpinned -- its
-full-range wrap points were never checked against the reference --, so filter 5 is compared on pixel-range input only,
-where no intermediate wraps; the pinned filters are also compared on full-range input, which exercises the s16 wrap points.
+pins on the reference's compiled Orc kernels for filters 0 - 4 and 6.  Those filters are compared on pixel-range input,
+where no intermediate wraps, and on full-range input, which exercises the wrap points.
+
+The Fidelity filter (5) has no compiled reference kernel to be pinned on ("parity unpinned" stays for the inverse Fidelity
+filter itself), but its FORWARD wrap points need none: filters 3 and 5, the two without a pre-shift, lift with wrap-around
+additions only, so the inverse is a bijection and inverse (forward (x)) == x for every input, full range included
+(tests/test_oracle_wavelet.py checks this of the oracle, and that it fails for the filters that lose the input's top
+bit).  The device inverse of filter 5 is compared with the oracle's at full range (tests/test_gpu_iiwt.py), so the forward
+transform of a full-range image is fixed as the one image that inverse maps back: the forward filter-5 comparison on
+full-range input rests on the inverse, by the full-range round trip on the device below, not on reference output.
 
 The round trip (forward on the device, then the existing inverse on the device, equals the input) is the design of the
 reference's testsuite/wavelet_2d.c; the footprint cases use tests/guard_lib.py.
@@ -22,7 +29,6 @@ from schroedinger_amd import frames
 pytestmark = pytest.mark.gpu
 
 FILTERS = range(7)
-PINNED = (0, 1, 2, 3, 4, 6)
 # (width, height): tiny, odd at a level (30 x 18: 15 x 9 sub-bands), one tile, several tiles, 1080p- and 2160p-sized
 SIZES = [(2, 2), (4, 4), (8, 2), (16, 16), (30, 18), (256, 256), (320, 240), (1920, 1088), (3840, 2160)]
 
@@ -61,9 +67,9 @@ def test_every_size_depth_and_range(ctx, filt, dtype):
         for depth in sorted({1, deepest(w, h)}):
             img = pixel_range(h, w, dtype, seed=w * 31 + h + depth)
             assert np.array_equal(gpu_iwt(ctx, img, depth, filt), O.forward_iwt(img, depth, filt)), (filt, w, h, depth, "pixel")
-            if filt in PINNED:  # (filter 5: the oracle's Fidelity filter is unpinned, see above)
-                fr = synth.full_range(h, w, dtype, seed=w * 7 + h + depth)
-                assert np.array_equal(gpu_iwt(ctx, fr, depth, filt), O.forward_iwt(fr, depth, filt)), (filt, w, h, depth, "full")
+            # (filter 5 too: its full-range wrap points are fixed by the inverse's, see above)
+            fr = synth.full_range(h, w, dtype, seed=w * 7 + h + depth)
+            assert np.array_equal(gpu_iwt(ctx, fr, depth, filt), O.forward_iwt(fr, depth, filt)), (filt, w, h, depth, "full")
 
 
 @pytest.mark.parametrize("dtype", [np.int16, np.int32])
@@ -102,6 +108,70 @@ def test_round_trip_is_the_identity(ctx, filt, dtype):
         got = back.download()
         [p.free() for p in (src, co, back)]
         assert np.array_equal(got, img), (filt, w, h, depth)
+
+
+def round_trip(ctx, img, depth, filt):
+    src = ctx.upload(img)
+    co = ctx.plane(img.shape[0], img.shape[1], img.dtype).fill(0x5a)
+    back = ctx.plane(img.shape[0], img.shape[1], img.dtype).fill(0xa5)
+    ctx.iwt_batch([(src, co)], depth, filt)
+    ctx.iiwt_batch([(co, back)], depth, filt)
+    got_co, got = co.download(), back.download()
+    [p.free() for p in (src, co, back)]
+    return got_co, got
+
+
+DEEP = [(64, 64, 6), (64, 128, 6), (32, 96, 5), (160, 96, 5)]      # (h, w, depth): last levels of 2 x 2 (1 x 2, 5 x 3 sub-bands)
+
+
+@pytest.mark.parametrize("dtype", [np.int16, np.int32])
+@pytest.mark.parametrize("filt", FILTERS)
+def test_depths_5_and_6(ctx, filt, dtype):
+    """The last levels read 4 x 4 and 2 x 2 images from the queue's scratch.  Pixel range: against the oracle, and the
+    device round trip gives the input back; full range: against the oracle (every filter: the pinned ones and, by the
+    argument at the top, filter 5), and the device inverse of the coefficients equals the oracle's inverse of them."""
+    for (h, w, depth) in DEEP:
+        img = pixel_range(h, w, dtype, seed=h * 13 + w + depth)
+        co, back = round_trip(ctx, img, depth, filt)
+        assert np.array_equal(co, O.forward_iwt(img, depth, filt)), (filt, w, h, depth, "pixel")
+        assert np.array_equal(back, img), (filt, w, h, depth, "pixel round trip")
+        fr = synth.full_range(h, w, dtype, seed=h * 5 + w + depth)
+        co, back = round_trip(ctx, fr, depth, filt)
+        want = O.forward_iwt(fr, depth, filt)
+        assert np.array_equal(co, want), (filt, w, h, depth, "full")
+        assert np.array_equal(back, O.inverse_iwt(want, depth, filt)), (filt, w, h, depth, "full inverse")
+        if filt in (3, 5):
+            assert np.array_equal(back, fr), (filt, w, h, depth, "full round trip")
+
+
+@pytest.mark.parametrize("dtype", [np.int16, np.int32])
+@pytest.mark.parametrize("filt", [3, 5])
+def test_full_range_round_trip_of_the_filters_without_a_pre_shift(ctx, filt, dtype):
+    """forward, then inverse, on the device equals full-range input (the property tests/test_oracle_wavelet.py shows of the
+    oracle): what the forward filter-5 comparison rests on."""
+    for (h, w, depth) in [(36, 60, 2), (256, 256, 4), (64, 64, 6)]:
+        fr = synth.full_range(h, w, dtype, seed=h + 3 * w + depth)
+        co, back = round_trip(ctx, fr, depth, filt)
+        assert np.array_equal(back, fr), (filt, w, h, depth)
+        assert np.array_equal(co, O.forward_iwt(fr, depth, filt)), (filt, w, h, depth, "coefficients")
+
+
+@pytest.mark.parametrize("filt", [1, 5])
+def test_256_planes_in_one_call(ctx, filt):
+    """The call's limit (the workgroup-to-job search goes round once per 64 jobs): 256 planes of mixed sizes from 2 x 2 to
+    16 x 24, depth 1, every plane against the oracle, in both orders."""
+    rng = np.random.default_rng(256 + filt)
+    shapes = [(2, 2), (16, 24)] + [(2 * int(rng.integers(1, 9)), 2 * int(rng.integers(1, 13))) for _ in range(254)]
+    imgs = [pixel_range(h, w, np.int16, seed=7 + n) for n, (h, w) in enumerate(shapes)]
+    want = [O.forward_iwt(a, 1, filt) for a in imgs]
+    srcs = [ctx.upload(a) for a in imgs]
+    for order in (list(range(256)), list(range(256))[::-1]):
+        dsts = [ctx.plane(shapes[n][0], shapes[n][1], np.int16).fill(0xa5) for n in order]
+        ctx.iwt_batch([(srcs[n], d) for n, d in zip(order, dsts)], 1, filt)
+        for n, d in zip(order, dsts):
+            assert np.array_equal(d.download(), want[n]), (filt, n, shapes[n], order[0])
+        [d.free() for d in dsts]
+    [p.free() for p in srcs]
 
 
 def run_guarded(ctx, planes, depth, filt, seed):

@@ -111,6 +111,26 @@ def test_matches_reference_kernels_in_reference_schedule(filt, dtype):
                            lambda: O.refdrv_iiwt_2d(fr, filt))
 
 
+FULL_RANGE_ROUND_TRIPS = [(64, 64, 6), (32, 96, 5), (48, 80, 4), (36, 60, 2), (2, 2, 1)]       # (h, w, depth)
+NO_PRE_SHIFT = (3, 5)
+
+
+@pytest.mark.parametrize("dtype", [np.int16, np.int32])
+def test_full_range_round_trip_holds_for_the_filters_without_a_pre_shift(dtype):
+    """The filters with no pre-shift (Haar0, Fidelity) lift with wrap-around additions only, so inverse (forward (x)) == x on
+    EVERY input, wraps included: the inverse is a bijection, and the forward transform of full-range input is the one
+    image the inverse maps back to it.  This is what licenses comparing the device's forward filter 5 on full-range input
+    (tests/test_gpu_iwt_forward.py): its wrap points are fixed by the inverse's.  The other filters shift the input left by
+    one bit first and lose its top bit: for them the property does not hold, and their forward wrap points rest on the
+    forward oracle alone."""
+    for (h, w, depth) in FULL_RANGE_ROUND_TRIPS:
+        x = synth.full_range(h, w, dtype, seed=11 * h + w + depth)
+        for filt in NO_PRE_SHIFT:
+            assert np.array_equal(O.inverse_iwt(O.forward_iwt(x, depth, filt), depth, filt), x), (filt, h, w, depth)
+        for filt in (0, 1, 2, 4, 6):
+            assert not np.array_equal(O.inverse_iwt(O.forward_iwt(x, depth, filt), depth, filt), x), (filt, h, w, depth)
+
+
 def test_rounding_and_wrap_pins():
     # (x+1)>>1 wraps at 16 bits for filters 0,1,2,6 (orc_interleave2_rrshift1_s16) but not for
     # Haar1 (avgsw): 32767 -> -16384 vs 16384
