@@ -191,7 +191,9 @@ float schro_hip_timer_end (SchroHipContext * ctx);
 #define SCHRO_HIP_KERNEL_SLICES 5
 #define SCHRO_HIP_KERNEL_DC_PREDICT 6
 #define SCHRO_HIP_KERNEL_DEQUANT 7
-#define SCHRO_HIP_KERNEL_CLASSES 8
+#define SCHRO_HIP_KERNEL_QUANTISE 8      /* encoder: quantise_kernel */
+#define SCHRO_HIP_KERNEL_QUANTISE_DC 9   /* encoder: quantise_dc_kernel (the intra LL recurrence) */
+#define SCHRO_HIP_KERNEL_CLASSES 10
 int schro_hip_profile_enable (SchroHipContext * ctx, int enable);
 int schro_hip_profile_reset (SchroHipContext * ctx);
 int schro_hip_profile_read (SchroHipContext * ctx, int kernel_class,
@@ -397,6 +399,11 @@ int schro_hip_convert_u8_batch (SchroHipContext * ctx,
  * orc_add_s16_u8_2d) = schro_gpuframe_add's (schrogpuframe.c:257-306).  `dst` of the plane is the int16 plane. */
 int schro_hip_add_batch (SchroHipContext * ctx, const SchroHipConvertPlane * planes, int nplanes,
     int src_bytes_per_sample);
+
+/* dst (int16) -= src (int16, or uint8 zero-extended when src_is_u8), 16-bit wrapping subtract over width x height:
+ * schro_frame_subtract's two cases on planes (schroframe.c:1031-1079: orc_subtract_s16, orc_subtract_s16_u8) -- the
+ * encoder's residual, picture - prediction.  The planes are schro_hip_add_batch's. */
+int schro_hip_subtract_batch (SchroHipContext * ctx, const SchroHipConvertPlane * planes, int nplanes, int src_is_u8);
 
 /* Copy-out of a decoded u8 picture into a packed output frame; replaces the
  * packed-destination case of schro_frame_convert (&output_picture, ref_output_frame)
@@ -831,6 +838,58 @@ void schro_hip_dequant_plan_free (SchroHipDequantPlan * plan);
 int schro_hip_codeblock_layout (int iwt_width, int iwt_height, int transform_depth, const int *horiz_codeblocks,
     const int *vert_codeblocks, int stride, int bytes_per_sample, SchroHipCodeblock * out, int max);
 
+/* ---- encoder: quantisation on the device ---------------------------------------------------
+ *
+ * schro_encoder_quantise_subband (schroencoder.c:3729-3785) per codeblock: the quantised value goes to the quant
+ * frame, and IN THE SAME PASS the dequantised value replaces the coefficient -- the reconstruction the encoder's local
+ * decode runs the inverse transform on (:2697-2700).  The arithmetic is the reference's, bit for bit:
+ *   s16 frames (schro_frame_data_quantise, :3485-3553): four 16-bit Orc programs by quant index -- 0: copy, the
+ *     coefficients stay; a multiple of 4: orc_quantdequant2_s16 (a shift); 3: orc_quantdequant3_s16; any other:
+ *     orc_quantdequant1_s16 (mulhuw by schro_table_inverse_quant, quant_offset-- above index 8).  Every step wraps at 16
+ *     bits, and the reciprocal multiply is NOT schro_quantise's division (they part as early as |x| = 47).
+ *   s32 frames: schro_quantise_s32 (schroutils.c:248-257), C int arithmetic with a truncating division; |x| < 2^28.
+ *   offsets: schro_table_offset_1_2 when is_intra, else schro_table_offset_3_8.
+ *   the LL band of an intra picture (dc_predict_first): schro_frame_data_quantise_dc_predict (:3591-3667) -- each
+ *     sample is predicted from its RECONSTRUCTED left, upper and upper-left neighbours (schro_divide3 on s16,
+ *     schro_divide (., 3) on s32), the difference goes through C schro_quantise / schro_dequantise, the s16 stores
+ *     truncate.  A codeblock never reads its right neighbour, so the band is one raster-order recurrence in which every
+ *     sample takes its own codeblock's quant index; the device sweeps its anti-diagonals.
+ * One departure, deliberate: the reference's zero test on s16 (schro_frame_data_is_zero, :4043-4070) sums |q| per row in
+ * 16 bits and calls a row zero when the sum is a non-zero multiple of 65536 (its own FIXME).  The summary below reports
+ * the true answer: nonzero == 0 exactly when every quantised sample of the codeblock is zero.
+ * schro_encoder_clean_up_transform is not part of this (it clears nothing for a real picture, :3417-3424). */
+typedef struct {
+  uint32_t nonzero;             /* quantised values != 0 in the codeblock: 0 = zero codeblock; the sum over a sub-band's
+                                 * records is its zero flag (schro_encoder_quantise_subband's return, :3784) */
+  uint32_t max_abs;             /* largest |q|: picks the 1 / 2 / 4-byte hand-over width (SchroHipCodeblock.src_bytes) */
+} SchroHipCodeblockSummary;
+
+/* the workgroup size of the DC recurrence: a band's anti-diagonal longer than this is walked in strides */
+#define SCHRO_HIP_QUANTISE_DC_THREADS 256
+/* ... and the most rows a DC band may have (two diagonals + the one being written live in LDS, indexed by row) */
+#define SCHRO_HIP_QUANTISE_DC_MAX_ROWS 4096
+
+typedef struct {
+  void *coeffs;                 /* the component's coefficient plane (device, s16 or s32): read, reconstruction written back */
+  void *quant;                  /* the quantised values (device), the SAME layout: a record's offsets and strides hold in both */
+  size_t bytes;                 /* what each of the two planes spans: no record may reach past it; the planes may not overlap */
+  const SchroHipCodeblock *codeblocks;  /* HOST array: dst_offset, dst_stride, width, height, quant_index; src_* ignored */
+  int ncodeblocks;
+  int is_intra;                 /* schro_table_offset_1_2, else _3_8 */
+  int dc_predict_first;         /* > 0: the first dc_predict_first records are sub-band 0 of an intra picture and take the
+                                 * DC recurrence; they share one dst_stride and tile ... */
+  int dc_width, dc_height;      /* ... this rectangle at the plane's base, each sample in exactly one of them */
+  SchroHipCodeblockSummary *summary;    /* device, ncodeblocks entries: cleared and filled by the call */
+} SchroHipQuantPlane;
+
+/* One launch of quantise_kernel for all planes of the call (unlike sizes and indices mix), one of quantise_dc_kernel
+ * (a workgroup per plane) where planes ask for DC prediction.  Refused with SCHRO_HIP_EINVAL before anything is launched,
+ * the message naming plane and record: a quant index above 60, bytes_per_sample not 2 or 4, a record of non-positive
+ * width or height, a stride shorter than a row or not a multiple of the sample size, `quant` overlapping `coeffs`, a record
+ * reaching outside `bytes`, DC records that do not tile the band.  (Only schro_hipframe_quantise, whose layouts of tiny
+ * sub-bands contain records of no width or height, skips those: their summary is zero.) */
+int schro_hip_quantise_batch (SchroHipContext * ctx, const SchroHipQuantPlane * planes, int nplanes, int bytes_per_sample);
+
 /* ---- frame layer: the reference's stage boundary ------------------------- */
 
 /* The structs of this layer are LAYOUT-IDENTICAL to the reference's (same members, same
@@ -1200,6 +1259,25 @@ int schro_motion_render_hip (SchroHipMotion * motion, SchroHipFrame * dest,
  * (schroframe.c:1000-1029) on device frames: dest (S16) += src (S16, or U8 zero-extended) of the same chroma format,
  * 16-bit wrapping add over the components' common size.  Other depth pairs: SCHRO_HIP_EINVAL (the reference asserts). */
 int schro_hipframe_add (SchroHipFrame * dest, SchroHipFrame * src);
+
+/* schro_frame_subtract (dest, src) (schroframe.c:1062-1079) on device frames: dest (S16) -= src (S16, or U8 zero-extended) of
+ * the same chroma format, 16-bit wrapping, over the components' common size -- the encoder's residual.  Other format pairs:
+ * SCHRO_HIP_EINVAL (the reference asserts). */
+int schro_hipframe_subtract (SchroHipFrame * dest, SchroHipFrame * src);
+
+/* schro_encoder_quantise_subband over every sub-band of every component (the loop of schro_encoder_encode_subband's
+ * callers, schroencoder.c:3789-3890) with frame->iwt_frame and frame->quant_frame on the device: both frames are device
+ * frames of one domain, depth (s16 / s32) and chroma format.  The codeblocks, their order and their counts are
+ * schro_hip_codeblock_layout's over params (iwt_luma_* / iwt_chroma_*, transform_depth, horiz_ / vert_codeblocks), the
+ * stream's; quant_indices[c] holds one index per record of component c in that order (the values
+ * schro_encoder_frame_get_quant_index returns).  A picture without references (params->num_refs == 0) is intra, and its
+ * sub-band 0 is DC-predicted.  summary[c]: HOST arrays of as many entries, copied back on the selected queue -- complete
+ * on return, or, when stage completion is off, once that queue has been waited for; allocate them with
+ * schro_hip_host_alloc then: into pageable memory the copy holds the caller until it is done.  The records and the device
+ * summaries -- a set per queue, so that pictures in flight on different queues do not share one -- are kept in a table of
+ * the context's, rebuilt when the geometry changes. */
+int schro_hipframe_quantise (SchroHipFrame * quant_frame, SchroHipFrame * iwt_frame, const SchroHipParams * params,
+    const int *const quant_indices[3], SchroHipCodeblockSummary * const summary[3]);
 
 /* schro_gpuframe_convert (schrogpuframe.h:20) replacement for the conversions the decode path
  * performs: s16/s32 -> u8 (+128, clamp, crop), u8 -> u8 copy, planar -> packed (YUYV, UYVY,

@@ -42,6 +42,9 @@ def metric_scan_setup(x, y, block_width, block_height, frame_width, frame_height
     return s.ref_x, s.ref_y, s.scan_width, s.scan_height
 
 
+QUANTISE_DC_THREADS = 256       # SCHRO_HIP_QUANTISE_DC_THREADS (include/schro_hip.h): the DC recurrence's workgroup size
+
+
 def device_count():
     return _lib.load().schro_hip_device_count()
 
@@ -287,7 +290,7 @@ class Context:
         return ms
 
     KERNEL_CLASSES = ("iiwt_finest", "iiwt_coarse", "upsample", "obmc", "convert", "slices", "dc_predict",
-                      "dequant")
+                      "dequant", "quantise", "quantise_dc")
 
     def profile_enable(self, on=True):
         check(self.lib.schro_hip_profile_enable(self.h, 1 if on else 0))
@@ -677,6 +680,40 @@ class Context:
             assert d.dtype == np.int16 and s.dtype.itemsize == pairs[0][1].dtype.itemsize
             arr[k] = _lib.ConvertPlane(s.ptr, s.stride, d.ptr, d.stride, min(d.width, s.width), min(d.height, s.height))
         check(self.lib.schro_hip_add_batch(self.h, arr, n, pairs[0][1].dtype.itemsize))
+
+    def subtract_batch(self, pairs):
+        """pairs: [(dst s16 DevicePlane, src s16 | u8 DevicePlane)]: dst -= src over their common size
+        (schro_frame_subtract on planes)."""
+        n = len(pairs)
+        arr = (_lib.ConvertPlane * n)()
+        for k, (d, s) in enumerate(pairs):
+            assert d.dtype == np.int16 and s.dtype == pairs[0][1].dtype and s.dtype in (np.int16, np.uint8)
+            arr[k] = _lib.ConvertPlane(s.ptr, s.stride, d.ptr, d.stride, min(d.width, s.width), min(d.height, s.height))
+        check(self.lib.schro_hip_subtract_batch(self.h, arr, n, 1 if pairs[0][1].dtype == np.uint8 else 0))
+
+    def quantise_batch(self, jobs):
+        """schro_hip_quantise_batch.  jobs: per component (coeffs DevicePlane (s16 / s32), quant DevicePlane of the same
+        layout, codeblocks -- a C table or a list of (dst_offset, dst_stride, width, height, src_offset, src_bytes,
+        quant_index) --, is_intra[, (dc_predict_first, dc_width, dc_height)]).  The coefficient planes receive the
+        reconstruction, the quant planes the quantised values.  Returns one DevicePlane per component holding its
+        SchroHipCodeblockSummary entries (download (): an (ncodeblocks, 2) uint32 array of nonzero, max_abs)."""
+        n = len(jobs)
+        arr = (_lib.QuantPlane * n)()
+        keep, summaries = [], []
+        for a, job in zip(arr, jobs):
+            coeffs, quant, cbs, intra = job[:4]
+            dc = job[4] if len(job) > 4 and job[4] else (0, 0, 0)
+            tab = cbs if isinstance(cbs, C.Array) else self.codeblock_table(cbs)
+            keep.append(tab)
+            assert quant.dtype == coeffs.dtype and quant.stride == coeffs.stride and quant.height >= coeffs.height
+            summ = DevicePlane(self, len(tab), 2, np.uint32, stride=8)
+            summaries.append(summ)
+            a.coeffs, a.quant, a.bytes = coeffs.ptr, quant.ptr, coeffs.stride * coeffs.height
+            a.codeblocks, a.ncodeblocks, a.is_intra = tab, len(tab), 1 if intra else 0
+            a.dc_predict_first, a.dc_width, a.dc_height = dc
+            a.summary = summ.ptr
+        check(self.lib.schro_hip_quantise_batch(self.h, arr, n, jobs[0][0].dtype.itemsize))
+        return summaries
 
     def upsample_batch(self, pairs):
         """pairs: [(src u8 plane h x w, dst HpPlane)] or [((src U, src V), dst pair HpPlane)]."""

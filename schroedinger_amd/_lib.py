@@ -43,7 +43,8 @@ EXPORTED_SYMBOLS = [
     "schro_hip_iiwt_pack_wide_batch",
     "schro_hipframe_shift_right", "schro_hip_add_batch", "schro_hipframe_add",
     "schro_hip_lowdelay_arith", "schro_hip_lowdelay_batch", "schro_hip_dc_predict_batch",
-    "schro_hip_dequant_batch",
+    "schro_hip_dequant_batch", "schro_hip_quantise_batch", "schro_hip_subtract_batch", "schro_hipframe_subtract",
+    "schro_hipframe_quantise",
     "schro_hip_decode_lowdelay_transform_data", "schro_hipframe_dequantise",
     "schro_hip_obmc_batch", "schro_hip_obmc_prediction_epoch", "schro_hip_obmc_overflowed",
     "schro_hip_frame_new_and_alloc", "schro_hip_frame_ref", "schro_hip_frame_unref",
@@ -148,6 +149,17 @@ class Codeblock(C.Structure):
 class DequantPlane(C.Structure):
     _fields_ = [("dst", C.c_void_p), ("values", C.c_void_p), ("codeblocks", C.POINTER(Codeblock)),
                 ("ncodeblocks", C.c_int), ("is_intra", C.c_int)]
+
+
+class CodeblockSummary(C.Structure):
+    _fields_ = [("nonzero", C.c_uint32), ("max_abs", C.c_uint32)]
+
+
+class QuantPlane(C.Structure):
+    """SchroHipQuantPlane (include/schro_hip.h): one component of schro_hip_quantise_batch."""
+    _fields_ = [("coeffs", C.c_void_p), ("quant", C.c_void_p), ("bytes", C.c_size_t), ("codeblocks", C.POINTER(Codeblock)),
+                ("ncodeblocks", C.c_int), ("is_intra", C.c_int), ("dc_predict_first", C.c_int), ("dc_width", C.c_int),
+                ("dc_height", C.c_int), ("summary", C.c_void_p)]
 
 
 class QuantisedPicture(C.Structure):
@@ -441,6 +453,15 @@ def load():
     L.schro_hipframe_add.restype = i
     L.schro_hip_dequant_batch.argtypes = [vp, C.POINTER(DequantPlane), i, i, i]
     L.schro_hip_dequant_batch.restype = i
+    L.schro_hip_quantise_batch.argtypes = [vp, C.POINTER(QuantPlane), i, i]
+    L.schro_hip_quantise_batch.restype = i
+    L.schro_hip_subtract_batch.argtypes = [vp, C.POINTER(ConvertPlane), i, i]
+    L.schro_hip_subtract_batch.restype = i
+    L.schro_hipframe_subtract.argtypes = [C.POINTER(Frame), C.POINTER(Frame)]
+    L.schro_hipframe_subtract.restype = i
+    L.schro_hipframe_quantise.argtypes = [C.POINTER(Frame), C.POINTER(Frame), C.POINTER(Params), C.POINTER(C.POINTER(C.c_int)),
+                                          C.POINTER(C.POINTER(CodeblockSummary))]
+    L.schro_hipframe_quantise.restype = i
     L.schro_hip_upsampled_bytes.argtypes = [i, i, C.POINTER(C.c_int)]
     L.schro_hip_upsampled_bytes.restype = C.c_size_t
     L.schro_hip_upsampled_download.argtypes = [vp, vp, i, vp, i, i, i]

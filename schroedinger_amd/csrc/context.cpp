@@ -688,6 +688,7 @@ schro_hip_context_free (SchroHipContext * ctx)
     schro_hip_dequant_plan_free (ctx->frame_dq_plan);
     ctx->frame_dq_plan = nullptr;
   }
+  frame_quant_table_free (ctx);
   for (auto & s : ctx->slots)
     (void) hipFree (s.ptr);
   if (ctx->dc_gave_up)

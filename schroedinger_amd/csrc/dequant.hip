@@ -69,31 +69,6 @@ dequant_one (int32_t q, uint32_t factor, uint32_t offset)
   }
 }
 
-// which job owns tile `bid`: three probes of 64 lanes in the dense arrays of first tiles behind the
-// jobs (every 4096th job, every 64th of that run, the 64 of that run)
-template < typename JOB >
-__device__ __forceinline__ int
-find_dequant_job (const JOB * jobs, int njobs, int bid)
-{
-  const int lane = threadIdx.x & 63;
-  const int *first = reinterpret_cast < const int *>(jobs + njobs);
-  const int n64 = (njobs + 63) / 64;
-  int lo = 0;
-  if (njobs > 4096) {
-    const int idx = lane;
-    const bool le = idx * 4096 < njobs && gload < int > (first + njobs + n64 + idx) <= bid;
-    lo = (__popcll (__ballot (le)) - 1) * 4096;
-  }
-  if (njobs > 64) {
-    const int idx = (lo >> 6) + lane;
-    const bool le = idx < n64 && gload < int > (first + njobs + idx) <= bid;
-    lo += (__popcll (__ballot (le)) - 1) * 64;
-  }
-  const int idx = lo + lane;
-  const bool le = idx < njobs && gload < int > (first + idx) <= bid;
-  return __builtin_amdgcn_readfirstlane (lo + __popcll (__ballot (le)) - 1);
-}
-
 // 4 quantised values of `bytes` bytes each from s (any alignment: one load of 4 * bytes bytes)
 template < typename Q >
 __device__ __forceinline__ void

@@ -967,6 +967,127 @@ schro_hipframe_add (SchroHipFrame * dest, SchroHipFrame * src)
   return stage_done (frame_ctx (dest), schro_hip_add_batch (frame_ctx (dest), planes, 3, format_bpp (src->format)));
 }
 
+// schro_frame_subtract (dest, src) (schroframe.c:1031-1079): dest (s16) -= src (s16 | u8) over the components' common size
+int
+schro_hipframe_subtract (SchroHipFrame * dest, SchroHipFrame * src)
+{
+  SCHRO_HIP_REQUIRE (dest && src && frame_ctx (dest) && src->domain == dest->domain,
+      "hipframe_subtract: both frames must live in the same device domain");
+  SCHRO_HIP_REQUIRE (!(dest->format & 0x100) && !(src->format & 0x100) && format_bpp (dest->format) == 2
+      && (format_bpp (src->format) == 1 || format_bpp (src->format) == 2)
+      && SCHRO_HIP_FORMAT_H_SHIFT (dest->format) == SCHRO_HIP_FORMAT_H_SHIFT (src->format)
+      && SCHRO_HIP_FORMAT_V_SHIFT (dest->format) == SCHRO_HIP_FORMAT_V_SHIFT (src->format),
+      "hipframe_subtract: s16 -= s16 | u8 of the same chroma format (subtract function unimplemented, schroframe.c:1078)");
+  SchroHipConvertPlane planes[3];
+  for (int k = 0; k < 3; k++) {
+    planes[k].src = src->components[k].data;
+    planes[k].src_stride = src->components[k].stride;
+    planes[k].dst = (uint8_t *) dest->components[k].data;
+    planes[k].dst_stride = dest->components[k].stride;
+    planes[k].width = std::min (dest->components[k].width, src->components[k].width);
+    planes[k].height = std::min (dest->components[k].height, src->components[k].height);
+  }
+  return stage_done (frame_ctx (dest), schro_hip_subtract_batch (frame_ctx (dest), planes, 3, format_bpp (src->format) == 1));
+}
+
+// schro_encoder_quantise_subband (schroencoder.c:3729-3785) over every sub-band of the three components, iwt_frame and
+// quant_frame on the device.  The records of a picture geometry (schro_hip_codeblock_layout) and the device summaries
+// behind them (a set per queue) are the context's, rebuilt when the geometry changes; a call fills in the quant indices.
+int
+schro_hipframe_quantise (SchroHipFrame * quant_frame, SchroHipFrame * iwt_frame, const SchroHipParams * params,
+    const int *const quant_indices[3], SchroHipCodeblockSummary * const summary[3])
+{
+  SCHRO_HIP_REQUIRE (quant_frame && iwt_frame && params && quant_indices && summary && frame_ctx (iwt_frame)
+      && quant_frame->domain == iwt_frame->domain, "hipframe_quantise: needs two device frames of one domain, the parameters, "
+      "the quant indices and the summaries");
+  SchroHipContext *ctx = frame_ctx (iwt_frame);
+  const int bpp = format_bpp (iwt_frame->format);
+  SCHRO_HIP_REQUIRE ((bpp == 2 || bpp == 4) && quant_frame->format == iwt_frame->format && !(iwt_frame->format & 0x100),
+      "hipframe_quantise: both frames must be planar s16 or s32 frames of one format");
+  const int depth = params->transform_depth;
+  SCHRO_HIP_REQUIRE (depth >= 0 && depth <= 6, "hipframe_quantise: transform_depth %d", depth);
+  (void) hipSetDevice (ctx->device);
+  std::vector < int >key = { bpp, depth, params->iwt_luma_width, params->iwt_luma_height, params->iwt_chroma_width,
+    params->iwt_chroma_height
+  };
+  for (int k = 0; k < 3; k++) {
+    const SchroHipFrameData & c = iwt_frame->components[k], &q = quant_frame->components[k];
+    const int w = k ? params->iwt_chroma_width : params->iwt_luma_width, h = k ? params->iwt_chroma_height : params->iwt_luma_height;
+    SCHRO_HIP_REQUIRE (quant_indices[k] && summary[k], "hipframe_quantise: component %d has no quant indices or no summary", k);
+    SCHRO_HIP_REQUIRE (w > 0 && h > 0 && c.width >= w && c.height >= h && q.stride == c.stride && q.height >= h
+        && (long long) c.stride >= (long long) w * bpp, "hipframe_quantise: component %d: the frames (%d x %d stride %d, %d x %d "
+        "stride %d) must both hold the %d x %d transform with one stride", k, c.width, c.height, c.stride, q.width, q.height,
+        q.stride, w, h);
+    key.push_back (c.stride);
+  }
+  for (int l = 0; l <= depth; l++) {
+    key.push_back (params->horiz_codeblocks[l]);
+    key.push_back (params->vert_codeblocks[l]);
+  }
+  FrameQuantTable *t = ctx->frame_q_table;
+  if (!t || t->key != key) {
+    frame_quant_table_free (ctx);
+    t = new FrameQuantTable ();
+    t->d_summary = nullptr;
+    size_t total = 0;
+    for (int k = 0; k < 3; k++) {
+      const int w = k ? params->iwt_chroma_width : params->iwt_luma_width, h = k ? params->iwt_chroma_height : params->iwt_luma_height;
+      const int stride = iwt_frame->components[k].stride;
+      const int n = schro_hip_codeblock_layout (w, h, depth, params->horiz_codeblocks, params->vert_codeblocks, stride, bpp, nullptr, 0);
+      if (n <= 0) {
+        delete t;
+        return n < 0 ? n : set_error (SCHRO_HIP_EINVAL, "hipframe_quantise: component %d has no codeblocks", k);
+      }
+      t->recs[k].resize (n);
+      (void) schro_hip_codeblock_layout (w, h, depth, params->horiz_codeblocks, params->vert_codeblocks, stride, bpp, t->recs[k].data (), n);
+      t->dc_first[k] = params->horiz_codeblocks[0] * params->vert_codeblocks[0];
+      total += (size_t) n;
+    }
+    t->total = total;
+    if (hipMalloc ((void **) &t->d_summary, SchroHipContext::kQueues * total * sizeof (SchroHipCodeblockSummary)) != hipSuccess) {
+      delete t;
+      return set_error (SCHRO_HIP_ENOMEM, "hipframe_quantise: %zu summaries", total);
+    }
+    t->key = key;
+    ctx->frame_q_table = t;
+  }
+  const int intra = params->num_refs == 0;
+  SchroHipCodeblockSummary *const d_summary = t->d_summary + (size_t) ctx->cur * t->total;       // the selected queue's
+  SchroHipQuantPlane planes[3];
+  size_t first = 0;
+  for (int k = 0; k < 3; k++) {
+    const int n = (int) t->recs[k].size ();
+    for (int c = 0; c < n; c++) {
+      SCHRO_HIP_REQUIRE (quant_indices[k][c] >= 0 && quant_indices[k][c] <= 60, "hipframe_quantise: component %d, codeblock %d: "
+          "quant index %d", k, c, quant_indices[k][c]);
+      t->recs[k][c].quant_index = (unsigned char) quant_indices[k][c];
+    }
+    const SchroHipFrameData & c = iwt_frame->components[k];
+    SchroHipQuantPlane & pl = planes[k];
+    memset (&pl, 0, sizeof (pl));
+    pl.coeffs = c.data;
+    pl.quant = quant_frame->components[k].data;
+    pl.bytes = (size_t) c.stride * (size_t) (k ? params->iwt_chroma_height : params->iwt_luma_height);
+    pl.codeblocks = t->recs[k].data ();
+    pl.ncodeblocks = n;
+    pl.is_intra = intra;
+    pl.dc_predict_first = intra ? t->dc_first[k] : 0;
+    pl.dc_width = (k ? params->iwt_chroma_width : params->iwt_luma_width) >> depth;
+    pl.dc_height = (k ? params->iwt_chroma_height : params->iwt_luma_height) >> depth;
+    pl.summary = d_summary + first;
+    first += (size_t) n;
+  }
+  int r = quantise_batch_run (ctx, planes, 3, bpp, true);
+  first = 0;
+  for (int k = 0; k < 3 && !r; k++) {
+    const size_t n = t->recs[k].size ();
+    if (hipMemcpyAsync (summary[k], d_summary + first, n * sizeof (SchroHipCodeblockSummary), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+      r = set_error (SCHRO_HIP_EDEVICE, "hipframe_quantise: the copy of component %d's summaries failed", k);
+    first += n;
+  }
+  return stage_done (ctx, r);
+}
+
 int
 schro_hipframe_shift_right (SchroHipFrame * frame, int shift)
 {

@@ -749,7 +749,8 @@ void shift_right_kernel (const ConvertJob * __restrict__ jobs, int njobs, int sh
 // schro_frame_add (schroframe.c:1000-1029, 1082-1135; schro_gpuframe_add, schrogpuframe.c:257-306): dst (s16) += src
 // (s16, or u8 zero-extended), 16-bit wrapping add -- orc_add_s16_2d / orc_add_s16_u8_2d (addw; convubw, addw).  8 samples
 // per lane; ConvertJob: src, dst the planes, w x h the common size.
-template < typename S >
+// SUB: dst -= src, schro_frame_subtract (schroframe.c:1031-1079: orc_subtract_s16, orc_subtract_s16_u8 -- subw; convubw, subw)
+template < typename S, bool SUB >
 __global__ __launch_bounds__ (kThreads)
 void add_kernel (const ConvertJob * __restrict__ jobs, int njobs)
 {
@@ -781,13 +782,17 @@ void add_kernel (const ConvertJob * __restrict__ jobs, int njobs)
       av[3] = __builtin_amdgcn_perm (0u, b.y, 0x0c030c02u);
     }
 #pragma unroll
-    for (int k = 0; k < 4; k++)
-      dv[k] = __builtin_bit_cast (uint32_t, (s16x2) (__builtin_bit_cast (s16x2, dv[k]) + __builtin_bit_cast (s16x2, av[k])));
+    for (int k = 0; k < 4; k++) {
+      const s16x2 a = __builtin_bit_cast (s16x2, dv[k]), b = __builtin_bit_cast (s16x2, av[k]);
+      dv[k] = __builtin_bit_cast (uint32_t, (s16x2) (SUB ? a - b : a + b));
+    }
     gstore < u32x4 > (drow, (u32x4) { dv[0], dv[1], dv[2], dv[3] });
     return;
   }
-  for (int e = 0; e < 8 && x + e < job.w; e++)
-    gstore < int16_t > (drow + e, (int16_t) (gload < int16_t > (drow + e) + (int16_t) gload < S > (srow + e)));
+  for (int e = 0; e < 8 && x + e < job.w; e++) {
+    const int16_t a = gload < int16_t > (drow + e), b = (int16_t) gload < S > (srow + e);
+    gstore < int16_t > (drow + e, (int16_t) (SUB ? a - b : a + b));
+  }
 }
 
 }                               // namespace
@@ -808,12 +813,16 @@ launch_shift_right (hipStream_t stream, const ConvertJob * d_jobs, int njobs, in
 }
 
 int
-launch_add (hipStream_t stream, const ConvertJob * d_jobs, int njobs, int total_tiles, int src_bpp)
+launch_add (hipStream_t stream, const ConvertJob * d_jobs, int njobs, int total_tiles, int src_bpp, bool subtract)
 {
-  if (src_bpp == 2)
-    SCHRO_LAUNCH ((add_kernel < int16_t >), dim3 (total_tiles), dim3 (kThreads), 0, stream, d_jobs, njobs);
+  if (src_bpp == 2 && subtract)
+    SCHRO_LAUNCH ((add_kernel < int16_t, true >), dim3 (total_tiles), dim3 (kThreads), 0, stream, d_jobs, njobs);
+  else if (subtract)
+    SCHRO_LAUNCH ((add_kernel < uint8_t, true >), dim3 (total_tiles), dim3 (kThreads), 0, stream, d_jobs, njobs);
+  else if (src_bpp == 2)
+    SCHRO_LAUNCH ((add_kernel < int16_t, false >), dim3 (total_tiles), dim3 (kThreads), 0, stream, d_jobs, njobs);
   else
-    SCHRO_LAUNCH ((add_kernel < uint8_t >), dim3 (total_tiles), dim3 (kThreads), 0, stream, d_jobs, njobs);
+    SCHRO_LAUNCH ((add_kernel < uint8_t, false >), dim3 (total_tiles), dim3 (kThreads), 0, stream, d_jobs, njobs);
   hipError_t e = hipGetLastError ();
   if (e != hipSuccess)
     return set_error (SCHRO_HIP_EDEVICE, "add launch: %s", hipGetErrorString (e));

@@ -49,11 +49,9 @@ schro_hip_convert_u8_batch (SchroHipContext * ctx, const SchroHipConvertPlane * 
 
 // dst (s16) += src (s16 | u8): schro_frame_add / schro_gpuframe_add on planes (schroframe.c:1082-1135,
 // schrogpuframe.c:257-306); width x height = the planes' common size
-int
-schro_hip_add_batch (SchroHipContext * ctx, const SchroHipConvertPlane * planes, int nplanes, int src_bytes_per_sample)
+static int
+add_batch_run (SchroHipContext * ctx, const SchroHipConvertPlane * planes, int nplanes, int src_bytes_per_sample, bool subtract)
 {
-  SCHRO_HIP_REQUIRE (ctx && planes && nplanes > 0 && nplanes <= kMaxJobs, "add_batch: bad arguments");
-  SCHRO_HIP_REQUIRE (src_bytes_per_sample == 1 || src_bytes_per_sample == 2, "add_batch: the source is u8 or s16");
   (void) hipSetDevice (ctx->device);
   int tw, th;
   convert_tile_geometry (&tw, &th);
@@ -63,7 +61,8 @@ schro_hip_add_batch (SchroHipContext * ctx, const SchroHipConvertPlane * planes,
     const SchroHipConvertPlane & pl = planes[p];
     SCHRO_HIP_REQUIRE (pl.src && pl.dst && pl.width > 0 && pl.height > 0 && pl.dst_stride >= 2 * pl.width
         && pl.src_stride >= src_bytes_per_sample * pl.width && ((uintptr_t) pl.dst | (uintptr_t) pl.dst_stride) % 2 == 0
-        && ((uintptr_t) pl.src | (uintptr_t) pl.src_stride) % src_bytes_per_sample == 0, "add_batch: plane %d invalid", p);
+        && ((uintptr_t) pl.src | (uintptr_t) pl.src_stride) % src_bytes_per_sample == 0, "%s_batch: plane %d invalid",
+        subtract ? "subtract" : "add", p);
     ConvertJob & j = jobs[p];
     memset (&j, 0, sizeof (j));
     j.src = pl.src;
@@ -81,7 +80,23 @@ schro_hip_add_batch (SchroHipContext * ctx, const SchroHipConvertPlane * planes,
   if (r)
     return r;
   ProfileScope ps (ctx, SCHRO_HIP_KERNEL_CONVERT);
-  return launch_add (ctx->stream, (const ConvertJob *) d_jobs, nplanes, tile_base, src_bytes_per_sample);
+  return launch_add (ctx->stream, (const ConvertJob *) d_jobs, nplanes, tile_base, src_bytes_per_sample, subtract);
+}
+
+int
+schro_hip_add_batch (SchroHipContext * ctx, const SchroHipConvertPlane * planes, int nplanes, int src_bytes_per_sample)
+{
+  SCHRO_HIP_REQUIRE (ctx && planes && nplanes > 0 && nplanes <= kMaxJobs, "add_batch: bad arguments");
+  SCHRO_HIP_REQUIRE (src_bytes_per_sample == 1 || src_bytes_per_sample == 2, "add_batch: the source is u8 or s16");
+  return add_batch_run (ctx, planes, nplanes, src_bytes_per_sample, false);
+}
+
+// dst (s16) -= src (s16 | u8): schro_frame_subtract on planes (schroframe.c:1031-1079)
+int
+schro_hip_subtract_batch (SchroHipContext * ctx, const SchroHipConvertPlane * planes, int nplanes, int src_is_u8)
+{
+  SCHRO_HIP_REQUIRE (ctx && planes && nplanes > 0 && nplanes <= kMaxJobs, "subtract_batch: bad arguments");
+  return add_batch_run (ctx, planes, nplanes, src_is_u8 ? 1 : 2, true);
 }
 
 }                               // extern "C"

@@ -367,6 +367,47 @@ struct DequantPlaneDyn {
   int pad;
 };
 
+// One codeblock of the encoder's quantisation (quant.hip): every per-codeblock constant resolved on the host.
+enum QuantForm {
+  kQuantCopy = 0,               // s16, index 0: quant = coefficient, the coefficient stays
+  kQuantShift = 1,              // s16, a multiple of 4: orc_quantdequant2_s16
+  kQuantRecip32 = 2,            // s16, index 3: orc_quantdequant3_s16
+  kQuantRecip16 = 3,            // s16, the rest: orc_quantdequant1_s16
+  kQuantDivide = 4              // s32: schro_quantise_s32
+};
+struct QuantJob {
+  void *coeffs;                 // first sample of the codeblock in the coefficient plane ...
+  void *quant;                  // ... and in the quant plane
+  SchroHipCodeblockSummary *summary;    // this codeblock's entry
+  int stride;                   // bytes between its rows (both planes)
+  int w, h;
+  int form;
+  uint32_t factor;              // schro_table_quant
+  uint32_t offset;              // schro_table_offset_1_2 / _3_8: the dead zone, and (+ 2) what dequantisation adds
+  int32_t qoff;                 // what is taken from 4 |x|: offset - factor / 2 (quantdequant1 above index 8: one less)
+  int shift;                    // (index >> 2) + 2; quantdequant3: + 16
+  uint32_t inverse;             // schro_table_inverse_quant
+  int tiles_x;
+  int tile_base;
+  int pad;
+};
+// The intra LL recurrence: one band per workgroup, the codeblocks that tile it (with their quantisers) behind the jobs.
+struct QuantDcJob {
+  void *coeffs;
+  void *quant;
+  SchroHipCodeblockSummary *summary;    // the plane's entries; record k of the band writes entry k
+  int stride;
+  int w, h;
+  int rec_base, nrec;           // its QuantDcRec run
+  int pad;
+};
+struct QuantDcRec {
+  int x0, y0, x1, y1;           // samples of the band, x1 / y1 exclusive
+  uint32_t factor, offset;
+  int index;                    // its summary entry
+  int pad;
+};
+
 constexpr int kMaxJobs = 256;
 
 // XCD-aware workgroup order.  The dispatcher deals workgroups round-robin over
@@ -529,6 +570,31 @@ find_job (const JOB * jobs, int njobs, int bid)
   }
   return __builtin_amdgcn_readfirstlane (n - 1);
 }
+
+// the same for the codeblock launches (dequant.hip, quant.hip), whose job count runs to 2^18: three probes of 64 lanes in the dense arrays of first tiles behind the
+// jobs (every 4096th job, every 64th of that run, the 64 of that run)
+template < typename JOB >
+__device__ __forceinline__ int
+find_dequant_job (const JOB * jobs, int njobs, int bid)
+{
+  const int lane = threadIdx.x & 63;
+  const int *first = reinterpret_cast < const int *>(jobs + njobs);
+  const int n64 = (njobs + 63) / 64;
+  int lo = 0;
+  if (njobs > 4096) {
+    const int idx = lane;
+    const bool le = idx * 4096 < njobs && gload < int > (first + njobs + n64 + idx) <= bid;
+    lo = (__popcll (__ballot (le)) - 1) * 4096;
+  }
+  if (njobs > 64) {
+    const int idx = (lo >> 6) + lane;
+    const bool le = idx < n64 && gload < int > (first + njobs + idx) <= bid;
+    lo += (__popcll (__ballot (le)) - 1) * 64;
+  }
+  const int idx = lo + lane;
+  const bool le = idx < njobs && gload < int > (first + idx) <= bid;
+  return __builtin_amdgcn_readfirstlane (lo + __popcll (__ballot (le)) - 1);
+}
 #endif
 
 // launchers (one per .hip file)
@@ -580,7 +646,7 @@ int launch_convert (hipStream_t stream, const ConvertJob * d_jobs, int njobs,
 void convert_tile_geometry (int *tw, int *th);
 int launch_pack (hipStream_t stream, const PackJob * d_jobs, int njobs, int total_tiles);
 int launch_shift_right (hipStream_t stream, const ConvertJob * d_jobs, int njobs, int total_tiles, int bpp, int shift);
-int launch_add (hipStream_t stream, const ConvertJob * d_jobs, int njobs, int total_tiles, int src_bpp);
+int launch_add (hipStream_t stream, const ConvertJob * d_jobs, int njobs, int total_tiles, int src_bpp, bool subtract);
 void pack_tile_geometry (int *groups_x, int *rows);
 // persist_grid > 0 (experiments build): that many persistent workgroups (all jobs of one form: pair images or planes)
 int launch_upsample (hipStream_t stream, const UpsampleJob * d_jobs,
@@ -626,6 +692,11 @@ int launch_dequant (hipStream_t stream, const DequantJob * d_jobs, int njobs, in
 int launch_dequant_plan (hipStream_t stream, const DequantGeo * d_geo, int njobs, int total_tiles,
     const SchroHipCodeblock * d_recs, const DequantPlaneDyn * d_planes, int bpp, int arith);
 void dequant_tile_geometry (int *tw, int *th);
+// quant.hip
+void quant_tile_geometry (int *tw, int *th);
+void quant_job_constants (QuantJob * job, int quant_index, int is_intra, int bpp);
+int launch_quantise (hipStream_t stream, const QuantJob * d_jobs, int njobs, int total_tiles, int bpp);
+int launch_quantise_dc (hipStream_t stream, const QuantDcJob * d_jobs, int njobs, const QuantDcRec * d_recs, int max_rows, int bpp);
 int launch_table_copy (hipStream_t stream, void *dst, const void *src, size_t bytes);
 // schro_table_quant[i] and schro_table_offset_1_2[i] (intra) / _3_8[i] (inter)
 void dequant_tables (int quant_index, int is_intra, uint32_t * factor, uint32_t * offset);
@@ -670,6 +741,10 @@ void obmc_tiles (int variant, int w, int h, int xoff, int *tiles_x, int *tiles_y
 }                               // namespace schro
 
 // ---- the context --------------------------------------------------------------
+
+namespace schro {
+struct FrameQuantTable;
+}
 
 struct SchroHipContext {
   int device;
@@ -809,6 +884,9 @@ struct SchroHipContext {
   // ... of schro_hip_iiwt_pack_wide_batch (schro_hip_wide_routes)
   long long wide_routes[SCHRO_HIP_WIDE_ROUTES] = {};
   int cus;                      // compute units of the device (launch shaping)
+  // the frame layer's quantisation table (schro_hipframe_quantise): the codeblock records of one picture geometry and the
+  // device summaries behind them
+  struct schro::FrameQuantTable *frame_q_table = nullptr;
 };
 
 namespace schro {
@@ -837,6 +915,20 @@ int rough_scan_nohint_run (SchroHipContext * ctx, const uint8_t * frame, int fra
     void *motion_vectors);
 // v216 / ARGB / AY64 (plane_frameops.cpp)
 bool is_wide_format (int format);
+// plane_quant.cpp: schro_hip_quantise_batch; allow_empty: records of no width or height are skipped (the frame layer's
+// layouts of tiny sub-bands have them), not refused
+int quantise_batch_run (SchroHipContext * ctx, const SchroHipQuantPlane * planes, int nplanes, int bpp, bool allow_empty);
+struct FrameQuantTable {
+  std::vector < int >key;       // what the records were laid out for
+  std::vector < SchroHipCodeblock > recs[3];
+  int dc_first[3];              // records of sub-band 0
+  size_t total;                 // records of the three components
+  // the three components' entries, one after the other: `total` of them PER QUEUE (kQueues runs in one allocation, the
+  // selected queue's is used) -- like the scratch and the staging buffers, so that a picture enqueued on one queue never
+  // has its summaries cleared or added to by a picture in flight on another
+  SchroHipCodeblockSummary *d_summary;
+};
+void frame_quant_table_free (SchroHipContext * ctx);
 // the launches made while a scope is open are timed under its kernel class (when profiling is on)
 struct ProfileScope {
   ProfileScope (SchroHipContext * c, int cls);
