@@ -890,6 +890,53 @@ typedef struct {
  * sub-bands contain records of no width or height, skips those: their summary is zero.) */
 int schro_hip_quantise_batch (SchroHipContext * ctx, const SchroHipQuantPlane * planes, int nplanes, int bytes_per_sample);
 
+/* ---- encoder: sub-band histograms on the device ----------------------------------------------
+ *
+ * The pass over the coefficients that every rate-controlled quantiser choice starts with
+ * (schro_encoder_generate_subband_histograms, schroquantiser.c:600-637): per sub-band, how many of its SAMPLED values --
+ * rows 0, skip, 2 skip ... < height, all columns -- fall into each of the 104 logarithmic bins of ilogx
+ * (schrohistogram.c:11-22): x = |v|, halved while x >= 16, i halvings, bin x + 8 i -- so |v| itself below 16, then 8
+ * bins per octave, bins 0 .. 103 covering |v| <= 32767.
+ *   plain form (schro_frame_data_generate_histogram, :345-357): the value counted is the coefficient;
+ *   DC-predict form (schro_frame_data_generate_histogram_dc_predict with x = y = 0, :359-391): the value counted is
+ *     line[i] - pred, pred from the ORIGINAL neighbours (no recurrence): 0 at (0, 0), line[i - 1] on row 0,
+ *     prev_line[i] in column 0, otherwise schro_divide3 (line[i - 1] + prev_line[i] + prev_line[i - 1] + 1) =
+ *     (a * 21845 + 10922) >> 16; prev_line is row j - 1 of the band, not the previous sampled row.  The form starts at
+ *     the band's own row 0: nothing above the band is read.
+ *   s32 planes (the reference reads s16 only): the same expressions in 32-bit wrapping ints, so that values within 16
+ *     bits give the s16 result.
+ * The counts are RAW: the reference's scale by skip (schro_histogram_scale) is the caller's, or
+ * schro_hipframe_subband_histograms'.
+ * One departure, deliberate: the reference indexes bins[ilogx (v)] without a bound -- a coefficient of -32768 lands on
+ * index 104, the DC form's differences reach +-65535, index 111, and both write past its array.  Here every sample whose
+ * index is >= 104 is counted in `overflow` and the 104 bins are left alone; the reference's n counts those samples, and so
+ * does bins[...] + overflow here. */
+#define SCHRO_HIP_HISTOGRAM_BINS 104
+typedef struct {
+  uint32_t bins[SCHRO_HIP_HISTOGRAM_BINS];
+  uint32_t overflow;
+} SchroHipHistogramCounts;      /* raw counts, before the scale by skip */
+typedef struct {
+  int offset, stride, width, height;    /* bytes from `coeffs` to sample (0, 0), bytes between rows, samples, samples */
+  int skip;                     /* a power of two >= 1: rows 0, skip, 2 skip ... are counted */
+  int dc_predict;               /* the DC-predict form */
+} SchroHipHistogramBand;
+typedef struct {
+  const void *coeffs;           /* the component's coefficient plane (device, s16 or s32): read, never written */
+  size_t bytes;                 /* what it spans: no band may reach past it */
+  const SchroHipHistogramBand *bands;   /* HOST array */
+  int nbands;
+  SchroHipHistogramCounts *counts;      /* device, nbands entries: cleared and filled by the call */
+} SchroHipHistogramPlane;
+
+/* One launch of histogram_kernel for every band of every plane of the call (unlike sizes, skips and forms mix).  Refused
+ * with SCHRO_HIP_EINVAL before anything is launched, the message naming plane and band: bytes_per_sample not 2 or 4, a
+ * non-positive width or height, a skip that is not a power of two >= 1, a stride shorter than a row or not a multiple of
+ * the sample size, a band reaching outside `bytes` (an offset in front of the plane included: the DC form's row 0 has no
+ * row above it to read, and none is read), a band of 2^32 or more sampled values.  Enqueued on the selected queue; the
+ * counts are complete once that queue has passed the call. */
+int schro_hip_histogram_batch (SchroHipContext * ctx, const SchroHipHistogramPlane * planes, int nplanes, int bytes_per_sample);
+
 /* ---- frame layer: the reference's stage boundary ------------------------- */
 
 /* The structs of this layer are LAYOUT-IDENTICAL to the reference's (same members, same
@@ -1278,6 +1325,27 @@ int schro_hipframe_subtract (SchroHipFrame * dest, SchroHipFrame * src);
  * the context's, rebuilt when the geometry changes. */
 int schro_hipframe_quantise (SchroHipFrame * quant_frame, SchroHipFrame * iwt_frame, const SchroHipParams * params,
     const int *const quant_indices[3], SchroHipCodeblockSummary * const summary[3]);
+
+/* schro_encoder_generate_subband_histograms (schroquantiser.c:618-637) with frame->iwt_frame on the device: what it
+ * leaves in frame->subband_hists.  SchroHipHistogram is LAYOUT-IDENTICAL to SchroHistogram (schrohistogram.h:16-20), so
+ * the reference's estimate and choice code (schro_histogram_estimate_entropy, schro_histogram_apply_table, ...) runs on
+ * the result unchanged.  hists: 3 * (1 + 3 * transform_depth) HOST entries, component-major, sub-band index minor;
+ * bins[k] = counts * skip and n = sampled values * skip, skip = 1 << max (0, SCHRO_SUBBAND_SHIFT (position) - 1).  The
+ * sub-band rectangles are schro_hip_codeblock_layout's with 1 x 1 codeblocks; sub-band 0 takes the DC-predict form when
+ * params->num_refs == 0; a sub-band of no width or height gives an all-zero histogram.  overflow (may be NULL): as many
+ * words, the samples of each sub-band whose bin index is >= 104, scaled by skip like the bins (see
+ * SchroHipHistogramCounts: n = the bins' sum + overflow); the reference would have written past its array for them.
+ * 840 bytes per sub-band cross the bus instead of the coefficient frame.  The integer counts are copied back on the
+ * selected queue and scaled to doubles by the host once that copy has completed, so the call ALWAYS waits for the selected
+ * queue (that queue only), whatever schro_hip_context_set_stage_completion says: hists and overflow are valid on
+ * return.  The band records and the counts -- on the device and in pinned host memory, a set per queue -- are kept in a
+ * table of the context's, rebuilt when the geometry changes. */
+typedef struct {
+  int n;
+  double bins[SCHRO_HIP_HISTOGRAM_BINS];
+} SchroHipHistogram;            /* layout-identical to SchroHistogram */
+int schro_hipframe_subband_histograms (SchroHipFrame * iwt_frame, const SchroHipParams * params,
+    SchroHipHistogram * hists, uint32_t * overflow /* may be NULL */);
 
 /* schro_gpuframe_convert (schrogpuframe.h:20) replacement for the conversions the decode path
  * performs: s16/s32 -> u8 (+128, clamp, crop), u8 -> u8 copy, planar -> packed (YUYV, UYVY,

@@ -72,6 +72,14 @@ class DevicePlane:
         v.free = lambda: None           # (the memory is the parent's)
         return v
 
+    def rows_view(self, first, count):
+        """Rows first .. first + count - 1 as a plane of their own: the same memory, upload () / download () work on it,
+        free () does nothing (the memory is the parent's)."""
+        assert 0 <= first and count >= 0 and first + count <= self.height
+        v = self.level_view(0)
+        v.height, v.nbytes, v.ptr = int(count), self.stride * int(count), self.ptr + int(first) * self.stride
+        return v
+
     def upload(self, a):
         a = np.ascontiguousarray(a, dtype=self.dtype)
         assert a.shape == (self.height, self.width), (a.shape, self.height, self.width)
@@ -714,6 +722,46 @@ class Context:
             a.summary = summ.ptr
         check(self.lib.schro_hip_quantise_batch(self.h, arr, n, jobs[0][0].dtype.itemsize))
         return summaries
+
+    def histogram_planes(self, jobs):
+        """The C table of a schro_hip_histogram_batch call and its device counts.  jobs: per component (coeffs DevicePlane
+        (s16 / s32), bands -- a list of (offset, stride, width, height, skip, dc_predict): bytes, bytes, samples, samples).
+        Returns (SchroHipHistogramPlane array, per component a view of its (nbands, 105) uint32 counts, the block): ONE
+        DevicePlane holds the counts of all components (the call clears counts that lie one behind the other with one
+        memset) and the band tables the array points to; the caller keeps it while the array is used and frees it."""
+        arr = (_lib.HistogramPlane * len(jobs))()
+        size = C.sizeof(_lib.HistogramCounts)
+        block = DevicePlane(self, sum(len(bands) for _, bands in jobs), _lib.HISTOGRAM_BINS + 1, np.uint32, stride=size)
+        block.tables, counts, first = [], [], 0
+        for a, (coeffs, bands) in zip(arr, jobs):
+            tab = (_lib.HistogramBand * len(bands))(*[_lib.HistogramBand(*(int(v) for v in b)) for b in bands])
+            block.tables.append(tab)
+            cnt = block.rows_view(first, len(bands))
+            counts.append(cnt)
+            first += len(bands)
+            a.coeffs, a.bytes, a.bands, a.nbands, a.counts = coeffs.ptr, coeffs.stride * coeffs.height, tab, len(bands), cnt.ptr
+        return arr, counts, block
+
+    def histogram_batch(self, jobs):
+        """schro_hip_histogram_batch over `jobs` (see histogram_planes): the raw counts of every band, before the scale by
+        skip -- per component an (nbands, 105) uint32 array, 104 bins and the overflow word.  Waits for the result."""
+        arr, counts, block = self.histogram_planes(jobs)
+        try:
+            check(self.lib.schro_hip_histogram_batch(self.h, arr, len(jobs), jobs[0][0].dtype.itemsize))
+            return [c.download() for c in counts]
+        finally:
+            block.free()
+
+    def subband_histograms(self, iwt_frame, params):
+        """schro_hipframe_subband_histograms on a device frame (frames.DeviceFrame / PlaneFrame): (n, bins, overflow) --
+        an int array of 3 * (1 + 3 * depth) entries, a float64 array of as many rows of 104 bins, a uint32 array -- what
+        schro_encoder_generate_subband_histograms leaves in frame->subband_hists, component-major."""
+        nh = 3 * (1 + 3 * params.transform_depth)
+        hists = (_lib.Histogram * nh)()
+        ovf = (C.c_uint32 * nh)()
+        check(self.lib.schro_hipframe_subband_histograms(iwt_frame.ptr(), C.byref(params), hists, ovf))
+        return (np.array([h.n for h in hists], np.int64), np.array([list(h.bins) for h in hists], np.float64).reshape(nh, -1),
+                np.array(list(ovf), np.uint32))
 
     def upsample_batch(self, pairs):
         """pairs: [(src u8 plane h x w, dst HpPlane)] or [((src U, src V), dst pair HpPlane)]."""

@@ -44,7 +44,7 @@ EXPORTED_SYMBOLS = [
     "schro_hipframe_shift_right", "schro_hip_add_batch", "schro_hipframe_add",
     "schro_hip_lowdelay_arith", "schro_hip_lowdelay_batch", "schro_hip_dc_predict_batch",
     "schro_hip_dequant_batch", "schro_hip_quantise_batch", "schro_hip_subtract_batch", "schro_hipframe_subtract",
-    "schro_hipframe_quantise",
+    "schro_hipframe_quantise", "schro_hip_histogram_batch", "schro_hipframe_subband_histograms",
     "schro_hip_decode_lowdelay_transform_data", "schro_hipframe_dequantise",
     "schro_hip_obmc_batch", "schro_hip_obmc_prediction_epoch", "schro_hip_obmc_overflowed",
     "schro_hip_frame_new_and_alloc", "schro_hip_frame_ref", "schro_hip_frame_unref",
@@ -160,6 +160,30 @@ class QuantPlane(C.Structure):
     _fields_ = [("coeffs", C.c_void_p), ("quant", C.c_void_p), ("bytes", C.c_size_t), ("codeblocks", C.POINTER(Codeblock)),
                 ("ncodeblocks", C.c_int), ("is_intra", C.c_int), ("dc_predict_first", C.c_int), ("dc_width", C.c_int),
                 ("dc_height", C.c_int), ("summary", C.c_void_p)]
+
+
+HISTOGRAM_BINS = 104            # SCHRO_HIP_HISTOGRAM_BINS (include/schro_hip.h)
+
+
+class HistogramCounts(C.Structure):
+    """SchroHipHistogramCounts: raw counts of one sub-band, before the scale by skip."""
+    _fields_ = [("bins", C.c_uint32 * HISTOGRAM_BINS), ("overflow", C.c_uint32)]
+
+
+class HistogramBand(C.Structure):
+    _fields_ = [("offset", C.c_int), ("stride", C.c_int), ("width", C.c_int), ("height", C.c_int), ("skip", C.c_int),
+                ("dc_predict", C.c_int)]
+
+
+class HistogramPlane(C.Structure):
+    """SchroHipHistogramPlane (include/schro_hip.h): one component of schro_hip_histogram_batch."""
+    _fields_ = [("coeffs", C.c_void_p), ("bytes", C.c_size_t), ("bands", C.POINTER(HistogramBand)), ("nbands", C.c_int),
+                ("counts", C.c_void_p)]
+
+
+class Histogram(C.Structure):
+    """SchroHipHistogram: layout-identical to the reference's SchroHistogram."""
+    _fields_ = [("n", C.c_int), ("bins", C.c_double * HISTOGRAM_BINS)]
 
 
 class QuantisedPicture(C.Structure):
@@ -462,6 +486,10 @@ def load():
     L.schro_hipframe_quantise.argtypes = [C.POINTER(Frame), C.POINTER(Frame), C.POINTER(Params), C.POINTER(C.POINTER(C.c_int)),
                                           C.POINTER(C.POINTER(CodeblockSummary))]
     L.schro_hipframe_quantise.restype = i
+    L.schro_hip_histogram_batch.argtypes = [vp, C.POINTER(HistogramPlane), i, i]
+    L.schro_hip_histogram_batch.restype = i
+    L.schro_hipframe_subband_histograms.argtypes = [C.POINTER(Frame), C.POINTER(Params), C.POINTER(Histogram), C.POINTER(C.c_uint32)]
+    L.schro_hipframe_subband_histograms.restype = i
     L.schro_hip_upsampled_bytes.argtypes = [i, i, C.POINTER(C.c_int)]
     L.schro_hip_upsampled_bytes.restype = C.c_size_t
     L.schro_hip_upsampled_download.argtypes = [vp, vp, i, vp, i, i, i]

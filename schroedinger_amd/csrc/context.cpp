@@ -689,6 +689,7 @@ schro_hip_context_free (SchroHipContext * ctx)
     ctx->frame_dq_plan = nullptr;
   }
   frame_quant_table_free (ctx);
+  frame_hist_table_free (ctx);
   for (auto & s : ctx->slots)
     (void) hipFree (s.ptr);
   if (ctx->dc_gave_up)

@@ -1088,6 +1088,105 @@ schro_hipframe_quantise (SchroHipFrame * quant_frame, SchroHipFrame * iwt_frame,
   return stage_done (ctx, r);
 }
 
+// schro_encoder_generate_subband_histograms (schroquantiser.c:618-637) with iwt_frame on the device.  The band records
+// of a picture geometry (schro_hip_codeblock_layout with 1 x 1 codeblocks: one record per sub-band) and the counts behind
+// them (on the device and in pinned host memory, a set per queue) are the context's, rebuilt when the geometry changes.
+int
+schro_hipframe_subband_histograms (SchroHipFrame * iwt_frame, const SchroHipParams * params, SchroHipHistogram * hists,
+    uint32_t * overflow)
+{
+  SCHRO_HIP_REQUIRE (iwt_frame && params && hists && frame_ctx (iwt_frame),
+      "hipframe_subband_histograms: needs a device frame, the parameters and the histograms");
+  SchroHipContext *ctx = frame_ctx (iwt_frame);
+  const int bpp = format_bpp (iwt_frame->format);
+  SCHRO_HIP_REQUIRE ((bpp == 2 || bpp == 4) && !(iwt_frame->format & 0x100),
+      "hipframe_subband_histograms: the frame must be a planar s16 or s32 frame");
+  const int depth = params->transform_depth;
+  SCHRO_HIP_REQUIRE (depth >= 0 && depth <= 6, "hipframe_subband_histograms: transform_depth %d", depth);
+  (void) hipSetDevice (ctx->device);
+  const int nb = 1 + 3 * depth;
+  std::vector < int >key = { bpp, depth, params->iwt_luma_width, params->iwt_luma_height, params->iwt_chroma_width,
+    params->iwt_chroma_height
+  };
+  for (int k = 0; k < 3; k++) {
+    const SchroHipFrameData & c = iwt_frame->components[k];
+    const int w = k ? params->iwt_chroma_width : params->iwt_luma_width, h = k ? params->iwt_chroma_height : params->iwt_luma_height;
+    SCHRO_HIP_REQUIRE (w > 0 && h > 0 && c.width >= w && c.height >= h && (long long) c.stride >= (long long) w * bpp,
+        "hipframe_subband_histograms: component %d: the frame (%d x %d stride %d) must hold the %d x %d transform", k, c.width,
+        c.height, c.stride, w, h);
+    key.push_back (c.stride);
+  }
+  FrameHistTable *t = ctx->frame_h_table;
+  if (!t || t->key != key) {
+    frame_hist_table_free (ctx);
+    t = new FrameHistTable ();
+    t->d_counts = t->h_counts = nullptr;
+    t->total = (size_t) 3 * nb;
+    const int ones[7] = { 1, 1, 1, 1, 1, 1, 1 };
+    std::vector < SchroHipCodeblock > recs (nb);
+    for (int k = 0; k < 3; k++) {
+      const int w = k ? params->iwt_chroma_width : params->iwt_luma_width, h = k ? params->iwt_chroma_height : params->iwt_luma_height;
+      const int n = schro_hip_codeblock_layout (w, h, depth, ones, ones, iwt_frame->components[k].stride, bpp, recs.data (), nb);
+      if (n != nb) {
+        delete t;
+        return n < 0 ? n : set_error (SCHRO_HIP_EINVAL, "hipframe_subband_histograms: component %d has %d sub-bands, not %d", k, n, nb);
+      }
+      t->bands[k].resize (nb);
+      for (int i = 0; i < nb; i++) {
+        const int level = i == 0 ? 0 : (i - 1) / 3;     // SCHRO_SUBBAND_SHIFT (position)
+        SchroHipHistogramBand & b = t->bands[k][i];
+        b.offset = recs[i].dst_offset;
+        b.stride = recs[i].dst_stride;
+        b.width = recs[i].width;
+        b.height = recs[i].height;
+        b.skip = 1 << std::max (0, level - 1);
+        b.dc_predict = 0;
+      }
+    }
+    const size_t bytes = SchroHipContext::kQueues * t->total * sizeof (SchroHipHistogramCounts);
+    if (hipMalloc ((void **) &t->d_counts, bytes) != hipSuccess || hipHostMalloc ((void **) &t->h_counts, bytes, hipHostMallocDefault) != hipSuccess) {
+      if (t->d_counts)
+        (void) hipFree (t->d_counts);
+      delete t;
+      return set_error (SCHRO_HIP_ENOMEM, "hipframe_subband_histograms: the counts of %d sub-bands", 3 * nb);
+    }
+    t->key = key;
+    ctx->frame_h_table = t;
+  }
+  SchroHipHistogramCounts *const d_counts = t->d_counts + (size_t) ctx->cur * t->total;  // the selected queue's
+  SchroHipHistogramCounts *const h_counts = t->h_counts + (size_t) ctx->cur * t->total;
+  SchroHipHistogramPlane planes[3];
+  for (int k = 0; k < 3; k++) {
+    const SchroHipFrameData & c = iwt_frame->components[k];
+    t->bands[k][0].dc_predict = params->num_refs == 0;
+    planes[k].coeffs = c.data;
+    planes[k].bytes = (size_t) c.stride * (size_t) (k ? params->iwt_chroma_height : params->iwt_luma_height);
+    planes[k].bands = t->bands[k].data ();
+    planes[k].nbands = nb;
+    planes[k].counts = d_counts + (size_t) k * nb;
+  }
+  int r = histogram_batch_run (ctx, planes, 3, bpp, true);
+  if (r)
+    return r;
+  SCHRO_HIP_CHECK (hipMemcpyAsync (h_counts, d_counts, t->total * sizeof (SchroHipHistogramCounts), hipMemcpyDeviceToHost, ctx->stream));
+  // the scale to doubles is the host's and needs the copy complete: this call waits for its queue whatever the stage setting
+  SCHRO_HIP_CHECK (hipStreamSynchronize (ctx->stream));
+  for (int k = 0; k < 3; k++)
+    for (int i = 0; i < nb; i++) {
+      const SchroHipHistogramBand & b = t->bands[k][i];
+      const SchroHipHistogramCounts & c = h_counts[k * nb + i];
+      SchroHipHistogram & out = hists[k * nb + i];
+      const double skip = b.skip;
+      for (int s = 0; s < SCHRO_HIP_HISTOGRAM_BINS; s++)
+        out.bins[s] = c.bins[s] * skip;                 // schro_histogram_scale
+      const long long rows = b.width > 0 && b.height > 0 ? (b.height + b.skip - 1) / b.skip : 0;
+      out.n = (int) (rows * b.width * b.skip);
+      if (overflow)
+        overflow[k * nb + i] = c.overflow * (uint32_t) b.skip;
+    }
+  return stage_done (ctx, 0);
+}
+
 int
 schro_hipframe_shift_right (SchroHipFrame * frame, int shift)
 {

@@ -407,6 +407,20 @@ struct QuantDcRec {
   int index;                    // its summary entry
   int pad;
 };
+// One sub-band of the histogram launch (hist.hip): its sampled rows as rows x gpr groups of 16 bytes, 2048 per workgroup.
+struct HistJob {
+  const void *base;             // sample (0, 0) of the band
+  uint32_t *counts;             // its SchroHipHistogramCounts: 104 bins, then the overflow word
+  int stride;                   // bytes between the band's rows
+  int w;
+  int skip_shift;               // sampled row r is row r << skip_shift of the band
+  int dc;                       // the DC-predict form
+  uint32_t gpr;                 // groups per row: div_up (w, 16 / bpp)
+  uint32_t items;               // sampled rows x gpr
+  uint32_t step_rows, step_groups;      // a lane's step from one of its groups to the next: 256 / gpr, 256 % gpr
+  int tile_base;
+  int pad;
+};
 
 constexpr int kMaxJobs = 256;
 
@@ -697,6 +711,9 @@ void quant_tile_geometry (int *tw, int *th);
 void quant_job_constants (QuantJob * job, int quant_index, int is_intra, int bpp);
 int launch_quantise (hipStream_t stream, const QuantJob * d_jobs, int njobs, int total_tiles, int bpp);
 int launch_quantise_dc (hipStream_t stream, const QuantDcJob * d_jobs, int njobs, const QuantDcRec * d_recs, int max_rows, int bpp);
+// hist.hip
+void hist_tile_geometry (int *group_bytes, int *groups_per_tile, int *groups_per_step);
+int launch_histogram (hipStream_t stream, const HistJob * d_jobs, int njobs, int total_tiles, int bpp);
 int launch_table_copy (hipStream_t stream, void *dst, const void *src, size_t bytes);
 // schro_table_quant[i] and schro_table_offset_1_2[i] (intra) / _3_8[i] (inter)
 void dequant_tables (int quant_index, int is_intra, uint32_t * factor, uint32_t * offset);
@@ -744,6 +761,7 @@ void obmc_tiles (int variant, int w, int h, int xoff, int *tiles_x, int *tiles_y
 
 namespace schro {
 struct FrameQuantTable;
+struct FrameHistTable;
 }
 
 struct SchroHipContext {
@@ -887,6 +905,9 @@ struct SchroHipContext {
   // the frame layer's quantisation table (schro_hipframe_quantise): the codeblock records of one picture geometry and the
   // device summaries behind them
   struct schro::FrameQuantTable *frame_q_table = nullptr;
+  // ... and its histogram table (schro_hipframe_subband_histograms): the sub-band records of one picture geometry, the
+  // device counts and their pinned host mirror
+  struct schro::FrameHistTable *frame_h_table = nullptr;
 };
 
 namespace schro {
@@ -929,6 +950,19 @@ struct FrameQuantTable {
   SchroHipCodeblockSummary *d_summary;
 };
 void frame_quant_table_free (SchroHipContext * ctx);
+// plane_hist.cpp: schro_hip_histogram_batch; allow_empty: bands of no width or height are skipped (their counts stay
+// zero), not refused -- the frame layer's tiny sub-bands
+int histogram_batch_run (SchroHipContext * ctx, const SchroHipHistogramPlane * planes, int nplanes, int bpp, bool allow_empty);
+struct FrameHistTable {
+  std::vector < int >key;       // what the bands were laid out for
+  std::vector < SchroHipHistogramBand > bands[3];
+  size_t total;                 // bands of the three components
+  // the three components' counts, one after the other: `total` of them PER QUEUE (kQueues runs in one allocation, the
+  // selected queue's is used), on the device and in pinned host memory -- a picture enqueued on one queue never has its
+  // counts cleared or added to by a picture in flight on another
+  SchroHipHistogramCounts *d_counts, *h_counts;
+};
+void frame_hist_table_free (SchroHipContext * ctx);
 // the launches made while a scope is open are timed under its kernel class (when profiling is on)
 struct ProfileScope {
   ProfileScope (SchroHipContext * c, int cls);
