@@ -635,6 +635,43 @@ int schro_hip_lowdelay_batch (SchroHipContext * ctx,
     const SchroHipLowDelayPicture * pictures, int npictures,
     const SchroHipLowDelayParams * params, int bytes_per_sample);
 
+/* ---- encoder: VC-2 low-delay slices written on the device -----------------------------------
+ * Replaces schro_encoder_encode_lowdelay_transform_data (schrolowdelay.c:764-1200) -- schro_encoder_pick_slice_index,
+ * _estimate_slice, quantise_block, quantise_dc_block, schro_dc_predict and _encode_slice, over schro_quantise /
+ * schro_dequantise (schroutils.c:179-235) and schro_pack_encode_sint / _estimate_sint (schropack.c:137-226): the bytes
+ * are those the reference puts into frame->pack.  Per slice the base index is searched as the reference searches it
+ * (index 0 if it fits; probes 32 .. 1 upwards; the result 1 .. 64), the sub-band indices are
+ * CLAMP (base - quant_matrix[i], 0, 60) with schro_table_quant / schro_table_offset_1_2, the LL band is predicted from
+ * the RECONSTRUCTED neighbours (int16_t, as the reference stores them: an LL difference at index 0 wraps), the
+ * slice_y_length field is sized per slice (ilog2up (8 * slice_bytes)), the slice is padded with 1-bits.  With
+ * schro_hip_iwt_batch in front this is a VC-2 low-delay intra encoder on the device.
+ *
+ * Two deliberate departures.  (1) The reference writes the dequantised high bands back into iwt_frame and throws the LL
+ * reconstruction away (:1064-1114); this call leaves the coefficient planes untouched -- its inputs are const -- and a
+ * caller that wants the reconstruction decodes the bytes with schro_hip_lowdelay_batch.  (2) Where even base index 64
+ * does not fit the reference asserts (:826-830); here such a slice is cut at its last bit and counted in *overruns.
+ *
+ * s16 coefficients only, as the reference's encoder.  Refused (SCHRO_HIP_EINVAL, nothing enqueued, the message naming
+ * the picture and member): bytes_per_sample 4 (s32 slices) or anything but 2; sizes that are not positive multiples of
+ * 1 << depth; a non-positive slice_bytes_denom or slice_bytes_num below it; a chroma LL band that is not the luma LL
+ * band in the frame's chroma format (the reference cuts its chroma LL rectangles from a reconstructed frame of THAT
+ * size, :1164-1166, and diverges from the band where they differ); LL bands of more than 2^28 samples in the picture
+ * or LL rectangles of more than 2^20 samples in one slice (the kernels index them with int); slices_bytes other than
+ * slice_bytes_num * slices / slice_bytes_denom; a stride shorter than the component or odd; a NULL or odd pointer. */
+typedef struct {
+  const void *comp[3];          /* device: Y, U, V coefficient planes (iwt_frame), s16; not written */
+  int stride[3];                /* bytes */
+  uint8_t *slices;              /* device: the picture's slices back to back */
+  size_t slices_bytes;          /* exactly slice_bytes_num * n_horiz_slices * n_vert_slices / slice_bytes_denom */
+  uint8_t *base_index;          /* device: one byte per slice, raster order: its base index 0 .. 64 */
+  uint32_t *overruns;           /* device: one word, set to the number of slices that were cut */
+} SchroHipLowDelayEncodePicture;
+
+/* all pictures share `params`; bytes_per_sample must be 2.  Three launches for the whole call */
+int schro_hip_lowdelay_encode_batch (SchroHipContext * ctx,
+    const SchroHipLowDelayEncodePicture * pictures, int npictures,
+    const SchroHipLowDelayParams * params, int bytes_per_sample);
+
 /* the DC prediction alone, in place on an LL band (also the intra DC prediction of the
  * core syntax, schrodecoder.c:3630-3636) */
 typedef struct {
@@ -1249,6 +1286,13 @@ int schro_frame_inverse_iwt_transform_shift_convert_hip (SchroHipFrame * packed,
  * copied to the device compressed; the frame's format picks s16 / s32.  Synchronous. */
 int schro_hip_decode_lowdelay_transform_data (SchroHipFrame * transform_frame,
     const void *slices, size_t slices_bytes, const SchroHipLowDelayParams * params);
+/* schro_encoder_encode_lowdelay_transform_data (frame), schrolowdelay.c:1150-1200, with frame->iwt_frame on the
+ * device (s16): `slices` (host, slices_bytes = slice_bytes_num * slices / slice_bytes_denom) receives what the reference
+ * appends to frame->pack, base_index (host, one byte per slice; may be NULL) the chosen indices, *overruns (may be NULL)
+ * the number of slices cut where the reference asserts.  The frame is not written (schro_hip_lowdelay_encode_batch's
+ * first departure).  Copies back on the selected queue and waits for it. */
+int schro_hip_encode_lowdelay_transform_data (const SchroHipFrame * iwt_frame, void *slices, size_t slices_bytes,
+    const SchroHipLowDelayParams * params, uint8_t * base_index, int *overruns);
 
 /* r05 -- the quantised hand-over behind the frame layer (VERDICT r04 "missing" 1): what a patched
  * schro_decoder_decode_subband (schrodecoder.c:3525-3640) leaves behind for one picture instead of a dense

@@ -612,6 +612,58 @@ class Context:
                 a.comp[k], a.stride[k] = planes[k].ptr, planes[k].stride
         check(self.lib.schro_hip_lowdelay_batch(self.h, arr, n, C.byref(self.lowdelay_params(P)), bpp))
 
+    def lowdelay_encode_batch(self, pictures, P, bpp=None):
+        """schro_hip_lowdelay_encode_batch.  pictures: per picture the [Y, U, V] coefficient DevicePlanes (s16; not
+        written) or (planes, slices, base_index, overruns) with caller-owned device buffers (u8 DevicePlanes of one row,
+        overruns 4 bytes); P: the parameter dict.  Mirrors schro_encoder_encode_lowdelay_transform_data.  Where the
+        buffers are the call's own, waits and returns per picture (bytes uint8 array, base indices uint8 array, number of
+        over-run slices); with caller-owned buffers the call is asynchronous and returns None."""
+        n = len(pictures)
+        arr = (_lib.LowDelayEncodePicture * n)()
+        nbytes = (int(P["slice_bytes_num"]) * int(P["n_horiz_slices"]) * int(P["n_vert_slices"])
+                  // max(int(P["slice_bytes_denom"]), 1))
+        nslices = int(P["n_horiz_slices"]) * int(P["n_vert_slices"])
+        own = []
+        for a, pic in zip(arr, pictures):
+            if isinstance(pic, tuple) and len(pic) == 4:
+                planes, sl, idx, ovr = pic
+                sb = sl.width
+            else:
+                sb = nbytes
+                planes = pic
+                sl = DevicePlane(self, 1, max(nbytes, 1), np.uint8)
+                idx = DevicePlane(self, 1, max(nslices, 1), np.uint8)
+                ovr = DevicePlane(self, 1, 1, np.uint32)
+                own.append((sl, idx, ovr))
+            for k in range(3):
+                a.comp[k], a.stride[k] = planes[k].ptr, planes[k].stride
+            a.slices, a.slices_bytes = sl.ptr, sb
+            a.base_index, a.overruns = idx.ptr, ovr.ptr
+        if bpp is None:
+            first = pictures[0][0] if isinstance(pictures[0], tuple) and len(pictures[0]) == 4 else pictures[0]
+            bpp = first[0].dtype.itemsize
+        try:
+            check(self.lib.schro_hip_lowdelay_encode_batch(self.h, arr, n, C.byref(self.lowdelay_params(P)), bpp))
+            if not own:
+                return None
+            return [(sl.download()[0, :nbytes].copy(), idx.download()[0, :nslices].copy(), int(ovr.download()[0, 0]))
+                    for sl, idx, ovr in own]
+        finally:
+            for bufs in own:
+                for b in bufs:
+                    b.free()
+
+    def encode_lowdelay(self, iwt_frame, P):
+        """schro_hip_encode_lowdelay_transform_data on a device frame (frames.DeviceFrame / PlaneFrame, s16): (bytes,
+        base indices, number of over-run slices), the first what the reference appends to frame->pack."""
+        nslices = int(P["n_horiz_slices"]) * int(P["n_vert_slices"])
+        nbytes = int(P["slice_bytes_num"]) * nslices // int(P["slice_bytes_denom"])
+        data, idx = np.zeros(max(nbytes, 1), np.uint8), np.zeros(nslices, np.uint8)
+        ovr = C.c_int(0)
+        check(self.lib.schro_hip_encode_lowdelay_transform_data(iwt_frame.ptr(), data.ctypes.data, nbytes,
+                                                                C.byref(self.lowdelay_params(P)), idx.ctypes.data, C.byref(ovr)))
+        return data[:nbytes], idx, int(ovr.value)
+
     @staticmethod
     def codeblock_table(cbs):
         """The C table (SchroHipCodeblock array) of a list of (dst_offset, dst_stride, width, height,

@@ -43,6 +43,7 @@ EXPORTED_SYMBOLS = [
     "schro_hip_iiwt_pack_wide_batch",
     "schro_hipframe_shift_right", "schro_hip_add_batch", "schro_hipframe_add",
     "schro_hip_lowdelay_arith", "schro_hip_lowdelay_batch", "schro_hip_dc_predict_batch",
+    "schro_hip_lowdelay_encode_batch", "schro_hip_encode_lowdelay_transform_data",
     "schro_hip_dequant_batch", "schro_hip_quantise_batch", "schro_hip_subtract_batch", "schro_hipframe_subtract",
     "schro_hipframe_quantise", "schro_hip_histogram_batch", "schro_hipframe_subband_histograms",
     "schro_hip_decode_lowdelay_transform_data", "schro_hipframe_dequantise",
@@ -138,6 +139,12 @@ class LowDelayParams(C.Structure):
 class LowDelayPicture(C.Structure):
     _fields_ = [("slices", C.c_void_p), ("slices_bytes", C.c_size_t),
                 ("comp", C.c_void_p * 3), ("stride", C.c_int * 3)]
+
+
+class LowDelayEncodePicture(C.Structure):
+    _fields_ = [("comp", C.c_void_p * 3), ("stride", C.c_int * 3),
+                ("slices", C.c_void_p), ("slices_bytes", C.c_size_t),
+                ("base_index", C.c_void_p), ("overruns", C.c_void_p)]
 
 
 class Codeblock(C.Structure):
@@ -463,6 +470,11 @@ def load():
     L.schro_hip_lowdelay_batch.restype = i
     L.schro_hip_decode_lowdelay_transform_data.argtypes = [C.POINTER(Frame), vp, C.c_size_t, C.POINTER(LowDelayParams)]
     L.schro_hip_decode_lowdelay_transform_data.restype = i
+    L.schro_hip_lowdelay_encode_batch.argtypes = [vp, C.POINTER(LowDelayEncodePicture), i, C.POINTER(LowDelayParams), i]
+    L.schro_hip_lowdelay_encode_batch.restype = i
+    L.schro_hip_encode_lowdelay_transform_data.argtypes = [C.POINTER(Frame), vp, C.c_size_t, C.POINTER(LowDelayParams),
+                                                           vp, C.POINTER(C.c_int)]
+    L.schro_hip_encode_lowdelay_transform_data.restype = i
     L.schro_hip_dc_predict_batch.argtypes = [vp, C.POINTER(DcPlane), i, i]
     L.schro_hip_dc_predict_batch.restype = i
     L.schro_hip_shift_right_batch.argtypes = [vp, C.POINTER(DcPlane), i, i, i]

@@ -614,6 +614,52 @@ schro_hip_decode_lowdelay_transform_data (SchroHipFrame * transform_frame, const
   return r ? r : rs;
 }
 
+// schro_encoder_encode_lowdelay_transform_data (schrolowdelay.c:1150-1200) with frame->iwt_frame on the device: the bytes
+// the reference appends to frame->pack come back to the host, compressed, instead of 2 bytes per coefficient.
+int
+schro_hip_encode_lowdelay_transform_data (const SchroHipFrame * iwt_frame, void *slices, size_t slices_bytes,
+    const SchroHipLowDelayParams * params, uint8_t * base_index, int *overruns)
+{
+  SCHRO_HIP_REQUIRE (iwt_frame && frame_ctx (iwt_frame) && slices && params,
+      "encode_lowdelay_transform_data: bad arguments (the iwt frame must be a device frame)");
+  SchroHipContext *ctx = frame_ctx (iwt_frame);
+  const int bpp = format_bpp (iwt_frame->format);
+  SCHRO_HIP_REQUIRE (bpp != 4, "encode_lowdelay_transform_data: s32 slices are not encoded (the reference's encoder is s16)");
+  SCHRO_HIP_REQUIRE (bpp == 2, "encode_lowdelay_transform_data: the frame must be s16");
+  for (int k = 0; k < 3; k++)
+    SCHRO_HIP_REQUIRE ((k ? params->iwt_chroma_width : params->iwt_luma_width) <= iwt_frame->components[k].width
+        && (k ? params->iwt_chroma_height : params->iwt_luma_height) <= iwt_frame->components[k].height,
+        "encode_lowdelay_transform_data: component %d smaller than the iwt size", k);
+  SCHRO_HIP_REQUIRE (params->n_horiz_slices > 0 && params->n_vert_slices > 0
+      && (int64_t) params->n_horiz_slices * params->n_vert_slices < (1 << 24), "encode_lowdelay_transform_data: bad slice counts");
+  const size_t nslices = (size_t) params->n_horiz_slices * params->n_vert_slices;
+  // one allocation: the slices, the base indices, the count
+  const size_t index_at = (slices_bytes + 15) & ~(size_t) 15, count_at = index_at + ((nslices + 15) & ~(size_t) 15);
+  char *d = (char *) schro_hip_domain_alloc (ctx, count_at + 16);
+  if (!d)
+    return SCHRO_HIP_ENOMEM;
+  SchroHipLowDelayEncodePicture pic;
+  for (int k = 0; k < 3; k++) {
+    pic.comp[k] = iwt_frame->components[k].data;
+    pic.stride[k] = iwt_frame->components[k].stride;
+  }
+  pic.slices = (uint8_t *) d;
+  pic.slices_bytes = slices_bytes;
+  pic.base_index = (uint8_t *) d + index_at;
+  pic.overruns = (uint32_t *) (d + count_at);
+  int r = schro_hip_lowdelay_encode_batch (ctx, &pic, 1, params, bpp);
+  uint32_t count = 0;
+  if (!r && (hipMemcpyAsync (slices, d, slices_bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess
+          || (base_index && hipMemcpyAsync (base_index, d + index_at, nslices, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+          || hipMemcpyAsync (&count, d + count_at, sizeof (count), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess))
+    r = set_error (SCHRO_HIP_EDEVICE, "encode_lowdelay_transform_data: copy of %zu bytes failed", slices_bytes);
+  const int rs = schro_hip_synchronize (ctx);   // the host buffers are filled, d is free again
+  schro_hip_domain_free (ctx, d);
+  if (!r && !rs && overruns)
+    *overruns = (int) count;
+  return r ? r : rs;
+}
+
 // r05 -- schro_decoder_decode_subband's data-parallel half on the device, behind the frame layer: the picture arrives
 // as codeblock records + quantised values (include/schro_hip.h), leaves as the dense transform frame x_wavelet_transform
 // reads.  Reference: schrodecoder.c:3525-3640 (the codeblock loop), :3311-3322 (zero codeblocks), :3060-3083 / :3400-3451

@@ -330,6 +330,29 @@ struct SliceParams {
   int run_cap;                          // slice_run_kernel: staging words per lane (launch_slices sets it)
 };
 
+// One picture of the slice encoder (lowdelay_enc.hip).
+struct EncJob {
+  const void *comp[3];
+  int stride[3];
+  int pad;
+  uint8_t *out;                 // the slices
+  uint8_t *index;               // a base index per slice
+  uint32_t *overrun;
+  uint32_t *est;                // scratch: per slice and base index 0 .. 64 the high-band bits (luma, chroma)
+  int16_t *recon;               // scratch: the reconstructed LL bands, Y then U then V, tight
+  int16_t *work;                // scratch: ldenc_choose_kernel's per-thread samples where LDS is too small
+};
+// ldenc_choose_kernel: where a thread keeps what (in int16 elements; element k of thread t lies at k * threads + t)
+struct EncChooseLayout {
+  int coef[3];                  // the slice's LL samples per component
+  int top[3];                   // the reconstructed row above, from one sample to the left
+  int left[3];                  // the reconstructed column to the left
+  int row;                      // the row being reconstructed
+  int per_thread;
+  int threads, lds_bytes, in_lds;
+  int recon_off[3];             // the components' LL bands in EncJob::recon
+};
+
 struct DcJob {
   void *data;
   int stride;
@@ -711,6 +734,9 @@ void quant_tile_geometry (int *tw, int *th);
 void quant_job_constants (QuantJob * job, int quant_index, int is_intra, int bpp);
 int launch_quantise (hipStream_t stream, const QuantJob * d_jobs, int njobs, int total_tiles, int bpp);
 int launch_quantise_dc (hipStream_t stream, const QuantDcJob * d_jobs, int njobs, const QuantDcRec * d_recs, int max_rows, int bpp);
+// lowdelay_enc.hip; stages: 1 estimate, 2 choose, 4 pack
+int launch_lowdelay_encode (hipStream_t stream, const EncJob * d_jobs, int njobs, const SliceParams & P,
+    const EncChooseLayout & L, int stages);
 // hist.hip
 void hist_tile_geometry (int *group_bytes, int *groups_per_tile, int *groups_per_step);
 int launch_histogram (hipStream_t stream, const HistJob * d_jobs, int njobs, int total_tiles, int bpp);
