@@ -29,7 +29,8 @@ def default_matrix(depth):
 
 def coefficients(P, kind, seed):
     """Three int16 planes of the iwt sizes.  small: wavelet-like, Laplacian within +-4095, the LL band smooth and larger;
-    full: uniform over all of s16; zero."""
+    tiny: the same at a scale of 1.5; steps: small with the lower half of every plane doubled (as turns_case scales its
+    last rows), so that slice rows of one picture land on unlike indices; full: uniform over all of s16; zero."""
     rng = np.random.default_rng(seed)
     out = []
     for c in range(3):
@@ -40,11 +41,13 @@ def coefficients(P, kind, seed):
             a = rng.integers(-32768, 32768, (h, w)).astype(np.int16)
             a.reshape(-1)[:4] = (-32768, 32767, -32768, 32767)
         else:
-            scale = {"small": 40.0, "tiny": 1.5}[kind]
+            scale = {"small": 40.0, "steps": 40.0, "tiny": 1.5}[kind]
             a = np.clip(np.rint(rng.laplace(0.0, scale, (h, w))), -4095, 4095).astype(np.int16)
             ll = R.subband(a, 0, P["transform_depth"], w, h)
             ll[...] = np.clip(np.rint(600 + 300 * np.sin(np.arange(ll.shape[1]) / 3.0)[None, :]
                                       + rng.normal(0, 60, ll.shape)), -4095, 4095).astype(np.int16)
+            if kind == "steps":
+                a[h // 2:] *= 2
         out.append(a)
     return out
 
@@ -70,10 +73,36 @@ def _cases():
     c["length_field"] = (params(64, 32, 422, 2, 4, 4, 63, 2), "small", 12, "the fast decoder sizes slice_y_length from the short slice")
     c["zero"] = (params(64, 32, 420, 3, 4, 4, 16, 1), "zero", 0, None)
     c["overrun"] = (params(64, 32, 420, 2, 4, 4, 5, 2), "full", 11, "over-run slices")
+    # the serial launch off LDS (leaves_lds below) with more than one thread: 32 x 32 LL rectangles per component on a diagonal
+    # of two slices; 3 x 5 slices of a 68 x 56 / 34 x 28 LL band, widths 22 23 23 / 11 11 12, heights 11 11 12 11 11 / 5 6 6 5 6
+    c["spill_2x2"] = (params(128, 128, 444, 1, 2, 2, 9217, 3), "steps", 13, None)
+    c["spill_3x5_420"] = (params(272, 224, 420, 2, 3, 5, 15001, 4), "steps", 14, None)
     return c
 
 
 CASES = _cases()
+SPILL_BATCH = ("spill_2x2", (("small", 43), ("full", 44), ("zero", 0)))       # geometry, the unlike pictures of one call
+
+
+def per_thread_samples(P):
+    """What a thread of the serial launch keeps, in samples: plane_lowdelay_enc.cpp:88-103 (EncChooseLayout) -- per
+    component the largest LL rectangle, the row above it from one sample to the left, the column to its left; and the
+    row being reconstructed."""
+    depth, nh, nv = P["transform_depth"], P["n_horiz_slices"], P["n_vert_slices"]
+    at = bw_max = 0
+    for c in range(3):
+        w = (P["iwt_chroma_width"] if c else P["iwt_luma_width"]) >> depth
+        h = (P["iwt_chroma_height"] if c else P["iwt_luma_height"]) >> depth
+        bw, bh = -(-w // nh), -(-h // nv)
+        at += bw * bh + bw + 1 + bh
+        bw_max = max(bw_max, bw)
+    return at + bw_max
+
+
+def leaves_lds(P):
+    """plane_lowdelay_enc.cpp:104-113: the launch keeps the samples in LDS while 64 threads' worth of them (int16) fit
+    48 KB -- 384 samples per thread; beyond that they go to the queue's scratch, element k of thread t at k * T + t."""
+    return per_thread_samples(P) * 2 * 64 > 48 << 10
 
 
 def span_case():

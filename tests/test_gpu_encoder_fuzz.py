@@ -1,8 +1,13 @@
 """GPU parity of the encoder-side kernels under random geometry: seeded draws of the forward wavelet (filters, depths 1 - 6,
 sample sizes, unlike planes in one call, strides and leads that are no multiple of anything, pixel- and full-range input),
 the downsample (sizes, aprons, destination alignments and strides, batches), the SAD scan (pictures, blocks from empty to
-64 x 64, windows, gravity positions, pictures full of ties) and the frame layer's pyramid and rough scan, each compared
-bit for bit with tests/oracle_lib.py or tests/analysis_ref.py.  The decoder side's draws are tests/test_gpu_fuzz.py; the
+64 x 64, windows, gravity positions, pictures full of ties), the frame layer's pyramid and rough scan, and the encoder's
+tail -- the codeblock quantiser (quant.hip: layouts, depths, both sample types, intra DC bands down to one sample a side), the
+sub-band histograms (hist.hip: every sub-band of random transforms, both forms, planes of equal samples) and the VC-2
+low-delay slice encoder (lowdelay_enc.hip: chroma formats, depths, slice counts beyond the LL band, fractional slice
+sizes, matrices, unlike pictures in one call, the serial launch in LDS and off it) -- each compared bit for bit with
+tests/oracle_lib.py, tests/analysis_ref.py, tests/quant_ref.py, tests/hist_ref.py or tests/lowdelay_enc_ref.py.  The tail's
+draws come from tests/encoder_tail_draws.py, which tests/dry_run_encoder_tail_cases.py walks without a device.  The decoder side's draws are tests/test_gpu_fuzz.py; the
 conventions are the same: SCHRO_FUZZ_SCALE multiplies the number of draws, SCHRO_FUZZ_SEED shifts the seeds (a long
 campaign is `SCHRO_FUZZ_SCALE=50 SCHRO_FUZZ_SEED=7 pytest tests/test_gpu_encoder_fuzz.py -m gpu`), and every failure
 message carries its draw."""
@@ -13,12 +18,17 @@ import numpy as np
 import pytest
 
 import analysis_ref as A
+import encoder_tail_draws as D
+import hist_cases as HC
+import lowdelay_enc_ref as R
 import oracle_lib as O
+import quant_cases as QC
 import schroedinger_amd as sa
 import synth
 from schroedinger_amd import frames
 from test_gpu_analysis_edges import check_scans, dst_view, make_scans
 from test_gpu_iwt_forward import pixel_range
+from test_gpu_lowdelay_encode import run as run_lowdelay_encode
 
 SCALE = int(os.environ.get("SCHRO_FUZZ_SCALE", "1"))
 SEED = int(os.environ.get("SCHRO_FUZZ_SEED", "0"))
@@ -179,3 +189,46 @@ def test_frame_layer_random_pyramids_and_rough_scans(ctx):
         assert got.tobytes() == want.tobytes(), tag
         fa.unref(), fb.unref()
         [p.free() for p in held]
+
+
+def tagged(tag, call):
+    """call (); an AssertionError leaves with the draw in front of its message"""
+    try:
+        return call()
+    except AssertionError as e:
+        raise AssertionError("%r: %s" % (tag, e)) from e
+
+
+def test_lowdelay_encode_random_pictures(ctx):
+    """schro_hip_lowdelay_encode_batch on the draws of encoder_tail_draws.lowdelay_draws, through the runner of
+    tests/test_gpu_lowdelay_encode.py (guarded memory: nothing beside the slices, the indices and the count is written,
+    the padded coefficient planes stay as they were): bytes, base indices and the over-run count of every picture equal
+    tests/lowdelay_enc_ref.py's.  Slices that over-run are cut and counted by both, so such draws are compared in full."""
+    for draw in D.lowdelay_draws(SCALE, SEED):
+        pictures = D.lowdelay_pictures(draw)
+        got = tagged(draw["tag"], lambda: run_lowdelay_encode(ctx, draw["P"], pictures, pads=draw["pads"], skew=draw["skew"]))
+        for n, (planes, (data, index, count)) in enumerate(zip(pictures, got)):
+            res = R.encode(planes, draw["P"])
+            tag = draw["tag"] + ("picture", n)
+            assert index.tolist() == res["index"].tolist(), tag + ("indices", index.tolist(), res["index"].tolist())
+            assert count == res["count"], tag + ("over-run count", count, res["count"])
+            assert data.size == res["bytes"].size, tag + ("bytes", data.size, res["bytes"].size)
+            bad = np.flatnonzero(data != res["bytes"])
+            assert bad.size == 0, tag + ("%d bytes differ, first at %d" % (bad.size, bad[0] if bad.size else -1),)
+
+
+def test_quantise_random_codeblocks(ctx):
+    """schro_hip_quantise_batch on the draws of encoder_tail_draws.quantise_draws through quant_cases.run_specs: quantised
+    values (the quant plane keeps its fill outside the records), the reconstruction left in the coefficient plane and the
+    codeblock summaries equal tests/quant_ref.py's"""
+    for draw in D.quantise_draws(SCALE, SEED):
+        tagged(draw["tag"], lambda: QC.run_specs(ctx, draw["specs"]))
+
+
+def test_histogram_random_bands(ctx):
+    """schro_hip_histogram_batch on the draws of encoder_tail_draws.histogram_draws through hist_cases.run_specs: the counts
+    of every band equal tests/hist_ref.py's.  The counts of all planes of a call lie one behind the other in one block and
+    every row of it is compared, so a count that lands in a neighbour's row shows; the planes are uploaded tight, so a
+    band's last row ends its allocation."""
+    for draw in D.histogram_draws(SCALE, SEED):
+        tagged(draw["tag"], lambda: HC.run_specs(ctx, draw["specs"]))

@@ -55,7 +55,8 @@ def assert_same(got, res):
 def test_bytes_indices_and_count(ctx, name):
     """Depths 1 .. 4 x three chroma formats with fractional slice sizes; 1 x 1 LL blocks on a long diagonal chain; unequal
     rectangles; one slice for a whole picture (the looping paths); base - matrix below 0; full-range values (the LL wrap);
-    all zero; over-run slices (cut and counted); indices spanning 0 .. 64."""
+    all zero; over-run slices (cut and counted); indices spanning 0 .. 64; the serial launch off LDS with several threads
+    (spill_2x2, spill_3x5_420: lowdelay_enc_cases.leaves_lds)."""
     P, planes, res = K.expected(name)
     assert_same(run(ctx, P, [planes])[0], res)
 
@@ -71,6 +72,19 @@ def test_batch_of_three_unlike_pictures(ctx):
     P = K.CASES["64x32_d3_422"][0]
     pics = [K.coefficients(P, kind, seed) for kind, seed in (("small", 41), ("full", 42), ("zero", 0))]
     import lowdelay_enc_ref as R
+    got = run(ctx, P, pics, pads=(2, 30, 0), skew=1)
+    for g, planes in zip(got, pics):
+        assert_same(g, R.encode(planes, P))
+
+
+def test_batch_of_three_unlike_pictures_off_lds(ctx):
+    """the spill_2x2 geometry, whose serial launch keeps its samples in the queue's scratch: three pictures' regions of it
+    live at once, each with two threads on the middle diagonal"""
+    import lowdelay_enc_ref as R
+    name, kinds = K.SPILL_BATCH
+    P = K.CASES[name][0]
+    assert K.leaves_lds(P)
+    pics = [K.coefficients(P, kind, seed) for kind, seed in kinds]
     got = run(ctx, P, pics, pads=(2, 30, 0), skew=1)
     for g, planes in zip(got, pics):
         assert_same(g, R.encode(planes, P))

@@ -96,6 +96,27 @@ def test_chosen_index_follows_the_search(name):
         assert bool(res["overrun"][s]) == (trace[-1][1] > room)
 
 
+def test_which_cases_leave_lds():
+    """lowdelay_enc_cases.leaves_lds restates the serial launch's choice between LDS and the queue's scratch: the spill
+    cases are beyond it (with unlike indices, unequal rectangles and no over-run: they join the round trip), the cases
+    meant for LDS are not -- neither can change sides unnoticed"""
+    for name in ("spill_2x2", "spill_3x5_420", K.SPILL_BATCH[0], "one_slice", "one_slice_444_d1"):
+        assert K.leaves_lds(K.CASES[name][0]), name
+    for name in ["turns", "large"] + [n for n in K.CASES if n.startswith("64x32_")]:
+        assert not K.leaves_lds(K.expected(name)[0]), name
+    assert K.per_thread_samples(K.CASES["spill_2x2"][0]) == 3 * (32 * 32 + 33 + 32) + 32
+    assert K.per_thread_samples(K.expected("turns")[0]) == 200          # (turns_case's own count)
+    for name in ("spill_2x2", "spill_3x5_420"):
+        P, _, res = K.expected(name)
+        assert len(set(res["index"].tolist())) > 1 and res["count"] == 0 and name in ROUND_TRIP
+    P = K.CASES["spill_2x2"][0]
+    assert min(P["n_horiz_slices"], P["n_vert_slices"]) == 2           # a diagonal of two threads
+    P = K.CASES["spill_3x5_420"][0]
+    assert P["iwt_chroma_width"] < P["iwt_luma_width"] and P["iwt_chroma_height"] < P["iwt_luma_height"]
+    for size, n in ((P["iwt_luma_width"] >> 2, 3), (P["iwt_luma_height"] >> 2, 5), (P["iwt_chroma_width"] >> 2, 3), (P["iwt_chroma_height"] >> 2, 5)):
+        assert len(set(R.codeblock(size, 1, k, 0, n, 1)[1] - R.codeblock(size, 1, k, 0, n, 1)[0] for k in range(n))) >= 2
+
+
 def test_span_and_exact_fits():
     _, _, res = K.expected("span")
     assert res["index"].min() == 0 and res["index"].max() == 64 and len(set(res["index"].tolist())) >= 40
