@@ -379,6 +379,81 @@ int schro_hip_metric_scan_setup (SchroHipMetricScan * scan, int frame_width, int
  * 64 x 64.  A refusal (SCHRO_HIP_EINVAL, nothing launched) names the picture and the scan. */
 int schro_hip_metric_scan_batch (SchroHipContext * ctx, const SchroHipMetricScanPicture * pictures, int npictures);
 
+/* ---- the hierarchical rough motion search on the device (schroroughmotion.c:47-300) ----
+ *
+ * A motion field on the device is a dense array of x_num_blocks * y_num_blocks SchroMotionVector records (20 bytes,
+ * schromotion.h:20-37), 4-byte aligned: downloaded, it is rme->motion_fields[shift] as it is.  A call writes EVERY record
+ * of every field it owns -- as schro_motion_field_set (mf, 0, 1) leaves them, then the blocks at multiples of 1 << shift --
+ * and nothing outside the fields.
+ *
+ * One workgroup of up to SCHRO_HIP_ROUGH_WAVES waves runs one (picture, reference) chain: the blocks of a hint level
+ * depend on their left, upper and upper-left neighbours, so the waves take the blocks of an anti-diagonal (i + j) / skip
+ * in turn, a workgroup barrier between diagonals and between levels; fewer waves where a wave's block and window need
+ * more of the workgroup's LDS (64 x 64 blocks).  No workgroup waits for another. */
+#define SCHRO_HIP_ROUGH_WAVES 16
+#define SCHRO_HIP_MAX_HIER_LEVELS 8     /* SCHRO_MAX_HIER_LEVELS, schromotionest.h:20 */
+
+/* The luma planes of a frame and of its reference frame at one pyramid level. */
+typedef struct {
+  const uint8_t *frame;         /* device, pixel (0, 0) */
+  int frame_stride;
+  const uint8_t *ref;
+  int ref_stride;
+  int width, height;            /* both planes */
+  int extension;                /* the apron the frames WOULD have (schro_metric_scan_setup); the kernel clamps coordinates */
+} SchroHipRoughPlane;
+
+/* One level of schro_rough_me_heirarchical_scan_hint (schroroughmotion.c:143-300) for one (frame, reference) pair:
+ * per block (i, j) at multiples of 1 << shift the candidates -- the zero vector, the records of hint_field at
+ * ((i +- skip) & mask, (j +- skip) & mask) that lie inside the field, the records of this level to the left, above and
+ * above-left -- are tested with a plain SAD (:232-268: a candidate in front of the picture or ending behind it is
+ * skipped, the strictly smallest metric wins, the first of equals; none left: the zero vector), then the window of
+ * `distance` around the winner >> shift is scanned as schro_hip_metric_scan_batch scans (:270-295).  A block of no
+ * width or height (x_num_blocks * xbsep_luma beyond the plane) has SAD 0 everywhere: its vector stays the zero vector
+ * with metric 0 (the reference reads its starting minimum outside the window there); a window of no width or height
+ * stores 0, 0, INT_MAX. */
+typedef struct {
+  const uint8_t *frame;         /* device: the planes at level `shift`, as in SchroHipRoughPlane */
+  int frame_stride;
+  const uint8_t *ref;
+  int ref_stride;
+  int width, height;
+  int extension;
+  int x_num_blocks, y_num_blocks, xbsep_luma, ybsep_luma;
+  int shift;                    /* 1 .. 7 */
+  int distance;                 /* 1 .. 20: a window of 2 * distance + 1 <= SCHRO_HIP_LIMIT_METRIC_SCAN positions */
+  int ref_index;                /* 0 or 1: which of dx[], dy[] is read from the candidates and written */
+  const void *hint_field;       /* device: the field of level shift + 1 (read) */
+  void *field;                  /* device: the field of level `shift` (written whole) */
+} SchroHipRoughHintPicture;
+
+/* One launch, one workgroup per picture; pictures of unlike geometry, shift and ref mix.  Enqueues, does not synchronise.
+ * Refused (SCHRO_HIP_EINVAL, nothing launched, the message names the picture): block counts of 0, a distance <= 0 or
+ * over 20, a block over 64 x 64, ref_index outside 0 / 1, a shift outside 1 .. 7, a stride shorter than a row, a field that
+ * overlaps another picture's, a plane or a hint field. */
+int schro_hip_rough_hint_batch (SchroHipContext * ctx, const SchroHipRoughHintPicture * pictures, int npictures);
+
+/* schro_rough_me_heirarchical_scan (schroroughmotion.c:47-62) for one (frame, reference) pair: the nohint level at
+ * n_levels, then the hint levels n_levels - 1 .. 1, all inside ONE launch -- the fields never leave the device. */
+typedef struct {
+  int n_levels;                 /* 1 .. SCHRO_HIP_MAX_HIER_LEVELS; 1: only the nohint level runs */
+  const SchroHipRoughPlane *levels;     /* HOST array of n_levels entries, copied by the call: levels[k] is level k + 1 */
+  int x_num_blocks, y_num_blocks, xbsep_luma, ybsep_luma;
+  int ref_index;                /* 0 or 1 */
+  void *fields[SCHRO_HIP_MAX_HIER_LEVELS];      /* device: fields[k] is the field of level k + 1 (written whole) */
+} SchroHipRoughChain;
+
+/* One launch, one workgroup per chain.  Enqueues, does not synchronise.  The reference's distances are 12 and 4 (:58-60).
+ * Refused (SCHRO_HIP_EINVAL, nothing launched, the message names the chain and the level): what
+ * schro_hip_rough_hint_batch refuses, n_levels outside 1 .. 8, a plane that is not (w + 1) / 2 x (h + 1) / 2 of the
+ * chain's level below it, overlapping fields. */
+int schro_hip_rough_me_batch (SchroHipContext * ctx, const SchroHipRoughChain * chains, int nchains, int nohint_distance,
+    int hint_distance);
+/* host only: the refusals of schro_hip_rough_hint_batch / schro_hip_rough_me_batch without a context -- 0 or
+ * SCHRO_HIP_EINVAL with the message the batch would give.  No pointer is dereferenced but the HOST arrays. */
+int schro_hip_rough_hint_check (const SchroHipRoughHintPicture * pictures, int npictures);
+int schro_hip_rough_me_check (const SchroHipRoughChain * chains, int nchains, int nohint_distance, int hint_distance);
+
 /* intra pictures: dst_u8 = sat_u8 (src + 128), cropped to width x height;
  * replaces schro_frame_convert (ref_output_frame, frame)
  * (schrodecoder.c:1788-1790) / schro_gpuframe_convert. */
@@ -1242,6 +1317,20 @@ int schro_hipframe_downsample (SchroHipFrame * dest, SchroHipFrame * src);
  * the metric (a scan of no width or height: 0, 0, INT_MAX).  Synchronises: the array is complete on return. */
 int schro_rough_me_heirarchical_scan_nohint_hip (SchroHipFrame * frame, SchroHipFrame * ref_frame,
     const SchroHipParams * params, int shift, int distance, int ref, void *motion_vectors);
+
+/* schro_rough_me_heirarchical_scan_hint (schroroughmotion.c:143-300) over the luma planes of two u8 device frames that
+ * are both at pyramid level `shift`.  hint_motion_vectors: the HOST field of level shift + 1 (read); motion_vectors: the
+ * HOST field of level `shift` (every record written).  The fields cross to the device and back through the queue's
+ * scratch.  Synchronises: the array is complete on return. */
+int schro_rough_me_heirarchical_scan_hint_hip (SchroHipFrame * frame, SchroHipFrame * ref_frame,
+    const SchroHipParams * params, int shift, int distance, int ref, const void *hint_motion_vectors, void *motion_vectors);
+/* schro_rough_me_heirarchical_scan (schroroughmotion.c:47-62): frames[k], ref_frames[k] are the u8 device frames at
+ * pyramid level k as get_downsampled (:303-312) returns them, motion_fields[k] the HOST field of level k, for k = 1 ..
+ * n_levels (entry 0 of the three arrays is not read).  The nohint level at distance 12, the hint levels at distance 4
+ * (:58-60), one launch; the fields stay on the device between the levels and are downloaded together.  Synchronises
+ * once, at the end. */
+int schro_rough_me_heirarchical_scan_hip (SchroHipFrame * const *frames, SchroHipFrame * const *ref_frames,
+    const SchroHipParams * params, int n_levels, int ref, void *const *motion_fields);
 
 /* schro_frame_inverse_iwt_transform_cuda (schrocuda.h:13-14) replacement, same arguments:
  * upload transform_frame (host) or use it where it is (device), run the multi-level inverse

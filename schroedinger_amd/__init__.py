@@ -42,6 +42,59 @@ def metric_scan_setup(x, y, block_width, block_height, frame_width, frame_height
     return s.ref_x, s.ref_y, s.scan_width, s.scan_height
 
 
+ROUGH_WAVES = 16                # SCHRO_HIP_ROUGH_WAVES (include/schro_hip.h): the most waves a rough-search workgroup has
+MAX_HIER_LEVELS = _lib.MAX_HIER_LEVELS
+
+
+def _block_geometry(params):
+    return tuple(int(params[k] if isinstance(params, dict) else getattr(params, k))
+                 for k in ("x_num_blocks", "y_num_blocks", "xbsep_luma", "ybsep_luma"))
+
+
+def rough_hint_pictures(pictures):
+    """The SchroHipRoughHintPicture array of [(frame, ref, extension, params, shift, distance, ref_index, hint_field,
+    field)]: frame, ref -- u8 planes of one size at level `shift` (anything with ptr, stride, width, height); params -- a
+    dict (or _lib.Params) with x_num_blocks, y_num_blocks, xbsep_luma, ybsep_luma; hint_field, field -- device fields
+    (Context.motion_field, or anything with ptr)."""
+    arr = (_lib.RoughHintPicture * len(pictures))()
+    for k, (f, r, ext, params, shift, dist, ref_index, hint, field) in enumerate(pictures):
+        assert (f.height, f.width) == (r.height, r.width)
+        arr[k] = _lib.RoughHintPicture(f.ptr, f.stride, r.ptr, r.stride, f.width, f.height, ext, *_block_geometry(params),
+                                       shift, dist, ref_index, hint.ptr, field.ptr)
+    return arr
+
+
+def rough_chains(chains):
+    """The SchroHipRoughChain array of [(levels, params, ref_index, fields)]: levels -- [(frame, ref, extension)] for
+    pyramid levels 1 .. n_levels, fields -- the device field of each.  Returns (array, what it points to)."""
+    arr, keep = (_lib.RoughChain * len(chains))(), []
+    for k, (levels, params, ref_index, fields) in enumerate(chains):
+        assert len(levels) == len(fields)
+        n = len(levels)
+        lv = (_lib.RoughPlane * max(n, 1))()
+        for m, (f, r, ext) in enumerate(levels):
+            assert (f.height, f.width) == (r.height, r.width)
+            lv[m] = _lib.RoughPlane(f.ptr, f.stride, r.ptr, r.stride, f.width, f.height, ext)
+        keep.append(lv)
+        arr[k].n_levels, arr[k].levels = n, lv
+        arr[k].x_num_blocks, arr[k].y_num_blocks, arr[k].xbsep_luma, arr[k].ybsep_luma = _block_geometry(params)
+        arr[k].ref_index = ref_index
+        for m, fld in enumerate(fields[:MAX_HIER_LEVELS]):
+            arr[k].fields[m] = fld.ptr
+    return arr, keep
+
+
+def rough_hint_check(pictures):
+    """The refusals of Context.rough_hint_batch on the host, without a context (schro_hip_rough_hint_check)."""
+    check(_lib.load().schro_hip_rough_hint_check(rough_hint_pictures(pictures), len(pictures)))
+
+
+def rough_me_check(chains, nohint_distance=12, hint_distance=4):
+    """The refusals of Context.rough_me_batch on the host, without a context (schro_hip_rough_me_check)."""
+    arr, keep = rough_chains(chains)
+    check(_lib.load().schro_hip_rough_me_check(arr, len(chains), nohint_distance, hint_distance))
+
+
 QUANTISE_DC_THREADS = 256       # SCHRO_HIP_QUANTISE_DC_THREADS (include/schro_hip.h): the DC recurrence's workgroup size
 
 
@@ -465,6 +518,60 @@ class Context:
         check(self.lib.schro_rough_me_heirarchical_scan_nohint_hip(fa.ptr(), fb.ptr(), C.byref(params), shift, distance, ref_index,
                                                                    mvs.ctypes.data_as(C.c_void_p)))
         return mvs
+
+    def motion_field(self, params):
+        """A device motion field: x_num_blocks * y_num_blocks SchroMotionVector records (one row of a DevicePlane)."""
+        nbx, nby = _block_geometry(params)[:2]
+        return DevicePlane(self, 1, nbx * nby * MV_DTYPE.itemsize, np.uint8, stride=nbx * nby * MV_DTYPE.itemsize)
+
+    @staticmethod
+    def download_field(field):
+        """The MV_DTYPE records of a device motion field: rme->motion_fields[shift] as it is."""
+        return field.download().reshape(-1).view(MV_DTYPE).copy()
+
+    def rough_hint_batch(self, pictures):
+        """One hint level of the rough search per picture (schro_rough_me_heirarchical_scan_hint), one launch:
+        pictures as rough_hint_pictures takes them.  Every record of each `field` is written; enqueued, not waited for."""
+        check(self.lib.schro_hip_rough_hint_batch(self.h, rough_hint_pictures(pictures), len(pictures)))
+
+    def rough_me_batch(self, chains, nohint_distance=12, hint_distance=4):
+        """schro_rough_me_heirarchical_scan per chain, one launch: chains as rough_chains takes them -- the nohint level at
+        n_levels, then the hint levels down to 1, the fields staying on the device.  Enqueued, not waited for."""
+        arr, keep = rough_chains(chains)
+        check(self.lib.schro_hip_rough_me_batch(self.h, arr, len(chains), nohint_distance, hint_distance))
+
+    def rough_scan_hint(self, frame, ref, params, shift, distance, ref_index, hint_mvs, extension=0):
+        """schro_rough_me_heirarchical_scan_hint_hip over two u8 luma DevicePlanes at pyramid level `shift`; hint_mvs: the
+        MV_DTYPE array of level shift + 1.  Returns the MV_DTYPE array of level `shift`, complete."""
+        from . import frames
+        if not isinstance(params, _lib.Params):
+            params = frames.make_params(**dict(zip(("x_num_blocks", "y_num_blocks", "xbsep_luma", "ybsep_luma"), _block_geometry(params))))
+        fa, fb = frames.PlaneFrame(self, [frame] * 3, extension), frames.PlaneFrame(self, [ref] * 3, extension)
+        hint = np.ascontiguousarray(hint_mvs, dtype=MV_DTYPE)
+        assert hint.size == params.x_num_blocks * params.y_num_blocks
+        mvs = np.zeros(hint.size, MV_DTYPE)
+        check(self.lib.schro_rough_me_heirarchical_scan_hint_hip(fa.ptr(), fb.ptr(), C.byref(params), shift, distance, ref_index,
+                                                                 hint.ctypes.data_as(C.c_void_p), mvs.ctypes.data_as(C.c_void_p)))
+        return mvs
+
+    def rough_scan(self, frames_by_level, refs_by_level, params, ref_index, extension=0):
+        """schro_rough_me_heirarchical_scan_hip: frames_by_level[k], refs_by_level[k] are the u8 luma DevicePlanes at
+        pyramid level k for k = 1 .. n_levels (entry 0, the full picture, is not read and may be None).  Returns the list
+        of MV_DTYPE arrays by level (entry 0: None), complete."""
+        from . import frames
+        if not isinstance(params, _lib.Params):
+            params = frames.make_params(**dict(zip(("x_num_blocks", "y_num_blocks", "xbsep_luma", "ybsep_luma"), _block_geometry(params))))
+        n = len(frames_by_level) - 1
+        assert len(refs_by_level) == n + 1
+        fa = [None] + [frames.PlaneFrame(self, [p] * 3, extension) for p in frames_by_level[1:]]
+        fb = [None] + [frames.PlaneFrame(self, [p] * 3, extension) for p in refs_by_level[1:]]
+        pa, pb = (C.POINTER(_lib.Frame) * (n + 1))(), (C.POINTER(_lib.Frame) * (n + 1))()
+        out = [None] + [np.zeros(params.x_num_blocks * params.y_num_blocks, MV_DTYPE) for _ in range(n)]
+        fields = (C.c_void_p * (n + 1))()
+        for k in range(1, n + 1):
+            pa[k], pb[k], fields[k] = C.pointer(fa[k].c), C.pointer(fb[k].c), out[k].ctypes.data
+        check(self.lib.schro_rough_me_heirarchical_scan_hip(pa, pb, C.byref(params), n, ref_index, fields))
+        return out
 
     def pack_u8_batch(self, jobs):
         """jobs: (planes [Y, U, V] DevicePlanes, h_shift, v_shift, dst DevicePlane of 4-byte

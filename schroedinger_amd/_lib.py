@@ -37,6 +37,8 @@ EXPORTED_SYMBOLS = [
     "schro_hip_iiwt_batch", "schro_hip_iwt_batch", "schro_hipframe_iwt_transform", "schro_hip_convert_u8_batch", "schro_hip_upsample_batch",
     "schro_hip_downsample_batch", "schro_hip_metric_scan_setup", "schro_hip_metric_scan_batch", "schro_hipframe_downsample",
     "schro_rough_me_heirarchical_scan_nohint_hip",
+    "schro_hip_rough_hint_batch", "schro_hip_rough_me_batch", "schro_hip_rough_hint_check", "schro_hip_rough_me_check",
+    "schro_rough_me_heirarchical_scan_hint_hip", "schro_rough_me_heirarchical_scan_hip",
     "schro_hip_upsampled_bytes", "schro_hip_upsampled_download", "schro_hip_upsampled_pair_bytes",
     "schro_hip_upsampled_pair_download", "schro_hip_pack_u8_batch",
     "schro_hip_pack_v210_batch", "schro_hip_iiwt_pack_v210_batch", "schro_hip_iiwt_pack_u8_batch", "schro_hip_pack_wide_batch", "schro_hip_shift_right_batch",
@@ -92,6 +94,29 @@ class MetricScanPicture(C.Structure):
                 ("width", C.c_int), ("height", C.c_int), ("extension", C.c_int),
                 ("scans", C.POINTER(MetricScan)), ("nscans", C.c_int),
                 ("results", C.c_void_p), ("metrics", C.c_void_p)]
+
+
+MAX_HIER_LEVELS = 8             # SCHRO_HIP_MAX_HIER_LEVELS
+
+
+class RoughPlane(C.Structure):
+    """The luma planes of a frame and its reference at one pyramid level."""
+    _fields_ = [("frame", C.c_void_p), ("frame_stride", C.c_int), ("ref", C.c_void_p), ("ref_stride", C.c_int),
+                ("width", C.c_int), ("height", C.c_int), ("extension", C.c_int)]
+
+
+class RoughHintPicture(C.Structure):
+    _fields_ = [("frame", C.c_void_p), ("frame_stride", C.c_int), ("ref", C.c_void_p), ("ref_stride", C.c_int),
+                ("width", C.c_int), ("height", C.c_int), ("extension", C.c_int),
+                ("x_num_blocks", C.c_int), ("y_num_blocks", C.c_int), ("xbsep_luma", C.c_int), ("ybsep_luma", C.c_int),
+                ("shift", C.c_int), ("distance", C.c_int), ("ref_index", C.c_int),
+                ("hint_field", C.c_void_p), ("field", C.c_void_p)]
+
+
+class RoughChain(C.Structure):
+    _fields_ = [("n_levels", C.c_int), ("levels", C.POINTER(RoughPlane)),
+                ("x_num_blocks", C.c_int), ("y_num_blocks", C.c_int), ("xbsep_luma", C.c_int), ("ybsep_luma", C.c_int),
+                ("ref_index", C.c_int), ("fields", C.c_void_p * MAX_HIER_LEVELS)]
 
 
 class ConvertPlane(C.Structure):
@@ -450,6 +475,19 @@ def load():
     L.schro_hipframe_downsample.restype = i
     L.schro_rough_me_heirarchical_scan_nohint_hip.argtypes = [C.POINTER(Frame), C.POINTER(Frame), C.POINTER(Params), i, i, i, vp]
     L.schro_rough_me_heirarchical_scan_nohint_hip.restype = i
+    L.schro_hip_rough_hint_batch.argtypes = [vp, C.POINTER(RoughHintPicture), i]
+    L.schro_hip_rough_hint_batch.restype = i
+    L.schro_hip_rough_me_batch.argtypes = [vp, C.POINTER(RoughChain), i, i, i]
+    L.schro_hip_rough_me_batch.restype = i
+    L.schro_hip_rough_hint_check.argtypes = [C.POINTER(RoughHintPicture), i]
+    L.schro_hip_rough_hint_check.restype = i
+    L.schro_hip_rough_me_check.argtypes = [C.POINTER(RoughChain), i, i, i]
+    L.schro_hip_rough_me_check.restype = i
+    L.schro_rough_me_heirarchical_scan_hint_hip.argtypes = [C.POINTER(Frame), C.POINTER(Frame), C.POINTER(Params), i, i, i, vp, vp]
+    L.schro_rough_me_heirarchical_scan_hint_hip.restype = i
+    L.schro_rough_me_heirarchical_scan_hip.argtypes = [C.POINTER(C.POINTER(Frame)), C.POINTER(C.POINTER(Frame)), C.POINTER(Params), i, i,
+                                                       C.POINTER(vp)]
+    L.schro_rough_me_heirarchical_scan_hip.restype = i
     L.schro_hip_convert_u8_batch.argtypes = [vp, C.POINTER(ConvertPlane), i, i]
     L.schro_hip_convert_u8_batch.restype = i
     L.schro_hip_upsample_batch.argtypes = [vp, C.POINTER(UpsamplePlane), i]

@@ -3,6 +3,7 @@
 // schrometric.c:31-171).  Integer arithmetic only: both are bit-exact against the reference.
 
 #include "schro_hip_internal.h"
+#include "scan_common.h"
 
 namespace schro {
 
@@ -125,6 +126,8 @@ launch_downsample (hipStream_t stream, const DownsampleJob * d_jobs, int njobs, 
 
 // ---- SAD scan --------------------------------------------------------------------------------------------------------
 //
+// (The LDS layout, the staging and the minimum are in scan_common.h: rough_hint.hip runs the same scan per block.)
+//
 // One wave per scan, four scans per workgroup.  The wave stages its block (rows padded with zeros to whole dwords) and
 // the reference window the scan touches -- (block_width + scan_width - 1) x (block_height + scan_height - 1) samples at
 // clamped coordinates: the edge-extended apron -- in its share of the LDS, then its lanes take positions p = i *
@@ -139,27 +142,6 @@ constexpr int kScanThreads = 256;
 constexpr int kScanWaves = kScanThreads / 64;
 constexpr size_t kScanLdsLimit = 65536;
 
-// bytes between the staged block's rows, the staged window's rows, and the window columns staged
-__host__ __device__ __forceinline__ int
-scan_block_pitch (int bw)
-{
-  return (bw + 3) & ~3;
-}
-
-// the window read of a position reaches (block dwords + 1) dwords from the dword its first column lies in
-__host__ __device__ __forceinline__ int
-scan_window_cols (int bw, int sw)
-{
-  return ((sw - 1) & ~3) + scan_block_pitch (bw) + 4;
-}
-
-__host__ __device__ __forceinline__ int
-scan_window_pitch (int bw, int sw)
-{
-  const int cols = scan_window_cols (bw, sw);
-  return (cols >> 2) & 1 ? cols : cols + 4;     // an odd number of dwords
-}
-
 size_t
 scan_lds_bytes (int bw, int bh, int sw, int sh)
 {
@@ -172,19 +154,6 @@ size_t
 scan_lds_limit ()
 {
   return kScanLdsLimit / kScanWaves;
-}
-
-// four samples of row `row` from column x on, coordinates clamped to the w x h picture, as one little-endian dword
-__device__ __forceinline__ uint32_t
-scan_fetch4 (const uint8_t * plane, int stride, int w, int h, int x, int y)
-{
-  const uint8_t *row = plane + (size_t) min (max (y, 0), h - 1) * stride;
-  if (x >= 0 && x + 3 <= w - 1)
-    return gload < u32_u > (row + x);
-  uint32_t v = 0;
-  for (int n = 0; n < 4; n++)
-    v |= (uint32_t) gload < uint8_t > (row + min (max (x + n, 0), w - 1)) << (8 * n);
-  return v;
 }
 
 __global__ __launch_bounds__ (kScanThreads)
@@ -205,53 +174,17 @@ void metric_scan_kernel (const ScanPicture * __restrict__ pics, const ScanJob * 
   uint32_t *block = scan_lds + (size_t) wave * (lds_per_wave >> 2);
   uint32_t *window = block + nd * rows;
 
+  const uint32_t tail = scan_tail_mask (s.bw);
   if (active) {
-    const uint32_t tail = s.bw & 3 ? (1u << (8 * (s.bw & 3))) - 1 : 0xffffffffu;
-    for (int n = lane; n < nd * rows; n += 64) {
-      const int r = n / nd, c = n - r * nd;
-      const uint32_t v = scan_fetch4 (pic.frame, pic.frame_stride, pic.width, pic.height, s.x + 4 * c, s.y + r);
-      block[n] = c == nd - 1 ? v & tail : v;
-    }
-    for (int n = lane; n < wcols * wrows; n += 64) {
-      const int r = n / wcols, c = n - r * wcols;
-      window[r * wd + c] = scan_fetch4 (pic.ref, pic.ref_stride, pic.width, pic.height, s.ref_x + 4 * c, s.ref_y + r);
-    }
+    scan_stage_block (block, pic.frame, pic.frame_stride, pic.width, pic.height, s.x, s.y, nd, rows, tail, lane);
+    scan_stage_window (window, pic.ref, pic.ref_stride, pic.width, pic.height, s.ref_x, s.ref_y, wd, wcols, wrows, lane);
   }
   __syncthreads ();
   if (!active)
     return;
 
-  const uint32_t tail = s.bw & 3 ? (1u << (8 * (s.bw & 3))) - 1 : 0xffffffffu;
-  const int npos = s.sw * s.sh;
-  const int pg = s.gi * s.sh + s.gj;
-  uint32_t best = 0xffffffffu;
   uint32_t *table = pic.metrics ? pic.metrics + (size_t) (sid - pic.scan_base) * (SCHRO_HIP_LIMIT_METRIC_SCAN * SCHRO_HIP_LIMIT_METRIC_SCAN) : nullptr;
-  for (int p = lane; p < npos; p += 64) {
-    const int i = mdiv (p, s.sh, s.m_sh);
-    const int j = p - i * s.sh;
-    const uint32_t *wrow = window + j * wd + (i >> 2);
-    const uint32_t *brow = block;
-    const uint32_t phase = i & 3;
-    uint32_t acc = 0;
-    for (int r = 0; r < rows; r++) {
-      uint32_t lo = wrow[0];
-      for (int c = 0; c < nd; c++) {
-        const uint32_t hi = wrow[c + 1];
-        uint32_t v = __builtin_amdgcn_alignbyte (hi, lo, phase);
-        if (c == nd - 1)
-          v &= tail;
-        acc = __builtin_amdgcn_sad_u8 (v, brow[c], acc);
-        lo = hi;
-      }
-      wrow += wd;
-      brow += nd;
-    }
-    if (table)
-      gstore < uint32_t > (table + p, acc);
-    best = min (best, (acc << 11) | (p == pg ? 0u : (uint32_t) (1 + p)));
-  }
-  for (int off = 32; off; off >>= 1)
-    best = min (best, (uint32_t) __shfl_xor ((int) best, off));
+  const uint32_t best = scan_wave_min (block, window, nd, rows, wd, tail, s.sw * s.sh, s.sh, s.m_sh, s.gi * s.sh + s.gj, table, lane);
   if (lane == 0) {
     const uint32_t order = best & 2047u;
     int dx = s.dx, dy = s.dy;

@@ -1293,4 +1293,60 @@ schro_rough_me_heirarchical_scan_nohint_hip (SchroHipFrame * frame, SchroHipFram
       params, shift, distance, ref, motion_vectors);
 }
 
+// the luma planes of two u8 device frames at one pyramid level, for the rough search
+static int
+rough_level_of (const char *who, int level, SchroHipFrame * frame, SchroHipFrame * ref_frame, SchroHipRoughPlane * out)
+{
+  SCHRO_HIP_REQUIRE (frame && ref_frame && frame_ctx (frame) && frame->domain == ref_frame->domain,
+      "%s: level %d needs two device frames of one domain", who, level);
+  SCHRO_HIP_REQUIRE (!(frame->format & 0x100) && !(ref_frame->format & 0x100) && format_bpp (frame->format) == 1
+      && format_bpp (ref_frame->format) == 1 && !frame->is_upsampled && !ref_frame->is_upsampled, "%s: level %d needs planar u8 frames", who,
+      level);
+  SCHRO_HIP_REQUIRE (frame->width == ref_frame->width && frame->height == ref_frame->height && frame->components[0].width == frame->width
+      && frame->components[0].height == frame->height && ref_frame->components[0].width == frame->width
+      && ref_frame->components[0].height == frame->height, "%s: level %d: the frames differ in size", who, level);
+  out->frame = (const uint8_t *) frame->components[0].data;
+  out->frame_stride = frame->components[0].stride;
+  out->ref = (const uint8_t *) ref_frame->components[0].data;
+  out->ref_stride = ref_frame->components[0].stride;
+  out->width = frame->width;
+  out->height = frame->height;
+  out->extension = frame->extension;
+  return 0;
+}
+
+int
+schro_rough_me_heirarchical_scan_hint_hip (SchroHipFrame * frame, SchroHipFrame * ref_frame, const SchroHipParams * params, int shift,
+    int distance, int ref, const void *hint_motion_vectors, void *motion_vectors)
+{
+  const char *who = "rough_me_heirarchical_scan_hint_hip";
+  SCHRO_HIP_REQUIRE (frame && ref_frame && params && hint_motion_vectors && motion_vectors,
+      "%s: needs two device frames, the parameters and both vector fields", who);
+  SchroHipRoughPlane level;
+  int r = rough_level_of (who, shift, frame, ref_frame, &level);
+  if (r)
+    return r;
+  // (complete on return whatever the stage-completion setting: the vectors are host memory)
+  return rough_me_host_run (frame_ctx (frame), who, &level, 1, shift, params, ref, distance, distance, hint_motion_vectors, &motion_vectors);
+}
+
+int
+schro_rough_me_heirarchical_scan_hip (SchroHipFrame * const *frames, SchroHipFrame * const *ref_frames, const SchroHipParams * params,
+    int n_levels, int ref, void *const *motion_fields)
+{
+  const char *who = "rough_me_heirarchical_scan_hip";
+  SCHRO_HIP_REQUIRE (frames && ref_frames && params && motion_fields, "%s: needs the frames of every level, the parameters and the fields", who);
+  SCHRO_HIP_REQUIRE (n_levels >= 1 && n_levels <= SCHRO_HIP_MAX_HIER_LEVELS, "%s: %d levels, outside 1 .. %d", who, n_levels,
+      SCHRO_HIP_MAX_HIER_LEVELS);
+  SchroHipRoughPlane levels[SCHRO_HIP_MAX_HIER_LEVELS];
+  for (int k = 1; k <= n_levels; k++) {
+    int r = rough_level_of (who, k, frames[k], ref_frames[k], &levels[k - 1]);
+    if (r)
+      return r;
+    SCHRO_HIP_REQUIRE (frames[k]->domain == frames[1]->domain, "%s: level %d is in another domain", who, k);
+  }
+  // schroroughmotion.c:58-60: distance 12 without a hint, 4 with one
+  return rough_me_host_run (frame_ctx (frames[1]), who, levels, n_levels, 1, params, ref, 12, 4, nullptr, motion_fields + 1);
+}
+
 }                               // extern "C"

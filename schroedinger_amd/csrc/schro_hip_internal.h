@@ -165,6 +165,29 @@ struct ScanJob {
 };
 static_assert (sizeof (ScanJob) == 64 && sizeof (ScanPicture) == 64, "scan tables: 64-byte records");
 
+// One (picture, reference) chain of the rough motion search (rough_hint.hip): the levels the launch runs, coarse to fine,
+// each with its planes and its field.  hint NULL: the level scans around the zero vector (the nohint level, every block
+// on its own); else the field of the level above -- the level before it in the chain, or the caller's.
+struct RoughLevel {
+  const uint8_t *frame;
+  const uint8_t *ref;
+  uint8_t *field;               // x_num_blocks * y_num_blocks SchroMotionVector records, written whole
+  const uint8_t *hint;
+  int frame_stride, ref_stride;
+  int w, h;                     // both planes
+  int ext;                      // the apron the frames would have (the kernel clamps coordinates)
+  int shift, dist;
+  int pad;
+};
+struct RoughChain {
+  int nbx, nby, xb, yb;         // x_num_blocks, y_num_blocks, xbsep_luma, ybsep_luma
+  int ref;                      // which of dx[], dy[] the chain fills
+  int nlevels;
+  int pad[2];
+  RoughLevel level[SCHRO_HIP_MAX_HIER_LEVELS];
+};
+static_assert (sizeof (RoughLevel) == 64 && sizeof (RoughChain) == 32 + 64 * SCHRO_HIP_MAX_HIER_LEVELS, "rough search tables");
+
 // r05: the three-level s32 Haar transform of a 4:2:2 picture with the v210 copy-out as its epilogue (iiwt_haar.hip)
 struct HaarPackJob {
   const void *src[3];           // the coefficient planes (Y, U, V), in-place sub-band layout
@@ -678,6 +701,8 @@ int launch_downsample (hipStream_t stream, const DownsampleJob * d_jobs, int njo
 size_t scan_lds_bytes (int bw, int bh, int sw, int sh);
 size_t scan_lds_limit ();
 int launch_metric_scan (hipStream_t stream, const ScanPicture * d_pics, const ScanJob * d_scans, int nscans, size_t lds_per_wave);
+// the rough motion search (rough_hint.hip): one workgroup per chain, of as many waves as lds_per_wave allows
+int launch_rough_hint (hipStream_t stream, const RoughChain * d_chains, int nchains, size_t lds_per_wave);
 int launch_convert (hipStream_t stream, const ConvertJob * d_jobs, int njobs,
     int total_tiles, int bpp);
 void convert_tile_geometry (int *tw, int *th);
@@ -960,6 +985,11 @@ int iwt_batch_run (SchroHipContext * ctx, const SchroHipIwtFwdPlane * planes, in
 int rough_scan_nohint_run (SchroHipContext * ctx, const uint8_t * frame, int frame_stride, const uint8_t * ref, int ref_stride,
     int width, int height, int extension, const SchroHipParams * params, int shift, int distance, int ref_index,
     void *motion_vectors);
+// the frame layer's rough search on host fields (plane_rough.cpp): the fields go through the queue's scratch, the call
+// waits for the queue.  levels[k], fields[k]: level first_shift + k; hint (or NULL): the host field of the level above the
+// last one given -- with it every level is a hint level, without it the last level is the nohint level
+int rough_me_host_run (SchroHipContext * ctx, const char *who, const SchroHipRoughPlane * levels, int nlevels, int first_shift,
+    const SchroHipParams * params, int ref_index, int nohint_distance, int hint_distance, const void *hint, void *const *fields);
 // v216 / ARGB / AY64 (plane_frameops.cpp)
 bool is_wide_format (int format);
 // plane_quant.cpp: schro_hip_quantise_batch; allow_empty: records of no width or height are skipped (the frame layer's
