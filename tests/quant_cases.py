@@ -1,6 +1,7 @@
-"""Shared by tests/test_gpu_quantise.py, tests/test_quantise_api.py and tests/dry_run_quant_cases.py: codeblock layouts as
-records, the planes of the geometry and DC cases, the runner that compares a schro_hip_quantise_batch call with
-tests/quant_ref.py bit for bit, and the refusal cases."""
+"""Shared by tests/test_gpu_quantise.py, tests/test_quantise_api.py, tests/dry_run_quant_cases.py and
+tests/encode_loop_draws.py: codeblock layouts as records, the decoder's tight hand-over of a quant plane (tight_values),
+the planes of the geometry and DC cases, the runner that compares a schro_hip_quantise_batch call with tests/quant_ref.py
+bit for bit, and the refusal cases."""
 import ctypes as C
 
 import numpy as np
@@ -43,6 +44,17 @@ def record_mask(shape, records, itemsize):
     for rec in records:
         m[Q._cells(rec, itemsize, m.size)] = True
     return m.reshape(shape)
+
+
+def tight_values(quant, records, itemsize):
+    """the quant plane's codeblocks as the decoder's hand-over: row-major, tight, `itemsize` bytes each"""
+    flat, blobs, recs, off = quant.reshape(-1), [], [], 0
+    for (o, st, w, h, qi) in records:
+        v = flat[Q._cells((o, st, w, h), quant.dtype.itemsize, flat.size)].astype({2: np.int16, 4: np.int32}[itemsize])
+        blobs.append(v.reshape(-1))
+        recs.append((o, st, w, h, off, itemsize, qi))
+        off += v.size * itemsize
+    return np.concatenate(blobs).view(np.uint8), recs
 
 
 def geometry_specs(dtype, seed):

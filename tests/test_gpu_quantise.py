@@ -41,17 +41,6 @@ def test_intra_ll_recurrence(ctx, dtype):
         assert Q.quantise_dc.truncated > 0
 
 
-def tight_values(quant, records, itemsize):
-    """the quant plane's codeblocks as the decoder's hand-over: row-major, tight, `itemsize` bytes each"""
-    flat, blobs, recs, off = quant.reshape(-1), [], [], 0
-    for (o, st, w, h, qi) in records:
-        v = flat[Q._cells((o, st, w, h), quant.dtype.itemsize, flat.size)].astype({2: np.int16, 4: np.int32}[itemsize])
-        blobs.append(v.reshape(-1))
-        recs.append((o, st, w, h, off, itemsize, qi))
-        off += v.size * itemsize
-    return np.concatenate(blobs).view(np.uint8), recs
-
-
 @pytest.mark.parametrize("dtype", [np.int16, np.int32])
 @pytest.mark.parametrize("intra", [0, 1])
 def test_round_trip_through_the_decoder_path(ctx, dtype, intra):
@@ -66,7 +55,7 @@ def test_round_trip_through_the_decoder_path(ctx, dtype, intra):
     buf = rng.integers(-4095, 4096, (h, pitch)).astype(dtype)
     spec = dict(buf=buf, records=recs, intra=intra, dc=(4, w >> depth, h >> depth) if intra else None)
     (q, r), = QC.run_specs(ctx, [spec])
-    blob, drecs = tight_values(q, recs, b)
+    blob, drecs = QC.tight_values(q, recs, b)
     dst = ctx.plane(h, pitch, dtype, stride=pitch * b).fill(0x33)
     vals = ctx.upload_bytes(blob)
     ctx.dequant_batch([(dst, vals, drecs, intra)], arith=0)
