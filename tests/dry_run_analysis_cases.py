@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+import encoder_front_draws
 import schroedinger_amd as sa
 from schroedinger_amd import _lib, frames
 
@@ -27,44 +28,21 @@ def ctx():
     c.close()
 
 
-def random_scans(rng, w, h, ext, n):
-    scans = np.zeros(n, sa.SCAN_DTYPE)
-    for s in scans:
-        bw, bh = int(rng.integers(-2, 65)), int(rng.integers(-2, 65))
-        x, y = int(rng.integers(0, w)), int(rng.integers(0, h))
-        dist = int(rng.integers(1, 21))
-        rx, ry, sw, sh = sa.metric_scan_setup(x, y, bw, bh, w, h, ext, int(rng.integers(-8, 9)), int(rng.integers(-8, 9)), dist)
-        if sw <= 0 or sh <= 0:
-            rx, ry, sw, sh = -ext, -ext, 1, 1
-            bw, bh = min(bw, 0), min(bh, 0)     # (an empty block fits anywhere)
-        s["x"], s["y"], s["block_width"], s["block_height"] = x, y, bw, bh
-        s["ref_x"], s["ref_y"], s["scan_width"], s["scan_height"] = rx, ry, sw, sh
-        s["gravity_x"], s["gravity_y"] = rx + int(rng.integers(0, sw)) - x, ry + int(rng.integers(0, sh)) - y
-        s["dx"], s["dy"] = int(rng.integers(-99, 100)), int(rng.integers(-99, 100))
-    return scans
-
-
 def test_100_random_batches(ctx):
-    rng = np.random.default_rng(1212)
-    for rnd in range(100):
+    for down, pictures, tables in encoder_front_draws.analysis_batches(100):
         jobs, keep = [], []
-        for n in range(int(rng.integers(1, 7))):
-            big = rng.integers(0, 8) == 0
-            w, h = int(rng.integers(1, 4097 if big else 400)), int(rng.integers(1, 2305 if big else 300))
-            ext = int(rng.choice([0, 0, 1, 8, 32]))
-            src = ctx.plane(h, w, np.uint8, stride=(w, -(-w // 64) * 64, w + 3)[int(rng.integers(0, 3))])
-            dw = (w + 1) // 2 + 2 * ext
-            dst = ctx.plane((h + 1) // 2 + 2 * ext, dw, np.uint8, stride=(dw, -(-dw // 64) * 64, dw + 5)[int(rng.integers(0, 3))])
-            jobs.append((src, dst, ext))
+        for d in down:
+            src = ctx.plane(d["h"], d["w"], np.uint8, stride=d["src_stride"])
+            dst = ctx.plane((d["h"] + 1) // 2 + 2 * d["ext"], (d["w"] + 1) // 2 + 2 * d["ext"], np.uint8, stride=d["dst_stride"])
+            jobs.append((src, dst, d["ext"]))
             keep += [src, dst]
         ctx.downsample_batch(jobs)
         pics = []
-        for n in range(int(rng.integers(1, 4))):
-            w, h, ext = int(rng.integers(1, 300)), int(rng.integers(1, 200)), int(rng.choice([0, 8, 32]))
-            f, r = ctx.plane(h, w, np.uint8), ctx.plane(h, w, np.uint8)
-            pics.append((f, r, ext, random_scans(rng, w, h, ext, int(rng.integers(1, 40)))))
+        for p in pictures:
+            f, r = ctx.plane(p["h"], p["w"], np.uint8), ctx.plane(p["h"], p["w"], np.uint8)
+            pics.append((f, r, p["ext"], p["scans"]))
             keep += [f, r]
-        for res, met in ctx.metric_scan_batch(pics, tables=bool(rnd & 1)):
+        for res, met in ctx.metric_scan_batch(pics, tables=tables):
             keep += [res] + ([met] if met is not None else [])
         ctx.synchronize()
         [p.free() for p in keep]

@@ -11,6 +11,7 @@ import os
 import numpy as np
 import pytest
 
+import encoder_front_draws
 import schroedinger_amd as sa
 from schroedinger_amd import _lib, frames
 
@@ -28,23 +29,12 @@ def ctx():
 
 
 def test_100_random_forward_batches(ctx):
-    rng = np.random.default_rng(1111)
-    for rnd in range(100):
-        depth, filt = int(rng.integers(1, 7)), int(rng.integers(0, 7))
-        dtype = (np.int16, np.int32)[int(rng.integers(0, 2))]
-        unit, bpp = 1 << depth, np.dtype(dtype).itemsize
+    for depth, filt, dtype, planes in encoder_front_draws.forward_batches(100):
         pairs, keep = [], []
-        for n in range(int(rng.integers(1, 7))):
-            big = rng.integers(0, 8) == 0
-            w = unit * int(rng.integers(1, (4096 if big else 700) // unit + 1))
-            h = unit * int(rng.integers(1, (2304 if big else 400) // unit + 1))
-            planes = []
-            for k in range(2):
-                # rows without padding, rounded to 64, or with an odd number of samples of padding
-                stride = (w * bpp, -(-w * bpp // 64) * 64, -(-w * bpp // 64) * 64 + 3 * bpp)[int(rng.integers(0, 3))]
-                planes.append(ctx.plane(h, w, dtype, stride=stride))
-            pairs.append(tuple(planes))
-            keep += planes
+        for w, h, src_stride, dst_stride in planes:
+            pair = (ctx.plane(h, w, dtype, stride=src_stride), ctx.plane(h, w, dtype, stride=dst_stride))
+            pairs.append(pair)
+            keep += pair
         ctx.iwt_batch(pairs, depth, filt)
         ctx.synchronize()
         [p.free() for p in keep]

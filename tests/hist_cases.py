@@ -102,13 +102,47 @@ class FramePicture:
         return n, bins, ovf
 
 
+REFUSAL_PLANE = (16, 32)        # rows x samples of the s16 plane the refusal cases describe
+
+
+def refusal_table(stride):
+    """(good bands, cases) for a plane of REFUSAL_PLANE samples and `stride` bytes a row: name -> (the bad plane's bands and
+    members, the words its message holds).  Read by refusal_cases below and by tests/encoder_walk_cases.py."""
+    good = [(0, stride, 16, 16, 1, 0), (32, stride, 16, 16, 2, 1)]
+
+    def rec(**kw):
+        r = dict(off=0, stride=stride, w=16, h=16, skip=1, dc=0)
+        r.update(kw)
+        return [good[0], (r["off"], r["stride"], r["w"], r["h"], r["skip"], r["dc"])]
+
+    cases = {
+        "bad sample size": (dict(bands=good, bps=3), ("bytes_per_sample",)),
+        "zero width": (dict(bands=rec(w=0)), ("plane 1", "band 1")),
+        "negative height": (dict(bands=rec(h=-4)), ("plane 1", "band 1")),
+        "skip zero": (dict(bands=rec(skip=0)), ("plane 1", "band 1", "skip")),
+        "skip not a power of two": (dict(bands=rec(skip=3)), ("plane 1", "band 1", "skip")),
+        "negative skip": (dict(bands=rec(skip=-2)), ("plane 1", "band 1", "skip")),
+        "stride shorter than a row": (dict(bands=rec(stride=30)), ("plane 1", "band 1", "stride")),
+        "stride not a multiple of the sample": (dict(bands=rec(stride=stride + 1)), ("plane 1", "band 1", "stride")),
+        "band past the plane": (dict(bands=rec(off=stride * 8)), ("plane 1", "band 1", "outside")),
+        "band past the plane's last row by one sample": (dict(bands=rec(off=34)), ("plane 1", "band 1", "outside")),
+        "band starting in front of the plane": (dict(bands=rec(off=-2)), ("plane 1", "band 1", "outside")),
+        "DC band whose row above would lie in front of the plane": (dict(bands=rec(off=-stride, dc=1)), ("plane 1", "band 1", "outside")),
+        "offset not a multiple of the sample": (dict(bands=rec(off=1)), ("plane 1", "band 1", "outside")),
+        "2^32 sampled values": (dict(bands=rec(w=1 << 16, h=1 << 16, stride=1 << 17), bytes=1 << 40), ("plane 1", "band 1", "sampled values")),
+        "no bands": (dict(bands=good, nbands=0), ("plane 1",)),
+        "no counts": (dict(bands=good, counts=None), ("plane 1",)),
+    }
+    return good, cases
+
+
 def refusal_cases(ctx):
     """Every refusal of schro_hip_histogram_batch: SCHRO_HIP_EINVAL, nothing launched, the message naming plane and band.
     The planes are real allocations of the context (a call that wrongly went through would only touch them)."""
     lib = ctx.lib
     # what a call that enqueued its clear or its launch before it had validated everything would touch: the counts (of the
     # good planes in front of the bad one too) hold a sentinel, the coefficients known values, compared after every refusal
-    coeffs = (np.arange(16 * 32, dtype=np.int64).reshape(16, 32) * 37 % 2001 - 1000).astype(np.int16)
+    coeffs = (np.arange(REFUSAL_PLANE[0] * REFUSAL_PLANE[1], dtype=np.int64).reshape(*REFUSAL_PLANE) * 37 % 2001 - 1000).astype(np.int16)
     co = ctx.upload(coeffs)
     cnt = ctx.plane(2, _lib.HISTOGRAM_BINS + 1, np.uint32, stride=C.sizeof(_lib.HistogramCounts)).fill(0xa5)
     sentinel = np.full((2, _lib.HISTOGRAM_BINS + 1), 0xa5a5a5a5, np.uint32)
@@ -117,7 +151,7 @@ def refusal_cases(ctx):
         ctx.synchronize()
         assert np.array_equal(cnt.download(), sentinel), (name, "the counts were written")
         assert np.array_equal(co.download(), coeffs), (name, "the coefficients were written")
-    good = [(0, co.stride, 16, 16, 1, 0), (32, co.stride, 16, 16, 2, 1)]
+    good, cases = refusal_table(co.stride)
 
     def call(bands, bps=2, plane=1, **kw):
         """the bad plane is plane `plane` of the call, behind good ones"""
@@ -136,29 +170,6 @@ def refusal_cases(ctx):
         msg = lib.schro_hip_last_error()
         return rc, (msg.decode() if msg else "")
 
-    def rec(**kw):
-        r = dict(off=0, stride=co.stride, w=16, h=16, skip=1, dc=0)
-        r.update(kw)
-        return [good[0], (r["off"], r["stride"], r["w"], r["h"], r["skip"], r["dc"])]
-
-    cases = {
-        "bad sample size": (dict(bands=good, bps=3), ("bytes_per_sample",)),
-        "zero width": (dict(bands=rec(w=0)), ("plane 1", "band 1")),
-        "negative height": (dict(bands=rec(h=-4)), ("plane 1", "band 1")),
-        "skip zero": (dict(bands=rec(skip=0)), ("plane 1", "band 1", "skip")),
-        "skip not a power of two": (dict(bands=rec(skip=3)), ("plane 1", "band 1", "skip")),
-        "negative skip": (dict(bands=rec(skip=-2)), ("plane 1", "band 1", "skip")),
-        "stride shorter than a row": (dict(bands=rec(stride=30)), ("plane 1", "band 1", "stride")),
-        "stride not a multiple of the sample": (dict(bands=rec(stride=co.stride + 1)), ("plane 1", "band 1", "stride")),
-        "band past the plane": (dict(bands=rec(off=co.stride * 8)), ("plane 1", "band 1", "outside")),
-        "band past the plane's last row by one sample": (dict(bands=rec(off=34)), ("plane 1", "band 1", "outside")),
-        "band starting in front of the plane": (dict(bands=rec(off=-2)), ("plane 1", "band 1", "outside")),
-        "DC band whose row above would lie in front of the plane": (dict(bands=rec(off=-co.stride, dc=1)), ("plane 1", "band 1", "outside")),
-        "offset not a multiple of the sample": (dict(bands=rec(off=1)), ("plane 1", "band 1", "outside")),
-        "2^32 sampled values": (dict(bands=rec(w=1 << 16, h=1 << 16, stride=1 << 17), bytes=1 << 40), ("plane 1", "band 1", "sampled values")),
-        "no bands": (dict(bands=good, nbands=0), ("plane 1",)),
-        "no counts": (dict(bands=good, counts=None), ("plane 1",)),
-    }
     for name, (kw, words) in cases.items():
         rc, msg = call(**kw)
         assert rc == EINVAL, (name, rc, msg)

@@ -84,6 +84,22 @@ CASES = _cases()
 SPILL_BATCH = ("spill_2x2", (("small", 43), ("full", 44), ("zero", 0)))       # geometry, the unlike pictures of one call
 
 
+REFUSED_CASE = "64x32_d3_420"
+
+
+def refused_params(P):
+    """What tests/test_gpu_lowdelay_encode.py::test_refusals changes in the parameters of REFUSED_CASE: (the word the
+    message holds, the parameters).  The last two are what the kernels index with int: the LL bands of a picture (depth 0:
+    the planes themselves) above 2^28 samples, one slice's LL samples above 2^20."""
+    return [("chroma LL", dict(P, iwt_chroma_width=P["iwt_chroma_width"] + 8)),
+            ("slice_bytes_denom", dict(P, slice_bytes_denom=0)),
+            ("slice_bytes_denom", dict(P, slice_bytes_denom=-3)),
+            ("LL bands", dict(P, transform_depth=0, iwt_luma_width=32767, iwt_luma_height=32767, iwt_chroma_width=16384,
+                              iwt_chroma_height=16384)),
+            ("LL rectangles", dict(P, transform_depth=0, iwt_luma_width=8192, iwt_luma_height=8192, iwt_chroma_width=4096,
+                                   iwt_chroma_height=4096, n_horiz_slices=1, n_vert_slices=1))]
+
+
 def per_thread_samples(P):
     """What a thread of the serial launch keeps, in samples: plane_lowdelay_enc.cpp:88-103 (EncChooseLayout) -- per
     component the largest LL rectangle, the row above it from one sample to the left, the column to its left; and the

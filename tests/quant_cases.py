@@ -148,16 +148,53 @@ def run_specs(ctx, specs):
     return out
 
 
+REFUSAL_PLANE = (16, 32)        # rows x samples of the s16 planes the refusal cases describe
+# the subtract call's refusal over the same planes: (dst_stride, width, height), a destination stride shorter than its row
+SUBTRACT_REFUSAL = (20, 16, 16)
+
+
+def refusal_table(stride):
+    """(good records, cases) for planes of REFUSAL_PLANE samples and `stride` bytes a row: name -> (the bad plane's records
+    and members, the words its message holds).  `quant_offset`: the quant plane lies that many bytes behind the coefficients'
+    first.  Read by refusal_cases below and by tests/encoder_walk_cases.py."""
+    good = [[0, stride, 16, 16, 5], [32, stride, 16, 16, 6]]
+
+    def rec(**kw):
+        r = dict(off=0, stride=stride, w=16, h=16, qi=5)
+        r.update(kw)
+        return [good[0], [r["off"], r["stride"], r["w"], r["h"], r["qi"]]]
+
+    cases = {
+        "quant index above 60": (dict(records=rec(qi=61)), ("plane 1", "codeblock 1", "quant_index 61")),
+        "bad sample size": (dict(records=good, bps=3), ("bytes_per_sample",)),
+        "zero width": (dict(records=rec(w=0)), ("plane 1", "codeblock 1")),
+        "negative height": (dict(records=rec(h=-4)), ("plane 1", "codeblock 1")),
+        "stride shorter than a row": (dict(records=rec(stride=30)), ("plane 1", "codeblock 1", "stride")),
+        "stride not a multiple of the sample": (dict(records=rec(stride=stride + 1)), ("plane 1", "codeblock 1", "stride")),
+        "quant overlapping coeffs": (dict(records=good, quant_offset=64), ("plane 1", "overlaps")),
+        "record past the plane": (dict(records=rec(off=stride * 8)), ("plane 1", "codeblock 1", "outside")),
+        "record starting in front of the plane": (dict(records=rec(off=-2)), ("plane 1", "codeblock 1", "outside")),
+        "DC records that do not tile the band": (dict(records=good, dc_predict_first=1, dc_width=32, dc_height=16),
+                                                 ("plane 1", "DC band")),
+        "DC record outside the band": (dict(records=good, dc_predict_first=2, dc_width=16, dc_height=16),
+                                       ("plane 1", "codeblock 1", "DC band")),
+        "no records": (dict(records=good, ncodeblocks=0), ("plane 1",)),
+    }
+    return good, cases
+
+
 def refusal_cases(ctx):
     """Every refusal of schro_hip_quantise_batch: SCHRO_HIP_EINVAL, nothing launched, the message naming plane and record.
     The planes are real allocations of the context (a call that wrongly went through would only touch them)."""
     lib = ctx.lib
-    co, qu = ctx.plane(16, 32, np.int16), ctx.plane(16, 32, np.int16)
+    co, qu = ctx.plane(*REFUSAL_PLANE, np.int16), ctx.plane(*REFUSAL_PLANE, np.int16)
     summ = ctx.plane(4, 2, np.uint32, stride=8)
-    good = [[0, co.stride, 16, 16, 5], [32, co.stride, 16, 16, 6]]
+    good, cases = refusal_table(co.stride)
 
-    def call(records, bps=2, plane=1, **kw):
+    def call(records, bps=2, plane=1, quant_offset=None, **kw):
         """the bad plane is plane `plane` of the call, behind good ones"""
+        if quant_offset is not None:
+            kw["quant"] = co.ptr + quant_offset
         arr = (_lib.QuantPlane * (plane + 1))()
         keep = []
         for k in range(plane + 1):
@@ -173,27 +210,6 @@ def refusal_cases(ctx):
         msg = lib.schro_hip_last_error()
         return rc, (msg.decode() if msg else "")
 
-    def rec(**kw):
-        r = dict(off=0, stride=co.stride, w=16, h=16, qi=5)
-        r.update(kw)
-        return [good[0], [r["off"], r["stride"], r["w"], r["h"], r["qi"]]]
-
-    cases = {
-        "quant index above 60": (dict(records=rec(qi=61)), ("plane 1", "codeblock 1", "quant_index 61")),
-        "bad sample size": (dict(records=good, bps=3), ("bytes_per_sample",)),
-        "zero width": (dict(records=rec(w=0)), ("plane 1", "codeblock 1")),
-        "negative height": (dict(records=rec(h=-4)), ("plane 1", "codeblock 1")),
-        "stride shorter than a row": (dict(records=rec(stride=30)), ("plane 1", "codeblock 1", "stride")),
-        "stride not a multiple of the sample": (dict(records=rec(stride=co.stride + 1)), ("plane 1", "codeblock 1", "stride")),
-        "quant overlapping coeffs": (dict(records=good, quant=co.ptr + 64), ("plane 1", "overlaps")),
-        "record past the plane": (dict(records=rec(off=co.stride * 8)), ("plane 1", "codeblock 1", "outside")),
-        "record starting in front of the plane": (dict(records=rec(off=-2)), ("plane 1", "codeblock 1", "outside")),
-        "DC records that do not tile the band": (dict(records=good, dc_predict_first=1, dc_width=32, dc_height=16),
-                                                 ("plane 1", "DC band")),
-        "DC record outside the band": (dict(records=good, dc_predict_first=2, dc_width=16, dc_height=16),
-                                       ("plane 1", "codeblock 1", "DC band")),
-        "no records": (dict(records=good, ncodeblocks=0), ("plane 1",)),
-    }
     for name, (kw, words) in cases.items():
         rc, msg = call(**kw)
         assert rc == EINVAL, (name, rc, msg)
@@ -203,7 +219,7 @@ def refusal_cases(ctx):
     assert rc == 0, msg
     ctx.synchronize()
     # the subtract call's refusals
-    bad = (_lib.ConvertPlane * 1)(_lib.ConvertPlane(co.ptr, co.stride, qu.ptr, 20, 16, 16))
+    bad = (_lib.ConvertPlane * 1)(_lib.ConvertPlane(co.ptr, co.stride, qu.ptr, *SUBTRACT_REFUSAL))
     assert lib.schro_hip_subtract_batch(ctx.h, bad, 1, 0) == EINVAL and b"subtract_batch: plane 0" in lib.schro_hip_last_error()
     assert lib.schro_hip_subtract_batch(None, bad, 1, 0) == EINVAL
     for p in (co, qu, summ):

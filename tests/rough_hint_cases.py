@@ -102,6 +102,16 @@ CASES = {
 }
 
 
+# What tests/test_gpu_rough_hint.py::test_a_refused_call_writes_nothing spoils in the second of two "one_row" pictures, one
+# at a time: (member of the case, value) -- "stride": the frame's stride relative to a row -- and the two aliasings: the
+# picture's hint field is its own output field; its output field is the first picture's.  tests/encoder_walk_cases.py
+# sends the same calls through the host code under the sanitizers.
+REFUSED_CASE = "one_row"
+REFUSED_MEMBERS = (("dist", 0), ("dist", -4), ("dist", 21), ("shift", 0), ("shift", 8), ("ref_index", 2), ("ref_index", -1),
+                   ("nbx", 0), ("nby", 0), ("xb", 65), ("yb", 0), ("stride", -1))
+REFUSED_ALIASES = ("hint_is_own_field", "field_is_first_field")
+
+
 def params_of(c):
     return dict(x_num_blocks=c["nbx"], y_num_blocks=c["nby"], xbsep_luma=c["xb"], ybsep_luma=c["yb"])
 

@@ -146,7 +146,7 @@ def test_refusals(ctx):
     """s32, the chroma LL mismatch, a wrong buffer size, bad strides, a non-positive denominator, LL bands or LL
     rectangles beyond what the kernels index: SCHRO_HIP_EINVAL with the
     member named, and nothing launched -- the guarded buffers keep their canaries"""
-    P, planes, _ = K.expected("64x32_d3_420")
+    P, planes, _ = K.expected(K.REFUSED_CASE)
     lay = G.Layout()
     comp = [lay.plane(p.shape[0], p.shape[1], np.int16, footprint=None) for p in planes]
     nbytes = P["slice_bytes_num"] * 16 // P["slice_bytes_denom"]
@@ -167,18 +167,15 @@ def test_refusals(ctx):
             assert word in str(e.value), str(e.value)
 
         refused("s32", bpp=4)
-        refused("chroma LL", P=dict(P, iwt_chroma_width=P["iwt_chroma_width"] + 8))
         refused("slices_bytes", slices=Shaped(blk[sl], width=nbytes - 1))
         refused("stride[1]", planes=[good[0], Shaped(good[1], stride=good[1].stride - 2), good[2]])
         refused("stride[0]", planes=[Shaped(good[0], stride=good[0].stride + 1), good[1], good[2]])
         refused("comp[2]", planes=[good[0], good[1], Shaped(good[2], ptr=good[2].ptr + 1)])
-        refused("slice_bytes_denom", P=dict(P, slice_bytes_denom=0))
-        refused("slice_bytes_denom", P=dict(P, slice_bytes_denom=-3))
-        # what the kernels index with int: the LL bands of a picture (depth 0: the planes themselves), one slice's LL samples
-        refused("LL bands", P=dict(P, transform_depth=0, iwt_luma_width=32767, iwt_luma_height=32767, iwt_chroma_width=16384,
-                                   iwt_chroma_height=16384))
-        refused("LL rectangles", P=dict(P, transform_depth=0, iwt_luma_width=8192, iwt_luma_height=8192, iwt_chroma_width=4096,
-                                        iwt_chroma_height=4096, n_horiz_slices=1, n_vert_slices=1))
+        # the parameters: the chroma LL mismatch, the denominators, and what the kernels index with int
+        changed = K.refused_params(P)
+        assert [w for w, _ in changed] == ["chroma LL", "slice_bytes_denom", "slice_bytes_denom", "LL bands", "LL rectangles"]
+        for word, bad in changed:
+            refused(word, P=bad)
         ctx.synchronize()
         blk.check()
     finally:

@@ -178,7 +178,7 @@ def test_frame_layer_hint_level(ctx, name):
 
 def test_a_refused_call_writes_nothing(ctx):
     """Refusals with a context: the second picture of the call is bad; neither field is touched."""
-    good = case_picture("one_row")
+    good = case_picture(K.REFUSED_CASE)
     pics = Pictures(ctx, [good, dict(good)], seed=5)
     try:
         args = pics.args()
@@ -189,11 +189,15 @@ def test_a_refused_call_writes_nothing(ctx):
             a[index] = value
             return [args[0], tuple(a)]
 
-        short = sa.SubPlane(args[1][FRAME], 0, 0, good["h"], good["w"], stride=good["w"] - 1)
-        bad = [second(DIST, 0), second(DIST, -4), second(DIST, 21), second(SHIFT, 0), second(SHIFT, 8), second(REF, 2), second(REF, -1),
-               second(PARAMS, dict(args[1][PARAMS], x_num_blocks=0)), second(PARAMS, dict(args[1][PARAMS], y_num_blocks=0)),
-               second(PARAMS, dict(args[1][PARAMS], xbsep_luma=65)), second(PARAMS, dict(args[1][PARAMS], ybsep_luma=0)),
-               second(FRAME, short)]
+        def spoilt(member, value):
+            if member == "stride":
+                return second(FRAME, sa.SubPlane(args[1][FRAME], 0, 0, good["h"], good["w"], stride=good["w"] + value))
+            if member in ("nbx", "nby", "xb", "yb"):
+                key = {"nbx": "x_num_blocks", "nby": "y_num_blocks", "xb": "xbsep_luma", "yb": "ybsep_luma"}[member]
+                return second(PARAMS, dict(args[1][PARAMS], **{key: value}))
+            return second({"dist": DIST, "shift": SHIFT, "ref_index": REF}[member], value)
+
+        bad = [spoilt(member, value) for member, value in K.REFUSED_MEMBERS]
         for call in bad:
             with pytest.raises(sa.SchroHipError, match="picture 1"):
                 ctx.rough_hint_batch(call)
