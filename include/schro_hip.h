@@ -454,6 +454,87 @@ int schro_hip_rough_me_batch (SchroHipContext * ctx, const SchroHipRoughChain * 
 int schro_hip_rough_hint_check (const SchroHipRoughHintPicture * pictures, int npictures);
 int schro_hip_rough_me_check (const SchroHipRoughChain * chains, int nchains, int nohint_distance, int hint_distance);
 
+/* ---- hierarchical block matching on the device: the DEFAULT encoder's motion search (schrohierbm.c:158-383) ----
+ *
+ * With enable_bigblock_estimation and enable_deep_estimation both on (the defaults, schroencoder.c:4500-4505, resolved
+ * at :638-640) the encoder searches with schro_hbm_scan and schro_hierarchical_bm_scan_hint (hbm, 0, 3), not with the
+ * rough search above.  Fields are laid out as above.  A call writes EVERY record of every field it owns: first as
+ * schro_motion_field_set (mf, split, ref_index + 1) leaves it -- split 0 for shift > 1, 1 for shift 1, 2 for shift 0 --
+ * then the blocks (i, j) at multiples of skip = 1 << shift whose origin (i * xbsep) >> shift, (j * ybsep) >> shift lies
+ * inside the level's luma plane (a block off the plane keeps the first form).  Per block:
+ *   * candidates, in this order: the zero vector; with a hint field, its records at (i & mask) + {0, -1, +1, 0, 0} * 2 *
+ *     skip, (j & mask) + {0, 0, 0, -1, +1} * 2 * skip that lie inside the block grid, mask = ~((1 << (shift + 1)) - 1);
+ *     this level's records to the left, above and above-left -- nine at the most;
+ *   * duplicates: an entry goes when a LATER entry has the same dx[ref_index], dy[ref_index] (unshifted); the last entry
+ *     always stays, the rest keep their order -- the order of last occurrence;
+ *   * choice: per entry dx = CLAMP ((v.dx >> shift) + x0, -width0, width) - x0, dy likewise, and the SAD over the luma
+ *     block AND both chroma blocks (schro_metric_block_sad_slow: chroma at x >> h_shift, (x + dx) >> h_shift, xbsep >>
+ *     h_shift wide, each component clipped to what the frame's plane has left); the strictly smallest wins, the first
+ *     of equals;
+ *   * scan: schro_metric_scan_setup around the winner >> shift (clamped as :357-358) with h_range, over the clipped luma
+ *     block, scanned as schro_hip_metric_scan_batch scans with the start vector as gravity; metric, chroma_metric 0 and
+ *     dx << shift, dy << shift (int16) are stored.  dx, dy of the other reference stay 0.
+ * Samples outside a plane are its edge-extended apron: the kernel clamps coordinates.  `extension` must be at least max
+ * (xbsep_luma, ybsep_luma): then no candidate fails schro_frame_block_is_valid (the reference returns INT_MAX there and
+ * asserts when all do, :347) and every window has a position.  The reference's frames have 32.
+ * NOT covered: use_chroma (enable_chroma_me, default off) -- the scan is luma only; for 4:2:2 and 4:4:4
+ * schro_metric_scan_do_scan reads uninitialised entries of its local table there (schrometric.c:84-111), so there is
+ * nothing to restate and the calls have no such switch.
+ *
+ * One workgroup of up to SCHRO_HIP_ROUGH_WAVES waves runs one (picture, reference) chain, anti-diagonal by
+ * anti-diagonal, level by level; a level without a hint field depends on its neighbours all the same.  No workgroup
+ * waits for another. */
+
+/* The three components of a frame and of its reference frame at one pyramid level. */
+typedef struct {
+  const uint8_t *frame[3];      /* device, pixel (0, 0) of Y, U, V */
+  int frame_stride[3];
+  const uint8_t *ref[3];
+  int ref_stride[3];
+  int width, height;            /* luma, both frames; chroma is ROUND_UP_SHIFT (width, h_shift) x ROUND_UP_SHIFT (height, v_shift) */
+  int h_shift, v_shift;         /* 0, 0 (4:4:4), 1, 0 (4:2:2) or 1, 1 (4:2:0) */
+  int extension;                /* the apron the frames WOULD have, >= max (xbsep_luma, ybsep_luma); the kernel clamps coordinates */
+} SchroHipHbmPlane;
+
+/* schro_hierarchical_bm_scan_hint (hbm, shift, h_range) for one (frame, reference) pair. */
+typedef struct {
+  SchroHipHbmPlane plane;       /* the frames at level `shift` */
+  int x_num_blocks, y_num_blocks, xbsep_luma, ybsep_luma;
+  int shift;                    /* 0 .. 8 */
+  int h_range;                  /* 1 .. 20: a window of 2 * h_range + 1 <= SCHRO_HIP_LIMIT_METRIC_SCAN positions */
+  int ref_index;                /* 0 or 1: which of dx[], dy[] is read from the candidates and written */
+  const void *hint_field;       /* device: the field of level shift + 1 (read), or NULL: no parents (the top level) */
+  void *field;                  /* device: the field of level `shift` (written whole) */
+} SchroHipHbmLevel;
+
+/* One launch, one workgroup per entry; entries of unlike geometry, chroma format, shift and ref mix.  Enqueues, does not
+ * synchronise.  Refused (SCHRO_HIP_EINVAL, nothing launched, the message names the entry and the level): block counts
+ * of 0, an h_range <= 0 or over 20, a block over 64 x 64, ref_index outside 0 / 1, a shift outside 0 .. 8, chroma shifts
+ * other than the three above, a missing component, a stride shorter than a row, an extension under max (xbsep_luma,
+ * ybsep_luma), a field that overlaps another entry's, a plane or a hint field. */
+int schro_hip_hbm_level_batch (SchroHipContext * ctx, const SchroHipHbmLevel * levels, int nlevels);
+
+/* schro_hbm_scan (schrohierbm.c:158-172) for one (frame, reference) pair -- levels n_levels .. 1 with h_range 20, 10, 5,
+ * then MAX (3, .) -- and, with_level0, schro_hierarchical_bm_scan_hint (hbm, 0, 3) of schro_encoder_motion_predict_pel
+ * (schromotionest.c:123-127) behind it, all inside ONE launch: the fields never leave the device. */
+typedef struct {
+  int n_levels;                 /* 1 .. SCHRO_HIP_MAX_HIER_LEVELS */
+  const SchroHipHbmPlane *levels;       /* HOST array of n_levels + 1 entries, copied by the call: levels[k] is level k */
+  int x_num_blocks, y_num_blocks, xbsep_luma, ybsep_luma;
+  int ref_index;                /* 0 or 1 */
+  void *fields[SCHRO_HIP_MAX_HIER_LEVELS + 1];  /* device: fields[k] is the field of level k (written whole) */
+} SchroHipHbmChain;
+
+/* One launch, one workgroup per chain.  Enqueues, does not synchronise.  Without with_level0, levels[0] and fields[0]
+ * are not read.  Refused (SCHRO_HIP_EINVAL, nothing launched, the message names the chain and the level): what
+ * schro_hip_hbm_level_batch refuses, n_levels outside 1 .. 8, a level whose chroma format differs from the chain's
+ * first, a luma plane that is not (w + 1) / 2 x (h + 1) / 2 of the chain's level below it, overlapping fields. */
+int schro_hip_hbm_batch (SchroHipContext * ctx, const SchroHipHbmChain * chains, int nchains, int with_level0);
+/* host only: the refusals of schro_hip_hbm_level_batch / schro_hip_hbm_batch without a context -- 0 or
+ * SCHRO_HIP_EINVAL with the message the batch would give.  No pointer is dereferenced but the HOST arrays. */
+int schro_hip_hbm_level_check (const SchroHipHbmLevel * levels, int nlevels);
+int schro_hip_hbm_check (const SchroHipHbmChain * chains, int nchains, int with_level0);
+
 /* intra pictures: dst_u8 = sat_u8 (src + 128), cropped to width x height;
  * replaces schro_frame_convert (ref_output_frame, frame)
  * (schrodecoder.c:1788-1790) / schro_gpuframe_convert. */
@@ -1331,6 +1412,21 @@ int schro_rough_me_heirarchical_scan_hint_hip (SchroHipFrame * frame, SchroHipFr
  * once, at the end. */
 int schro_rough_me_heirarchical_scan_hip (SchroHipFrame * const *frames, SchroHipFrame * const *ref_frames,
     const SchroHipParams * params, int n_levels, int ref, void *const *motion_fields);
+
+/* schro_hierarchical_bm_scan_hint (schrohierbm.c:174-383) over all three components of two u8 device frames of one
+ * chroma format that are both at pyramid level `shift` (0: the full pictures).  hint_motion_vectors: the HOST field of
+ * level shift + 1 (read), or NULL at the top level; motion_vectors: the HOST field of level `shift` (every record
+ * written).  frame->extension must be at least max (xbsep_luma, ybsep_luma).  The fields cross to the device and back
+ * through the queue's scratch.  Synchronises: the array is complete on return. */
+int schro_hierarchical_bm_scan_hint_hip (SchroHipFrame * frame, SchroHipFrame * ref_frame,
+    const SchroHipParams * params, int shift, int h_range, int ref, const void *hint_motion_vectors, void *motion_vectors);
+/* schro_hbm_scan (schrohierbm.c:158-172) and, with_level0, the level-0 call of schro_encoder_motion_predict_pel
+ * (schromotionest.c:123-127): frames[k], ref_frames[k] are the u8 device frames at pyramid level k, motion_fields[k] the
+ * HOST field of level k, for k = 0 .. n_levels (without with_level0 entry 0 of the three arrays is not read).  One
+ * launch; the fields stay on the device between the levels and are downloaded together.  Synchronises once, at the
+ * end. */
+int schro_hbm_scan_hip (SchroHipFrame * const *frames, SchroHipFrame * const *ref_frames,
+    const SchroHipParams * params, int n_levels, int ref, int with_level0, void *const *motion_fields);
 
 /* schro_frame_inverse_iwt_transform_cuda (schrocuda.h:13-14) replacement, same arguments:
  * upload transform_frame (host) or use it where it is (device), run the multi-level inverse

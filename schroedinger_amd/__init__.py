@@ -95,6 +95,64 @@ def rough_me_check(chains, nohint_distance=12, hint_distance=4):
     check(_lib.load().schro_hip_rough_me_check(arr, len(chains), nohint_distance, hint_distance))
 
 
+def _hbm_plane(frame, ref, ext, h_shift, v_shift):
+    """The SchroHipHbmPlane of (Y, U, V) planes of a frame and of its reference at one level."""
+    assert len(frame) == len(ref) == 3
+    pl = _lib.HbmPlane()
+    for k in range(3):
+        assert (frame[k].height, frame[k].width) == (ref[k].height, ref[k].width)
+        pl.frame[k], pl.frame_stride[k] = frame[k].ptr, frame[k].stride
+        pl.ref[k], pl.ref_stride[k] = ref[k].ptr, ref[k].stride
+    pl.width, pl.height, pl.h_shift, pl.v_shift, pl.extension = frame[0].width, frame[0].height, h_shift, v_shift, ext
+    return pl
+
+
+def hbm_levels(levels):
+    """The SchroHipHbmLevel array of [(frame, ref, extension, h_shift, v_shift, params, shift, h_range, ref_index,
+    hint_field, field)]: frame, ref -- the (Y, U, V) u8 planes at level `shift` (anything with ptr, stride, width, height);
+    params -- a dict (or _lib.Params) with x_num_blocks, y_num_blocks, xbsep_luma, ybsep_luma; hint_field -- the device
+    field of level shift + 1 or None, field -- the device field written (Context.motion_field, or anything with ptr)."""
+    arr = (_lib.HbmLevel * len(levels))()
+    for k, (f, r, ext, hs, vs, params, shift, h_range, ref_index, hint, field) in enumerate(levels):
+        arr[k].plane = _hbm_plane(f, r, ext, hs, vs)
+        arr[k].x_num_blocks, arr[k].y_num_blocks, arr[k].xbsep_luma, arr[k].ybsep_luma = _block_geometry(params)
+        arr[k].shift, arr[k].h_range, arr[k].ref_index = shift, h_range, ref_index
+        arr[k].hint_field, arr[k].field = (hint.ptr if hint is not None else None), field.ptr
+    return arr
+
+
+def hbm_chains(chains):
+    """The SchroHipHbmChain array of [(levels, h_shift, v_shift, params, ref_index, fields)]: levels -- [(frame, ref,
+    extension)] with (Y, U, V) planes for pyramid levels 0 .. n_levels, fields -- the device field of each; entry 0 of
+    both may be None for a call without level 0.  Returns (array, what it points to)."""
+    arr, keep = (_lib.HbmChain * len(chains))(), []
+    for k, (levels, hs, vs, params, ref_index, fields) in enumerate(chains):
+        assert len(levels) == len(fields)
+        n = len(levels) - 1
+        lv = (_lib.HbmPlane * max(n + 1, 1))()
+        for m, t in enumerate(levels):
+            if t is not None:
+                lv[m] = _hbm_plane(t[0], t[1], t[2], hs, vs)
+        keep.append(lv)
+        arr[k].n_levels, arr[k].levels = n, lv
+        arr[k].x_num_blocks, arr[k].y_num_blocks, arr[k].xbsep_luma, arr[k].ybsep_luma = _block_geometry(params)
+        arr[k].ref_index = ref_index
+        for m, fld in enumerate(fields[:MAX_HIER_LEVELS + 1]):
+            arr[k].fields[m] = fld.ptr if fld is not None else None
+    return arr, keep
+
+
+def hbm_level_check(levels):
+    """The refusals of Context.hbm_level_batch on the host, without a context (schro_hip_hbm_level_check)."""
+    check(_lib.load().schro_hip_hbm_level_check(hbm_levels(levels), len(levels)))
+
+
+def hbm_check(chains, with_level0=True):
+    """The refusals of Context.hbm_batch on the host, without a context (schro_hip_hbm_check)."""
+    arr, keep = hbm_chains(chains)
+    check(_lib.load().schro_hip_hbm_check(arr, len(chains), int(bool(with_level0))))
+
+
 QUANTISE_DC_THREADS = 256       # SCHRO_HIP_QUANTISE_DC_THREADS (include/schro_hip.h): the DC recurrence's workgroup size
 
 
@@ -571,6 +629,61 @@ class Context:
         for k in range(1, n + 1):
             pa[k], pb[k], fields[k] = C.pointer(fa[k].c), C.pointer(fb[k].c), out[k].ctypes.data
         check(self.lib.schro_rough_me_heirarchical_scan_hip(pa, pb, C.byref(params), n, ref_index, fields))
+        return out
+
+    def hbm_level_batch(self, levels):
+        """One level of the hierarchical block matching per entry (schro_hierarchical_bm_scan_hint), one launch: levels as
+        hbm_levels takes them.  Every record of each `field` is written; enqueued, not waited for."""
+        check(self.lib.schro_hip_hbm_level_batch(self.h, hbm_levels(levels), len(levels)))
+
+    def hbm_batch(self, chains, with_level0=True):
+        """schro_hbm_scan per chain and, with_level0, the level-0 call behind it, one launch: chains as hbm_chains takes
+        them, the fields staying on the device.  Enqueued, not waited for."""
+        arr, keep = hbm_chains(chains)
+        check(self.lib.schro_hip_hbm_batch(self.h, arr, len(chains), int(bool(with_level0))))
+
+    def _hbm_params(self, params):
+        from . import frames
+        if isinstance(params, _lib.Params):
+            return params
+        return frames.make_params(**dict(zip(("x_num_blocks", "y_num_blocks", "xbsep_luma", "ybsep_luma"), _block_geometry(params))))
+
+    def hbm_scan_hint(self, frame, ref, params, shift, h_range, ref_index, hint_mvs=None, extension=0, h_shift=0, v_shift=0):
+        """schro_hierarchical_bm_scan_hint_hip over the (Y, U, V) u8 DevicePlanes of two frames at pyramid level `shift`,
+        each plane with `extension` samples of apron on every side; hint_mvs: the MV_DTYPE array of level shift + 1 or
+        None.  Returns the MV_DTYPE array of level `shift`, complete."""
+        from . import frames
+        params = self._hbm_params(params)
+        fa = frames.PlaneFrame(self, frame, extension, h_shift, v_shift)
+        fb = frames.PlaneFrame(self, ref, extension, h_shift, v_shift)
+        n = params.x_num_blocks * params.y_num_blocks
+        hint = None
+        if hint_mvs is not None:
+            hint = np.ascontiguousarray(hint_mvs, dtype=MV_DTYPE)
+            assert hint.size == n
+        mvs = np.zeros(n, MV_DTYPE)
+        check(self.lib.schro_hierarchical_bm_scan_hint_hip(fa.ptr(), fb.ptr(), C.byref(params), shift, h_range, ref_index,
+                                                           hint.ctypes.data_as(C.c_void_p) if hint is not None else None,
+                                                           mvs.ctypes.data_as(C.c_void_p)))
+        return mvs
+
+    def hbm_scan(self, frames_by_level, refs_by_level, params, ref_index, with_level0=True, extension=0, h_shift=0, v_shift=0):
+        """schro_hbm_scan_hip: frames_by_level[k], refs_by_level[k] are the (Y, U, V) u8 DevicePlanes at pyramid level k for
+        k = 0 .. n_levels, each with `extension` samples of apron (entry 0 is not read and may be None without
+        with_level0).  Returns the list of MV_DTYPE arrays by level (entry 0: None without with_level0), complete."""
+        from . import frames
+        params = self._hbm_params(params)
+        n = len(frames_by_level) - 1
+        assert len(refs_by_level) == n + 1
+        first = 0 if with_level0 else 1
+        fa = [frames.PlaneFrame(self, p, extension, h_shift, v_shift) if k >= first else None for k, p in enumerate(frames_by_level)]
+        fb = [frames.PlaneFrame(self, p, extension, h_shift, v_shift) if k >= first else None for k, p in enumerate(refs_by_level)]
+        pa, pb = (C.POINTER(_lib.Frame) * (n + 1))(), (C.POINTER(_lib.Frame) * (n + 1))()
+        out = [np.zeros(params.x_num_blocks * params.y_num_blocks, MV_DTYPE) if k >= first else None for k in range(n + 1)]
+        fields = (C.c_void_p * (n + 1))()
+        for k in range(first, n + 1):
+            pa[k], pb[k], fields[k] = C.pointer(fa[k].c), C.pointer(fb[k].c), out[k].ctypes.data
+        check(self.lib.schro_hbm_scan_hip(pa, pb, C.byref(params), n, ref_index, int(bool(with_level0)), fields))
         return out
 
     def pack_u8_batch(self, jobs):

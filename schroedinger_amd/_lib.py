@@ -39,6 +39,8 @@ EXPORTED_SYMBOLS = [
     "schro_rough_me_heirarchical_scan_nohint_hip",
     "schro_hip_rough_hint_batch", "schro_hip_rough_me_batch", "schro_hip_rough_hint_check", "schro_hip_rough_me_check",
     "schro_rough_me_heirarchical_scan_hint_hip", "schro_rough_me_heirarchical_scan_hip",
+    "schro_hip_hbm_level_batch", "schro_hip_hbm_batch", "schro_hip_hbm_level_check", "schro_hip_hbm_check",
+    "schro_hierarchical_bm_scan_hint_hip", "schro_hbm_scan_hip",
     "schro_hip_upsampled_bytes", "schro_hip_upsampled_download", "schro_hip_upsampled_pair_bytes",
     "schro_hip_upsampled_pair_download", "schro_hip_pack_u8_batch",
     "schro_hip_pack_v210_batch", "schro_hip_iiwt_pack_v210_batch", "schro_hip_iiwt_pack_u8_batch", "schro_hip_pack_wide_batch", "schro_hip_shift_right_batch",
@@ -117,6 +119,25 @@ class RoughChain(C.Structure):
     _fields_ = [("n_levels", C.c_int), ("levels", C.POINTER(RoughPlane)),
                 ("x_num_blocks", C.c_int), ("y_num_blocks", C.c_int), ("xbsep_luma", C.c_int), ("ybsep_luma", C.c_int),
                 ("ref_index", C.c_int), ("fields", C.c_void_p * MAX_HIER_LEVELS)]
+
+
+class HbmPlane(C.Structure):
+    """The three components of a frame and its reference at one pyramid level."""
+    _fields_ = [("frame", C.c_void_p * 3), ("frame_stride", C.c_int * 3), ("ref", C.c_void_p * 3), ("ref_stride", C.c_int * 3),
+                ("width", C.c_int), ("height", C.c_int), ("h_shift", C.c_int), ("v_shift", C.c_int), ("extension", C.c_int)]
+
+
+class HbmLevel(C.Structure):
+    _fields_ = [("plane", HbmPlane),
+                ("x_num_blocks", C.c_int), ("y_num_blocks", C.c_int), ("xbsep_luma", C.c_int), ("ybsep_luma", C.c_int),
+                ("shift", C.c_int), ("h_range", C.c_int), ("ref_index", C.c_int),
+                ("hint_field", C.c_void_p), ("field", C.c_void_p)]
+
+
+class HbmChain(C.Structure):
+    _fields_ = [("n_levels", C.c_int), ("levels", C.POINTER(HbmPlane)),
+                ("x_num_blocks", C.c_int), ("y_num_blocks", C.c_int), ("xbsep_luma", C.c_int), ("ybsep_luma", C.c_int),
+                ("ref_index", C.c_int), ("fields", C.c_void_p * (MAX_HIER_LEVELS + 1))]
 
 
 class ConvertPlane(C.Structure):
@@ -488,6 +509,19 @@ def load():
     L.schro_rough_me_heirarchical_scan_hip.argtypes = [C.POINTER(C.POINTER(Frame)), C.POINTER(C.POINTER(Frame)), C.POINTER(Params), i, i,
                                                        C.POINTER(vp)]
     L.schro_rough_me_heirarchical_scan_hip.restype = i
+    L.schro_hip_hbm_level_batch.argtypes = [vp, C.POINTER(HbmLevel), i]
+    L.schro_hip_hbm_level_batch.restype = i
+    L.schro_hip_hbm_batch.argtypes = [vp, C.POINTER(HbmChain), i, i]
+    L.schro_hip_hbm_batch.restype = i
+    L.schro_hip_hbm_level_check.argtypes = [C.POINTER(HbmLevel), i]
+    L.schro_hip_hbm_level_check.restype = i
+    L.schro_hip_hbm_check.argtypes = [C.POINTER(HbmChain), i, i]
+    L.schro_hip_hbm_check.restype = i
+    L.schro_hierarchical_bm_scan_hint_hip.argtypes = [C.POINTER(Frame), C.POINTER(Frame), C.POINTER(Params), i, i, i, vp, vp]
+    L.schro_hierarchical_bm_scan_hint_hip.restype = i
+    L.schro_hbm_scan_hip.argtypes = [C.POINTER(C.POINTER(Frame)), C.POINTER(C.POINTER(Frame)), C.POINTER(Params), i, i, i,
+                                     C.POINTER(C.c_void_p)]
+    L.schro_hbm_scan_hip.restype = i
     L.schro_hip_convert_u8_batch.argtypes = [vp, C.POINTER(ConvertPlane), i, i]
     L.schro_hip_convert_u8_batch.restype = i
     L.schro_hip_upsample_batch.argtypes = [vp, C.POINTER(UpsamplePlane), i]

@@ -1349,4 +1349,66 @@ schro_rough_me_heirarchical_scan_hip (SchroHipFrame * const *frames, SchroHipFra
   return rough_me_host_run (frame_ctx (frames[1]), who, levels, n_levels, 1, params, ref, 12, 4, nullptr, motion_fields + 1);
 }
 
+// the three components of two u8 device frames at one pyramid level, for the block matching
+static int
+hbm_level_of (const char *who, int level, SchroHipFrame * frame, SchroHipFrame * ref_frame, SchroHipHbmPlane * out)
+{
+  SCHRO_HIP_REQUIRE (frame && ref_frame && frame_ctx (frame) && frame->domain == ref_frame->domain,
+      "%s: level %d needs two device frames of one domain", who, level);
+  SCHRO_HIP_REQUIRE (!(frame->format & 0x100) && !(ref_frame->format & 0x100) && format_bpp (frame->format) == 1
+      && frame->format == ref_frame->format && !frame->is_upsampled && !ref_frame->is_upsampled,
+      "%s: level %d needs two planar u8 frames of one chroma format", who, level);
+  const int hs = SCHRO_HIP_FORMAT_H_SHIFT (frame->format), vs = SCHRO_HIP_FORMAT_V_SHIFT (frame->format);
+  for (int k = 0; k < 3; k++) {
+    const SchroHipFrameData & a = frame->components[k], &b = ref_frame->components[k];
+    const int cw = k ? (frame->width + (1 << hs) - 1) >> hs : frame->width, chh = k ? (frame->height + (1 << vs) - 1) >> vs : frame->height;
+    SCHRO_HIP_REQUIRE (frame->width == ref_frame->width && frame->height == ref_frame->height && a.width == cw && a.height == chh
+        && b.width == cw && b.height == chh, "%s: level %d: component %d of the frames is not %dx%d", who, level, k, cw, chh);
+    out->frame[k] = (const uint8_t *) a.data;
+    out->frame_stride[k] = a.stride;
+    out->ref[k] = (const uint8_t *) b.data;
+    out->ref_stride[k] = b.stride;
+  }
+  out->width = frame->width;
+  out->height = frame->height;
+  out->h_shift = hs;
+  out->v_shift = vs;
+  out->extension = std::min (frame->extension, ref_frame->extension);
+  return 0;
+}
+
+int
+schro_hierarchical_bm_scan_hint_hip (SchroHipFrame * frame, SchroHipFrame * ref_frame, const SchroHipParams * params, int shift, int h_range,
+    int ref, const void *hint_motion_vectors, void *motion_vectors)
+{
+  const char *who = "hierarchical_bm_scan_hint_hip";
+  SCHRO_HIP_REQUIRE (frame && ref_frame && params && motion_vectors, "%s: needs two device frames, the parameters and the vector field", who);
+  SCHRO_HIP_REQUIRE (h_range > 0, "%s: level %d: h_range %d", who, shift, h_range);
+  SchroHipHbmPlane level;
+  int r = hbm_level_of (who, shift, frame, ref_frame, &level);
+  if (r)
+    return r;
+  // (complete on return whatever the stage-completion setting: the vectors are host memory)
+  return hbm_host_run (frame_ctx (frame), who, &level, 1, shift, h_range, 0, params, ref, hint_motion_vectors, &motion_vectors);
+}
+
+int
+schro_hbm_scan_hip (SchroHipFrame * const *frames, SchroHipFrame * const *ref_frames, const SchroHipParams * params, int n_levels, int ref,
+    int with_level0, void *const *motion_fields)
+{
+  const char *who = "hbm_scan_hip";
+  SCHRO_HIP_REQUIRE (frames && ref_frames && params && motion_fields, "%s: needs the frames of every level, the parameters and the fields", who);
+  SCHRO_HIP_REQUIRE (n_levels >= 1 && n_levels <= SCHRO_HIP_MAX_HIER_LEVELS, "%s: %d levels, outside 1 .. %d", who, n_levels,
+      SCHRO_HIP_MAX_HIER_LEVELS);
+  SchroHipHbmPlane levels[SCHRO_HIP_MAX_HIER_LEVELS + 1];
+  memset (levels, 0, sizeof (levels));
+  for (int k = n_levels; k >= (with_level0 ? 0 : 1); k--) {
+    int r = hbm_level_of (who, k, frames[k], ref_frames[k], &levels[k]);
+    if (r)
+      return r;
+    SCHRO_HIP_REQUIRE (frames[k]->domain == frames[n_levels]->domain, "%s: level %d is in another domain", who, k);
+  }
+  return hbm_host_run (frame_ctx (frames[n_levels]), who, levels, n_levels, 0, 0, with_level0 ? 1 : 0, params, ref, nullptr, motion_fields);
+}
+
 }                               // extern "C"

@@ -188,6 +188,29 @@ struct RoughChain {
 };
 static_assert (sizeof (RoughLevel) == 64 && sizeof (RoughChain) == 32 + 64 * SCHRO_HIP_MAX_HIER_LEVELS, "rough search tables");
 
+// One (picture, reference) chain of the hierarchical block matching (hier_bm.hip): the levels the launch runs, coarse to
+// fine, each with the three components of its frames and its field.  hint NULL: no parents in the candidate list.
+struct HbmLevel {
+  const uint8_t *frame[3];
+  const uint8_t *ref[3];
+  uint8_t *field;               // x_num_blocks * y_num_blocks SchroMotionVector records, written whole
+  const uint8_t *hint;
+  int frame_stride[3], ref_stride[3];
+  int w, h;                     // luma, both frames
+  int hs, vs;                   // chroma shifts
+  int ext;                      // the apron the frames would have (the kernel clamps coordinates)
+  int shift, range;
+  int pad[3];
+};
+struct HbmChain {
+  int nbx, nby, xb, yb;         // x_num_blocks, y_num_blocks, xbsep_luma, ybsep_luma
+  int ref;                      // which of dx[], dy[] the chain fills
+  int nlevels;
+  int pad[2];
+  HbmLevel level[SCHRO_HIP_MAX_HIER_LEVELS + 1];
+};
+static_assert (sizeof (HbmLevel) == 128 && sizeof (HbmChain) == 32 + 128 * (SCHRO_HIP_MAX_HIER_LEVELS + 1), "block matching tables");
+
 // r05: the three-level s32 Haar transform of a 4:2:2 picture with the v210 copy-out as its epilogue (iiwt_haar.hip)
 struct HaarPackJob {
   const void *src[3];           // the coefficient planes (Y, U, V), in-place sub-band layout
@@ -703,6 +726,8 @@ size_t scan_lds_limit ();
 int launch_metric_scan (hipStream_t stream, const ScanPicture * d_pics, const ScanJob * d_scans, int nscans, size_t lds_per_wave);
 // the rough motion search (rough_hint.hip): one workgroup per chain, of as many waves as lds_per_wave allows
 int launch_rough_hint (hipStream_t stream, const RoughChain * d_chains, int nchains, size_t lds_per_wave);
+// the hierarchical block matching (hier_bm.hip): likewise
+int launch_hier_bm (hipStream_t stream, const HbmChain * d_chains, int nchains, size_t lds_per_wave);
 int launch_convert (hipStream_t stream, const ConvertJob * d_jobs, int njobs,
     int total_tiles, int bpp);
 void convert_tile_geometry (int *tw, int *th);
@@ -990,6 +1015,11 @@ int rough_scan_nohint_run (SchroHipContext * ctx, const uint8_t * frame, int fra
 // last one given -- with it every level is a hint level, without it the last level is the nohint level
 int rough_me_host_run (SchroHipContext * ctx, const char *who, const SchroHipRoughPlane * levels, int nlevels, int first_shift,
     const SchroHipParams * params, int ref_index, int nohint_distance, int hint_distance, const void *hint, void *const *fields);
+// the frame layer's block matching on host fields (plane_hbm.cpp), likewise.  One level (`hint` read, or NULL) when
+// h_range > 0: levels[0], fields[0] are level `shift`.  Else the chain: levels[k], fields[k] are level k, k = 0 ..
+// nlevels, entry 0 only with_level0
+int hbm_host_run (SchroHipContext * ctx, const char *who, const SchroHipHbmPlane * levels, int nlevels, int shift, int h_range,
+    int with_level0, const SchroHipParams * params, int ref_index, const void *hint, void *const *fields);
 // v216 / ARGB / AY64 (plane_frameops.cpp)
 bool is_wide_format (int format);
 // plane_quant.cpp: schro_hip_quantise_batch; allow_empty: records of no width or height are skipped (the frame layer's
