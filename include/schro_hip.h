@@ -535,6 +535,81 @@ int schro_hip_hbm_batch (SchroHipContext * ctx, const SchroHipHbmChain * chains,
 int schro_hip_hbm_level_check (const SchroHipHbmLevel * levels, int nlevels);
 int schro_hip_hbm_check (const SchroHipHbmChain * chains, int nchains, int with_level0);
 
+/* ---- sub-pel motion refinement on the device: schro_encoder_motion_predict_subpel_deep (schromotionest.c:246-354) ----
+ *
+ * The stage behind the level-0 field of the block matching above (schro_encoder_predict_subpel_picture,
+ * schroencoder.c:2294-2322).  One chain is one (picture, reference) pair: the destination field is first a copy of the
+ * source field; then for mvprec = 1 .. mv_precision, for every block (i, j) in raster order
+ *   * a block with i * xbsep_luma >= width or j * ybsep_luma >= height is skipped, its record not even shifted;
+ *   * dx[ref_index], dy[ref_index] are doubled (in int, stored back as int16) and schro_mf_vector_prediction
+ *     (schromotion.c:259-312) is taken from the records to the left, above and above-left, which this pass has already
+ *     doubled and refined;
+ *   * min_score = estimate_sint (dx - pred_x) + estimate_sint (dy - pred_y) + lambda * metric (schropack.c:204-226);
+ *   * the eight neighbours {-1,-1} {0,-1} {1,-1} {-1,0} {1,0} {-1,1} {0,1} {1,1} at x = i * (xbsep << mvprec) + dx + d.dx,
+ *     y likewise, admissible iff -extension < x, (width << mvprec) + extension > x + xbsep - 1 and the same in y (the
+ *     extension is not scaled, the test takes xbsep and not the clipped width): error = the SAD of the luma block clipped
+ *     to MIN (xbsep, width - i * xbsep) x MIN (ybsep, height - j * ybsep) against
+ *     schro_upsampled_frame_get_block_fast_precN (upframe, 0, x, y, mvprec), score = entropy of the moved vector + lambda
+ *     * error; a strictly smaller score wins, the centre and earlier candidates keep ties;
+ *   * a winner's offset is added, metric = its error; nothing else of the record changes.
+ * `entropy + lambda * error` is a rounded product and a rounded sum as the reference's x86-64 build computes it; the
+ * device code does not fuse them.
+ *
+ * The fetch (schroframe.c:2166-2207, 2288-2413, 2459-2482) in terms of half-pel samples S (X, Y) of the tiled image
+ * above: precision 1 reads S (x + 2c, y + 2r); precision 2 is precision 3 at (2x, 2y); precision 3 has hx = x >> 2,
+ * rx = x & 3 (y likewise) and gives ((4-ry)(4-rx) S (hx, hy) + (4-ry)rx S (hx+1, hy) + ry(4-rx) S (hx, hy+1) +
+ * ry rx S (hx+1, hy+1) + 8) >> 4 at (+ 2c, + 2r) -- for (rx, ry) = (0, 0) the sample itself, for (2, 0) and (0, 2) the
+ * reference's avgub, for the rest its orc_combine4_nxm_u8, all the same numbers.  Each tap is a RAW read of the plane
+ * its parity selects; the reference's planes are edge-extended such that a raw read in the aprons is S with X clamped to
+ * [0, 2 * width - 2] and Y to [0, 2 * height - 2] -- what the tiled image holds in its 32 apron columns and what the
+ * kernel's row clamp gives.
+ *
+ * REACH.  Admissible x lie in -extension + 1 .. (width << mvprec) + extension - xbsep.  The rightmost plane column a
+ * row of xbsep samples reads is
+ *   precision 1:  ((2 width + e - b) >> 1) + b - 1            = width + (e + b) / 2 - 1
+ *   precision 2:  ((((4 width + e - b) >> 1) + 1) >> 1) + b - 1 <= width + (e + 3 b + 2) / 4 - 1
+ *   precision 3:  ((((8 width + e - b) >> 2) + 1) >> 1) + b - 1 <= width + (e + 7 b + 4) / 8 - 1
+ * (e = extension, b = xbsep; the + 1 is the right tap), the leftmost (1 - e) >> mvprec >> (mvprec > 1) >= -e / 2.  With
+ * b <= e all three are <= width + e - 1: inside the reference's apron of e columns; with e <= 32 they are <= width + 31:
+ * inside the tiled image's.  Rows likewise.  So the calls refuse an extension under max (xbsep_luma, ybsep_luma) or over
+ * 32.  (The kernel clamps the column to the image's aprons all the same.) */
+typedef struct {
+  const uint8_t *src;           /* device: the luma plane of the source picture, linear u8 */
+  int src_stride;
+  const uint8_t *ref_up;        /* device: the tiled upsampled luma image of the reference (schro_hip_upsampled_bytes), 128-byte aligned */
+  int ref_up_stride;            /* bytes per band of 4 rows, as schro_hip_upsampled_bytes gives it */
+  int width, height;            /* luma, both pictures */
+  int extension;                /* max (xbsep_luma, ybsep_luma) .. 32: the apron the reference's frames WOULD have */
+  int x_num_blocks, y_num_blocks, xbsep_luma, ybsep_luma;
+  int mv_precision;             /* 0 .. 3 */
+  int ref_index;                /* 0 or 1: which of dx[], dy[] is refined */
+  double lambda;                /* >= 0 and finite */
+  const void *src_field;        /* device: the level-0 field (read; may be `field`) */
+  void *field;                  /* device: subpel_mf, x_num_blocks * y_num_blocks records */
+} SchroHipSubpelChain;
+
+/* One precision pass's errors: tables[c] (device, 4-byte aligned) receives 8 * x_num_blocks * y_num_blocks int32, eight
+ * per block in candidate order -- the SAD of an admissible candidate, -1 for an inadmissible one, eight times -1 for a
+ * skipped block; every entry is written.  The centre of a block is its record in chains[c].field doubled as pass mvprec
+ * (1 .. chains[c].mv_precision) doubles it; the field is read, not written, src_field is not read.  One launch over the
+ * blocks of all chains; chains of unlike geometry mix.  Enqueues, does not synchronise. */
+int schro_hip_subpel_error_batch (SchroHipContext * ctx, const SchroHipSubpelChain * chains, int nchains, int mvprec, void *const *tables);
+/* One precision pass's choice from given tables (read): chains[c].field is updated in place, src_field is not read.  One
+ * workgroup per chain walks the anti-diagonals of the block grid; no workgroup waits for another.  Enqueues. */
+int schro_hip_subpel_choose_batch (SchroHipContext * ctx, const SchroHipSubpelChain * chains, int nchains, int mvprec, void *const *tables);
+/* The whole stage on the context's queue: the copy of src_field to field (where they differ), then max (mv_precision)
+ * x (error, choose) with tables from the context's scratch; a chain sits out the passes beyond its own mv_precision,
+ * mv_precision 0 is the copy alone.  Enqueues, does not synchronise.
+ * All three refuse (SCHRO_HIP_EINVAL, nothing enqueued, the message names the chain): mv_precision outside 0 .. 3 (and a
+ * pass outside 1 .. mv_precision), blocks over 32, block counts of 0, an extension outside max (xbsep_luma, ybsep_luma) ..
+ * 32, (max (width, height) << mv_precision) + extension > 32767, a stride shorter than a row, an upsampled image that is
+ * not 128-byte aligned or whose stride is not schro_hip_upsampled_bytes's, ref_index outside 0 / 1, a lambda that is
+ * negative or not finite, NULL pointers, a field or table that overlaps anything of another chain or a picture, image
+ * or table of its own (src_field == field is allowed; any other overlap of the two is not). */
+int schro_hip_subpel_batch (SchroHipContext * ctx, const SchroHipSubpelChain * chains, int nchains);
+/* host only: the refusals of schro_hip_subpel_batch without a context.  No pointer is dereferenced but `chains`. */
+int schro_hip_subpel_check (const SchroHipSubpelChain * chains, int nchains);
+
 /* intra pictures: dst_u8 = sat_u8 (src + 128), cropped to width x height;
  * replaces schro_frame_convert (ref_output_frame, frame)
  * (schrodecoder.c:1788-1790) / schro_gpuframe_convert. */
@@ -1351,6 +1426,12 @@ SCHRO_HIP_LAYOUT (SchroHipMemoryDomain, ctx, 32040);
 SCHRO_HIP_LAYOUT (SchroHipMotion, motion_vectors, 16);
 SCHRO_HIP_LAYOUT (SchroHipMotion, params, 24);
 SCHRO_HIP_LAYOUT (SchroHipMotion, ref_weight_precision, 32);
+SCHRO_HIP_SIZE (SchroHipSubpelChain, 88);
+SCHRO_HIP_LAYOUT (SchroHipSubpelChain, ref_up, 16);
+SCHRO_HIP_LAYOUT (SchroHipSubpelChain, width, 28);
+SCHRO_HIP_LAYOUT (SchroHipSubpelChain, mv_precision, 56);
+SCHRO_HIP_LAYOUT (SchroHipSubpelChain, lambda, 64);
+SCHRO_HIP_LAYOUT (SchroHipSubpelChain, field, 80);
 #endif
 
 /* schro_frame_new_and_alloc (schroframe.c:60-191) on the device domain:
@@ -1427,6 +1508,16 @@ int schro_hierarchical_bm_scan_hint_hip (SchroHipFrame * frame, SchroHipFrame * 
  * end. */
 int schro_hbm_scan_hip (SchroHipFrame * const *frames, SchroHipFrame * const *ref_frames,
     const SchroHipParams * params, int n_levels, int ref, int with_level0, void *const *motion_fields);
+
+/* schro_encoder_motion_predict_subpel_deep (schromotionest.c:246-354): src -- the u8 device frame of the picture,
+ * ref_upframes -- params->num_refs (1 or 2) upsampled device frames (schro_upsampled_hipframe_upsample), subpel_fields --
+ * as many HOST fields of params->x_num_blocks * params->y_num_blocks records, each holding the level-0 field of its
+ * reference (schro_encoder_predict_subpel_picture's copy, schroencoder.c:2307-2317) and refined in place to
+ * params->mv_precision; field r refines dx[r], dy[r].  src->extension must lie in max (xbsep_luma, ybsep_luma) .. 32.  The
+ * fields cross to the device and back through the queue's scratch, the references are the chains of one
+ * schro_hip_subpel_batch.  One wait, at the end. */
+int schro_encoder_motion_predict_subpel_deep_hip (SchroHipFrame * src, SchroHipFrame * const *ref_upframes,
+    const SchroHipParams * params, double lambda, void *const *subpel_fields);
 
 /* schro_frame_inverse_iwt_transform_cuda (schrocuda.h:13-14) replacement, same arguments:
  * upload transform_frame (host) or use it where it is (device), run the multi-level inverse

@@ -153,6 +153,36 @@ def hbm_check(chains, with_level0=True):
     check(_lib.load().schro_hip_hbm_check(arr, len(chains), int(bool(with_level0))))
 
 
+def subpel_chains(chains):
+    """The SchroHipSubpelChain array of [(src, ref_up, extension, params, mv_precision, ref_index, lambda, src_field,
+    field)]: src -- the u8 luma plane of the picture (anything with ptr, stride, width, height); ref_up -- the tiled
+    upsampled luma image of the reference (Context.hp_plane, or anything with ptr, stride); params -- a dict (or
+    _lib.Params) with x_num_blocks, y_num_blocks, xbsep_luma, ybsep_luma; src_field, field -- device fields
+    (Context.motion_field, or anything with ptr; they may be one); src_field may be None for the single-pass calls."""
+    arr = (_lib.SubpelChain * len(chains))()
+    for k, (src, up, ext, params, prec, ref_index, lam, src_field, field) in enumerate(chains):
+        a = arr[k]
+        a.src, a.src_stride, a.ref_up, a.ref_up_stride = src.ptr, src.stride, up.ptr, up.stride
+        a.width, a.height, a.extension = src.width, src.height, ext
+        a.x_num_blocks, a.y_num_blocks, a.xbsep_luma, a.ybsep_luma = _block_geometry(params)
+        a.mv_precision, a.ref_index = prec, ref_index
+        setattr(a, "lambda", float(lam))
+        a.src_field, a.field = (src_field.ptr if src_field is not None else None), field.ptr
+    return arr
+
+
+def subpel_check(chains):
+    """The refusals of Context.subpel_batch on the host, without a context (schro_hip_subpel_check)."""
+    check(_lib.load().schro_hip_subpel_check(subpel_chains(chains), len(chains)))
+
+
+def _subpel_tables(tables):
+    arr = (C.c_void_p * len(tables))()
+    for k, t in enumerate(tables):
+        arr[k] = t.ptr
+    return arr
+
+
 QUANTISE_DC_THREADS = 256       # SCHRO_HIP_QUANTISE_DC_THREADS (include/schro_hip.h): the DC recurrence's workgroup size
 
 
@@ -684,6 +714,43 @@ class Context:
         for k in range(first, n + 1):
             pa[k], pb[k], fields[k] = C.pointer(fa[k].c), C.pointer(fb[k].c), out[k].ctypes.data
         check(self.lib.schro_hbm_scan_hip(pa, pb, C.byref(params), n, ref_index, int(bool(with_level0)), fields))
+        return out
+
+    def subpel_error_batch(self, chains, mvprec, tables):
+        """The errors of precision pass `mvprec` of the sub-pel refinement, one launch over the blocks of all chains: chains
+        as subpel_chains takes them; tables[c] -- device memory (anything with ptr) for 8 * x_num_blocks * y_num_blocks
+        int32, written whole; the fields are read.  Enqueued, not waited for."""
+        check(self.lib.schro_hip_subpel_error_batch(self.h, subpel_chains(chains), len(chains), mvprec, _subpel_tables(tables)))
+
+    def subpel_choose_batch(self, chains, mvprec, tables):
+        """The choice of precision pass `mvprec` from the given tables: each chain's `field` is doubled and refined in place,
+        one workgroup per chain.  Enqueued, not waited for."""
+        check(self.lib.schro_hip_subpel_choose_batch(self.h, subpel_chains(chains), len(chains), mvprec, _subpel_tables(tables)))
+
+    def subpel_batch(self, chains):
+        """schro_encoder_motion_predict_subpel_deep per chain: field <- src_field, then mv_precision x (errors, choice) with
+        tables from the context's scratch.  Enqueued, not waited for."""
+        check(self.lib.schro_hip_subpel_batch(self.h, subpel_chains(chains), len(chains)))
+
+    def subpel_deep(self, src, ref_upframes, params, lam, fields, extension=32):
+        """schro_encoder_motion_predict_subpel_deep_hip: src -- the u8 luma DevicePlane of the picture with `extension`
+        samples of apron on every side; ref_upframes -- one upsampled frames.DeviceFrame per reference; params -- a dict
+        (or _lib.Params) with the block geometry and mv_precision; fields -- the MV_DTYPE level-0 field of each reference.
+        Returns the refined MV_DTYPE arrays, complete."""
+        from . import frames
+        if not isinstance(params, _lib.Params):
+            params = frames.make_params(mv_precision=params["mv_precision"],
+                                        **dict(zip(("x_num_blocks", "y_num_blocks", "xbsep_luma", "ybsep_luma"), _block_geometry(params))))
+        n = len(ref_upframes)
+        assert len(fields) == n
+        params.num_refs = n
+        fa = frames.PlaneFrame(self, [src] * 3, extension)
+        out = [np.ascontiguousarray(f, dtype=MV_DTYPE).copy() for f in fields]
+        ups, ptrs = (C.POINTER(_lib.Frame) * n)(), (C.c_void_p * n)()
+        for k in range(n):
+            assert out[k].size == params.x_num_blocks * params.y_num_blocks
+            ups[k], ptrs[k] = ref_upframes[k].ptr(), out[k].ctypes.data
+        check(self.lib.schro_encoder_motion_predict_subpel_deep_hip(fa.ptr(), ups, C.byref(params), float(lam), ptrs))
         return out
 
     def pack_u8_batch(self, jobs):

@@ -41,6 +41,8 @@ EXPORTED_SYMBOLS = [
     "schro_rough_me_heirarchical_scan_hint_hip", "schro_rough_me_heirarchical_scan_hip",
     "schro_hip_hbm_level_batch", "schro_hip_hbm_batch", "schro_hip_hbm_level_check", "schro_hip_hbm_check",
     "schro_hierarchical_bm_scan_hint_hip", "schro_hbm_scan_hip",
+    "schro_hip_subpel_error_batch", "schro_hip_subpel_choose_batch", "schro_hip_subpel_batch", "schro_hip_subpel_check",
+    "schro_encoder_motion_predict_subpel_deep_hip",
     "schro_hip_upsampled_bytes", "schro_hip_upsampled_download", "schro_hip_upsampled_pair_bytes",
     "schro_hip_upsampled_pair_download", "schro_hip_pack_u8_batch",
     "schro_hip_pack_v210_batch", "schro_hip_iiwt_pack_v210_batch", "schro_hip_iiwt_pack_u8_batch", "schro_hip_pack_wide_batch", "schro_hip_shift_right_batch",
@@ -138,6 +140,15 @@ class HbmChain(C.Structure):
     _fields_ = [("n_levels", C.c_int), ("levels", C.POINTER(HbmPlane)),
                 ("x_num_blocks", C.c_int), ("y_num_blocks", C.c_int), ("xbsep_luma", C.c_int), ("ybsep_luma", C.c_int),
                 ("ref_index", C.c_int), ("fields", C.c_void_p * (MAX_HIER_LEVELS + 1))]
+
+
+class SubpelChain(C.Structure):
+    """One (picture, reference) pair of the sub-pel refinement."""
+    _fields_ = [("src", C.c_void_p), ("src_stride", C.c_int), ("ref_up", C.c_void_p), ("ref_up_stride", C.c_int),
+                ("width", C.c_int), ("height", C.c_int), ("extension", C.c_int),
+                ("x_num_blocks", C.c_int), ("y_num_blocks", C.c_int), ("xbsep_luma", C.c_int), ("ybsep_luma", C.c_int),
+                ("mv_precision", C.c_int), ("ref_index", C.c_int), ("lambda", C.c_double),
+                ("src_field", C.c_void_p), ("field", C.c_void_p)]
 
 
 class ConvertPlane(C.Structure):
@@ -522,6 +533,17 @@ def load():
     L.schro_hbm_scan_hip.argtypes = [C.POINTER(C.POINTER(Frame)), C.POINTER(C.POINTER(Frame)), C.POINTER(Params), i, i, i,
                                      C.POINTER(C.c_void_p)]
     L.schro_hbm_scan_hip.restype = i
+    L.schro_hip_subpel_error_batch.argtypes = [vp, C.POINTER(SubpelChain), i, i, C.POINTER(C.c_void_p)]
+    L.schro_hip_subpel_error_batch.restype = i
+    L.schro_hip_subpel_choose_batch.argtypes = [vp, C.POINTER(SubpelChain), i, i, C.POINTER(C.c_void_p)]
+    L.schro_hip_subpel_choose_batch.restype = i
+    L.schro_hip_subpel_batch.argtypes = [vp, C.POINTER(SubpelChain), i]
+    L.schro_hip_subpel_batch.restype = i
+    L.schro_hip_subpel_check.argtypes = [C.POINTER(SubpelChain), i]
+    L.schro_hip_subpel_check.restype = i
+    L.schro_encoder_motion_predict_subpel_deep_hip.argtypes = [C.POINTER(Frame), C.POINTER(C.POINTER(Frame)), C.POINTER(Params), C.c_double,
+                                                               C.POINTER(C.c_void_p)]
+    L.schro_encoder_motion_predict_subpel_deep_hip.restype = i
     L.schro_hip_convert_u8_batch.argtypes = [vp, C.POINTER(ConvertPlane), i, i]
     L.schro_hip_convert_u8_batch.restype = i
     L.schro_hip_upsample_batch.argtypes = [vp, C.POINTER(UpsamplePlane), i]

@@ -1411,4 +1411,44 @@ schro_hbm_scan_hip (SchroHipFrame * const *frames, SchroHipFrame * const *ref_fr
   return hbm_host_run (frame_ctx (frames[n_levels]), who, levels, n_levels, 0, 0, with_level0 ? 1 : 0, params, ref, nullptr, motion_fields);
 }
 
+int
+schro_encoder_motion_predict_subpel_deep_hip (SchroHipFrame * src, SchroHipFrame * const *ref_upframes, const SchroHipParams * params,
+    double lambda, void *const *subpel_fields)
+{
+  const char *who = "encoder_motion_predict_subpel_deep_hip";
+  SCHRO_HIP_REQUIRE (src && ref_upframes && params && subpel_fields, "%s: needs the picture, the upsampled references, the parameters and the fields",
+      who);
+  SCHRO_HIP_REQUIRE (params->num_refs == 1 || params->num_refs == 2, "%s: %d references", who, params->num_refs);
+  SCHRO_HIP_REQUIRE (frame_ctx (src) && !(src->format & 0x100) && format_bpp (src->format) == 1 && !src->is_upsampled
+      && src->components[0].width == src->width && src->components[0].height == src->height, "%s: the picture must be a planar u8 device frame",
+      who);
+  SchroHipSubpelChain chains[2];
+  memset (chains, 0, sizeof (chains));
+  for (int r = 0; r < params->num_refs; r++) {
+    const SchroHipFrame *up = ref_upframes[r];
+    SCHRO_HIP_REQUIRE (up && up->is_upsampled && up->domain == src->domain && up->width == src->width && up->height == src->height
+        && up->components[0].width == src->width && up->components[0].height == src->height,
+        "%s: reference %d must be an upsampled device frame of the picture's size and domain", who, r);
+    SCHRO_HIP_REQUIRE (subpel_fields[r], "%s: reference %d has no motion field", who, r);
+    SchroHipSubpelChain & c = chains[r];
+    c.src = (const uint8_t *) src->components[0].data;
+    c.src_stride = src->components[0].stride;
+    c.ref_up = (const uint8_t *) up->components[0].data;
+    c.ref_up_stride = up->components[0].stride;
+    c.width = src->width;
+    c.height = src->height;
+    c.extension = src->extension;
+    c.x_num_blocks = params->x_num_blocks;
+    c.y_num_blocks = params->y_num_blocks;
+    c.xbsep_luma = params->xbsep_luma;
+    c.ybsep_luma = params->ybsep_luma;
+    c.mv_precision = params->mv_precision;
+    c.ref_index = r;
+    c.lambda = lambda;
+    c.src_field = subpel_fields[r];     // (the HOST field: subpel_host_run puts both fields into the queue's scratch)
+  }
+  // (complete on return whatever the stage-completion setting: the fields are host memory)
+  return subpel_host_run (frame_ctx (src), chains, params->num_refs);
+}
+
 }                               // extern "C"

@@ -211,6 +211,22 @@ struct HbmChain {
 };
 static_assert (sizeof (HbmLevel) == 128 && sizeof (HbmChain) == 32 + 128 * (SCHRO_HIP_MAX_HIER_LEVELS + 1), "block matching tables");
 
+// One (picture, reference) chain of the sub-pel refinement (subpel.hip), as one precision pass sees it.
+struct SubpelChain {
+  const uint8_t *src;           // the source picture's luma, linear
+  const uint8_t *up;            // the reference's tiled upsampled luma
+  uint8_t *field;               // the records the pass doubles and refines
+  int32_t *table;               // eight errors per block, candidate order
+  double lambda;
+  int src_stride, up_stride;
+  int w, h, ext;
+  int nbx, nby, xb, yb;
+  int ref;
+  int tile_base;                // the chain's first workgroup of the error launch
+  int pad;
+};
+static_assert (sizeof (SubpelChain) == 88, "sub-pel tables");
+
 // r05: the three-level s32 Haar transform of a 4:2:2 picture with the v210 copy-out as its epilogue (iiwt_haar.hip)
 struct HaarPackJob {
   const void *src[3];           // the coefficient planes (Y, U, V), in-place sub-band layout
@@ -728,6 +744,11 @@ int launch_metric_scan (hipStream_t stream, const ScanPicture * d_pics, const Sc
 int launch_rough_hint (hipStream_t stream, const RoughChain * d_chains, int nchains, size_t lds_per_wave);
 // the hierarchical block matching (hier_bm.hip): likewise
 int launch_hier_bm (hipStream_t stream, const HbmChain * d_chains, int nchains, size_t lds_per_wave);
+// the sub-pel refinement (subpel.hip): the errors of pass mvprec over the blocks of all chains, subpel_error_blocks ()
+// blocks per workgroup; and the choice, one workgroup per chain
+int subpel_error_blocks ();
+int launch_subpel_error (hipStream_t stream, const SubpelChain * d_chains, int nchains, int total_groups, int mvprec);
+int launch_subpel_choose (hipStream_t stream, const SubpelChain * d_chains, int nchains, int mvprec);
 int launch_convert (hipStream_t stream, const ConvertJob * d_jobs, int njobs,
     int total_tiles, int bpp);
 void convert_tile_geometry (int *tw, int *th);
@@ -1020,6 +1041,9 @@ int rough_me_host_run (SchroHipContext * ctx, const char *who, const SchroHipRou
 // nlevels, entry 0 only with_level0
 int hbm_host_run (SchroHipContext * ctx, const char *who, const SchroHipHbmPlane * levels, int nlevels, int shift, int h_range,
     int with_level0, const SchroHipParams * params, int ref_index, const void *hint, void *const *fields);
+// the frame layer's sub-pel refinement on host fields (plane_subpel.cpp): chains[c].src_field is the HOST field refined in
+// place, chains[c].field is not read -- both become scratch of the queue; waits for the queue
+int subpel_host_run (SchroHipContext * ctx, SchroHipSubpelChain * chains, int nchains);
 // v216 / ARGB / AY64 (plane_frameops.cpp)
 bool is_wide_format (int format);
 // plane_quant.cpp: schro_hip_quantise_batch; allow_empty: records of no width or height are skipped (the frame layer's
