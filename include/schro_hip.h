@@ -610,6 +610,112 @@ int schro_hip_subpel_batch (SchroHipContext * ctx, const SchroHipSubpelChain * c
 /* host only: the refusals of schro_hip_subpel_batch without a context.  No pointer is dereferenced but `chains`. */
 int schro_hip_subpel_check (const SchroHipSubpelChain * chains, int nchains);
 
+/* ---- mode decision on the device, the split-2 level: schro_do_split2 (schromotionest.c:1600-1807) --------------------
+ *
+ * The stage behind the sub-pel refinement above.  One PICTURE is a source frame with one or two references and one
+ * sub-pel field per reference (field r: dx[r], dy[r] and metric are read; schro_hip_subpel_batch's output as it stands).
+ * The result is SchroMotion.motion_vectors as schro_mode_decision's loop (:2616-2670) leaves it when, for every
+ * superblock in raster order, it ran schro_do_split2 and then schro_motion_copy_to and nothing else: every superblock
+ * split 2, every block reference 1, reference 2, both, or DC -- a field schro_hip_obmc_batch renders -- and per superblock
+ * block.error, block.entropy and block.score, what a split-1 / split-0 level compares against.
+ *
+ * Per block (x, y), components k = 0, 1, 2 with blocks of xbsep >> shift x ybsep >> shift:
+ *   0. x * xbsep_luma >= width or y * ybsep_luma >= height: the final record is best_mv = { split 2, pred_mode 1, else 0 },
+ *      total_entropy += 2.  (While its superblock is worked on the reference keeps another record there, with the
+ *      predicted mode and vector.  Only records of other blocks outside the picture are derived from it -- x * xbsep <
+ *      width implies (x - 1) * xbsep < width, so no block inside has a neighbour outside -- and schro_motion_copy_to
+ *      overwrites them all: it is not computed here.)
+ *   1. per reference r: mv = field r's record with split 2, pred_mode r + 1, using_global 0 (the other bits of the flags
+ *      word stay); entropy[r] = estimate_sint (dx[r] - pred_x) + estimate_sint (dy[r] - pred_y) with
+ *      schro_motion_vector_prediction (schromotion.c:315-368) over the records to the left, above and above-left AS
+ *      DECIDED, which skips a neighbour whose pred_mode lacks bit r (DC, and the other reference alone);
+ *      schro_get_split2_metric: mv.metric == INT_MAX gives error = INT_MAX and leaves chroma_metric as copied, else
+ *      chroma_metric = the SAD of the U and V blocks at (x * cb << p) + (dx[r] >> h_shift), y likewise, and error =
+ *      chroma_metric + metric; score = entropy[r] + error * lambda; a strictly smaller score wins and sets best_error =
+ *      metric -- LUMA ALONE.
+ *   2. two references: mv (reference 2's trial) takes dx[0], dy[0] of field 0 and dx[1], dy[1] of field 1, pred_mode 3.
+ *      Admissible iff for both references -extension <= X, -extension <= Y, (width << p) + extension > X + bw - 1 and the
+ *      same in y, X = x * (xbsep << p) + dx[r], bw x bh the block CLIPPED to the picture, luma only.  Then metric =
+ *      schro_metric_get_biref (weights 1, 1, shift 1: |orig - ((a + b + 1) >> 1)|) over luma, chroma_metric the same over U
+ *      and V, score = entropy[0] + entropy[1] + (metric + chroma_metric) * lambda; a strictly smaller score wins and sets
+ *      best_error = metric + chroma_metric.  Inadmissible: mv keeps reference 2's metric and chroma_metric.
+ *      AT mv_precision 2 AND 3 the reference fetches the three components of a reference into ONE buffer (fd[ref],
+ *      :2600-2609, filled at :1698-1737) and measures afterwards: luma is measured against V's prediction in its top-left
+ *      bw[2] x bh[2] samples and U against V's prediction.  That is restated; precision 0 and 1 point into the frames.
+ *   3. DC, considered iff 4 * (bw[0] * bh[0] + 2 * bw[1] * bh[1]) < best_error -- the sizes are set in step 2 only: with one
+ *      reference they are 0 and the test is 0 < best_error.  The record is built IN PLACE over mv: pred_mode 0, dc[k] =
+ *      schro_block_average's rounded mean - 128 over the first six bytes of the union (bytes 6-7, dy[1], stay), metric =
+ *      the summed error, chroma_metric stays.  It wins iff error < best_error; its entropy is the estimate_sint of the
+ *      three values, no predictor.
+ *   4. total_error += best_error, total_entropy += best_entropy; per superblock error, entropy (int32, wrapping) and
+ *      score = total_entropy + lambda * total_error.
+ * Every product with lambda is a rounded product followed by a rounded sum, as in the sub-pel stage.
+ * A block reads only the records to its left, above and above-left: any order that has those three first gives the
+ * reference's result; the device walks anti-diagonals.
+ *
+ * The TABLE ENTRY of a block, SCHRO_HIP_SPLIT2_TABLE_INTS int32, what reads the pictures (schro_hip_split2_metric_batch):
+ *   [0], [1]  chroma_metric of step 1 for reference 0, 1; -1 for a block outside the picture and for a reference the
+ *             picture does not have.  (Computed whatever mv.metric is.)
+ *   [2]       step 2 admissible (0 / 1); [3] its metric, [4] its chroma_metric (0 where inadmissible)
+ *   [5 .. 7]  dc[0 .. 2]; [8] the summed DC error, -1 for SCHRO_METRIC_INVALID_2 (a block outside the picture)
+ *   [9]       bw[0] * bh[0] + 2 * bw[1] * bh[1] of step 3 -- 0 with one reference
+ *   [10 .. 15] 0
+ *
+ * REACH.  The luma metric of step 1 is the field's: nothing tests there whether a vector is admissible, and the chroma
+ * reads go where the vector says.  With e = extension, b = xbsep_luma, p = mv_precision, a field that keeps every block
+ * inside the picture plus e samples, -(e << p) <= X <= (width + e - b) << p -- what the block matching's level 0 gives
+ * and the sub-pel passes (REACH above) keep -- has, for a component of shift s (xbsep a multiple of 1 << s, so x * (b >> s)
+ * << p is X's origin >> s), the chroma position floor (X / 2^s): its leftmost sample column is >= -(e >> s), its
+ * rightmost floor ((width + e - b) / 2^s) + (b >> s) - 1 (+ 1, the right tap, only when the position has a fraction, and
+ * then the floor is one less) <= chroma width + e / 2^s - 1.  Both lie inside the reference's apron of e columns, and with
+ * e <= 32 inside the tiled image's.  Rows likewise.  The bi-reference trial tests its luma reads itself.  So the calls
+ * refuse an extension under max (xbsep_luma, ybsep_luma) or over 32 and a block separation that is no multiple of the
+ * chroma subsampling; the kernel clamps rows and columns to the image all the same -- a field that breaks the rule reads
+ * what the clamp gives, where the reference reads outside its frame.
+ *
+ * OUT OF SCOPE: split 1 and split 0 (schro_do_split1, schro_do_split0), schro_do_split0_biref_zero, the statistics of
+ * :2655-2681 (mc_error, badblock_ratio, dcblock_ratio), global motion, and a plain-plane reference for mv_precision 0:
+ * the tiled image serves all four precisions, precision 0 reads S (2x, 2y). */
+#define SCHRO_HIP_SPLIT2_TABLE_INTS 16
+typedef struct {
+  const uint8_t *src[3];        /* device: Y, U, V of the source picture, linear u8 */
+  int src_stride[3];
+  int num_refs;                 /* 1 or 2 */
+  const uint8_t *ref_up[2][3];  /* device: per reference the tiled upsampled images of Y, U, V, 128-byte aligned */
+  int ref_up_stride[3];         /* bytes per band of 4 rows, as schro_hip_upsampled_bytes gives it for the component */
+  int width, height;            /* luma; a chroma component has (width + (1 << h_shift) - 1) >> h_shift columns, rows likewise */
+  int h_shift, v_shift;         /* 0,0 / 1,0 / 1,1 */
+  int extension;                /* max (xbsep_luma, ybsep_luma) .. 32 */
+  int x_num_blocks, y_num_blocks;       /* multiples of 4 */
+  int xbsep_luma, ybsep_luma;   /* multiples of 1 << h_shift, 1 << v_shift; at most 32 */
+  int mv_precision;             /* 0 .. 3 */
+  int chroma_pairs;             /* nonzero: ref_up[r][1] is the (U, V) pair image of an upsampled frame
+                                 * (schro_hip_upsampled_pair_bytes, ref_up_stride[1] its stride), ref_up[r][2] is not read */
+  double lambda;                /* >= 0 and finite */
+  const void *fields[2];        /* device: the sub-pel field of each reference (read) */
+  void *motion;                 /* device: x_num_blocks * y_num_blocks records of 20 bytes (written whole) */
+  void *superblocks;            /* device: per superblock, raster order, int32 error, int32 entropy, double score (written whole) */
+} SchroHipSplit2Picture;
+
+/* What reads the pictures: tables[c] (device, 4-byte aligned) receives SCHRO_HIP_SPLIT2_TABLE_INTS int32 per block of
+ * picture c; every entry is written.  motion and superblocks are not touched (but checked).  One launch over the
+ * blocks of all pictures; pictures of unlike geometry, chroma format and num_refs mix.  Enqueues, does not synchronise. */
+int schro_hip_split2_metric_batch (SchroHipContext * ctx, const SchroHipSplit2Picture * pictures, int n, void *const *tables);
+/* The choice from given tables and the fields (read): motion and superblocks are written.  No picture or image is read
+ * (but checked).  One workgroup per picture walks the anti-diagonals of the block grid; no workgroup waits
+ * for another.  Enqueues. */
+int schro_hip_split2_choose_batch (SchroHipContext * ctx, const SchroHipSplit2Picture * pictures, int n, void *const *tables);
+/* The whole stage on the context's queue: both launches, tables from the context's scratch.  Behind
+ * schro_hip_subpel_batch on the same queue it takes that call's fields without a download; schro_hip_obmc_batch behind it
+ * takes `motion`.  Enqueues, does not synchronise.
+ * All three refuse (SCHRO_HIP_EINVAL, nothing enqueued, the message names the picture): what the sub-pel calls refuse;
+ * num_refs outside 1 / 2; chroma shifts other than 0,0 / 1,0 / 1,1; a block separation that is no multiple of the
+ * subsampling; a missing component, image, field or output; block counts that are no multiples of 4; a motion field,
+ * table or superblock table that overlaps anything else of the call. */
+int schro_hip_split2_batch (SchroHipContext * ctx, const SchroHipSplit2Picture * pictures, int n);
+/* host only: the refusals of schro_hip_split2_batch without a context.  No pointer is dereferenced but `pictures`. */
+int schro_hip_split2_check (const SchroHipSplit2Picture * pictures, int n);
+
 /* intra pictures: dst_u8 = sat_u8 (src + 128), cropped to width x height;
  * replaces schro_frame_convert (ref_output_frame, frame)
  * (schrodecoder.c:1788-1790) / schro_gpuframe_convert. */
@@ -1432,6 +1538,13 @@ SCHRO_HIP_LAYOUT (SchroHipSubpelChain, width, 28);
 SCHRO_HIP_LAYOUT (SchroHipSubpelChain, mv_precision, 56);
 SCHRO_HIP_LAYOUT (SchroHipSubpelChain, lambda, 64);
 SCHRO_HIP_LAYOUT (SchroHipSubpelChain, field, 80);
+SCHRO_HIP_SIZE (SchroHipSplit2Picture, 184);
+SCHRO_HIP_LAYOUT (SchroHipSplit2Picture, num_refs, 36);
+SCHRO_HIP_LAYOUT (SchroHipSplit2Picture, ref_up, 40);
+SCHRO_HIP_LAYOUT (SchroHipSplit2Picture, width, 100);
+SCHRO_HIP_LAYOUT (SchroHipSplit2Picture, mv_precision, 136);
+SCHRO_HIP_LAYOUT (SchroHipSplit2Picture, lambda, 144);
+SCHRO_HIP_LAYOUT (SchroHipSplit2Picture, motion, 168);
 #endif
 
 /* schro_frame_new_and_alloc (schroframe.c:60-191) on the device domain:
@@ -1518,6 +1631,13 @@ int schro_hbm_scan_hip (SchroHipFrame * const *frames, SchroHipFrame * const *re
  * schro_hip_subpel_batch.  One wait, at the end. */
 int schro_encoder_motion_predict_subpel_deep_hip (SchroHipFrame * src, SchroHipFrame * const *ref_upframes,
     const SchroHipParams * params, double lambda, void *const *subpel_fields);
+/* The split-2 level of schro_mode_decision (schromotionest.c:2587-2688; schro_hip_split2_batch above): src -- the u8
+ * device frame of the picture, ref_upframes -- params->num_refs (1 or 2) upsampled device frames of its format,
+ * subpel_fields -- per reference the HOST sub-pel field (read), motion -- HOST memory for x_num_blocks * y_num_blocks
+ * records, superblocks -- HOST memory for 16 bytes per superblock.  The chroma shifts are the frame format's, the
+ * extension is src->extension.  One wait, at the end. */
+int schro_mode_decision_split2_hip (SchroHipFrame * src, SchroHipFrame * const *ref_upframes, const SchroHipParams * params, double lambda,
+    const void *const *subpel_fields, void *motion, void *superblocks);
 
 /* schro_frame_inverse_iwt_transform_cuda (schrocuda.h:13-14) replacement, same arguments:
  * upload transform_frame (host) or use it where it is (device), run the multi-level inverse

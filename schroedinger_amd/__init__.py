@@ -183,6 +183,46 @@ def _subpel_tables(tables):
     return arr
 
 
+SB_DTYPE = np.dtype([("error", "<i4"), ("entropy", "<i4"), ("score", "<f8")])    # a superblock of the split-2 mode decision
+SPLIT2_TABLE_INTS = 16          # SCHRO_HIP_SPLIT2_TABLE_INTS (include/schro_hip.h)
+
+
+def split2_pictures(pictures):
+    """The SchroHipSplit2Picture array of [(src, refs, shifts, extension, params, lambda, fields, motion, superblocks)]:
+    src -- the Y, U, V planes of the picture, linear u8 (anything with ptr, stride, width, height; entries may be None
+    only to be refused); refs -- per reference the tiled upsampled images of Y, U, V (Context.hp_plane, or anything with
+    ptr, stride); shifts -- (h_shift, v_shift); params -- a dict with x_num_blocks, y_num_blocks, xbsep_luma, ybsep_luma
+    and mv_precision; fields -- per reference the device sub-pel field; motion, superblocks -- device memory for 20 bytes
+    per block and 16 per superblock (Context.motion_field, or anything with ptr)."""
+    arr = (_lib.Split2Picture * len(pictures))()
+    for n, (src, refs, shifts, ext, params, lam, fields, motion, superblocks) in enumerate(pictures):
+        a = arr[n]
+        for k in range(3):
+            if src[k] is not None:
+                a.src[k], a.src_stride[k] = src[k].ptr, src[k].stride
+        a.width, a.height = src[0].width, src[0].height
+        a.num_refs = len(refs)
+        for r, ups in enumerate(refs[:2]):
+            for k in range(3):
+                if ups[k] is not None:
+                    a.ref_up[r][k], a.ref_up_stride[k] = ups[k].ptr, ups[k].stride
+        a.h_shift, a.v_shift = shifts
+        a.extension = ext
+        a.x_num_blocks, a.y_num_blocks, a.xbsep_luma, a.ybsep_luma = _block_geometry(params)
+        a.mv_precision = params["mv_precision"]
+        setattr(a, "lambda", float(lam))
+        for r, f in enumerate(fields[:2]):
+            a.fields[r] = f.ptr if f is not None else None
+        a.motion = motion.ptr if motion is not None else None
+        a.superblocks = superblocks.ptr if superblocks is not None else None
+    return arr
+
+
+def split2_check(pictures):
+    """The refusals of Context.split2_batch on the host, without a context (schro_hip_split2_check)."""
+    check(_lib.load().schro_hip_split2_check(split2_pictures(pictures), len(pictures)))
+
+
 QUANTISE_DC_THREADS = 256       # SCHRO_HIP_QUANTISE_DC_THREADS (include/schro_hip.h): the DC recurrence's workgroup size
 
 
@@ -752,6 +792,43 @@ class Context:
             ups[k], ptrs[k] = ref_upframes[k].ptr(), out[k].ctypes.data
         check(self.lib.schro_encoder_motion_predict_subpel_deep_hip(fa.ptr(), ups, C.byref(params), float(lam), ptrs))
         return out
+
+    def split2_metric_batch(self, pictures, tables):
+        """What the split-2 mode decision reads from the pictures, one launch over the blocks of all of them: pictures as
+        split2_pictures takes them; tables[c] -- device memory (anything with ptr) for SPLIT2_TABLE_INTS int32 per block,
+        written whole.  Enqueued, not waited for."""
+        check(self.lib.schro_hip_split2_metric_batch(self.h, split2_pictures(pictures), len(pictures), _subpel_tables(tables)))
+
+    def split2_choose_batch(self, pictures, tables):
+        """The choice from the given tables and the sub-pel fields: motion and superblocks are written, one workgroup per
+        picture.  Enqueued, not waited for."""
+        check(self.lib.schro_hip_split2_choose_batch(self.h, split2_pictures(pictures), len(pictures), _subpel_tables(tables)))
+
+    def split2_batch(self, pictures):
+        """schro_do_split2 for every superblock of every picture: both launches, tables from the context's scratch.
+        Enqueued, not waited for."""
+        check(self.lib.schro_hip_split2_batch(self.h, split2_pictures(pictures), len(pictures)))
+
+    def mode_decision_split2(self, src_planes, ref_upframes, params, lam, fields, extension=32, h_shift=1, v_shift=1):
+        """schro_mode_decision_split2_hip: src_planes -- the u8 Y, U, V DevicePlanes of the picture, each with `extension`
+        samples of apron on every side; ref_upframes -- one upsampled frames.DeviceFrame per reference; params -- a dict
+        with the block geometry and mv_precision; fields -- the MV_DTYPE sub-pel field of each reference.  Returns (motion
+        as MV_DTYPE, the superblocks as SB_DTYPE), complete."""
+        from . import frames
+        nbx, nby, xb, yb = _block_geometry(params)
+        P = frames.make_params(mv_precision=params["mv_precision"], x_num_blocks=nbx, y_num_blocks=nby, xbsep_luma=xb, ybsep_luma=yb)
+        n = len(ref_upframes)
+        assert len(fields) == n
+        P.num_refs = n
+        fa = frames.PlaneFrame(self, src_planes, extension, h_shift, v_shift)
+        keep = [np.ascontiguousarray(f, dtype=MV_DTYPE) for f in fields]
+        ups, ptrs = (C.POINTER(_lib.Frame) * n)(), (C.c_void_p * n)()
+        for k in range(n):
+            assert keep[k].size == nbx * nby
+            ups[k], ptrs[k] = ref_upframes[k].ptr(), keep[k].ctypes.data
+        motion, sb = np.zeros(nbx * nby, MV_DTYPE), np.zeros(nbx * nby // 16, SB_DTYPE)
+        check(self.lib.schro_mode_decision_split2_hip(fa.ptr(), ups, C.byref(P), float(lam), ptrs, motion.ctypes.data, sb.ctypes.data))
+        return motion, sb
 
     def pack_u8_batch(self, jobs):
         """jobs: (planes [Y, U, V] DevicePlanes, h_shift, v_shift, dst DevicePlane of 4-byte

@@ -43,6 +43,8 @@ EXPORTED_SYMBOLS = [
     "schro_hierarchical_bm_scan_hint_hip", "schro_hbm_scan_hip",
     "schro_hip_subpel_error_batch", "schro_hip_subpel_choose_batch", "schro_hip_subpel_batch", "schro_hip_subpel_check",
     "schro_encoder_motion_predict_subpel_deep_hip",
+    "schro_hip_split2_metric_batch", "schro_hip_split2_choose_batch", "schro_hip_split2_batch", "schro_hip_split2_check",
+    "schro_mode_decision_split2_hip",
     "schro_hip_upsampled_bytes", "schro_hip_upsampled_download", "schro_hip_upsampled_pair_bytes",
     "schro_hip_upsampled_pair_download", "schro_hip_pack_u8_batch",
     "schro_hip_pack_v210_batch", "schro_hip_iiwt_pack_v210_batch", "schro_hip_iiwt_pack_u8_batch", "schro_hip_pack_wide_batch", "schro_hip_shift_right_batch",
@@ -149,6 +151,16 @@ class SubpelChain(C.Structure):
                 ("x_num_blocks", C.c_int), ("y_num_blocks", C.c_int), ("xbsep_luma", C.c_int), ("ybsep_luma", C.c_int),
                 ("mv_precision", C.c_int), ("ref_index", C.c_int), ("lambda", C.c_double),
                 ("src_field", C.c_void_p), ("field", C.c_void_p)]
+
+
+class Split2Picture(C.Structure):
+    """One picture of the split-2 mode decision."""
+    _fields_ = [("src", C.c_void_p * 3), ("src_stride", C.c_int * 3), ("num_refs", C.c_int),
+                ("ref_up", (C.c_void_p * 3) * 2), ("ref_up_stride", C.c_int * 3),
+                ("width", C.c_int), ("height", C.c_int), ("h_shift", C.c_int), ("v_shift", C.c_int), ("extension", C.c_int),
+                ("x_num_blocks", C.c_int), ("y_num_blocks", C.c_int), ("xbsep_luma", C.c_int), ("ybsep_luma", C.c_int),
+                ("mv_precision", C.c_int), ("chroma_pairs", C.c_int), ("lambda", C.c_double),
+                ("fields", C.c_void_p * 2), ("motion", C.c_void_p), ("superblocks", C.c_void_p)]
 
 
 class ConvertPlane(C.Structure):
@@ -544,6 +556,16 @@ def load():
     L.schro_encoder_motion_predict_subpel_deep_hip.argtypes = [C.POINTER(Frame), C.POINTER(C.POINTER(Frame)), C.POINTER(Params), C.c_double,
                                                                C.POINTER(C.c_void_p)]
     L.schro_encoder_motion_predict_subpel_deep_hip.restype = i
+    for name in ("schro_hip_split2_metric_batch", "schro_hip_split2_choose_batch"):
+        getattr(L, name).argtypes = [vp, C.POINTER(Split2Picture), i, C.POINTER(C.c_void_p)]
+        getattr(L, name).restype = i
+    L.schro_hip_split2_batch.argtypes = [vp, C.POINTER(Split2Picture), i]
+    L.schro_hip_split2_batch.restype = i
+    L.schro_hip_split2_check.argtypes = [C.POINTER(Split2Picture), i]
+    L.schro_hip_split2_check.restype = i
+    L.schro_mode_decision_split2_hip.argtypes = [C.POINTER(Frame), C.POINTER(C.POINTER(Frame)), C.POINTER(Params), C.c_double,
+                                                 C.POINTER(C.c_void_p), vp, vp]
+    L.schro_mode_decision_split2_hip.restype = i
     L.schro_hip_convert_u8_batch.argtypes = [vp, C.POINTER(ConvertPlane), i, i]
     L.schro_hip_convert_u8_batch.restype = i
     L.schro_hip_upsample_batch.argtypes = [vp, C.POINTER(UpsamplePlane), i]

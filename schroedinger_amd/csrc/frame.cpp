@@ -1451,4 +1451,49 @@ schro_encoder_motion_predict_subpel_deep_hip (SchroHipFrame * src, SchroHipFrame
   return subpel_host_run (frame_ctx (src), chains, params->num_refs);
 }
 
+int
+schro_mode_decision_split2_hip (SchroHipFrame * src, SchroHipFrame * const *ref_upframes, const SchroHipParams * params, double lambda,
+    const void *const *subpel_fields, void *motion, void *superblocks)
+{
+  const char *who = "mode_decision_split2_hip";
+  SCHRO_HIP_REQUIRE (src && ref_upframes && params && subpel_fields && motion && superblocks,
+      "%s: needs the picture, the upsampled references, the parameters, the fields and the two outputs", who);
+  SCHRO_HIP_REQUIRE (params->num_refs == 1 || params->num_refs == 2, "%s: %d references", who, params->num_refs);
+  SCHRO_HIP_REQUIRE (frame_ctx (src) && !(src->format & 0x100) && format_bpp (src->format) == 1 && !src->is_upsampled
+      && src->components[0].width == src->width && src->components[0].height == src->height, "%s: the picture must be a planar u8 device frame",
+      who);
+  SchroHipSplit2Picture pic;
+  memset (&pic, 0, sizeof (pic));
+  pic.num_refs = params->num_refs;
+  pic.width = src->width;
+  pic.height = src->height;
+  pic.h_shift = SCHRO_HIP_FORMAT_H_SHIFT (src->format);
+  pic.v_shift = SCHRO_HIP_FORMAT_V_SHIFT (src->format);
+  pic.extension = src->extension;
+  pic.x_num_blocks = params->x_num_blocks;
+  pic.y_num_blocks = params->y_num_blocks;
+  pic.xbsep_luma = params->xbsep_luma;
+  pic.ybsep_luma = params->ybsep_luma;
+  pic.mv_precision = params->mv_precision;
+  pic.lambda = lambda;
+  for (int k = 0; k < 3; k++) {
+    pic.src[k] = (const uint8_t *) src->components[k].data;
+    pic.src_stride[k] = src->components[k].stride;
+  }
+  for (int r = 0; r < params->num_refs; r++) {
+    const SchroHipFrame *up = ref_upframes[r];
+    SCHRO_HIP_REQUIRE (up && up->is_upsampled && up->domain == src->domain && up->format == src->format && up->width == src->width
+        && up->height == src->height, "%s: reference %d must be an upsampled device frame of the picture's format, size and domain", who, r);
+    SCHRO_HIP_REQUIRE (subpel_fields[r], "%s: reference %d has no motion field", who, r);
+    pic.chroma_pairs = up->is_upsampled == 2;   // (the format decides: both references have the same form)
+    for (int k = 0; k < 3; k++) {
+      pic.ref_up[r][k] = (const uint8_t *) up->components[k].data;
+      pic.ref_up_stride[k] = up->components[k].stride;
+    }
+    pic.fields[r] = subpel_fields[r];   // (the HOST field: split2_host_run puts the fields into the queue's scratch)
+  }
+  // (complete on return whatever the stage-completion setting: the outputs are host memory)
+  return split2_host_run (frame_ctx (src), &pic, motion, superblocks);
+}
+
 }                               // extern "C"

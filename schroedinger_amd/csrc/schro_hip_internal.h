@@ -227,6 +227,26 @@ struct SubpelChain {
 };
 static_assert (sizeof (SubpelChain) == 88, "sub-pel tables");
 
+// One picture of the split-2 mode decision (mode_split2.hip), as both of its launches see it.
+struct Split2Job {
+  const uint8_t *src[3];        // the source picture: Y, U, V, linear
+  const uint8_t *up[2][3];      // the references' tiled upsampled images; pair: [r][1] is the (U, V) pair image
+  const uint8_t *field[2];      // the sub-pel field of each reference
+  uint8_t *motion;              // the records the level decides
+  int32_t *table;               // SCHRO_HIP_SPLIT2_TABLE_INTS per block
+  uint8_t *sb;                  // error, entropy, score per superblock
+  double lambda;
+  int src_stride[3];
+  int up_stride[2];             // luma, chroma
+  int w, h, cw, ch;
+  int ext, nbx, nby, xb, yb;
+  int hs, vs, prec, num_refs;
+  int pair;
+  int tile_base;                // the picture's first workgroup of the metric launch
+  int pad;
+};
+static_assert (sizeof (Split2Job) == 208, "split-2 tables");
+
 // r05: the three-level s32 Haar transform of a 4:2:2 picture with the v210 copy-out as its epilogue (iiwt_haar.hip)
 struct HaarPackJob {
   const void *src[3];           // the coefficient planes (Y, U, V), in-place sub-band layout
@@ -749,6 +769,12 @@ int launch_hier_bm (hipStream_t stream, const HbmChain * d_chains, int nchains, 
 int subpel_error_blocks ();
 int launch_subpel_error (hipStream_t stream, const SubpelChain * d_chains, int nchains, int total_groups, int mvprec);
 int launch_subpel_choose (hipStream_t stream, const SubpelChain * d_chains, int nchains, int mvprec);
+
+// the split-2 mode decision (mode_split2.hip): the table entries over the blocks of all pictures, split2_metric_blocks ()
+// blocks per workgroup and jobs[].tile_base laid out accordingly; then the choice, one workgroup per picture
+int split2_metric_blocks ();
+int launch_split2_metric (hipStream_t stream, const Split2Job * d_jobs, int njobs, int total_groups);
+int launch_split2_choose (hipStream_t stream, const Split2Job * d_jobs, int njobs);
 int launch_convert (hipStream_t stream, const ConvertJob * d_jobs, int njobs,
     int total_tiles, int bpp);
 void convert_tile_geometry (int *tw, int *th);
@@ -1044,6 +1070,10 @@ int hbm_host_run (SchroHipContext * ctx, const char *who, const SchroHipHbmPlane
 // the frame layer's sub-pel refinement on host fields (plane_subpel.cpp): chains[c].src_field is the HOST field refined in
 // place, chains[c].field is not read -- both become scratch of the queue; waits for the queue
 int subpel_host_run (SchroHipContext * ctx, SchroHipSubpelChain * chains, int nchains);
+// the frame layer's split-2 mode decision (plane_split2.cpp): pic->fields[r] are the HOST fields, pic->motion and
+// pic->superblocks are not read -- all become scratch of the queue; `motion` and `superblocks` are the host outputs; waits
+// for the queue
+int split2_host_run (SchroHipContext * ctx, SchroHipSplit2Picture * pic, void *motion, void *superblocks);
 // v216 / ARGB / AY64 (plane_frameops.cpp)
 bool is_wide_format (int format);
 // plane_quant.cpp: schro_hip_quantise_batch; allow_empty: records of no width or height are skipped (the frame layer's
