@@ -673,8 +673,8 @@ int schro_hip_subpel_check (const SchroHipSubpelChain * chains, int nchains);
  * chroma subsampling; the kernel clamps rows and columns to the image all the same -- a field that breaks the rule reads
  * what the clamp gives, where the reference reads outside its frame.
  *
- * OUT OF SCOPE: split 1 and split 0 (schro_do_split1, schro_do_split0), schro_do_split0_biref_zero, the statistics of
- * :2655-2681 (mc_error, badblock_ratio, dcblock_ratio), global motion, and a plain-plane reference for mv_precision 0:
+ * OUT OF SCOPE here: split 1 and split 0, schro_do_split0_biref_zero and the statistics of :2655-2681 are the stage below
+ * (schro_hip_mode_decision_batch).  Out of scope of both: global motion, and a plain-plane reference for mv_precision 0:
  * the tiled image serves all four precisions, precision 0 reads S (2x, 2y). */
 #define SCHRO_HIP_SPLIT2_TABLE_INTS 16
 typedef struct {
@@ -715,6 +715,106 @@ int schro_hip_split2_choose_batch (SchroHipContext * ctx, const SchroHipSplit2Pi
 int schro_hip_split2_batch (SchroHipContext * ctx, const SchroHipSplit2Picture * pictures, int n);
 /* host only: the refusals of schro_hip_split2_batch without a context.  No pointer is dereferenced but `pictures`. */
 int schro_hip_split2_check (const SchroHipSplit2Picture * pictures, int n);
+
+/* ---- mode decision on the device, entire: schro_mode_decision (schromotionest.c:2587-2688) ---------------------------
+ *
+ * Per superblock, in raster order in the reference: schro_do_split2 (the stage above), schro_do_split1, schro_do_split0 if
+ * split 1 won, schro_do_split0_biref_zero with two references, schro_block_fixup and schro_motion_copy_to of the winner,
+ * and the three statistics schroencoder.c:2366-2368 reads.  A PICTURE is the split-2 stage's plus, per reference, the
+ * block matching's level-1 and level-2 fields (schro_hip_hbm_batch's fields[1] and fields[2]: full grids with records
+ * every 2 and every 4 blocks).  split1_mf and split0_mf of the reference are working state and no output.
+ *
+ * What the C text does, restated (tests/mode_ref.py is the executable form; the numbers are its rules):
+ *   1. schro_do_split1 adds best_error + best_chroma_error per quadrant, and best_chroma_error stays INT_MAX unless the
+ *      bi-reference trial won the quadrant.  That is signed overflow in C; the reference's build wraps, and int32
+ *      two's-complement wrapping is what is restated -- AN ASSUMPTION ABOUT THE BUILD.  With s single-reference quadrants
+ *      inside the picture the sum is off by s * (2^31 - 1) mod 2^32: hugely negative for odd s, the honest sum minus s for
+ *      even s.  block.error, block.score, the bad-block test and mc_error all take the wrapped value.
+ *   2. The hints of a split-1 quadrant and reference: its four sub-pel records, then the level-1 record, each skipped when
+ *      its metric is INT_MAX or when (its vector << mv_precision) equals a listed hint's vector -- for the sub-pel records
+ *      too, which are in sub-pel units already.  The level-1 hint is a COPY of the record with dx[r], dy[r] shifted; its
+ *      other slot and its flag bytes travel into the winner.  Split 0: the split-1 winners of the four quadrants and
+ *      reference with shift 0, then the level-2 record with shift mv_precision.
+ *   3. A quadrant outside the picture keeps the predicted form at split 1: split 1, the predicted mode forced to 1 unless
+ *      it is 1 or 2, the predicted vector (of reference 1) in that slot; total_entropy += 2.  Split 0 inherits the zero
+ *      vector from it.
+ *   4. A quadrant with no admissible hint in either reference makes the split-1 trial invalid; what the reference writes
+ *      after that reaches no result, the device stops there.
+ *   5. Bound tests: -extension <= X, Y and (size << p) + extension > X + bw - 1, luma, bw x bh the block CLIPPED to the
+ *      picture, before any fetch of the candidate.
+ *   6. The shared fetch buffers of mv_precision 2 and 3 (step 2 of the stage above) hold for the bi-reference trials of
+ *      split 1, split 0 and the zero vectors, with 2x and 4x blocks.
+ *   7. min_score is not updated when split 0 wins: the zero-vector trial is compared with split 1's score and can
+ *      replace a split-0 winner that scores better than it.
+ *   8. The split-0 trial writes only mv[0][0] of the try block; the zero-vector trial builds its record over what the
+ *      earlier trials left there (bytes 1-3 and the upper flag bits stay).
+ *   9. Every product with lambda is a rounded product followed by a rounded sum.
+ *  10. block_size = 16 * xbsep * ybsep * 2 / 3 (integers); mc_error = sum over superblocks in raster order of
+ *      (double) error * error / (double) (block_size * block_size), then / (240.0 * 240.0) / x_num_blocks * y_num_blocks / 16
+ *      from left to right; badblock_ratio = #(error > 10 * block_size) / (x_num_blocks * y_num_blocks / 16);
+ *      dcblock_ratio = #(pred_mode 0) / (x_num_blocks * y_num_blocks).
+ *  11. A split-1 / split-0 candidate is a copy of its hint with split and pred_mode set; using_global is NOT cleared, so a
+ *      hint whose bit is set has entropy 0 and carries the bit into the field.
+ *  12. A superblock whose origin lies outside the picture runs into SCHRO_ASSERT (0) in the reference: refused.
+ *
+ * The TABLE ENTRY of a superblock, SCHRO_HIP_MODE_TABLE_INTS int32, what reads the pictures and depends on no decision
+ * (schro_hip_mode_metric_batch).  Per reference r, at [264 r], 22 candidates of 12 int32: candidate 5 q + m of quadrant q
+ * (0 .. 3: ii = 2 (q & 1), jj = 2 (q >> 1)) is the sub-pel record (ii + (m & 1), jj + (m >> 1)) for m < 4 and the level-1
+ * record (shifted) for m = 4; candidate 20 is the level-2 record (shifted), 21 the zero vector.  Of a candidate:
+ *   [0]        the split-1 bound test on its own quadrant (0 / 1); -1 for candidates 20, 21 and a quadrant outside
+ *   [1]        the split-0 bound test on the superblock (0 / 1)
+ *   [2 + 2 q'] the luma SAD of the vector over quadrant q', [3 + 2 q'] the chroma SAD; -1, -1 for a quadrant outside the
+ *              picture and where neither [1] nor ([0] and q' its own quadrant) holds -- nothing may ask for it
+ *   [10], [11] 0
+ * Every int of a reference the picture does not have is -1.  A split-0 SAD is the sum over the quadrants: clipping and
+ * the bilinear form are per sample.  [528 .. 531]: the zero-vector trial admissible (0 / 1), its luma and chroma metric
+ * (0 where inadmissible), 0; all -1 with one reference.  The bi-reference metrics of a split-1 quadrant and of split 0
+ * depend on the chosen pair and are measured inside the walk.
+ *
+ * REACH.  Single-reference hints of split 1 and split 0 are bound-tested on luma before anything of them is fetched: an
+ * admissible hint has -e <= X and X + bw - 1 < (width << p) + e for its block clipped to the picture (e = extension, p =
+ * mv_precision, X in units of 2^-p samples).  The test is the reference's own and is loose at p > 0 -- it compares units
+ * with samples -- so it also admits hints whose block leaves the frame on the right; the reference then reads outside its
+ * frame, here columns are clamped to the tiled image's aprons and rows to [0, 2 h - 2], as everywhere.  For the vectors
+ * the block matching and the sub-pel stage produce (REACH above: every block inside the picture plus e samples; the
+ * level-1 and level-2 vectors are such vectors of 2 x 2 and 4 x 4 blocks, shifted) an admissible hint's luma block of bw
+ * columns lies within [-e, width + e) samples, and its chroma reads go to floor (X / 2^s) with a block of bw >> s columns:
+ * leftmost column >= -(e >> s), rightmost <= floor ((width + e - bw) / 2^s) + (bw >> s) - 1 (+ 1, the right tap, only with
+ * a fraction, and then the floor is one less) <= chroma width + e / 2^s - 1 -- the argument of the split-2 stage with bw
+ * in place of b, which needs bw a multiple of 2^s or the block clipped at the picture's edge, where the bound is the
+ * picture's.  Both lie inside the e-column apron under the same refusals: extension in max (xbsep_luma, ybsep_luma) .. 32,
+ * separations multiples of the subsampling.  Rows likewise.  The bi-reference trials test their luma reads themselves. */
+#define SCHRO_HIP_MODE_TABLE_INTS 532
+typedef struct {
+  int32_t state;                /* 1: valid, 0: tried and invalid, -1: not tried */
+  int32_t error, entropy;       /* 0 unless state is 1 */
+  int32_t pad;                  /* 0 */
+  double score;                 /* 0 unless state is 1 */
+} SchroHipModeTrial;
+typedef struct {
+  SchroHipSplit2Picture split2; /* everything of the split-2 stage; motion and superblocks receive the WINNER's */
+  const void *hbm_fields[2][2]; /* device: per reference the block matching's level-1 and level-2 field (read) */
+  void *trials;                 /* device, 8-byte aligned: per superblock four SchroHipModeTrial -- split 2, split 1, split 0,
+                                 * the zero vectors (written whole) */
+  void *stats;                  /* device, 8-byte aligned: three doubles -- mc_error, badblock_ratio, dcblock_ratio */
+} SchroHipModePicture;
+
+/* What reads the pictures: tables[2 c] receives the split-2 table of picture c (SCHRO_HIP_SPLIT2_TABLE_INTS int32 per
+ * block, by the split-2 stage's launch), tables[2 c + 1] SCHRO_HIP_MODE_TABLE_INTS int32 per superblock; every entry is
+ * written.  Two launches over all pictures.  Enqueues. */
+int schro_hip_mode_metric_batch (SchroHipContext * ctx, const SchroHipModePicture * pictures, int n, void *const *tables);
+/* The walk from given tables (2 n pointers as above), the fields and -- for the bi-reference trials of split 1 and
+ * split 0 -- the pictures: motion, superblocks, trials and stats are written.  One workgroup per picture walks the
+ * anti-diagonals of superblocks, one wave per superblock; no workgroup waits for another.  Enqueues. */
+int schro_hip_mode_choose_batch (SchroHipContext * ctx, const SchroHipModePicture * pictures, int n, void *const *tables);
+/* The whole stage on the context's queue, tables from the context's scratch.  Behind schro_hip_hbm_batch and
+ * schro_hip_subpel_batch on the same queue it takes their fields without a download; schro_hip_obmc_batch behind it takes
+ * `motion`.  Enqueues, does not synchronise.
+ * All three refuse what the split-2 stage refuses, a missing level-1 / level-2 field, trial table or statistics, a grid
+ * with a superblock whose origin lies outside the picture, and an output that overlaps anything else of the call. */
+int schro_hip_mode_decision_batch (SchroHipContext * ctx, const SchroHipModePicture * pictures, int n);
+/* host only: the refusals of schro_hip_mode_decision_batch without a context. */
+int schro_hip_mode_decision_check (const SchroHipModePicture * pictures, int n);
 
 /* intra pictures: dst_u8 = sat_u8 (src + 128), cropped to width x height;
  * replaces schro_frame_convert (ref_output_frame, frame)
@@ -1545,6 +1645,12 @@ SCHRO_HIP_LAYOUT (SchroHipSplit2Picture, width, 100);
 SCHRO_HIP_LAYOUT (SchroHipSplit2Picture, mv_precision, 136);
 SCHRO_HIP_LAYOUT (SchroHipSplit2Picture, lambda, 144);
 SCHRO_HIP_LAYOUT (SchroHipSplit2Picture, motion, 168);
+SCHRO_HIP_SIZE (SchroHipModeTrial, 24);
+SCHRO_HIP_LAYOUT (SchroHipModeTrial, score, 16);
+SCHRO_HIP_SIZE (SchroHipModePicture, 232);
+SCHRO_HIP_LAYOUT (SchroHipModePicture, hbm_fields, 184);
+SCHRO_HIP_LAYOUT (SchroHipModePicture, trials, 216);
+SCHRO_HIP_LAYOUT (SchroHipModePicture, stats, 224);
 #endif
 
 /* schro_frame_new_and_alloc (schroframe.c:60-191) on the device domain:
@@ -1638,6 +1744,12 @@ int schro_encoder_motion_predict_subpel_deep_hip (SchroHipFrame * src, SchroHipF
  * extension is src->extension.  One wait, at the end. */
 int schro_mode_decision_split2_hip (SchroHipFrame * src, SchroHipFrame * const *ref_upframes, const SchroHipParams * params, double lambda,
     const void *const *subpel_fields, void *motion, void *superblocks);
+/* schro_mode_decision entire (schro_hip_mode_decision_batch above), the same arguments and: hbm_fields -- per reference
+ * the HOST level-1 and level-2 fields of the block matching, hbm_fields[2 r] and hbm_fields[2 r + 1]; trials -- HOST
+ * memory for four SchroHipModeTrial per superblock, or NULL; stats -- three doubles: mc_error, badblock_ratio,
+ * dcblock_ratio.  One wait, at the end. */
+int schro_mode_decision_hip (SchroHipFrame * src, SchroHipFrame * const *ref_upframes, const SchroHipParams * params, double lambda,
+    const void *const *subpel_fields, const void *const *hbm_fields, void *motion, void *superblocks, void *trials, double *stats);
 
 /* schro_frame_inverse_iwt_transform_cuda (schrocuda.h:13-14) replacement, same arguments:
  * upload transform_frame (host) or use it where it is (device), run the multi-level inverse

@@ -223,6 +223,34 @@ def split2_check(pictures):
     check(_lib.load().schro_hip_split2_check(split2_pictures(pictures), len(pictures)))
 
 
+MODE_TABLE_INTS = 532           # SCHRO_HIP_MODE_TABLE_INTS (include/schro_hip.h): per superblock
+MODE_CANDIDATES, MODE_CANDIDATE_INTS, MODE_ZERO_TRIAL = 22, 12, 528     # per reference 22 candidates of 12 int32; the zero-vector trial
+# a trial of a superblock (SchroHipModeTrial): four per superblock -- split 2, split 1, split 0, the zero vectors
+MODE_TRIAL_DTYPE = np.dtype([("state", "<i4"), ("error", "<i4"), ("entropy", "<i4"), ("pad", "<i4"), ("score", "<f8")])
+
+
+def mode_pictures(pictures):
+    """The SchroHipModePicture array of [(src, refs, shifts, extension, params, lambda, fields, level1, level2, motion,
+    superblocks, trials, stats)]: as split2_pictures takes them, and level1, level2 -- per reference the device level-1
+    and level-2 field of the block matching; trials -- device memory for four MODE_TRIAL_DTYPE per superblock; stats --
+    device memory for three doubles."""
+    arr = (_lib.ModePicture * len(pictures))()
+    for n, (src, refs, shifts, ext, params, lam, fields, level1, level2, motion, superblocks, trials, stats) in enumerate(pictures):
+        one = split2_pictures([(src, refs, shifts, ext, params, lam, fields, motion, superblocks)])
+        C.memmove(C.byref(arr[n].split2), one, C.sizeof(_lib.Split2Picture))
+        for r in range(min(len(refs), 2)):
+            for level, f in enumerate((level1, level2)):
+                arr[n].hbm_fields[r][level] = f[r].ptr if r < len(f) and f[r] is not None else None
+        arr[n].trials = trials.ptr if trials is not None else None
+        arr[n].stats = stats.ptr if stats is not None else None
+    return arr
+
+
+def mode_check(pictures):
+    """The refusals of Context.mode_decision_batch on the host, without a context (schro_hip_mode_decision_check)."""
+    check(_lib.load().schro_hip_mode_decision_check(mode_pictures(pictures), len(pictures)))
+
+
 QUANTISE_DC_THREADS = 256       # SCHRO_HIP_QUANTISE_DC_THREADS (include/schro_hip.h): the DC recurrence's workgroup size
 
 
@@ -829,6 +857,46 @@ class Context:
         motion, sb = np.zeros(nbx * nby, MV_DTYPE), np.zeros(nbx * nby // 16, SB_DTYPE)
         check(self.lib.schro_mode_decision_split2_hip(fa.ptr(), ups, C.byref(P), float(lam), ptrs, motion.ctypes.data, sb.ctypes.data))
         return motion, sb
+
+    def mode_metric_batch(self, pictures, tables):
+        """What the whole mode decision reads from the pictures without a decision: pictures as mode_pictures takes them;
+        tables[2 c] -- device memory for SPLIT2_TABLE_INTS int32 per block, tables[2 c + 1] -- for MODE_TABLE_INTS int32 per
+        superblock, both written whole.  Two launches over all pictures.  Enqueued, not waited for."""
+        check(self.lib.schro_hip_mode_metric_batch(self.h, mode_pictures(pictures), len(pictures), _subpel_tables(tables)))
+
+    def mode_choose_batch(self, pictures, tables):
+        """The walk from the given tables: motion, superblocks, trials and stats are written, one workgroup per picture.
+        Enqueued, not waited for."""
+        check(self.lib.schro_hip_mode_choose_batch(self.h, mode_pictures(pictures), len(pictures), _subpel_tables(tables)))
+
+    def mode_decision_batch(self, pictures):
+        """schro_mode_decision for every picture: the metric launches and the walk, tables from the context's scratch.
+        Enqueued, not waited for."""
+        check(self.lib.schro_hip_mode_decision_batch(self.h, mode_pictures(pictures), len(pictures)))
+
+    def mode_decision(self, src_planes, ref_upframes, params, lam, fields, level1, level2, extension=32, h_shift=1, v_shift=1):
+        """schro_mode_decision_hip: as mode_decision_split2, and level1, level2 -- the MV_DTYPE level-1 and level-2 field of
+        the block matching per reference.  Returns (motion as MV_DTYPE, the superblocks as SB_DTYPE, the trials as
+        (superblocks, 4) MODE_TRIAL_DTYPE, the three statistics), complete."""
+        from . import frames
+        nbx, nby, xb, yb = _block_geometry(params)
+        P = frames.make_params(mv_precision=params["mv_precision"], x_num_blocks=nbx, y_num_blocks=nby, xbsep_luma=xb, ybsep_luma=yb)
+        n = len(ref_upframes)
+        assert len(fields) == n and len(level1) == n and len(level2) == n
+        P.num_refs = n
+        fa = frames.PlaneFrame(self, src_planes, extension, h_shift, v_shift)
+        keep = [np.ascontiguousarray(f, dtype=MV_DTYPE) for f in fields]
+        levels = [np.ascontiguousarray(f[k], dtype=MV_DTYPE) for k in range(n) for f in (level1, level2)]
+        ups, ptrs, lptrs = (C.POINTER(_lib.Frame) * n)(), (C.c_void_p * n)(), (C.c_void_p * (2 * n))()
+        for k in range(n):
+            assert keep[k].size == nbx * nby and levels[2 * k].size == nbx * nby and levels[2 * k + 1].size == nbx * nby
+            ups[k], ptrs[k] = ref_upframes[k].ptr(), keep[k].ctypes.data
+            lptrs[2 * k], lptrs[2 * k + 1] = levels[2 * k].ctypes.data, levels[2 * k + 1].ctypes.data
+        motion, sb = np.zeros(nbx * nby, MV_DTYPE), np.zeros(nbx * nby // 16, SB_DTYPE)
+        trials, stats = np.zeros((nbx * nby // 16, 4), MODE_TRIAL_DTYPE), np.zeros(3, np.float64)
+        check(self.lib.schro_mode_decision_hip(fa.ptr(), ups, C.byref(P), float(lam), ptrs, lptrs, motion.ctypes.data, sb.ctypes.data,
+                                               trials.ctypes.data, stats.ctypes.data_as(C.POINTER(C.c_double))))
+        return motion, sb, trials, stats
 
     def pack_u8_batch(self, jobs):
         """jobs: (planes [Y, U, V] DevicePlanes, h_shift, v_shift, dst DevicePlane of 4-byte

@@ -45,6 +45,8 @@ EXPORTED_SYMBOLS = [
     "schro_encoder_motion_predict_subpel_deep_hip",
     "schro_hip_split2_metric_batch", "schro_hip_split2_choose_batch", "schro_hip_split2_batch", "schro_hip_split2_check",
     "schro_mode_decision_split2_hip",
+    "schro_hip_mode_metric_batch", "schro_hip_mode_choose_batch", "schro_hip_mode_decision_batch", "schro_hip_mode_decision_check",
+    "schro_mode_decision_hip",
     "schro_hip_upsampled_bytes", "schro_hip_upsampled_download", "schro_hip_upsampled_pair_bytes",
     "schro_hip_upsampled_pair_download", "schro_hip_pack_u8_batch",
     "schro_hip_pack_v210_batch", "schro_hip_iiwt_pack_v210_batch", "schro_hip_iiwt_pack_u8_batch", "schro_hip_pack_wide_batch", "schro_hip_shift_right_batch",
@@ -161,6 +163,11 @@ class Split2Picture(C.Structure):
                 ("x_num_blocks", C.c_int), ("y_num_blocks", C.c_int), ("xbsep_luma", C.c_int), ("ybsep_luma", C.c_int),
                 ("mv_precision", C.c_int), ("chroma_pairs", C.c_int), ("lambda", C.c_double),
                 ("fields", C.c_void_p * 2), ("motion", C.c_void_p), ("superblocks", C.c_void_p)]
+
+
+class ModePicture(C.Structure):
+    """One picture of the whole mode decision."""
+    _fields_ = [("split2", Split2Picture), ("hbm_fields", (C.c_void_p * 2) * 2), ("trials", C.c_void_p), ("stats", C.c_void_p)]
 
 
 class ConvertPlane(C.Structure):
@@ -566,6 +573,16 @@ def load():
     L.schro_mode_decision_split2_hip.argtypes = [C.POINTER(Frame), C.POINTER(C.POINTER(Frame)), C.POINTER(Params), C.c_double,
                                                  C.POINTER(C.c_void_p), vp, vp]
     L.schro_mode_decision_split2_hip.restype = i
+    for name in ("schro_hip_mode_metric_batch", "schro_hip_mode_choose_batch"):
+        getattr(L, name).argtypes = [vp, C.POINTER(ModePicture), i, C.POINTER(C.c_void_p)]
+        getattr(L, name).restype = i
+    L.schro_hip_mode_decision_batch.argtypes = [vp, C.POINTER(ModePicture), i]
+    L.schro_hip_mode_decision_batch.restype = i
+    L.schro_hip_mode_decision_check.argtypes = [C.POINTER(ModePicture), i]
+    L.schro_hip_mode_decision_check.restype = i
+    L.schro_mode_decision_hip.argtypes = [C.POINTER(Frame), C.POINTER(C.POINTER(Frame)), C.POINTER(Params), C.c_double,
+                                          C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), vp, vp, vp, C.POINTER(C.c_double)]
+    L.schro_mode_decision_hip.restype = i
     L.schro_hip_convert_u8_batch.argtypes = [vp, C.POINTER(ConvertPlane), i, i]
     L.schro_hip_convert_u8_batch.restype = i
     L.schro_hip_upsample_batch.argtypes = [vp, C.POINTER(UpsamplePlane), i]

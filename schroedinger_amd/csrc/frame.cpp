@@ -1451,18 +1451,15 @@ schro_encoder_motion_predict_subpel_deep_hip (SchroHipFrame * src, SchroHipFrame
   return subpel_host_run (frame_ctx (src), chains, params->num_refs);
 }
 
-int
-schro_mode_decision_split2_hip (SchroHipFrame * src, SchroHipFrame * const *ref_upframes, const SchroHipParams * params, double lambda,
-    const void *const *subpel_fields, void *motion, void *superblocks)
+// the picture of the split-2 stage from the frame layer's arguments; fields[r] are the HOST fields
+static int
+mode_fill_picture (const char *who, SchroHipFrame * src, SchroHipFrame * const *ref_upframes, const SchroHipParams * params, double lambda,
+    const void *const *subpel_fields, SchroHipSplit2Picture & pic)
 {
-  const char *who = "mode_decision_split2_hip";
-  SCHRO_HIP_REQUIRE (src && ref_upframes && params && subpel_fields && motion && superblocks,
-      "%s: needs the picture, the upsampled references, the parameters, the fields and the two outputs", who);
   SCHRO_HIP_REQUIRE (params->num_refs == 1 || params->num_refs == 2, "%s: %d references", who, params->num_refs);
   SCHRO_HIP_REQUIRE (frame_ctx (src) && !(src->format & 0x100) && format_bpp (src->format) == 1 && !src->is_upsampled
       && src->components[0].width == src->width && src->components[0].height == src->height, "%s: the picture must be a planar u8 device frame",
       who);
-  SchroHipSplit2Picture pic;
   memset (&pic, 0, sizeof (pic));
   pic.num_refs = params->num_refs;
   pic.width = src->width;
@@ -1492,8 +1489,42 @@ schro_mode_decision_split2_hip (SchroHipFrame * src, SchroHipFrame * const *ref_
     }
     pic.fields[r] = subpel_fields[r];   // (the HOST field: split2_host_run puts the fields into the queue's scratch)
   }
+  return 0;
+}
+
+int
+schro_mode_decision_split2_hip (SchroHipFrame * src, SchroHipFrame * const *ref_upframes, const SchroHipParams * params, double lambda,
+    const void *const *subpel_fields, void *motion, void *superblocks)
+{
+  const char *who = "mode_decision_split2_hip";
+  SCHRO_HIP_REQUIRE (src && ref_upframes && params && subpel_fields && motion && superblocks,
+      "%s: needs the picture, the upsampled references, the parameters, the fields and the two outputs", who);
+  SchroHipSplit2Picture pic;
+  const int r = mode_fill_picture (who, src, ref_upframes, params, lambda, subpel_fields, pic);
+  if (r)
+    return r;
   // (complete on return whatever the stage-completion setting: the outputs are host memory)
   return split2_host_run (frame_ctx (src), &pic, motion, superblocks);
+}
+
+int
+schro_mode_decision_hip (SchroHipFrame * src, SchroHipFrame * const *ref_upframes, const SchroHipParams * params, double lambda,
+    const void *const *subpel_fields, const void *const *hbm_fields, void *motion, void *superblocks, void *trials, double *stats)
+{
+  const char *who = "mode_decision_hip";
+  SCHRO_HIP_REQUIRE (src && ref_upframes && params && subpel_fields && hbm_fields && motion && superblocks && stats,
+      "%s: needs the picture, the upsampled references, the parameters, the fields, the two outputs and the statistics", who);
+  SchroHipModePicture pic;
+  memset (&pic, 0, sizeof (pic));
+  const int r = mode_fill_picture (who, src, ref_upframes, params, lambda, subpel_fields, pic.split2);
+  if (r)
+    return r;
+  for (int k = 0; k < params->num_refs; k++)
+    for (int level = 0; level < 2; level++) {
+      SCHRO_HIP_REQUIRE (hbm_fields[2 * k + level], "%s: reference %d has no level-%d field", who, k, level + 1);
+      pic.hbm_fields[k][level] = hbm_fields[2 * k + level];     // (HOST fields: mode_host_run puts them into the queue's scratch)
+    }
+  return mode_host_run (frame_ctx (src), &pic, motion, superblocks, trials, stats);
 }
 
 }                               // extern "C"

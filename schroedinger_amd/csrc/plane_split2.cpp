@@ -25,18 +25,15 @@ constexpr size_t kEntryBytes = SCHRO_HIP_SPLIT2_TABLE_INTS * sizeof (int32_t);
 
 enum Call { kMetric, kChoose, kStage };
 
-// a range of device memory a call reads or writes, and whose it is
-struct Span {
-  uintptr_t begin, end;
-  bool written;
-  int picture;
-  const char *name;
-};
+}                               // namespace
+
+namespace schro {
 
 // nothing written overlaps anything else
 int
-check_spans (const char *who, std::vector < Span > &spans)
+split2_check_spans (const char *who, std::vector < Split2Span > &spans)
 {
+  typedef Split2Span Span;
   std::sort (spans.begin (), spans.end (), [](const Span & a, const Span & b) {
         return a.begin < b.begin;}
   );
@@ -53,17 +50,14 @@ check_spans (const char *who, std::vector < Span > &spans)
   return 0;
 }
 
-// The refusals, and the kernels' records: `out` receives one Split2Job per picture (table NULL where `tables` is).
+// The refusals of one picture but for the overlaps, its kernel record and its spans (the table's too where `table` is
+// given).
 int
-build_jobs (const char *who, Call call, const SchroHipSplit2Picture * in, int n, void *const *tables, std::vector < Split2Job > &out)
+split2_collect (const char *who, const SchroHipSplit2Picture & s, int c, bool stage, void *table, Split2Job & jb, std::vector < Split2Span > &spans)
 {
   static const char *const comp[3] = { "Y", "U", "V" };
-  SCHRO_HIP_REQUIRE (in && n > 0 && (call == kStage || tables), "%s: bad arguments", who);
-  SCHRO_HIP_REQUIRE (n <= kMaxJobs, "%s: at most %d pictures per call", who, kMaxJobs);
-  std::vector < Span > spans;
-  out.resize (n);
-  for (int c = 0; c < n; c++) {
-    const SchroHipSplit2Picture & s = in[c];
+  const Call call = stage ? kStage : kMetric;
+  {
     SCHRO_HIP_REQUIRE (s.num_refs == 1 || s.num_refs == 2, "%s: picture %d: %d references, neither 1 nor 2", who, c, s.num_refs);
     SCHRO_HIP_REQUIRE ((s.h_shift == 0 || s.h_shift == 1) && (s.v_shift == 0 || s.v_shift == 1) && s.v_shift <= s.h_shift,
         "%s: picture %d: chroma shifts %d,%d are none of 0,0 / 1,0 / 1,1", who, c, s.h_shift, s.v_shift);
@@ -87,14 +81,13 @@ build_jobs (const char *who, Call call, const SchroHipSplit2Picture * in, int n,
         s.width, s.height, s.mv_precision, reach);
     SCHRO_HIP_REQUIRE (std::isfinite (s.lambda) && s.lambda >= 0, "%s: picture %d: lambda %g is negative or not finite", who, c, s.lambda);
     SCHRO_HIP_REQUIRE (s.motion && s.superblocks, "%s: picture %d: the motion field or the superblock table is a NULL pointer", who, c);
-    SCHRO_HIP_REQUIRE (call == kStage || tables[c], "%s: picture %d: the table is a NULL pointer", who, c);
-    SCHRO_HIP_REQUIRE (((uintptr_t) s.motion & 3) == 0 && ((uintptr_t) s.superblocks & 7) == 0 && (call == kStage || ((uintptr_t) tables[c] & 3) == 0),
+    SCHRO_HIP_REQUIRE (call == kStage || table, "%s: picture %d: the table is a NULL pointer", who, c);
+    SCHRO_HIP_REQUIRE (((uintptr_t) s.motion & 3) == 0 && ((uintptr_t) s.superblocks & 7) == 0 && (call == kStage || ((uintptr_t) table & 3) == 0),
         "%s: picture %d: the motion field or the table is not 4-byte aligned, or the superblock table not 8-byte aligned", who, c);
     const size_t records = (size_t) s.x_num_blocks * s.y_num_blocks;
     const int cw = (s.width + (1 << s.h_shift) - 1) >> s.h_shift, ch = (s.height + (1 << s.v_shift) - 1) >> s.v_shift;
     const bool pair = s.chroma_pairs != 0;
     SCHRO_HIP_REQUIRE (!pair || s.h_shift == 1, "%s: picture %d: only a horizontally subsampled picture has pair images", who, c);
-    Split2Job & jb = out[c];
     memset (&jb, 0, sizeof (jb));
     for (int k = 0; k < 3; k++) {
       const int w = k ? cw : s.width, h = k ? ch : s.height;
@@ -129,17 +122,37 @@ build_jobs (const char *who, Call call, const SchroHipSplit2Picture * in, int n,
     spans.push_back ({(uintptr_t) s.motion, (uintptr_t) s.motion + records * kMvBytes, true, c, "the motion field"});
     spans.push_back ({(uintptr_t) s.superblocks, (uintptr_t) s.superblocks + records / 16 * kSbBytes, true, c, "the superblock table"});
     if (call != kStage)
-      spans.push_back ({(uintptr_t) tables[c], (uintptr_t) tables[c] + records * kEntryBytes, true, c, "the table"});
+      spans.push_back ({(uintptr_t) table, (uintptr_t) table + records * kEntryBytes, true, c, "the table"});
     jb.motion = (uint8_t *) s.motion;
     jb.sb = (uint8_t *) s.superblocks;
-    jb.table = call == kStage ? nullptr : (int32_t *) tables[c];
+    jb.table = call == kStage ? nullptr : (int32_t *) table;
     jb.lambda = s.lambda;
     jb.w = s.width, jb.h = s.height, jb.cw = cw, jb.ch = ch, jb.ext = s.extension;
     jb.nbx = s.x_num_blocks, jb.nby = s.y_num_blocks, jb.xb = s.xbsep_luma, jb.yb = s.ybsep_luma;
     jb.hs = s.h_shift, jb.vs = s.v_shift, jb.prec = s.mv_precision, jb.num_refs = s.num_refs;
     jb.pair = pair;
   }
-  return check_spans (who, spans);
+  return 0;
+}
+
+}                               // namespace schro
+
+namespace {
+
+// The refusals, and the kernels' records: `out` receives one Split2Job per picture (table NULL where `tables` is).
+int
+build_jobs (const char *who, Call call, const SchroHipSplit2Picture * in, int n, void *const *tables, std::vector < Split2Job > &out)
+{
+  SCHRO_HIP_REQUIRE (in && n > 0 && (call == kStage || tables), "%s: bad arguments", who);
+  SCHRO_HIP_REQUIRE (n <= kMaxJobs, "%s: at most %d pictures per call", who, kMaxJobs);
+  std::vector < Split2Span > spans;
+  out.resize (n);
+  for (int c = 0; c < n; c++) {
+    const int r = split2_collect (who, in[c], c, call == kStage, call == kStage ? nullptr : tables[c], out[c], spans);
+    if (r)
+      return r;
+  }
+  return split2_check_spans (who, spans);
 }
 
 // the workgroups of the metric launch, picture by picture; returns their number

@@ -247,6 +247,19 @@ struct Split2Job {
 };
 static_assert (sizeof (Split2Job) == 208, "split-2 tables");
 
+// One picture of the whole mode decision (mode_decision.hip): the split-2 level's record, whose table the unchanged
+// split2_metric_kernel fills, and what the further levels add.
+struct ModeJob {
+  Split2Job s;
+  const uint8_t *hbm[2][2];     // [reference][0: the level-1 field, 1: the level-2 field] of the block matching
+  int32_t *table;               // SCHRO_HIP_MODE_TABLE_INTS per superblock
+  uint8_t *trials;              // four SchroHipModeTrial per superblock
+  double *stats;                // mc_error, badblock_ratio, dcblock_ratio
+  int tile_base;                // the picture's first workgroup of the mode metric launch
+  int pad;
+};
+static_assert (sizeof (ModeJob) == 272, "mode decision tables");
+
 // r05: the three-level s32 Haar transform of a 4:2:2 picture with the v210 copy-out as its epilogue (iiwt_haar.hip)
 struct HaarPackJob {
   const void *src[3];           // the coefficient planes (Y, U, V), in-place sub-band layout
@@ -775,6 +788,13 @@ int launch_subpel_choose (hipStream_t stream, const SubpelChain * d_chains, int 
 int split2_metric_blocks ();
 int launch_split2_metric (hipStream_t stream, const Split2Job * d_jobs, int njobs, int total_groups);
 int launch_split2_choose (hipStream_t stream, const Split2Job * d_jobs, int njobs);
+// the whole mode decision (mode_decision.hip): the table entries of the split-1 / split-0 candidates and the zero-vector
+// trial over the superblocks of all pictures, mode_metric_units () waves per superblock and mode_metric_waves () per
+// workgroup, jobs[].tile_base laid out accordingly; then the walk, one workgroup per picture
+int mode_metric_units ();
+int mode_metric_waves ();
+int launch_mode_metric (hipStream_t stream, const ModeJob * d_jobs, int njobs, int total_groups);
+int launch_mode_choose (hipStream_t stream, const ModeJob * d_jobs, int njobs);
 int launch_convert (hipStream_t stream, const ConvertJob * d_jobs, int njobs,
     int total_tiles, int bpp);
 void convert_tile_geometry (int *tw, int *th);
@@ -1074,6 +1094,20 @@ int subpel_host_run (SchroHipContext * ctx, SchroHipSubpelChain * chains, int nc
 // pic->superblocks are not read -- all become scratch of the queue; `motion` and `superblocks` are the host outputs; waits
 // for the queue
 int split2_host_run (SchroHipContext * ctx, SchroHipSplit2Picture * pic, void *motion, void *superblocks);
+// a range of device memory a mode-decision call reads or writes, and whose it is
+struct Split2Span {
+  uintptr_t begin, end;
+  bool written;
+  int picture;
+  const char *name;
+};
+// plane_split2.cpp, for plane_mode.cpp: the refusals of one picture of the split-2 stage but for the overlaps, its kernel
+// record and its spans (`table`: the split-2 table, NULL in a stage call); nothing written overlaps anything else
+int split2_collect (const char *who, const SchroHipSplit2Picture & s, int c, bool stage, void *table, Split2Job & jb, std::vector < Split2Span > &spans);
+int split2_check_spans (const char *who, std::vector < Split2Span > &spans);
+// the frame layer's whole mode decision (plane_mode.cpp): pic->fields[r] and pic->hbm_fields[r][] are the HOST fields;
+// motion, superblocks, trials (may be NULL) and stats are the host outputs; waits for the queue
+int mode_host_run (SchroHipContext * ctx, SchroHipModePicture * pic, void *motion, void *superblocks, void *trials, double *stats);
 // v216 / ARGB / AY64 (plane_frameops.cpp)
 bool is_wide_format (int format);
 // plane_quant.cpp: schro_hip_quantise_batch; allow_empty: records of no width or height are skipped (the frame layer's
