@@ -27,31 +27,15 @@
 // The host refuses an extension under max (xbsep, ybsep): with it schro_frame_block_is_valid holds for every candidate
 // (the clamp keeps x + dx in -width0 .. width), the window has a position and contains the start vector.  The launch first
 // writes every record of every field as schro_motion_field_set (mf, split, ref + 1) leaves it.
+// That preamble, the walk, the scan with its three stores and the launch are motion_common.h's (fill_fields,
+// walk_diagonals, scan_and_store, launch_chains), shared with rough_hint.hip; the ScanRules below say where this search
+// differs.
 
-#include "schro_hip_internal.h"
-#include "scan_common.h"
-
-#include <algorithm>
-#include <climits>
+#include "motion_common.h"
 
 namespace schro {
 
-constexpr int kHbmWaves = SCHRO_HIP_ROUGH_WAVES;
-constexpr int kHbmThreads = kHbmWaves * 64;
-constexpr size_t kHbmLdsLimit = 65536;
-constexpr int kHbmMvBytes = 20; // SchroMotionVector (schromotion.h:20-37): flags, metric, chroma_metric, dx[2], dy[2]
-constexpr int kHbmMvMetric = 4, kHbmMvDx = 12, kHbmMvDy = 16;
 constexpr int kHbmSlots = 9;    // LIST_LENGTH, schrohierbm.c:191
-
-// what the wave's lanes stored in LDS is read by other lanes of the same wave: LDS serves a wave's accesses in order, the
-// compiler must not reorder them
-__device__ __forceinline__ void
-hbm_wave_sync ()
-{
-  __builtin_amdgcn_fence (__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier ();
-  __builtin_amdgcn_fence (__ATOMIC_ACQUIRE, "wavefront");
-}
 
 __device__ __forceinline__ int
 hbm_clamp (int x, int a, int b)
@@ -96,9 +80,9 @@ hbm_block (const HbmChain * ch, const HbmLevel & lv, int i, int j, uint32_t * ld
   const uint32_t tail = scan_tail_mask (bw);
   uint32_t *block = lds, *window = lds + nd * bh;
 
-  hbm_wave_sync ();             // (the block before this one is through with the LDS)
+  wave_sync ();                 // (the block before this one is through with the LDS)
   scan_stage_block (block, lv.frame[0], lv.frame_stride[0], w, h, x, y, nd, bh, tail, lane);
-  hbm_wave_sync ();
+  wave_sync ();
 
   // ---- the candidates: slot c of the list in lane c (and in lanes c + 16, c + 32, c + 48) ----
   const int c = lane & 15, rg = lane >> 4;
@@ -110,23 +94,14 @@ hbm_block (const HbmChain * ch, const HbmLevel & lv, int i, int j, uint32_t * ld
       const int ox = m == 1 ? -1 : (m == 2 ? 1 : 0), oy = m == 3 ? -1 : (m == 4 ? 1 : 0);      // :266
       const int ll = (i & mask) + ox * skip * 2, kk = (j & mask) + oy * skip * 2;
       if (ll >= 0 && ll < nbx && kk >= 0 && kk < nby)
-        rec = lv.hint + ((size_t) kk * nbx + ll) * kHbmMvBytes;
+        rec = mv_record (lv.hint, nbx, ll, kk);
     }
-  } else if (c == 6) {
-    if (i > 0)
-      rec = lv.field + ((size_t) j * nbx + (i - skip)) * kHbmMvBytes;
-  } else if (c == 7) {
-    if (j > 0)
-      rec = lv.field + ((size_t) (j - skip) * nbx + i) * kHbmMvBytes;
-  } else if (c == 8) {
-    if (i > 0 && j > 0)
-      rec = lv.field + ((size_t) (j - skip) * nbx + (i - skip)) * kHbmMvBytes;
+  } else if (c >= 6 && c <= 8) {
+    rec = mv_neighbour (lv.field, nbx, i, j, skip, c - 6);
   }
   int cdx = 0, cdy = 0;
-  if (rec) {
-    cdx = gload < int16_t > (rec + kHbmMvDx + 2 * ref);
-    cdy = gload < int16_t > (rec + kHbmMvDy + 2 * ref);
-  }
+  if (rec)
+    mv_vector (rec, ref, &cdx, &cdy);
   const bool present = c == 0 || rec != nullptr;
   // :298-321: gone when a later present entry holds the same vector (every lane of a 16-lane row holds the same list)
   bool alive = present;
@@ -170,39 +145,14 @@ hbm_block (const HbmChain * ch, const HbmLevel & lv, int i, int j, uint32_t * ld
   gx = max (-bw - x, min (w - x, gx));  // :357-358
   gy = max (-bh - y, min (h - y, gy));
 
-  // ---- schro_metric_scan_setup (schrometric.c:174-214) and the scan ----
-  const int dist = lv.range, ext = lv.ext;
-  const int ref_x = max (max (-bw, x + gx - dist), -ext), ref_y = max (max (-bh, y + gy - dist), -ext);
-  const int sw = min (min (w, x + gx + dist), w - bw + ext) - ref_x + 1;
-  const int sh = min (min (h, y + gy + dist), h - bh + ext) - ref_y + 1;
-  int dx = gx, dy = gy;
-  uint32_t metric = (uint32_t) INT_MAX;
+  // ---- the scan: the window holds the start vector, and a window without a position stores it ----
   // (ext >= max (xb, yb): 0 < sw, sh <= 2 * dist + 1 and the start vector lies inside; checked all the same -- a window
   // the LDS was not sized for is not staged)
-  if (sw > 0 && sh > 0 && sw <= 2 * dist + 1 && sh <= 2 * dist + 1) {
-    const int wd = scan_window_pitch (bw, sw) >> 2, wcols = scan_window_cols (bw, sw) >> 2;
-    scan_stage_window (window, lv.ref[0], lv.ref_stride[0], w, h, ref_x, ref_y, wd, wcols, bh + sh - 1, lane);
-    hbm_wave_sync ();
-    const uint32_t m_sh = sh > 1 ? kDivMagic.m[sh] : 0u;
-    const uint32_t best = scan_wave_min (block, window, nd, bh, wd, tail, sw * sh, sh, m_sh, (gx + x - ref_x) * sh + (gy + y - ref_y), nullptr, lane);
-    metric = best >> 11;
-    const uint32_t order = best & 2047u;
-    if (order) {
-      const int p = (int) order - 1;
-      const int pi = mdiv (p, sh, m_sh);
-      dx = ref_x + pi - x;
-      dy = ref_y + (p - pi * sh) - y;
-    }
-  }
-  if (lane == 0) {
-    uint8_t *out = lv.field + ((size_t) j * nbx + i) * kHbmMvBytes;
-    gstore < uint32_t > (out + kHbmMvMetric, metric);
-    gstore < uint16_t > (out + kHbmMvDx + 2 * ref, (uint16_t) ((uint32_t) dx << shift));
-    gstore < uint16_t > (out + kHbmMvDy + 2 * ref, (uint16_t) ((uint32_t) dy << shift));
-  }
+  const ScanRules rules = { false, false, true, false };
+  scan_and_store (lv, lv.ref[0], lv.ref_stride[0], w, h, shift, mv_record (lv.field, nbx, i, j), ref, x, y, bw, bh, gx, gy, block, window, rules, lane);
 }
 
-__global__ __launch_bounds__ (kHbmThreads)
+__global__ __launch_bounds__ (kChainThreads)
 void hier_bm_kernel (const HbmChain * __restrict__ chains, int lds_per_wave)
 {
   extern __shared__ __attribute__ ((aligned (16))) uint32_t hbm_lds[];
@@ -211,43 +161,26 @@ void hier_bm_kernel (const HbmChain * __restrict__ chains, int lds_per_wave)
   uint32_t *lds = hbm_lds + (size_t) wave * (lds_per_wave >> 2);
   const int nbx = ch->nbx, nby = ch->nby, nlevels = ch->nlevels;
 
-  // schro_motion_field_set (mf, split, ref + 1) on every field: five dwords per record, the first one pred_mode | split << 3
-  const size_t records = (size_t) nbx * nby;
-  for (int n = 0; n < nlevels; n++) {
-    uint8_t *field = ch->level[n].field;
-    const int shift = ch->level[n].shift;
-    const uint32_t flags = (uint32_t) (ch->ref + 1) | ((shift > 1 ? 0u : (shift == 1 ? 1u : 2u)) << 3);
-    for (size_t k = threadIdx.x; k < records; k += blockDim.x)
-      for (int m = 0; m < kHbmMvBytes / 4; m++)
-        gstore < uint32_t > (field + k * kHbmMvBytes + 4 * m, m == 0 ? flags : 0u);
-  }
-  __syncthreads ();
+  // schro_motion_field_set (mf, split, ref + 1): pred_mode | split << 3
+  const int ref = ch->ref;
+  fill_fields (ch, [ref](const HbmLevel & lv) {
+        return (uint32_t) (ref + 1) | ((lv.shift > 1 ? 0u : (lv.shift == 1 ? 1u : 2u)) << 3);
+      });
 
   for (int n = 0; n < nlevels; n++) {
     const HbmLevel & lv = ch->level[n];   // (read where it is used: 32 scalars held across the block would spill)
     const int shift = lv.shift;
     const int cols = (nbx + (1 << shift) - 1) >> shift, rws = (nby + (1 << shift) - 1) >> shift;       // the level's grid
-    for (int d = 0; d < cols + rws - 1; d++) {
-      const int jlo = max (0, d - (cols - 1)), jhi = min (d, rws - 1);
-      for (int bj = jlo + wave; bj <= jhi; bj += nwaves)
-        hbm_block (ch, lv, (d - bj) << shift, bj << shift, lds, lane);
-      __syncthreads ();         // the next diagonal reads this one's records
-    }
+    walk_diagonals (cols, rws, wave, nwaves, [&](int bi, int bj) {
+          hbm_block (ch, lv, bi << shift, bj << shift, lds, lane);
+        });
   }
 }
 
 int
 launch_hier_bm (hipStream_t stream, const HbmChain * d_chains, int nchains, size_t lds_per_wave)
 {
-  if (lds_per_wave > kHbmLdsLimit)
-    return set_error (SCHRO_HIP_EINVAL, "block matching launch: %zu bytes of LDS per wave", lds_per_wave);
-  // as many waves as the workgroup's LDS holds, and at least one
-  const int waves = lds_per_wave ? (int) std::min < size_t > (kHbmWaves, kHbmLdsLimit / lds_per_wave) : kHbmWaves;
-  SCHRO_LAUNCH (hier_bm_kernel, dim3 (nchains), dim3 (waves * 64), lds_per_wave * waves, stream, d_chains, (int) lds_per_wave);
-  hipError_t e = hipGetLastError ();
-  if (e != hipSuccess)
-    return set_error (SCHRO_HIP_EDEVICE, "block matching launch: %s", hipGetErrorString (e));
-  return 0;
+  return launch_chains (hier_bm_kernel, "block matching", stream, d_chains, nchains, lds_per_wave);
 }
 
 }                               // namespace schro

@@ -24,7 +24,7 @@
 // (tests/test_mode_ref.py shows it) and are not written; the trial stops at its first invalid quadrant.  After the last
 // diagonal the workgroup counts the bad and the DC blocks and one lane sums mc_error in raster order of superblocks.
 // No workgroup waits for another; every loop is bounded by the geometry; rows and columns of every image read are
-// clamped (split2_tap), whatever a field holds.
+// clamped (tap, motion_common.h), whatever a field holds.
 
 #include "mode_common.h"
 
@@ -71,7 +71,7 @@ mode_sad_share (const Split2Job * jb, int ref, int k, int x0, int y0, int w, int
   for (int u = lane; u < segs * h; u += 64) {
     const int r = u / segs, seg = u - r * segs;
     const int tx = x0 + 16 * seg, ty = y0 + r, valid = w - 16 * seg;
-    const u32x4 pred = split2_predict (jb->up[ref][pair ? c : k], jb->up_stride[c], tw, th, (tx << mvprec) + (vx >> hs), (ty << mvprec) + (vy >> vs),
+    const u32x4 pred = predict (jb->up[ref][pair ? c : k], jb->up_stride[c], tw, th, (tx << mvprec) + (vx >> hs), (ty << mvprec) + (vy >> vs),
         mvprec, k ? pair : 0, k == 2);
 #pragma unroll
     for (int d = 0; d < 4; d++) {
@@ -114,16 +114,16 @@ mode_biref (const Split2Job * jb, int x, int y, int scale, int vx0, int vy0, int
       const bool from_v = corner || (shared && k == 1);
       u32x4 both = { 0, 0, 0, 0 };
       if (!(shared && k == 1)) {
-        const u32x4 pred0 = split2_predict (jb->up[0][pair ? c : k], up_stride, tw, th, (tx << mvprec) + (vx0 >> hs), (ty << mvprec) + (vy0 >> vs), mvprec,
+        const u32x4 pred0 = predict (jb->up[0][pair ? c : k], up_stride, tw, th, (tx << mvprec) + (vx0 >> hs), (ty << mvprec) + (vy0 >> vs), mvprec,
             k ? pair : 0, k == 2);
-        const u32x4 pred1 = split2_predict (jb->up[1][pair ? c : k], up_stride, tw, th, (tx << mvprec) + (vx1 >> hs), (ty << mvprec) + (vy1 >> vs), mvprec,
+        const u32x4 pred1 = predict (jb->up[1][pair ? c : k], up_stride, tw, th, (tx << mvprec) + (vx1 >> hs), (ty << mvprec) + (vy1 >> vs), mvprec,
             k ? pair : 0, k == 2);
         both = split2_average (pred0, pred1);
       }
       if (from_v) {
         const int xv = (xo1 + 16 * seg) << mvprec, yv = (yo1 + r) << mvprec;
-        const u32x4 other0 = split2_predict (jb->up[0][pair ? 1 : 2], jb->up_stride[1], w1, h1, xv + (vx0 >> jb->hs), yv + (vy0 >> jb->vs), mvprec, pair, 1);
-        const u32x4 other1 = split2_predict (jb->up[1][pair ? 1 : 2], jb->up_stride[1], w1, h1, xv + (vx1 >> jb->hs), yv + (vy1 >> jb->vs), mvprec, pair, 1);
+        const u32x4 other0 = predict (jb->up[0][pair ? 1 : 2], jb->up_stride[1], w1, h1, xv + (vx0 >> jb->hs), yv + (vy0 >> jb->vs), mvprec, pair, 1);
+        const u32x4 other1 = predict (jb->up[1][pair ? 1 : 2], jb->up_stride[1], w1, h1, xv + (vx1 >> jb->hs), yv + (vy1 >> jb->vs), mvprec, pair, 1);
         const u32x4 v = split2_average (other0, other1);
         const int nv = k ? 16 : bw1 - 16 * seg; // V's samples of this segment
 #pragma unroll
@@ -146,14 +146,6 @@ mode_biref (const Split2Job * jb, int x, int y, int scale, int vx0, int vy0, int
   *luma = split2_wave_sum (bi_luma);
   *chroma = split2_wave_sum (bi_chroma);
   return true;
-}
-
-// dx[ref], dy[ref] of the record at p
-__device__ __forceinline__ void
-mode_field_vector (const uint8_t * p, int ref, int *vx, int *vy)
-{
-  *vx = gload < int16_t > (p + 12 + 2 * ref);
-  *vy = gload < int16_t > (p + 16 + 2 * ref);
 }
 
 __global__ __launch_bounds__ (kModeThreads)
@@ -190,13 +182,13 @@ void mode_metric_kernel (const ModeJob * __restrict__ jobs, int njobs)
   if (c < kM_Level2) {
     const int x = i + 2 * (q & 1), y = j + 2 * (q >> 1);
     if (m < kM_Level1)
-      mode_field_vector (jb->field[ref] + ((size_t) (y + (m >> 1)) * nbx + x + (m & 1)) * 20, ref, &vx, &vy);
+      mv_vector (mv_record (jb->field[ref], nbx, x + (m & 1), y + (m >> 1)), ref, &vx, &vy);
     else {
-      mode_field_vector (mj->hbm[ref][0] + ((size_t) y * nbx + x) * 20, ref, &vx, &vy);
+      mv_vector (mv_record (mj->hbm[ref][0], nbx, x, y), ref, &vx, &vy);
       vx = (int16_t) (vx * (1 << mvprec)), vy = (int16_t) (vy * (1 << mvprec));
     }
   } else if (c == kM_Level2) {
-    mode_field_vector (mj->hbm[ref][1] + ((size_t) j * nbx + i) * 20, ref, &vx, &vy);
+    mv_vector (mv_record (mj->hbm[ref][1], nbx, i, j), ref, &vx, &vy);
     vx = (int16_t) (vx * (1 << mvprec)), vy = (int16_t) (vy * (1 << mvprec));
   }
   const int w0 = jb->w, h0 = jb->h, w1 = jb->cw, h1 = jb->ch;
@@ -245,7 +237,7 @@ void mode_metric_kernel (const ModeJob * __restrict__ jobs, int njobs)
 // a superblock's working state, one per wave
 struct ModeWork {
   uint32_t w[16][3];            // the records its own blocks are seen as: flags, dx[0] | dx[1] << 16, dy[0] | dy[1] << 16
-  uint32_t b[16][5];            // block.mv: what the split-2 level decided
+  uint32_t b[16][kMvDwords];    // block.mv: what the split-2 level decided
   int error[16], entropy[16];   // ... and its best_error, best_entropy per block
 };
 
@@ -254,17 +246,21 @@ struct ModeRecords {
   const uint8_t *motion;
   int nbx, sx, sy;
   const ModeWork *work;
-  __device__ __forceinline__ void operator () (int x, int y, uint32_t * flags, uint32_t * dx, uint32_t * dy) const
+  __device__ __forceinline__ void raw (int x, int y, uint32_t * flags, uint32_t * dx, uint32_t * dy) const
   {
     if ((x >> 2) == sx && (y >> 2) == sy) {
       const int n = (y & 3) * 4 + (x & 3);
       *flags = work->w[n][0], *dx = work->w[n][1], *dy = work->w[n][2];
     } else {
-      const uint8_t *mv = motion + ((size_t) y * nbx + x) * 20;
-      *flags = gload < uint32_t > (mv);
-      *dx = gload < uint32_t > (mv + 12);
-      *dy = gload < uint32_t > (mv + 16);
+      const GlobalRecords field = { motion, nbx };
+      field.raw (x, y, flags, dx, dy);
     }
+  }
+  __device__ __forceinline__ bool operator () (int x, int y, int mode, int *vx, int *vy) const
+  {
+    uint32_t flags, dx, dy;
+    raw (x, y, &flags, &dx, &dy);
+    return mv_predicts (flags, dx, dy, mode, vx, vy);
   }
 };
 
@@ -276,16 +272,16 @@ mode_mode_prediction (const ModeRecords & get, int x, int y)
   if (y == 0) {
     if (x == 0)
       return 0;
-    get (x - 1, 0, &a, &dx, &dy);
+    get.raw (x - 1, 0, &a, &dx, &dy);
     return (int) (a & 3);
   }
   if (x == 0) {
-    get (0, y - 1, &a, &dx, &dy);
+    get.raw (0, y - 1, &a, &dx, &dy);
     return (int) (a & 3);
   }
-  get (x - 1, y, &a, &dx, &dy);
-  get (x, y - 1, &b, &dx, &dy);
-  get (x - 1, y - 1, &c, &dx, &dy);
+  get.raw (x - 1, y, &a, &dx, &dy);
+  get.raw (x, y - 1, &b, &dx, &dy);
+  get.raw (x - 1, y - 1, &c, &dx, &dy);
   a &= 3, b &= 3, c &= 3;
   return (int) ((a & b) | (b & c) | (c & a));
 }
@@ -301,9 +297,9 @@ mode_entropy (const ModeRecords & get, int x, int y, const Split2Record & mv, in
   for (int mode = 1; mode <= 2; mode++)
     if (modes & mode) {
       int px, py;
-      split2_vector_prediction (get, x, y, mode, &px, &py);
+      vector_prediction (get, x, y, mode, &px, &py);
       const int dx = (int16_t) (mv.w[3] >> (16 * (mode - 1))), dy = (int16_t) (mv.w[4] >> (16 * (mode - 1)));
-      entropy += split2_estimate_sint (dx - px) + split2_estimate_sint (dy - py);
+      entropy += estimate_sint (dx - px) + estimate_sint (dy - py);
     }
   return entropy;
 }
@@ -464,7 +460,7 @@ mode_superblock (const ModeJob * mj, ModeWork * work, int sx, int sy, int lane)
       if (mode != 1 && mode != 2)
         mode = 1;
       int px, py;
-      split2_vector_prediction (get, x, y, 1, &px, &py);
+      vector_prediction (get, x, y, 1, &px, &py);
       best = { {0x08u | (uint32_t) mode, 0, 0, ((uint32_t) px & 0xffffu) << (16 * (mode - 1)), ((uint32_t) py & 0xffffu) << (16 * (mode - 1))} };
       total_entropy += 2;
       mf[0][q] = { {0x09u, 0, 0, 0, 0} };
@@ -484,8 +480,8 @@ mode_superblock (const ModeJob * mj, ModeWork * work, int sx, int sy, int lane)
         h.n = 0;
 #pragma unroll
         for (int m = 0; m < 4; m++)
-          mode_hint_add (h, split2_load (jb->field[ref] + ((size_t) (y + (m >> 1)) * nbx + x + (m & 1)) * 20), 5 * q + m, ref, mvprec, 0);
-        mode_hint_add (h, split2_load (mj->hbm[ref][0] + ((size_t) y * nbx + x) * 20), 5 * q + kM_Level1, ref, mvprec, mvprec);
+          mode_hint_add (h, split2_load (mv_record (jb->field[ref], nbx, x + (m & 1), y + (m >> 1))), 5 * q + m, ref, mvprec, 0);
+        mode_hint_add (h, split2_load (mv_record (mj->hbm[ref][0], nbx, x, y)), 5 * q + kM_Level1, ref, mvprec, mvprec);
         one[ref] = mode_best_hint (h, table + ref * kM_RefInts, get, x, y, ref, 1, q, lambda);
         if (one[ref].valid) {
           mf[ref][q] = one[ref].mv;
@@ -562,7 +558,7 @@ mode_superblock (const ModeJob * mj, ModeWork * work, int sx, int sy, int lane)
 #pragma unroll
       for (int q = 0; q < 4; q++)
         mode_hint_add (h, mf[ref][q], mf_slot[ref][q], ref, 0, 0);        // (the slot of the quadrant's winner in the table)
-      mode_hint_add (h, split2_load (mj->hbm[ref][1] + ((size_t) j * nbx + i) * 20), kM_Level2, ref, mvprec, mvprec);
+      mode_hint_add (h, split2_load (mv_record (mj->hbm[ref][1], nbx, i, j)), kM_Level2, ref, mvprec, mvprec);
       one[ref] = mode_best_hint (h, table + ref * kM_RefInts, get, i, j, ref, 0, 0, lambda);
       if (one[ref].valid) {
         const double score = (double) one[ref].entropy + lambda * (double) one[ref].error;
@@ -627,7 +623,7 @@ mode_superblock (const ModeJob * mj, ModeWork * work, int sx, int sy, int lane)
     Split2Record rec;
     if (winner == 0) {
 #pragma unroll
-      for (int n = 0; n < 5; n++)
+      for (int n = 0; n < kMvDwords; n++)
         rec.w[n] = work->b[lane][n];
     } else if (winner == 1) {
       const int q = (ii >> 1) + 2 * (jj >> 1);
@@ -638,10 +634,7 @@ mode_superblock (const ModeJob * mj, ModeWork * work, int sx, int sy, int lane)
           rec = quad[k];
     } else
       rec = winner == 2 ? split0_rec : zero_rec;
-    uint8_t *p = jb->motion + ((size_t) (j + jj) * nbx + i + ii) * 20;
-#pragma unroll
-    for (int n = 0; n < 5; n++)
-      gstore < uint32_t > (p + 4 * n, rec.w[n]);
+    split2_store (mv_record (jb->motion, nbx, i + ii, j + jj), rec);
   }
   if (lane == 0) {
     ModeTrial won = trial[0];
@@ -685,7 +678,7 @@ void mode_choose_kernel (const ModeJob * __restrict__ jobs)
             rec = split2_block_trial (jb, get, x, y, &error, &entropy);
           }
 #pragma unroll
-          for (int n = 0; n < 5; n++)
+          for (int n = 0; n < kMvDwords; n++)
             work->b[lane][n] = rec.w[n];
           work->w[lane][0] = rec.w[0], work->w[lane][1] = rec.w[3], work->w[lane][2] = rec.w[4];
           work->error[lane] = error, work->entropy[lane] = entropy;
@@ -705,7 +698,7 @@ void mode_choose_kernel (const ModeJob * __restrict__ jobs)
   const int block_size = 16 * jb->xb * jb->yb * 2 / 3;
   int bad = 0, dc = 0;
   for (int n = (int) threadIdx.x; n < nbx * nby; n += (int) blockDim.x)
-    dc += (gload < uint32_t > (jb->motion + (size_t) n * 20) & 3u) == 0;
+    dc += (gload < uint32_t > (jb->motion + (size_t) n * kMvBytes + kMvFlags) & 3u) == 0;
   for (int s = (int) threadIdx.x; s < nsb; s += (int) blockDim.x)
     bad += gload < int32_t > ((const int32_t *) (jb->sb + (size_t) s * 16)) > 10 * block_size;
   if (dc)

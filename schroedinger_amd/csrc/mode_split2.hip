@@ -34,6 +34,9 @@
 // origin lies outside the picture takes no part in the walk: its final record is the constant best_mv, and no block inside
 // the picture has such a neighbour (i * xbsep < width implies (i - 1) * xbsep < width), so the record the reference keeps
 // for it while its superblock is worked on reaches only other outside records and never the result.
+//
+// The prediction of a row segment (predict), the vector prediction over the final field (GlobalRecords) and the walk over
+// the anti-diagonals are motion_common.h's; the trial of a block is mode_common.h's.
 
 #include "mode_common.h"
 
@@ -86,13 +89,10 @@ void split2_metric_kernel (const Split2Job * __restrict__ jobs, int njobs)
   const int bw0 = min (bx0, w0 - xo0), bh0 = min (by0, h0 - yo0);
   const int bw1 = max (min (bx1, w1 - xo1), 0), bh1 = max (min (by1, h1 - yo1), 0);
   // the vectors: dx[0], dy[0] of field 0 and dx[1], dy[1] of field 1
-  const uint8_t *rec0 = jb->field[0] + (size_t) blk * 20;
-  const int vx0 = gload < int16_t > (rec0 + 12), vy0 = gload < int16_t > (rec0 + 16);
-  int vx1 = 0, vy1 = 0;
-  if (nrefs == 2) {
-    const uint8_t *rec1 = jb->field[1] + (size_t) blk * 20;
-    vx1 = gload < int16_t > (rec1 + 14), vy1 = gload < int16_t > (rec1 + 18);
-  }
+  int vx0, vy0, vx1 = 0, vy1 = 0;
+  mv_vector (mv_record (jb->field[0], nbx, i, j), 0, &vx0, &vy0);
+  if (nrefs == 2)
+    mv_vector (mv_record (jb->field[1], nbx, i, j), 1, &vx1, &vy1);
   // the bi-reference trial's admissibility: luma, the clipped block, the unscaled extension
   bool bi = nrefs == 2;
 #pragma unroll
@@ -131,15 +131,15 @@ void split2_metric_kernel (const Split2Job * __restrict__ jobs, int njobs)
     const bool from_v = bi && (corner || (shared && k == 1));
     const int up_stride = jb->up_stride[c];
     u32x4 pred0, pred1 = { 0, 0, 0, 0 }, other0 = pred1, other1 = pred1;
-    pred0 = split2_predict (jb->up[0][pair ? c : k], up_stride, tw, th, (tx << mvprec) + (vx0 >> hs), (ty << mvprec) + (vy0 >> vs), mvprec,
+    pred0 = predict (jb->up[0][pair ? c : k], up_stride, tw, th, (tx << mvprec) + (vx0 >> hs), (ty << mvprec) + (vy0 >> vs), mvprec,
         k ? pair : 0, k == 2);
     if (nrefs == 2)
-      pred1 = split2_predict (jb->up[1][pair ? c : k], up_stride, tw, th, (tx << mvprec) + (vx1 >> hs), (ty << mvprec) + (vy1 >> vs), mvprec,
+      pred1 = predict (jb->up[1][pair ? c : k], up_stride, tw, th, (tx << mvprec) + (vx1 >> hs), (ty << mvprec) + (vy1 >> vs), mvprec,
           k ? pair : 0, k == 2);
     if (from_v) {
       const int xv = (xo1 + 16 * a.seg) << mvprec, yv = (yo1 + a.r) << mvprec;
-      other0 = split2_predict (jb->up[0][pair ? 1 : 2], jb->up_stride[1], w1, h1, xv + (vx0 >> jb->hs), yv + (vy0 >> jb->vs), mvprec, pair, 1);
-      other1 = split2_predict (jb->up[1][pair ? 1 : 2], jb->up_stride[1], w1, h1, xv + (vx1 >> jb->hs), yv + (vy1 >> jb->vs), mvprec, pair, 1);
+      other0 = predict (jb->up[0][pair ? 1 : 2], jb->up_stride[1], w1, h1, xv + (vx0 >> jb->hs), yv + (vy0 >> jb->vs), mvprec, pair, 1);
+      other1 = predict (jb->up[1][pair ? 1 : 2], jb->up_stride[1], w1, h1, xv + (vx1 >> jb->hs), yv + (vy1 >> jb->vs), mvprec, pair, 1);
     }
     if (k) {
 #pragma unroll
@@ -226,14 +226,9 @@ __device__ __forceinline__ void
 split2_choose_block (const Split2Job * jb, int i, int j)
 {
   const int nbx = jb->nbx;
-  const size_t blk = (size_t) j * nbx + i;
-  uint8_t *rec = jb->motion + blk * 20;
-  const Split2GlobalRecords get = { jb->motion, nbx };
+  const GlobalRecords get = { jb->motion, nbx };
   int best_error, best_entropy;
-  const Split2Record best = split2_block_trial (jb, get, i, j, &best_error, &best_entropy);
-#pragma unroll
-  for (int n = 0; n < 5; n++)
-    gstore < uint32_t > (rec + 4 * n, best.w[n]);
+  split2_store (mv_record (jb->motion, nbx, i, j), split2_block_trial (jb, get, i, j, &best_error, &best_entropy));
   int32_t *sb = (int32_t *) (jb->sb + ((size_t) (j >> 2) * (nbx >> 2) + (i >> 2)) * 16);
   atomicAdd (sb, best_error);
   atomicAdd (sb + 1, best_entropy);
@@ -257,21 +252,14 @@ void split2_choose_kernel (const Split2Job * __restrict__ jobs)
   // ... and their records are the constant best_mv: split 2, pred_mode 1, everything else 0
   for (int n = (int) threadIdx.x; n < nbx * nby; n += (int) blockDim.x) {
     const int j = n / nbx, i = n - j * nbx;
-    if (i >= cols || j >= rws) {
-      uint8_t *rec = jb->motion + (size_t) n * 20;
-#pragma unroll
-      for (int k = 0; k < 5; k++)
-        gstore < uint32_t > (rec + 4 * k, k ? 0u : 0x11u);
-    }
+    if (i >= cols || j >= rws)
+      split2_store (mv_record (jb->motion, nbx, i, j), Split2Record { {0x11u, 0, 0, 0, 0} });
   }
   __threadfence ();
   __syncthreads ();
-  for (int d = 0; d < cols + rws - 1; d++) {
-    const int jlo = max (0, d - (cols - 1)), jhi = min (d, rws - 1);
-    for (int j = jlo + (int) threadIdx.x; j <= jhi; j += (int) blockDim.x)
-      split2_choose_block (jb, d - j, j);
-    __syncthreads ();           // the next diagonal reads this one's records
-  }
+  walk_diagonals (cols, rws, (int) threadIdx.x, (int) blockDim.x, [&](int i, int j) {
+        split2_choose_block (jb, i, j);
+      });
   __threadfence ();
   __syncthreads ();
   // block->score = total_entropy + lambda * total_error

@@ -14,40 +14,14 @@ using namespace schro;
 
 namespace {
 
-constexpr int kMaxPlaneSize = 1 << 16;
-constexpr int kMaxExtension = 1024;
-constexpr int kMaxBlocks = 1 << 14;
 constexpr int kMaxRange = (SCHRO_HIP_LIMIT_METRIC_SCAN - 1) / 2;        // a window of 2 * h_range + 1 positions
 constexpr int kMaxShift = SCHRO_HIP_MAX_HIER_LEVELS;
-constexpr size_t kMvBytes = 20; // SchroMotionVector (schromotion.h:20-37)
-
-struct Geometry {
-  int nbx, nby, xb, yb, ref;
-};
-
-// a range of device memory a launch reads or writes, and whose it is
-struct Span {
-  uintptr_t begin, end;
-  bool written;
-  int chain, level;
-};
-
-// the refusals that do not depend on the level: `who` names the call, `what` the chain or the entry
-int
-check_geometry (const char *who, const char *what, int c, const Geometry & g)
-{
-  SCHRO_HIP_REQUIRE (g.nbx > 0 && g.nby > 0 && g.nbx <= kMaxBlocks && g.nby <= kMaxBlocks, "%s: %s %d: %d x %d blocks", who, what, c,
-      g.nbx, g.nby);
-  SCHRO_HIP_REQUIRE (g.xb > 0 && g.yb > 0 && g.xb <= SCHRO_HIP_LIMIT_BLOCK_SIZE && g.yb <= SCHRO_HIP_LIMIT_BLOCK_SIZE,
-      "%s: %s %d: a block of %d x %d is outside 1 .. %d", who, what, c, g.xb, g.yb, SCHRO_HIP_LIMIT_BLOCK_SIZE);
-  SCHRO_HIP_REQUIRE (g.ref == 0 || g.ref == 1, "%s: %s %d: reference %d is neither 0 nor 1", who, what, c, g.ref);
-  return 0;
-}
+const char *const kField = "the field", *const kInput = "a plane or hint field";
 
 // one level of a chain into the kernel's record, its memory into `spans`
 int
-add_level (const char *who, const char *what, int c, int shift, const SchroHipHbmPlane & pl, const Geometry & g, int range,
-    const void *hint, void *field, HbmLevel * out, std::vector < Span > &spans)
+add_level (const char *who, const char *what, int c, int shift, const SchroHipHbmPlane & pl, const MotionGeometry & g, int range,
+    const void *hint, void *field, HbmLevel * out, std::vector < MotionSpan > &spans)
 {
   SCHRO_HIP_REQUIRE (shift >= 0 && shift <= kMaxShift, "%s: %s %d level %d: the shift of a level is 0 .. %d", who, what, c, shift, kMaxShift);
   SCHRO_HIP_REQUIRE ((pl.h_shift == 0 || pl.h_shift == 1) && (pl.v_shift == 0 || pl.v_shift == 1) && pl.v_shift <= pl.h_shift,
@@ -56,13 +30,13 @@ add_level (const char *who, const char *what, int c, int shift, const SchroHipHb
     SCHRO_HIP_REQUIRE (pl.frame[k] && pl.ref[k], "%s: %s %d level %d: component %d has a NULL pointer%s", who, what, c, shift, k,
         k ? " (the metric runs over the chroma planes too)" : "");
   SCHRO_HIP_REQUIRE (field, "%s: %s %d level %d: the field is a NULL pointer", who, what, c, shift);
-  SCHRO_HIP_REQUIRE (pl.width > 0 && pl.height > 0 && pl.width <= kMaxPlaneSize && pl.height <= kMaxPlaneSize,
+  SCHRO_HIP_REQUIRE (pl.width > 0 && pl.height > 0 && pl.width <= kMaxMotionPlaneSize && pl.height <= kMaxMotionPlaneSize,
       "%s: %s %d level %d: plane size %dx%d out of range", who, what, c, shift, pl.width, pl.height);
   const int cw = (pl.width + (1 << pl.h_shift) - 1) >> pl.h_shift, chh = (pl.height + (1 << pl.v_shift) - 1) >> pl.v_shift;
   for (int k = 0; k < 3; k++)
     SCHRO_HIP_REQUIRE (pl.frame_stride[k] >= (k ? cw : pl.width) && pl.ref_stride[k] >= (k ? cw : pl.width),
         "%s: %s %d level %d: component %d has a stride shorter than a row of %d", who, what, c, shift, k, k ? cw : pl.width);
-  SCHRO_HIP_REQUIRE (pl.extension >= 0 && pl.extension <= kMaxExtension, "%s: %s %d level %d: extension %d out of range", who, what, c, shift,
+  SCHRO_HIP_REQUIRE (pl.extension >= 0 && pl.extension <= kMaxMotionExtension, "%s: %s %d level %d: extension %d out of range", who, what, c, shift,
       pl.extension);
   // schro_metric_block_sad_slow returns INT_MAX for a block outside the apron, the caller asserts when every candidate
   // does (schrohierbm.c:347): neither happens from this extension on
@@ -81,8 +55,8 @@ add_level (const char *who, const char *what, int c, int shift, const SchroHipHb
     out->frame_stride[k] = pl.frame_stride[k];
     out->ref_stride[k] = pl.ref_stride[k];
     const size_t row = k ? cw : pl.width, rows = k ? chh : pl.height;
-    spans.push_back ({(uintptr_t) pl.frame[k], (uintptr_t) pl.frame[k] + (size_t) pl.frame_stride[k] * (rows - 1) + row, false, c, shift});
-    spans.push_back ({(uintptr_t) pl.ref[k], (uintptr_t) pl.ref[k] + (size_t) pl.ref_stride[k] * (rows - 1) + row, false, c, shift});
+    spans.push_back ({(uintptr_t) pl.frame[k], (uintptr_t) pl.frame[k] + (size_t) pl.frame_stride[k] * (rows - 1) + row, false, c, shift, kInput});
+    spans.push_back ({(uintptr_t) pl.ref[k], (uintptr_t) pl.ref[k] + (size_t) pl.ref_stride[k] * (rows - 1) + row, false, c, shift, kInput});
   }
   out->field = (uint8_t *) field;
   out->hint = (const uint8_t *) hint;
@@ -92,42 +66,9 @@ add_level (const char *who, const char *what, int c, int shift, const SchroHipHb
   out->vs = pl.v_shift;
   out->ext = pl.extension;
   out->shift = shift;
-  out->range = range;
-  spans.push_back ({(uintptr_t) field, (uintptr_t) field + bytes, true, c, shift});
+  out->dist = range;
+  spans.push_back ({(uintptr_t) field, (uintptr_t) field + bytes, true, c, shift, kField});
   return 0;
-}
-
-// no field overlaps another field or anything the launch reads (a field of another workgroup's, most of all)
-int
-check_spans (const char *who, const char *what, std::vector < Span > &spans)
-{
-  std::sort (spans.begin (), spans.end (), [](const Span & a, const Span & b) {
-        return a.begin < b.begin;}
-  );
-  const Span *any = nullptr, *written = nullptr;        // the spans seen so far that end last
-  for (const Span & s:spans) {
-    const Span *hit = s.written ? any : written;
-    SCHRO_HIP_REQUIRE (!hit || hit->end <= s.begin, "%s: %s %d level %d: %s overlaps %s of %s %d level %d", who, what, s.chain, s.level,
-        s.written ? "the field" : "a plane or hint field", hit && hit->written ? "the field" : "a plane or hint field", what,
-        hit ? hit->chain : 0, hit ? hit->level : 0);
-    if (!any || s.end > any->end)
-      any = &s;
-    if (s.written && (!written || s.end > written->end))
-      written = &s;
-  }
-  return 0;
-}
-
-// LDS bytes a wave of the launch needs: the largest block and window of any level
-size_t
-chain_lds (const HbmChain & ch)
-{
-  size_t lds = 0;
-  for (int n = 0; n < ch.nlevels; n++) {
-    const int span = 2 * ch.level[n].range + 1;
-    lds = std::max (lds, scan_lds_bytes (ch.xb, ch.yb, span, span));
-  }
-  return lds;
 }
 
 int
@@ -136,12 +77,12 @@ build_levels (const SchroHipHbmLevel * levels, int nlevels, std::vector < HbmCha
   const char *who = "hbm_level_batch", *what = "entry";
   SCHRO_HIP_REQUIRE (levels && nlevels > 0, "%s: bad arguments", who);
   SCHRO_HIP_REQUIRE (nlevels <= kMaxJobs, "%s: at most %d entries per call", who, kMaxJobs);
-  std::vector < Span > spans;
+  std::vector < MotionSpan > spans;
   chains.resize (nlevels);
   for (int p = 0; p < nlevels; p++) {
     const SchroHipHbmLevel & lv = levels[p];
-    const Geometry g = { lv.x_num_blocks, lv.y_num_blocks, lv.xbsep_luma, lv.ybsep_luma, lv.ref_index };
-    int r = check_geometry (who, what, p, g);
+    const MotionGeometry g = { lv.x_num_blocks, lv.y_num_blocks, lv.xbsep_luma, lv.ybsep_luma, lv.ref_index };
+    int r = motion_check_geometry (who, what, p, g, SCHRO_HIP_LIMIT_BLOCK_SIZE);
     if (r)
       return r;
     HbmChain & ch = chains[p];
@@ -152,9 +93,9 @@ build_levels (const SchroHipHbmLevel * levels, int nlevels, std::vector < HbmCha
     if (r)
       return r;
     if (lv.hint_field)
-      spans.push_back ({(uintptr_t) lv.hint_field, (uintptr_t) lv.hint_field + (size_t) g.nbx * g.nby * kMvBytes, false, p, lv.shift});
+      spans.push_back ({(uintptr_t) lv.hint_field, (uintptr_t) lv.hint_field + (size_t) g.nbx * g.nby * kMvBytes, false, p, lv.shift, kInput});
   }
-  return check_spans (who, what, spans);
+  return motion_check_spans (who, what, spans);
 }
 
 int
@@ -163,12 +104,12 @@ build_chains (const SchroHipHbmChain * in, int nchains, int with_level0, std::ve
   const char *who = "hbm_batch", *what = "chain";
   SCHRO_HIP_REQUIRE (in && nchains > 0, "%s: bad arguments", who);
   SCHRO_HIP_REQUIRE (nchains <= kMaxJobs, "%s: at most %d chains per call", who, kMaxJobs);
-  std::vector < Span > spans;
+  std::vector < MotionSpan > spans;
   chains.resize (nchains);
   for (int c = 0; c < nchains; c++) {
     const SchroHipHbmChain & src = in[c];
-    const Geometry g = { src.x_num_blocks, src.y_num_blocks, src.xbsep_luma, src.ybsep_luma, src.ref_index };
-    int r = check_geometry (who, what, c, g);
+    const MotionGeometry g = { src.x_num_blocks, src.y_num_blocks, src.xbsep_luma, src.ybsep_luma, src.ref_index };
+    int r = motion_check_geometry (who, what, c, g, SCHRO_HIP_LIMIT_BLOCK_SIZE);
     if (r)
       return r;
     SCHRO_HIP_REQUIRE (src.n_levels >= 1 && src.n_levels <= SCHRO_HIP_MAX_HIER_LEVELS, "%s: %s %d: %d levels, outside 1 .. %d", who, what, c,
@@ -200,21 +141,7 @@ build_chains (const SchroHipHbmChain * in, int nchains, int with_level0, std::ve
         return r;
     }
   }
-  return check_spans (who, what, spans);
-}
-
-int
-run_chains (SchroHipContext * ctx, const std::vector < HbmChain > &chains)
-{
-  size_t lds = 0;
-  for (const HbmChain & ch:chains)
-    lds = std::max (lds, chain_lds (ch));
-  (void) hipSetDevice (ctx->device);
-  void *dev;
-  int r = push_big_table (ctx, chains.data (), sizeof (HbmChain) * chains.size (), &dev);
-  if (r)
-    return r;
-  return launch_hier_bm (ctx->stream, (const HbmChain *) dev, (int) chains.size (), lds);
+  return motion_check_spans (who, what, spans);
 }
 
 }                               // namespace
@@ -225,8 +152,8 @@ int
 hbm_host_run (SchroHipContext * ctx, const char *who, const SchroHipHbmPlane * levels, int nlevels, int shift, int h_range, int with_level0,
     const SchroHipParams * params, int ref_index, const void *hint, void *const *fields)
 {
-  SCHRO_HIP_REQUIRE (params->x_num_blocks > 0 && params->y_num_blocks > 0 && params->x_num_blocks <= kMaxBlocks
-      && params->y_num_blocks <= kMaxBlocks, "%s: %d x %d blocks", who, params->x_num_blocks, params->y_num_blocks);
+  SCHRO_HIP_REQUIRE (params->x_num_blocks > 0 && params->y_num_blocks > 0 && params->x_num_blocks <= kMaxMotionBlocks
+      && params->y_num_blocks <= kMaxMotionBlocks, "%s: %d x %d blocks", who, params->x_num_blocks, params->y_num_blocks);
   const size_t bytes = (size_t) params->x_num_blocks * params->y_num_blocks * kMvBytes, slot = round_up (bytes, 256);
   (void) hipSetDevice (ctx->device);
   if (h_range > 0) {

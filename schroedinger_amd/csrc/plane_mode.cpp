@@ -13,7 +13,6 @@ using namespace schro;
 
 namespace {
 
-constexpr size_t kMvBytes = 20;
 constexpr size_t kSbBytes = 16;
 constexpr size_t kTrialBytes = 4 * sizeof (SchroHipModeTrial);  // per superblock
 constexpr size_t kEntry2Bytes = SCHRO_HIP_SPLIT2_TABLE_INTS * sizeof (int32_t);        // per block
@@ -26,7 +25,7 @@ build_jobs (const char *who, const SchroHipModePicture * in, int n, void *const 
 {
   SCHRO_HIP_REQUIRE (in && n > 0, "%s: bad arguments", who);
   SCHRO_HIP_REQUIRE (n <= kMaxJobs, "%s: at most %d pictures per call", who, kMaxJobs);
-  std::vector < Split2Span > spans;
+  std::vector < MotionSpan > spans;
   out.resize (n);
   for (int c = 0; c < n; c++) {
     const SchroHipModePicture & p = in[c];
@@ -47,23 +46,23 @@ build_jobs (const char *who, const SchroHipModePicture * in, int n, void *const 
         const void *f = p.hbm_fields[ref][level];
         SCHRO_HIP_REQUIRE (f, "%s: picture %d: the level-%d field of reference %d is a NULL pointer", who, c, level + 1, ref);
         SCHRO_HIP_REQUIRE (((uintptr_t) f & 3) == 0, "%s: picture %d: the level-%d field of reference %d is not 4-byte aligned", who, c, level + 1, ref);
-        spans.push_back ({(uintptr_t) f, (uintptr_t) f + records * kMvBytes, false, c, level ? "a level-2 field" : "a level-1 field"});
+        spans.push_back ({(uintptr_t) f, (uintptr_t) f + records * kMvBytes, false, c, -1, level ? "a level-2 field" : "a level-1 field"});
         mj.hbm[ref][level] = (const uint8_t *) f;
       }
     SCHRO_HIP_REQUIRE (p.trials && p.stats, "%s: picture %d: the trial table or the statistics are a NULL pointer", who, c);
     SCHRO_HIP_REQUIRE (((uintptr_t) p.trials & 7) == 0 && ((uintptr_t) p.stats & 7) == 0, "%s: picture %d: the trial table or the statistics are not 8-byte aligned",
         who, c);
-    spans.push_back ({(uintptr_t) p.trials, (uintptr_t) p.trials + superblocks * kTrialBytes, true, c, "the trial table"});
-    spans.push_back ({(uintptr_t) p.stats, (uintptr_t) p.stats + 3 * sizeof (double), true, c, "the statistics"});
+    spans.push_back ({(uintptr_t) p.trials, (uintptr_t) p.trials + superblocks * kTrialBytes, true, c, -1, "the trial table"});
+    spans.push_back ({(uintptr_t) p.stats, (uintptr_t) p.stats + 3 * sizeof (double), true, c, -1, "the statistics"});
     if (tables) {
       SCHRO_HIP_REQUIRE (((uintptr_t) tables[2 * c + 1] & 3) == 0, "%s: picture %d: the mode table is not 4-byte aligned", who, c);
-      spans.push_back ({(uintptr_t) tables[2 * c + 1], (uintptr_t) tables[2 * c + 1] + superblocks * kEntryBytes, true, c, "the mode table"});
+      spans.push_back ({(uintptr_t) tables[2 * c + 1], (uintptr_t) tables[2 * c + 1] + superblocks * kEntryBytes, true, c, -1, "the mode table"});
       mj.table = (int32_t *) tables[2 * c + 1];
     }
     mj.trials = (uint8_t *) p.trials;
     mj.stats = (double *) p.stats;
   }
-  return split2_check_spans (who, spans);
+  return motion_check_spans (who, "picture", spans);
 }
 
 // the workgroups of the two metric launches, picture by picture; `split2` receives the split-2 stage's records

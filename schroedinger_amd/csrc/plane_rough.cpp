@@ -14,46 +14,20 @@ using namespace schro;
 
 namespace {
 
-constexpr int kMaxPlaneSize = 1 << 16;
-constexpr int kMaxExtension = 1024;
-constexpr int kMaxBlocks = 1 << 14;
 constexpr int kMaxDistance = (SCHRO_HIP_LIMIT_METRIC_SCAN - 1) / 2;     // a window of 2 * distance + 1 positions
-constexpr size_t kMvBytes = 20; // SchroMotionVector (schromotion.h:20-37)
-
-struct Geometry {
-  int nbx, nby, xb, yb, ref;
-};
-
-// a range of device memory a launch reads or writes, and whose it is
-struct Span {
-  uintptr_t begin, end;
-  bool written;
-  int chain, level;
-};
-
-// the refusals that do not depend on the level: `who` names the call, `what` the chain or the picture
-int
-check_geometry (const char *who, const char *what, int c, const Geometry & g)
-{
-  SCHRO_HIP_REQUIRE (g.nbx > 0 && g.nby > 0 && g.nbx <= kMaxBlocks && g.nby <= kMaxBlocks, "%s: %s %d: %d x %d blocks", who, what, c,
-      g.nbx, g.nby);
-  SCHRO_HIP_REQUIRE (g.xb > 0 && g.yb > 0 && g.xb <= SCHRO_HIP_LIMIT_BLOCK_SIZE && g.yb <= SCHRO_HIP_LIMIT_BLOCK_SIZE,
-      "%s: %s %d: a block of %d x %d is outside 1 .. %d", who, what, c, g.xb, g.yb, SCHRO_HIP_LIMIT_BLOCK_SIZE);
-  SCHRO_HIP_REQUIRE (g.ref == 0 || g.ref == 1, "%s: %s %d: reference %d is neither 0 nor 1", who, what, c, g.ref);
-  return 0;
-}
+const char *const kField = "the field", *const kInput = "a plane or hint field";
 
 // one level of a chain into the kernel's record, its memory into `spans`
 int
-add_level (const char *who, const char *what, int c, int shift, const SchroHipRoughPlane & pl, const Geometry & g, int dist,
-    const void *hint, void *field, RoughLevel * out, std::vector < Span > &spans)
+add_level (const char *who, const char *what, int c, int shift, const SchroHipRoughPlane & pl, const MotionGeometry & g, int dist,
+    const void *hint, void *field, RoughLevel * out, std::vector < MotionSpan > &spans)
 {
   SCHRO_HIP_REQUIRE (pl.frame && pl.ref && field, "%s: %s %d level %d has a NULL pointer", who, what, c, shift);
-  SCHRO_HIP_REQUIRE (pl.width > 0 && pl.height > 0 && pl.width <= kMaxPlaneSize && pl.height <= kMaxPlaneSize,
+  SCHRO_HIP_REQUIRE (pl.width > 0 && pl.height > 0 && pl.width <= kMaxMotionPlaneSize && pl.height <= kMaxMotionPlaneSize,
       "%s: %s %d level %d: plane size %dx%d out of range", who, what, c, shift, pl.width, pl.height);
   SCHRO_HIP_REQUIRE (pl.frame_stride >= pl.width && pl.ref_stride >= pl.width, "%s: %s %d level %d: a stride shorter than a row", who, what, c,
       shift);
-  SCHRO_HIP_REQUIRE (pl.extension >= 0 && pl.extension <= kMaxExtension, "%s: %s %d level %d: extension %d out of range", who, what, c, shift,
+  SCHRO_HIP_REQUIRE (pl.extension >= 0 && pl.extension <= kMaxMotionExtension, "%s: %s %d level %d: extension %d out of range", who, what, c, shift,
       pl.extension);
   SCHRO_HIP_REQUIRE (dist > 0, "%s: %s %d level %d: distance %d", who, what, c, shift, dist);
   SCHRO_HIP_REQUIRE (dist <= kMaxDistance, "%s: %s %d level %d: distance %d gives a window of %d positions, over the limit of %d", who, what, c,
@@ -73,43 +47,10 @@ add_level (const char *who, const char *what, int c, int shift, const SchroHipRo
   out->shift = shift;
   out->dist = dist;
   const size_t plane = (size_t) pl.width, bytes = (size_t) g.nbx * g.nby * kMvBytes;
-  spans.push_back ({(uintptr_t) pl.frame, (uintptr_t) pl.frame + (size_t) pl.frame_stride * (pl.height - 1) + plane, false, c, shift});
-  spans.push_back ({(uintptr_t) pl.ref, (uintptr_t) pl.ref + (size_t) pl.ref_stride * (pl.height - 1) + plane, false, c, shift});
-  spans.push_back ({(uintptr_t) field, (uintptr_t) field + bytes, true, c, shift});
+  spans.push_back ({(uintptr_t) pl.frame, (uintptr_t) pl.frame + (size_t) pl.frame_stride * (pl.height - 1) + plane, false, c, shift, kInput});
+  spans.push_back ({(uintptr_t) pl.ref, (uintptr_t) pl.ref + (size_t) pl.ref_stride * (pl.height - 1) + plane, false, c, shift, kInput});
+  spans.push_back ({(uintptr_t) field, (uintptr_t) field + bytes, true, c, shift, kField});
   return 0;
-}
-
-// no field overlaps another field or anything the launch reads (a field of another workgroup's, most of all)
-int
-check_spans (const char *who, const char *what, std::vector < Span > &spans)
-{
-  std::sort (spans.begin (), spans.end (), [](const Span & a, const Span & b) {
-        return a.begin < b.begin;}
-  );
-  const Span *any = nullptr, *written = nullptr;        // the spans seen so far that end last
-  for (const Span & s:spans) {
-    const Span *hit = s.written ? any : written;
-    SCHRO_HIP_REQUIRE (!hit || hit->end <= s.begin, "%s: %s %d level %d: %s overlaps %s of %s %d level %d", who, what, s.chain, s.level,
-        s.written ? "the field" : "a plane or hint field", hit && hit->written ? "the field" : "a plane or hint field", what,
-        hit ? hit->chain : 0, hit ? hit->level : 0);
-    if (!any || s.end > any->end)
-      any = &s;
-    if (s.written && (!written || s.end > written->end))
-      written = &s;
-  }
-  return 0;
-}
-
-// LDS bytes a wave of the launch needs: the largest block and window of any level
-size_t
-chain_lds (const RoughChain & ch)
-{
-  size_t lds = 0;
-  for (int n = 0; n < ch.nlevels; n++) {
-    const int span = 2 * ch.level[n].dist + 1;
-    lds = std::max (lds, scan_lds_bytes (ch.xb, ch.yb, span, span));
-  }
-  return lds;
 }
 
 int
@@ -118,12 +59,12 @@ build_hint (const SchroHipRoughHintPicture * pictures, int npictures, std::vecto
   const char *who = "rough_hint_batch", *what = "picture";
   SCHRO_HIP_REQUIRE (pictures && npictures > 0, "%s: bad arguments", who);
   SCHRO_HIP_REQUIRE (npictures <= kMaxJobs, "%s: at most %d pictures per call", who, kMaxJobs);
-  std::vector < Span > spans;
+  std::vector < MotionSpan > spans;
   chains.resize (npictures);
   for (int p = 0; p < npictures; p++) {
     const SchroHipRoughHintPicture & pic = pictures[p];
-    const Geometry g = { pic.x_num_blocks, pic.y_num_blocks, pic.xbsep_luma, pic.ybsep_luma, pic.ref_index };
-    int r = check_geometry (who, what, p, g);
+    const MotionGeometry g = { pic.x_num_blocks, pic.y_num_blocks, pic.xbsep_luma, pic.ybsep_luma, pic.ref_index };
+    int r = motion_check_geometry (who, what, p, g, SCHRO_HIP_LIMIT_BLOCK_SIZE);
     if (r)
       return r;
     SCHRO_HIP_REQUIRE (pic.shift >= 1 && pic.shift <= SCHRO_HIP_MAX_HIER_LEVELS - 1, "%s: %s %d level %d: the shift of a hint level is 1 .. %d", who,
@@ -139,9 +80,9 @@ build_hint (const SchroHipRoughHintPicture * pictures, int npictures, std::vecto
     r = add_level (who, what, p, pic.shift, pl, g, pic.distance, pic.hint_field, pic.field, &ch.level[0], spans);
     if (r)
       return r;
-    spans.push_back ({(uintptr_t) pic.hint_field, (uintptr_t) pic.hint_field + (size_t) g.nbx * g.nby * kMvBytes, false, p, pic.shift});
+    spans.push_back ({(uintptr_t) pic.hint_field, (uintptr_t) pic.hint_field + (size_t) g.nbx * g.nby * kMvBytes, false, p, pic.shift, kInput});
   }
-  return check_spans (who, what, spans);
+  return motion_check_spans (who, what, spans);
 }
 
 int
@@ -150,12 +91,12 @@ build_chains (const SchroHipRoughChain * in, int nchains, int nohint_distance, i
   const char *who = "rough_me_batch", *what = "chain";
   SCHRO_HIP_REQUIRE (in && nchains > 0, "%s: bad arguments", who);
   SCHRO_HIP_REQUIRE (nchains <= kMaxJobs, "%s: at most %d chains per call", who, kMaxJobs);
-  std::vector < Span > spans;
+  std::vector < MotionSpan > spans;
   chains.resize (nchains);
   for (int c = 0; c < nchains; c++) {
     const SchroHipRoughChain & src = in[c];
-    const Geometry g = { src.x_num_blocks, src.y_num_blocks, src.xbsep_luma, src.ybsep_luma, src.ref_index };
-    int r = check_geometry (who, what, c, g);
+    const MotionGeometry g = { src.x_num_blocks, src.y_num_blocks, src.xbsep_luma, src.ybsep_luma, src.ref_index };
+    int r = motion_check_geometry (who, what, c, g, SCHRO_HIP_LIMIT_BLOCK_SIZE);
     if (r)
       return r;
     SCHRO_HIP_REQUIRE (src.n_levels >= 1 && src.n_levels <= SCHRO_HIP_MAX_HIER_LEVELS, "%s: %s %d: %d levels, outside 1 .. %d", who, what, c,
@@ -181,21 +122,7 @@ build_chains (const SchroHipRoughChain * in, int nchains, int nohint_distance, i
         return r;
     }
   }
-  return check_spans (who, what, spans);
-}
-
-int
-run_chains (SchroHipContext * ctx, const std::vector < RoughChain > &chains)
-{
-  size_t lds = 0;
-  for (const RoughChain & ch:chains)
-    lds = std::max (lds, chain_lds (ch));
-  (void) hipSetDevice (ctx->device);
-  void *dev;
-  int r = push_big_table (ctx, chains.data (), sizeof (RoughChain) * chains.size (), &dev);
-  if (r)
-    return r;
-  return launch_rough_hint (ctx->stream, (const RoughChain *) dev, (int) chains.size (), lds);
+  return motion_check_spans (who, what, spans);
 }
 
 }                               // namespace
@@ -206,8 +133,8 @@ int
 rough_me_host_run (SchroHipContext * ctx, const char *who, const SchroHipRoughPlane * levels, int nlevels, int first_shift,
     const SchroHipParams * params, int ref_index, int nohint_distance, int hint_distance, const void *hint, void *const *fields)
 {
-  SCHRO_HIP_REQUIRE (params->x_num_blocks > 0 && params->y_num_blocks > 0 && params->x_num_blocks <= kMaxBlocks
-      && params->y_num_blocks <= kMaxBlocks, "%s: %d x %d blocks", who, params->x_num_blocks, params->y_num_blocks);
+  SCHRO_HIP_REQUIRE (params->x_num_blocks > 0 && params->y_num_blocks > 0 && params->x_num_blocks <= kMaxMotionBlocks
+      && params->y_num_blocks <= kMaxMotionBlocks, "%s: %d x %d blocks", who, params->x_num_blocks, params->y_num_blocks);
   for (int k = 0; k < nlevels; k++)
     SCHRO_HIP_REQUIRE (fields[k], "%s: level %d has no motion field", who, first_shift + k);
   const size_t bytes = (size_t) params->x_num_blocks * params->y_num_blocks * kMvBytes, slot = round_up (bytes, 256);

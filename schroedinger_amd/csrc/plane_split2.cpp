@@ -15,11 +15,6 @@ using namespace schro;
 
 namespace {
 
-constexpr int kMaxBlocks = 1 << 14;
-constexpr int kMaxBlock = 32;   // two 16-sample tasks per row (mode_split2.hip)
-constexpr int kMaxExtension = 32;       // the tiled image's apron columns (kHpApron)
-constexpr int kMaxVector = 32767;
-constexpr size_t kMvBytes = 20; // SchroMotionVector (schromotion.h:20-37)
 constexpr size_t kSbBytes = 16; // int32 error, int32 entropy, double score
 constexpr size_t kEntryBytes = SCHRO_HIP_SPLIT2_TABLE_INTS * sizeof (int32_t);
 
@@ -29,57 +24,33 @@ enum Call { kMetric, kChoose, kStage };
 
 namespace schro {
 
-// nothing written overlaps anything else
-int
-split2_check_spans (const char *who, std::vector < Split2Span > &spans)
-{
-  typedef Split2Span Span;
-  std::sort (spans.begin (), spans.end (), [](const Span & a, const Span & b) {
-        return a.begin < b.begin;}
-  );
-  const Span *any = nullptr, *written = nullptr;        // the spans seen so far that end last
-  for (const Span & s:spans) {
-    const Span *hit = s.written ? any : written;
-    SCHRO_HIP_REQUIRE (!hit || hit->end <= s.begin, "%s: picture %d: %s overlaps %s of picture %d", who, s.picture, s.name, hit ? hit->name : "",
-        hit ? hit->picture : 0);
-    if (!any || s.end > any->end)
-      any = &s;
-    if (s.written && (!written || s.end > written->end))
-      written = &s;
-  }
-  return 0;
-}
-
 // The refusals of one picture but for the overlaps, its kernel record and its spans (the table's too where `table` is
 // given).
 int
-split2_collect (const char *who, const SchroHipSplit2Picture & s, int c, bool stage, void *table, Split2Job & jb, std::vector < Split2Span > &spans)
+split2_collect (const char *who, const SchroHipSplit2Picture & s, int c, bool stage, void *table, Split2Job & jb, std::vector < MotionSpan > &spans)
 {
   static const char *const comp[3] = { "Y", "U", "V" };
+  const char *what = "picture";
   const Call call = stage ? kStage : kMetric;
   {
     SCHRO_HIP_REQUIRE (s.num_refs == 1 || s.num_refs == 2, "%s: picture %d: %d references, neither 1 nor 2", who, c, s.num_refs);
     SCHRO_HIP_REQUIRE ((s.h_shift == 0 || s.h_shift == 1) && (s.v_shift == 0 || s.v_shift == 1) && s.v_shift <= s.h_shift,
         "%s: picture %d: chroma shifts %d,%d are none of 0,0 / 1,0 / 1,1", who, c, s.h_shift, s.v_shift);
-    SCHRO_HIP_REQUIRE (s.x_num_blocks > 0 && s.y_num_blocks > 0 && s.x_num_blocks <= kMaxBlocks && s.y_num_blocks <= kMaxBlocks,
-        "%s: picture %d: %d x %d blocks", who, c, s.x_num_blocks, s.y_num_blocks);
+    int r = motion_check_blocks (who, what, c, s.x_num_blocks, s.y_num_blocks);
+    if (r)
+      return r;
     SCHRO_HIP_REQUIRE (s.x_num_blocks % 4 == 0 && s.y_num_blocks % 4 == 0, "%s: picture %d: %d x %d blocks are not whole superblocks", who, c,
         s.x_num_blocks, s.y_num_blocks);
-    SCHRO_HIP_REQUIRE (s.xbsep_luma > 0 && s.ybsep_luma > 0 && s.xbsep_luma <= kMaxBlock && s.ybsep_luma <= kMaxBlock,
-        "%s: picture %d: a block of %d x %d is outside 1 .. %d", who, c, s.xbsep_luma, s.ybsep_luma, kMaxBlock);
+    r = motion_check_block_size (who, what, c, s.xbsep_luma, s.ybsep_luma, kMaxTiledBlock);
+    if (r)
+      return r;
     SCHRO_HIP_REQUIRE (s.xbsep_luma % (1 << s.h_shift) == 0 && s.ybsep_luma % (1 << s.v_shift) == 0,
         "%s: picture %d: a block of %d x %d is no multiple of the chroma subsampling", who, c, s.xbsep_luma, s.ybsep_luma);
-    SCHRO_HIP_REQUIRE (s.mv_precision >= 0 && s.mv_precision <= 3, "%s: picture %d: mv_precision %d is outside 0 .. 3", who, c, s.mv_precision);
-    SCHRO_HIP_REQUIRE (s.width > 0 && s.height > 0 && s.width <= kMaxVector && s.height <= kMaxVector, "%s: picture %d: picture size %dx%d out of range",
-        who, c, s.width, s.height);
-    const int block = std::max (s.xbsep_luma, s.ybsep_luma);
-    SCHRO_HIP_REQUIRE (s.extension >= block, "%s: picture %d: extension %d is under the block separation %d", who, c, s.extension, block);
-    SCHRO_HIP_REQUIRE (s.extension <= kMaxExtension, "%s: picture %d: extension %d is over the %d apron columns of an upsampled image", who, c,
-        s.extension, kMaxExtension);
-    const int reach = (std::max (s.width, s.height) << s.mv_precision) + s.extension;
-    SCHRO_HIP_REQUIRE (reach <= kMaxVector, "%s: picture %d: %dx%d at mv_precision %d: a coordinate of %d does not fit a vector of 16 bits", who, c,
-        s.width, s.height, s.mv_precision, reach);
-    SCHRO_HIP_REQUIRE (std::isfinite (s.lambda) && s.lambda >= 0, "%s: picture %d: lambda %g is negative or not finite", who, c, s.lambda);
+    r = motion_check_precision (who, what, c, s.mv_precision);
+    if (!r)
+      r = motion_check_picture (who, what, c, s.width, s.height, s.xbsep_luma, s.ybsep_luma, s.extension, s.mv_precision, s.lambda);
+    if (r)
+      return r;
     SCHRO_HIP_REQUIRE (s.motion && s.superblocks, "%s: picture %d: the motion field or the superblock table is a NULL pointer", who, c);
     SCHRO_HIP_REQUIRE (call == kStage || table, "%s: picture %d: the table is a NULL pointer", who, c);
     SCHRO_HIP_REQUIRE (((uintptr_t) s.motion & 3) == 0 && ((uintptr_t) s.superblocks & 7) == 0 && (call == kStage || ((uintptr_t) table & 3) == 0),
@@ -94,7 +65,7 @@ split2_collect (const char *who, const SchroHipSplit2Picture & s, int c, bool st
       SCHRO_HIP_REQUIRE (s.src[k], "%s: picture %d: component %s of the picture is a NULL pointer", who, c, comp[k]);
       SCHRO_HIP_REQUIRE (s.src_stride[k] >= w, "%s: picture %d: component %s: stride %d is shorter than a row of %d", who, c, comp[k],
           s.src_stride[k], w);
-      spans.push_back ({(uintptr_t) s.src[k], (uintptr_t) s.src[k] + (size_t) s.src_stride[k] * (h - 1) + w, false, c, "the picture"});
+      spans.push_back ({(uintptr_t) s.src[k], (uintptr_t) s.src[k] + (size_t) s.src_stride[k] * (h - 1) + w, false, c, -1, "the picture"});
       jb.src[k] = s.src[k];
       jb.src_stride[k] = s.src_stride[k];
       if (pair && k == 2)
@@ -107,7 +78,7 @@ split2_collect (const char *who, const SchroHipSplit2Picture & s, int c, bool st
         SCHRO_HIP_REQUIRE (s.ref_up[r][k], "%s: picture %d: the upsampled %s image of reference %d is a NULL pointer", who, c, comp[k], r);
         SCHRO_HIP_REQUIRE (((uintptr_t) s.ref_up[r][k] & 127) == 0, "%s: picture %d: the upsampled %s image of reference %d is not 128-byte aligned",
             who, c, comp[k], r);
-        spans.push_back ({(uintptr_t) s.ref_up[r][k], (uintptr_t) s.ref_up[r][k] + up_bytes, false, c, "an upsampled image"});
+        spans.push_back ({(uintptr_t) s.ref_up[r][k], (uintptr_t) s.ref_up[r][k] + up_bytes, false, c, -1, "an upsampled image"});
         jb.up[r][k] = s.ref_up[r][k];
       }
       if (k < 2)
@@ -116,13 +87,13 @@ split2_collect (const char *who, const SchroHipSplit2Picture & s, int c, bool st
     for (int r = 0; r < s.num_refs; r++) {
       SCHRO_HIP_REQUIRE (s.fields[r], "%s: picture %d: the field of reference %d is a NULL pointer", who, c, r);
       SCHRO_HIP_REQUIRE (((uintptr_t) s.fields[r] & 3) == 0, "%s: picture %d: the field of reference %d is not 4-byte aligned", who, c, r);
-      spans.push_back ({(uintptr_t) s.fields[r], (uintptr_t) s.fields[r] + records * kMvBytes, false, c, "a sub-pel field"});
+      spans.push_back ({(uintptr_t) s.fields[r], (uintptr_t) s.fields[r] + records * kMvBytes, false, c, -1, "a sub-pel field"});
       jb.field[r] = (const uint8_t *) s.fields[r];
     }
-    spans.push_back ({(uintptr_t) s.motion, (uintptr_t) s.motion + records * kMvBytes, true, c, "the motion field"});
-    spans.push_back ({(uintptr_t) s.superblocks, (uintptr_t) s.superblocks + records / 16 * kSbBytes, true, c, "the superblock table"});
+    spans.push_back ({(uintptr_t) s.motion, (uintptr_t) s.motion + records * kMvBytes, true, c, -1, "the motion field"});
+    spans.push_back ({(uintptr_t) s.superblocks, (uintptr_t) s.superblocks + records / 16 * kSbBytes, true, c, -1, "the superblock table"});
     if (call != kStage)
-      spans.push_back ({(uintptr_t) table, (uintptr_t) table + records * kEntryBytes, true, c, "the table"});
+      spans.push_back ({(uintptr_t) table, (uintptr_t) table + records * kEntryBytes, true, c, -1, "the table"});
     jb.motion = (uint8_t *) s.motion;
     jb.sb = (uint8_t *) s.superblocks;
     jb.table = call == kStage ? nullptr : (int32_t *) table;
@@ -145,14 +116,14 @@ build_jobs (const char *who, Call call, const SchroHipSplit2Picture * in, int n,
 {
   SCHRO_HIP_REQUIRE (in && n > 0 && (call == kStage || tables), "%s: bad arguments", who);
   SCHRO_HIP_REQUIRE (n <= kMaxJobs, "%s: at most %d pictures per call", who, kMaxJobs);
-  std::vector < Split2Span > spans;
+  std::vector < MotionSpan > spans;
   out.resize (n);
   for (int c = 0; c < n; c++) {
     const int r = split2_collect (who, in[c], c, call == kStage, call == kStage ? nullptr : tables[c], out[c], spans);
     if (r)
       return r;
   }
-  return split2_check_spans (who, spans);
+  return motion_check_spans (who, "picture", spans);
 }
 
 // the workgroups of the metric launch, picture by picture; returns their number

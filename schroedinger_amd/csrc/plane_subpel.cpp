@@ -15,40 +15,7 @@ using namespace schro;
 
 namespace {
 
-constexpr int kMaxBlocks = 1 << 14;
-constexpr int kMaxBlock = 32;   // two 16-column loads per row and tap (subpel.hip)
-constexpr int kMaxExtension = 32;       // the tiled image's apron columns (kHpApron)
-constexpr int kMaxVector = 32767;
-constexpr size_t kMvBytes = 20; // SchroMotionVector (schromotion.h:20-37)
-
 enum Call { kError, kChoose, kStage };
-
-// a range of device memory a call reads or writes, and whose it is
-struct Span {
-  uintptr_t begin, end;
-  bool written;
-  int chain;
-  const char *name;
-};
-
-// nothing written overlaps anything else (a field of another chain's workgroup, most of all)
-int
-check_spans (const char *who, std::vector < Span > &spans)
-{
-  std::sort (spans.begin (), spans.end (), [](const Span & a, const Span & b) {
-        return a.begin < b.begin;}
-  );
-  const Span *any = nullptr, *written = nullptr;        // the spans seen so far that end last
-  for (const Span & s:spans) {
-    const Span *hit = s.written ? any : written;
-    SCHRO_HIP_REQUIRE (!hit || hit->end <= s.begin, "%s: chain %d: %s overlaps %s of chain %d", who, s.chain, s.name, hit ? hit->name : "", hit ? hit->chain : 0);
-    if (!any || s.end > any->end)
-      any = &s;
-    if (s.written && (!written || s.end > written->end))
-      written = &s;
-  }
-  return 0;
-}
 
 // The refusals, and the kernels' records: `out` receives one SubpelChain per chain (table NULL where `tables` is).
 // mvprec: the pass of the error and choice calls (checked against the chain's precision); 0 for the whole stage.
@@ -56,31 +23,25 @@ int
 build_chains (const char *who, Call call, const SchroHipSubpelChain * in, int nchains, int mvprec, void *const *tables,
     std::vector < SubpelChain > &out)
 {
+  const char *what = "chain";
   SCHRO_HIP_REQUIRE (in && nchains > 0 && (call == kStage || tables), "%s: bad arguments", who);
   SCHRO_HIP_REQUIRE (nchains <= kMaxJobs, "%s: at most %d chains per call", who, kMaxJobs);
-  std::vector < Span > spans;
+  std::vector < MotionSpan > spans;
   out.resize (nchains);
   for (int c = 0; c < nchains; c++) {
     const SchroHipSubpelChain & s = in[c];
-    SCHRO_HIP_REQUIRE (s.x_num_blocks > 0 && s.y_num_blocks > 0 && s.x_num_blocks <= kMaxBlocks && s.y_num_blocks <= kMaxBlocks,
-        "%s: chain %d: %d x %d blocks", who, c, s.x_num_blocks, s.y_num_blocks);
-    SCHRO_HIP_REQUIRE (s.xbsep_luma > 0 && s.ybsep_luma > 0 && s.xbsep_luma <= kMaxBlock && s.ybsep_luma <= kMaxBlock,
-        "%s: chain %d: a block of %d x %d is outside 1 .. %d", who, c, s.xbsep_luma, s.ybsep_luma, kMaxBlock);
-    SCHRO_HIP_REQUIRE (s.ref_index == 0 || s.ref_index == 1, "%s: chain %d: reference %d is neither 0 nor 1", who, c, s.ref_index);
-    SCHRO_HIP_REQUIRE (s.mv_precision >= 0 && s.mv_precision <= 3, "%s: chain %d: mv_precision %d is outside 0 .. 3", who, c, s.mv_precision);
+    const MotionGeometry g = { s.x_num_blocks, s.y_num_blocks, s.xbsep_luma, s.ybsep_luma, s.ref_index };
+    int r = motion_check_geometry (who, what, c, g, kMaxTiledBlock);
+    if (!r)
+      r = motion_check_precision (who, what, c, s.mv_precision);
+    if (r)
+      return r;
     if (call != kStage)
       SCHRO_HIP_REQUIRE (mvprec >= 1 && mvprec <= s.mv_precision, "%s: chain %d: pass %d is outside 1 .. mv_precision %d", who, c, mvprec,
           s.mv_precision);
-    SCHRO_HIP_REQUIRE (s.width > 0 && s.height > 0 && s.width <= kMaxVector && s.height <= kMaxVector, "%s: chain %d: picture size %dx%d out of range",
-        who, c, s.width, s.height);
-    const int block = std::max (s.xbsep_luma, s.ybsep_luma);
-    SCHRO_HIP_REQUIRE (s.extension >= block, "%s: chain %d: extension %d is under the block separation %d", who, c, s.extension, block);
-    SCHRO_HIP_REQUIRE (s.extension <= kMaxExtension, "%s: chain %d: extension %d is over the %d apron columns of an upsampled image", who, c,
-        s.extension, kMaxExtension);
-    const int reach = (std::max (s.width, s.height) << s.mv_precision) + s.extension;
-    SCHRO_HIP_REQUIRE (reach <= kMaxVector, "%s: chain %d: %dx%d at mv_precision %d: a coordinate of %d does not fit a vector of 16 bits", who, c,
-        s.width, s.height, s.mv_precision, reach);
-    SCHRO_HIP_REQUIRE (std::isfinite (s.lambda) && s.lambda >= 0, "%s: chain %d: lambda %g is negative or not finite", who, c, s.lambda);
+    r = motion_check_picture (who, what, c, s.width, s.height, s.xbsep_luma, s.ybsep_luma, s.extension, s.mv_precision, s.lambda);
+    if (r)
+      return r;
     SCHRO_HIP_REQUIRE (s.src && s.ref_up, "%s: chain %d: the picture or the upsampled image is a NULL pointer", who, c);
     SCHRO_HIP_REQUIRE (s.field && (call != kStage || s.src_field), "%s: chain %d: a field is a NULL pointer", who, c);
     SCHRO_HIP_REQUIRE (call == kStage || tables[c], "%s: chain %d: the table is a NULL pointer", who, c);
@@ -93,13 +54,13 @@ build_chains (const char *who, Call call, const SchroHipSubpelChain * in, int nc
     SCHRO_HIP_REQUIRE (((uintptr_t) s.field & 3) == 0 && (call != kStage || ((uintptr_t) s.src_field & 3) == 0)
         && (call == kStage || ((uintptr_t) tables[c] & 3) == 0), "%s: chain %d: a field or table is not 4-byte aligned", who, c);
     const size_t records = (size_t) s.x_num_blocks * s.y_num_blocks, bytes = records * kMvBytes;
-    spans.push_back ({(uintptr_t) s.src, (uintptr_t) s.src + (size_t) s.src_stride * (s.height - 1) + s.width, false, c, "the picture"});
-    spans.push_back ({(uintptr_t) s.ref_up, (uintptr_t) s.ref_up + up_bytes, false, c, "the upsampled image"});
-    spans.push_back ({(uintptr_t) s.field, (uintptr_t) s.field + bytes, true, c, "the field"});
+    spans.push_back ({(uintptr_t) s.src, (uintptr_t) s.src + (size_t) s.src_stride * (s.height - 1) + s.width, false, c, -1, "the picture"});
+    spans.push_back ({(uintptr_t) s.ref_up, (uintptr_t) s.ref_up + up_bytes, false, c, -1, "the upsampled image"});
+    spans.push_back ({(uintptr_t) s.field, (uintptr_t) s.field + bytes, true, c, -1, "the field"});
     if (call == kStage && s.src_field != s.field)
-      spans.push_back ({(uintptr_t) s.src_field, (uintptr_t) s.src_field + bytes, false, c, "the source field"});
+      spans.push_back ({(uintptr_t) s.src_field, (uintptr_t) s.src_field + bytes, false, c, -1, "the source field"});
     if (call != kStage)
-      spans.push_back ({(uintptr_t) tables[c], (uintptr_t) tables[c] + records * 8 * sizeof (int32_t), true, c, "the table"});
+      spans.push_back ({(uintptr_t) tables[c], (uintptr_t) tables[c] + records * 8 * sizeof (int32_t), true, c, -1, "the table"});
     SubpelChain & ch = out[c];
     memset (&ch, 0, sizeof (ch));
     ch.src = s.src;
@@ -113,7 +74,7 @@ build_chains (const char *who, Call call, const SchroHipSubpelChain * in, int nc
     ch.nbx = s.x_num_blocks, ch.nby = s.y_num_blocks, ch.xb = s.xbsep_luma, ch.yb = s.ybsep_luma;
     ch.ref = s.ref_index;
   }
-  return check_spans (who, spans);
+  return motion_check_spans (who, what, spans);
 }
 
 // the workgroups of the error launch, chain by chain; returns their number

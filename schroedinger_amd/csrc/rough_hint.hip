@@ -22,30 +22,13 @@
 // position: the gravity vector is kept with metric 0 -- also where the reference's gravity position lies outside the
 // window, which happens for such blocks only.  A window of no width or height stores 0, 0, INT_MAX.
 // The launch first writes every record of every field as schro_motion_field_set (mf, 0, 1) leaves it.
+// That preamble, the walk over the anti-diagonals, the scan with its three stores and the launch are motion_common.h's
+// (fill_fields, walk_diagonals, scan_and_store, launch_chains), shared with hier_bm.hip; the ScanRules below say where
+// this search differs.
 
-#include "schro_hip_internal.h"
-#include "scan_common.h"
-
-#include <algorithm>
-#include <climits>
+#include "motion_common.h"
 
 namespace schro {
-
-constexpr int kRoughWaves = SCHRO_HIP_ROUGH_WAVES;
-constexpr int kRoughThreads = kRoughWaves * 64;
-constexpr size_t kRoughLdsLimit = 65536;
-constexpr int kMvBytes = 20;    // SchroMotionVector (schromotion.h:20-37): flags, metric, chroma_metric, dx[2], dy[2]
-constexpr int kMvMetric = 4, kMvDx = 12, kMvDy = 16;
-
-// what the wave's lanes stored in LDS is read by other lanes of the same wave: LDS serves a wave's accesses in order, the
-// compiler must not reorder them
-__device__ __forceinline__ void
-rough_wave_sync ()
-{
-  __builtin_amdgcn_fence (__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier ();
-  __builtin_amdgcn_fence (__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // block (i, j) of level lv, by one wave
 __device__ __forceinline__ void
@@ -61,9 +44,9 @@ rough_block (const RoughChain * ch, const RoughLevel & lv, int i, int j, uint32_
   const uint32_t tail = scan_tail_mask (bw);
   uint32_t *block = lds, *window = lds + nd * rows;
 
-  rough_wave_sync ();           // (the block before this one is through with the LDS)
+  wave_sync ();                 // (the block before this one is through with the LDS)
   scan_stage_block (block, lv.frame, lv.frame_stride, w, h, x, y, nd, rows, tail, lane);
-  rough_wave_sync ();
+  wave_sync ();
 
   int gx = 0, gy = 0;           // the scan's vector: the winner >> shift
   if (lv.hint) {
@@ -74,22 +57,13 @@ rough_block (const RoughChain * ch, const RoughLevel & lv, int i, int j, uint32_
       const int m = c - 1;
       const int l = (i + skip * (-1 + 2 * (m & 1))) & mask, k = (j + skip * (-1 + (m & 2))) & mask;    // negative stays negative
       if (l >= 0 && l < nbx && k >= 0 && k < nby)
-        rec = lv.hint + ((size_t) k * nbx + l) * kMvBytes;
-    } else if (c == 5) {
-      if (i > 0)
-        rec = lv.field + ((size_t) j * nbx + (i - skip)) * kMvBytes;
-    } else if (c == 6) {
-      if (j > 0)
-        rec = lv.field + ((size_t) (j - skip) * nbx + i) * kMvBytes;
-    } else if (c == 7) {
-      if (i > 0 && j > 0)
-        rec = lv.field + ((size_t) (j - skip) * nbx + (i - skip)) * kMvBytes;
+        rec = mv_record (lv.hint, nbx, l, k);
+    } else if (c >= 5) {
+      rec = mv_neighbour (lv.field, nbx, i, j, skip, c - 5);
     }
     int cdx = 0, cdy = 0;
-    if (rec) {
-      cdx = gload < int16_t > (rec + kMvDx + 2 * ref);
-      cdy = gload < int16_t > (rec + kMvDy + 2 * ref);
-    }
+    if (rec)
+      mv_vector (rec, ref, &cdx, &cdy);
     const int cx = (i * xb + cdx) >> shift, cy = (j * yb + cdy) >> shift;
     // :245-260: skipped in front of the picture, with an empty block, or where the reference picture ends inside the block
     const bool ok = (c == 0 || rec) && !empty && cx >= 0 && cy >= 0 && max (0, w - cx) >= bw && max (0, h - cy) >= bh;
@@ -114,44 +88,12 @@ rough_block (const RoughChain * ch, const RoughLevel & lv, int i, int j, uint32_
     gy = __shfl (cdy, win) >> shift;
   }
 
-  // schro_metric_scan_setup (schrometric.c:174-214)
-  const int dist = lv.dist, ext = lv.ext;
-  const int ref_x = max (max (-bw, x + gx - dist), -ext), ref_y = max (max (-bh, y + gy - dist), -ext);
-  const int sw = min (min (w, x + gx + dist), w - bw + ext) - ref_x + 1;
-  const int sh = min (min (h, y + gy + dist), h - bh + ext) - ref_y + 1;
-  if (!lv.hint) {               // :106-109: the gravity of the nohint level is the window's first position
-    gx = ref_x - x;
-    gy = ref_y - y;
-  }
-  int dx = gx, dy = gy;
-  uint32_t metric = 0;
-  if (sw <= 0 || sh <= 0) {
-    dx = dy = 0;
-    metric = (uint32_t) INT_MAX;        // SCHRO_METRIC_INVALID
-  } else if (!empty) {
-    const int wd = scan_window_pitch (bw, sw) >> 2, wcols = scan_window_cols (bw, sw) >> 2;
-    scan_stage_window (window, lv.ref, lv.ref_stride, w, h, ref_x, ref_y, wd, wcols, rows + sh - 1, lane);
-    rough_wave_sync ();
-    const uint32_t m_sh = sh > 1 ? kDivMagic.m[sh] : 0u;
-    const uint32_t best = scan_wave_min (block, window, nd, rows, wd, tail, sw * sh, sh, m_sh, (gx + x - ref_x) * sh + (gy + y - ref_y), nullptr, lane);
-    metric = best >> 11;
-    const uint32_t order = best & 2047u;
-    if (order) {
-      const int p = (int) order - 1;
-      const int pi = mdiv (p, sh, m_sh);
-      dx = ref_x + pi - x;
-      dy = ref_y + (p - pi * sh) - y;
-    }
-  }
-  if (lane == 0) {
-    uint8_t *out = lv.field + ((size_t) j * nbx + i) * kMvBytes;
-    gstore < uint32_t > (out + kMvMetric, metric);
-    gstore < uint16_t > (out + kMvDx + 2 * ref, (uint16_t) ((uint32_t) dx << shift));
-    gstore < uint16_t > (out + kMvDy + 2 * ref, (uint16_t) ((uint32_t) dy << shift));
-  }
+  // (:106-109: the gravity of the nohint level is the window's first position; a window of no width or height stores 0, 0)
+  const ScanRules rules = { !lv.hint, true, false, empty };
+  scan_and_store (lv, lv.ref, lv.ref_stride, w, h, shift, mv_record (lv.field, nbx, i, j), ref, x, y, bw, bh, gx, gy, block, window, rules, lane);
 }
 
-__global__ __launch_bounds__ (kRoughThreads)
+__global__ __launch_bounds__ (kChainThreads)
 void rough_hint_kernel (const RoughChain * __restrict__ chains, int lds_per_wave)
 {
   extern __shared__ __attribute__ ((aligned (16))) uint32_t rough_lds[];
@@ -160,15 +102,7 @@ void rough_hint_kernel (const RoughChain * __restrict__ chains, int lds_per_wave
   uint32_t *lds = rough_lds + (size_t) wave * (lds_per_wave >> 2);
   const int nbx = ch->nbx, nby = ch->nby, nlevels = ch->nlevels;
 
-  // schro_motion_field_set (mf, 0, 1) on every field: five dwords per record, the first one 1
-  const size_t records = (size_t) nbx * nby;
-  for (int n = 0; n < nlevels; n++) {
-    uint8_t *field = ch->level[n].field;
-    for (size_t k = threadIdx.x; k < records; k += blockDim.x)
-      for (int m = 0; m < kMvBytes / 4; m++)
-        gstore < uint32_t > (field + k * kMvBytes + 4 * m, m == 0 ? 1u : 0u);
-  }
-  __syncthreads ();
+  fill_fields (ch, [](const RoughLevel &) { return 1u; });     // schro_motion_field_set (mf, 0, 1)
 
   for (int n = 0; n < nlevels; n++) {
     const RoughLevel lv = ch->level[n];
@@ -183,27 +117,16 @@ void rough_hint_kernel (const RoughChain * __restrict__ chains, int lds_per_wave
       __syncthreads ();
       continue;
     }
-    for (int d = 0; d < cols + rws - 1; d++) {
-      const int jlo = max (0, d - (cols - 1)), jhi = min (d, rws - 1);
-      for (int bj = jlo + wave; bj <= jhi; bj += nwaves)
-        rough_block (ch, lv, (d - bj) << shift, bj << shift, lds, lane);
-      __syncthreads ();         // the next diagonal reads this one's records
-    }
+    walk_diagonals (cols, rws, wave, nwaves, [&](int bi, int bj) {
+          rough_block (ch, lv, bi << shift, bj << shift, lds, lane);
+        });
   }
 }
 
 int
 launch_rough_hint (hipStream_t stream, const RoughChain * d_chains, int nchains, size_t lds_per_wave)
 {
-  if (lds_per_wave > kRoughLdsLimit)
-    return set_error (SCHRO_HIP_EINVAL, "rough search launch: %zu bytes of LDS per wave", lds_per_wave);
-  // as many waves as the workgroup's LDS holds, and at least one
-  const int waves = lds_per_wave ? (int) std::min < size_t > (kRoughWaves, kRoughLdsLimit / lds_per_wave) : kRoughWaves;
-  SCHRO_LAUNCH (rough_hint_kernel, dim3 (nchains), dim3 (waves * 64), lds_per_wave * waves, stream, d_chains, (int) lds_per_wave);
-  hipError_t e = hipGetLastError ();
-  if (e != hipSuccess)
-    return set_error (SCHRO_HIP_EDEVICE, "rough search launch: %s", hipGetErrorString (e));
-  return 0;
+  return launch_chains (rough_hint_kernel, "rough search", stream, d_chains, nchains, lds_per_wave);
 }
 
 }                               // namespace schro

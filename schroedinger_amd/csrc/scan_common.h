@@ -1,5 +1,5 @@
 // scan_common.h -- the wave-level SAD scan (schro_metric_scan_do_scan + schro_metric_scan_get_min, schrometric.c:31-171)
-// shared by metric_scan_kernel (analysis.hip), rough_hint_kernel (rough_hint.hip) and hier_bm_kernel (hier_bm.hip): the LDS layout of a wave's block
+// shared by metric_scan_kernel (analysis.hip) and, through scan_and_store of motion_common.h, rough_hint_kernel and hier_bm_kernel: the LDS layout of a wave's block
 // and window, their staging, and the minimum over the window's positions.  analysis.hip describes the layout.
 #pragma once
 

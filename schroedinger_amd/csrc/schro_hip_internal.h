@@ -165,6 +165,11 @@ struct ScanJob {
 };
 static_assert (sizeof (ScanJob) == 64 && sizeof (ScanPicture) == 64, "scan tables: 64-byte records");
 
+// A motion vector record, SchroMotionVector (schromotion.h:20-37): flags (pred_mode, using_global << 2, split << 3),
+// metric, chroma_metric, dx[2], dy[2] as int16 -- or, for an intra block, dc[3] in place of dx[] and dy[0]
+constexpr int kMvBytes = 20, kMvDwords = kMvBytes / 4;
+constexpr int kMvFlags = 0, kMvMetric = 4, kMvChromaMetric = 8, kMvDx = 12, kMvDy = 16;
+
 // One (picture, reference) chain of the rough motion search (rough_hint.hip): the levels the launch runs, coarse to fine,
 // each with its planes and its field.  hint NULL: the level scans around the zero vector (the nohint level, every block
 // on its own); else the field of the level above -- the level before it in the chain, or the caller's.
@@ -199,7 +204,7 @@ struct HbmLevel {
   int w, h;                     // luma, both frames
   int hs, vs;                   // chroma shifts
   int ext;                      // the apron the frames would have (the kernel clamps coordinates)
-  int shift, range;
+  int shift, dist;              // dist: h_range
   int pad[3];
 };
 struct HbmChain {
@@ -1094,17 +1099,40 @@ int subpel_host_run (SchroHipContext * ctx, SchroHipSubpelChain * chains, int nc
 // pic->superblocks are not read -- all become scratch of the queue; `motion` and `superblocks` are the host outputs; waits
 // for the queue
 int split2_host_run (SchroHipContext * ctx, SchroHipSplit2Picture * pic, void *motion, void *superblocks);
-// a range of device memory a mode-decision call reads or writes, and whose it is
-struct Split2Span {
+// ---- what the plane layers of the motion stages share (plane_motion.cpp) ----
+// the limits: blocks along an axis; a plane of the two searches and its apron; under a tiled upsampled image a block of
+// two 16-column loads per row, its apron columns (kHpApron), and a coordinate that fits a vector's 16 bits
+constexpr int kMaxMotionBlocks = 1 << 14;
+constexpr int kMaxMotionPlaneSize = 1 << 16, kMaxMotionExtension = 1024;
+constexpr int kMaxTiledBlock = 32, kMaxTiledExtension = 32, kMaxVector = 32767;
+// the refusals of a block grid -- count, size up to max_block, reference index -- in that order; `who` names the call,
+// `what` ("picture", "entry", "chain") and c the one refused
+int motion_check_blocks (const char *who, const char *what, int c, int nbx, int nby);
+int motion_check_block_size (const char *who, const char *what, int c, int xb, int yb, int max_block);
+struct MotionGeometry {
+  int nbx, nby, xb, yb, ref;
+};
+int motion_check_geometry (const char *who, const char *what, int c, const MotionGeometry & g, int max_block);
+// ... and of a picture whose references are tiled upsampled images: mv_precision; then the picture's size, the extension
+// under the block or over the apron, the reach of a coordinate in 16 bits, lambda
+int motion_check_precision (const char *who, const char *what, int c, int mv_precision);
+int motion_check_picture (const char *who, const char *what, int c, int width, int height, int xb, int yb, int extension, int mv_precision,
+    double lambda);
+// a range of device memory a call reads or writes, and whose it is (level < 0: the refusal names no level)
+struct MotionSpan {
   uintptr_t begin, end;
   bool written;
-  int picture;
+  int owner, level;
   const char *name;
 };
+// nothing written overlaps anything else the call reads or writes (a field of another workgroup's, most of all)
+int motion_check_spans (const char *who, const char *what, std::vector < MotionSpan > &spans);
+// a batch of chains to the device and its launch, with the LDS per wave its largest block and window need
+int run_chains (SchroHipContext * ctx, const std::vector < RoughChain > &chains);
+int run_chains (SchroHipContext * ctx, const std::vector < HbmChain > &chains);
 // plane_split2.cpp, for plane_mode.cpp: the refusals of one picture of the split-2 stage but for the overlaps, its kernel
-// record and its spans (`table`: the split-2 table, NULL in a stage call); nothing written overlaps anything else
-int split2_collect (const char *who, const SchroHipSplit2Picture & s, int c, bool stage, void *table, Split2Job & jb, std::vector < Split2Span > &spans);
-int split2_check_spans (const char *who, std::vector < Split2Span > &spans);
+// record and its spans (`table`: the split-2 table, NULL in a stage call)
+int split2_collect (const char *who, const SchroHipSplit2Picture & s, int c, bool stage, void *table, Split2Job & jb, std::vector < MotionSpan > &spans);
 // the frame layer's whole mode decision (plane_mode.cpp): pic->fields[r] and pic->hbm_fields[r][] are the HOST fields;
 // motion, superblocks, trials (may be NULL) and stats are the host outputs; waits for the queue
 int mode_host_run (SchroHipContext * ctx, SchroHipModePicture * pic, void *motion, void *superblocks, void *trials, double *stats);

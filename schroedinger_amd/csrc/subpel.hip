@@ -25,9 +25,11 @@
 // subpel_choose_kernel: `score = entropy + lambda * error` is a rounded product, then a rounded sum, as the reference's
 // x86-64 build has it.  hipcc would contract the two into an FMA, and that changes decisions (lambda 0.1: entropy 27,
 // metric 2557 against entropy 25, error 2577); contraction is switched off for this file by the pragma below.
+//
+// The tap fetch and the bilinear form (predict_halfpel), the entropy estimate, the vector prediction and the walk over the
+// anti-diagonals are motion_common.h's, shared with the mode decision.
 
-#include "schro_hip_internal.h"
-#include "scan_common.h"
+#include "motion_common.h"
 
 #pragma clang fp contract(off)
 
@@ -37,22 +39,14 @@ constexpr int kSubpelWaves = 4;
 constexpr int kSubpelThreads = kSubpelWaves * 64;
 constexpr int kSubpelChooseThreads = 256;
 constexpr int kSubpelMaxBlock = 32;
-constexpr int kSubpelMvBytes = 20;      // SchroMotionVector (schromotion.h:20-37): flags, metric, chroma_metric, dx[2], dy[2]
-constexpr int kSubpelMvMetric = 4, kSubpelMvDx = 12, kSubpelMvDy = 16;
 
+// the vector of a record after `mv->u.vec.dx[ref] <<= 1` on an int16_t, and dy likewise
 __device__ __forceinline__ void
-subpel_wave_sync ()
+subpel_doubled (const uint8_t * rec, int ref, int *dx, int *dy)
 {
-  __builtin_amdgcn_fence (__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier ();
-  __builtin_amdgcn_fence (__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// `mv->u.vec.dx[ref] <<= 1` on an int16_t
-__device__ __forceinline__ int
-subpel_double (int v)
-{
-  return (int16_t) ((uint32_t) v << 1);
+  mv_vector (rec, ref, dx, dy);
+  *dx = (int16_t) ((uint32_t) * dx << 1);
+  *dy = (int16_t) ((uint32_t) * dy << 1);
 }
 
 // offset k of sp_matches (schromotionest.c:259-262)
@@ -63,15 +57,6 @@ subpel_offset (int k, int *ox, int *oy)
   const int q = kk >= 6 ? 2 : (kk >= 3 ? 1 : 0);
   *ox = kk - 3 * q - 1;
   *oy = q - 1;
-}
-
-// 16 columns from half-pel column X (and every second one after it) of half-pel row Y: one load
-__device__ __forceinline__ u32x4
-subpel_tap (const uint8_t * up, int stride, int w, int h, int X, int Y)
-{
-  const int Yc = min (max (Y, 0), 2 * h - 2);
-  const int xp = min (max (X >> 1, -kHpApron), w + kHpApron - 1) + kHpApron;
-  return gload < u32x4_u > (up + hp_row_offset (Yc >> 1, stride) + hp_col_offset (xp) + (size_t) (((X & 1) + 2 * (Yc & 1)) * 128));
 }
 
 __global__ __launch_bounds__ (kSubpelThreads)
@@ -97,11 +82,10 @@ void subpel_error_kernel (const SubpelChain * __restrict__ chains, int nchains, 
   const uint32_t tail = scan_tail_mask (bw);
   uint32_t *block = subpel_lds[wave];
   scan_stage_block (block, ch->src, ch->src_stride, w, h, x0, y0, nd, bh, tail, lane);
-  subpel_wave_sync ();
+  wave_sync ();
 
-  const uint8_t *rec = ch->field + (size_t) blk * kSubpelMvBytes;
-  const int dx = subpel_double (gload < int16_t > (rec + kSubpelMvDx + 2 * ch->ref));
-  const int dy = subpel_double (gload < int16_t > (rec + kSubpelMvDy + 2 * ch->ref));
+  int dx, dy;
+  subpel_doubled (mv_record (ch->field, nbx, i, j), ch->ref, &dx, &dy);
   const int k = lane & 7, rg = lane >> 3;
   int ox, oy;
   subpel_offset (k, &ox, &oy);
@@ -109,15 +93,8 @@ void subpel_error_kernel (const SubpelChain * __restrict__ chains, int nchains, 
   const int ext = ch->ext;
   const bool ok = -ext < x && (w << mvprec) + ext > x + xb - 1 && -ext < y && (h << mvprec) + ext > y + yb - 1;
   // the half-pel origin and the remainder in eighths
-  int hx = x, hy = y, rx = 0, ry = 0;
-  if (mvprec == 2) {
-    hx = x >> 1, rx = (x & 1) << 1;
-    hy = y >> 1, ry = (y & 1) << 1;
-  } else if (mvprec == 3) {
-    hx = x >> 2, rx = x & 3;
-    hy = y >> 2, ry = y & 3;
-  }
-  const uint32_t wt[4] = { (uint32_t) ((4 - ry) * (4 - rx)), (uint32_t) ((4 - ry) * rx), (uint32_t) (ry * (4 - rx)), (uint32_t) (ry * rx) };
+  int hx, hy, rx, ry;
+  halfpel_split (x, y, mvprec, &hx, &hy, &rx, &ry);
   const uint8_t *up = ch->up;
   const int stride = ch->up_stride;
   uint32_t acc = 0;
@@ -125,20 +102,7 @@ void subpel_error_kernel (const SubpelChain * __restrict__ chains, int nchains, 
     for (int r = rg; r < bh; r += 8) {
       const uint32_t *brow = block + r * nd;
       for (int seg = 0; seg * 4 < nd; seg++) {
-        u32x4 v;
-        if (wt[0] == 16) {
-          v = subpel_tap (up, stride, w, h, hx + 32 * seg, hy + 2 * r);
-        } else {
-          u32x4 even = { 0x00080008u, 0x00080008u, 0x00080008u, 0x00080008u }, odd = even;
-#pragma unroll
-          for (int t = 0; t < 4; t++)
-            if (wt[t]) {
-              const u32x4 s = subpel_tap (up, stride, w, h, hx + (t & 1) + 32 * seg, hy + (t >> 1) + 2 * r);
-              even += (s & 0x00ff00ffu) * wt[t];
-              odd += ((s >> 8) & 0x00ff00ffu) * wt[t];
-            }
-          v = ((even >> 4) & 0x00ff00ffu) | (((odd >> 4) & 0x00ff00ffu) << 8);
-        }
+        const u32x4 v = predict_halfpel (up, stride, w, h, hx + 32 * seg, hy + 2 * r, rx, ry, 0, 0);
 #pragma unroll
         for (int d = 0; d < 4; d++) {
           const int n = seg * 4 + d;
@@ -155,20 +119,19 @@ void subpel_error_kernel (const SubpelChain * __restrict__ chains, int nchains, 
     gstore < int32_t > (out + lane, ok ? (int32_t) acc : -1);
 }
 
-// schro_pack_estimate_sint (schropack.c:204-226)
-__device__ __forceinline__ int
-subpel_estimate_sint (int value)
-{
-  const uint32_t a = (uint32_t) (value < 0 ? -value : value);
-  const int n_bits = 32 - __clz ((int) (a + 1));        // maxbit (value + 1)
-  return n_bits + n_bits - 1 + (a ? 1 : 0);
-}
-
-__device__ __forceinline__ int
-subpel_median3 (int a, int b, int c)
-{
-  return max (min (a, b), min (max (a, b), c));
-}
+// The field of a pass as a source of the neighbour records of block (i, j), whose record is `rec`: single-reference and
+// never intra, so every neighbour predicts.  A neighbour is addressed from `rec` -- a constant or one row away: the
+// choice is one dependent chain per lane, and a record's address from the field's start would be three more 64-bit
+// products on it.
+struct SubpelRecords {
+  const uint8_t *rec;
+  int i, j, nbx;
+  __device__ __forceinline__ bool operator () (int x, int y, int mode, int *vx, int *vy) const
+  {
+    mv_vector (rec + ((ptrdiff_t) (y - j) * nbx + (x - i)) * kMvBytes, mode - 1, vx, vy);
+    return true;
+  }
+};
 
 // block (i, j) of pass mvprec, by one lane: doubles the vector, predicts it, scores the centre and the candidates
 __device__ __forceinline__ void
@@ -176,35 +139,15 @@ subpel_choose_block (const SubpelChain * ch, int i, int j)
 {
   const int nbx = ch->nbx, ref = ch->ref;
   const size_t blk = (size_t) j * nbx + i;
-  uint8_t *rec = ch->field + blk * kSubpelMvBytes;
-  const int dx = subpel_double (gload < int16_t > (rec + kSubpelMvDx + 2 * ref));
-  const int dy = subpel_double (gload < int16_t > (rec + kSubpelMvDy + 2 * ref));
-  // schro_mf_vector_prediction (schromotion.c:259-312)
-  int vx[3], vy[3], n = 0;
-  if (i > 0) {
-    vx[n] = gload < int16_t > (rec - kSubpelMvBytes + kSubpelMvDx + 2 * ref);
-    vy[n++] = gload < int16_t > (rec - kSubpelMvBytes + kSubpelMvDy + 2 * ref);
-  }
-  if (j > 0) {
-    const uint8_t *above = rec - (size_t) nbx * kSubpelMvBytes;
-    vx[n] = gload < int16_t > (above + kSubpelMvDx + 2 * ref);
-    vy[n++] = gload < int16_t > (above + kSubpelMvDy + 2 * ref);
-    if (i > 0) {
-      vx[n] = gload < int16_t > (above - kSubpelMvBytes + kSubpelMvDx + 2 * ref);
-      vy[n++] = gload < int16_t > (above - kSubpelMvBytes + kSubpelMvDy + 2 * ref);
-    }
-  }
-  int px = 0, py = 0;
-  if (n == 1)
-    px = vx[0], py = vy[0];
-  else if (n == 2)
-    px = (vx[0] + vx[1] + 1) >> 1, py = (vy[0] + vy[1] + 1) >> 1;
-  else if (n == 3)
-    px = subpel_median3 (vx[0], vx[1], vx[2]), py = subpel_median3 (vy[0], vy[1], vy[2]);
+  uint8_t *rec = mv_record (ch->field, nbx, i, j);
+  int dx, dy, px, py;
+  subpel_doubled (rec, ref, &dx, &dy);
+  const SubpelRecords get = { rec, i, j, nbx };
+  vector_prediction (get, i, j, ref + 1, &px, &py);     // schro_mf_vector_prediction (schromotion.c:259-312)
 
   const double lambda = ch->lambda;
-  const uint32_t metric = gload < uint32_t > (rec + kSubpelMvMetric);
-  int entropy = subpel_estimate_sint (dx - px) + subpel_estimate_sint (dy - py);
+  const uint32_t metric = gload < uint32_t > (rec + kMvMetric);
+  int entropy = estimate_sint (dx - px) + estimate_sint (dy - py);
   double min_score = (double) entropy + lambda * (double) metric;       // (not contracted: the pragma above)
   int m = -1, min_error = 0;
   const int32_t *errors = ch->table + blk * 8;
@@ -213,7 +156,7 @@ subpel_choose_block (const SubpelChain * ch, int i, int j)
     const int error = gload < int32_t > (errors + k);
     int ox, oy;
     subpel_offset (k, &ox, &oy);
-    entropy = subpel_estimate_sint (dx + ox - px) + subpel_estimate_sint (dy + oy - py);
+    entropy = estimate_sint (dx + ox - px) + estimate_sint (dy + oy - py);
     const double score = (double) entropy + lambda * (double) error;
     if (error >= 0 && min_score > score) {
       min_score = score;
@@ -227,10 +170,10 @@ subpel_choose_block (const SubpelChain * ch, int i, int j)
     subpel_offset (m, &ox, &oy);
     ndx += ox;
     ndy += oy;
-    gstore < uint32_t > (rec + kSubpelMvMetric, (uint32_t) min_error);
+    gstore < uint32_t > (rec + kMvMetric, (uint32_t) min_error);
   }
-  gstore < uint16_t > (rec + kSubpelMvDx + 2 * ref, (uint16_t) ndx);
-  gstore < uint16_t > (rec + kSubpelMvDy + 2 * ref, (uint16_t) ndy);
+  gstore < uint16_t > (rec + kMvDx + 2 * ref, (uint16_t) ndx);
+  gstore < uint16_t > (rec + kMvDy + 2 * ref, (uint16_t) ndy);
 }
 
 __global__ __launch_bounds__ (kSubpelChooseThreads)
@@ -239,12 +182,9 @@ void subpel_choose_kernel (const SubpelChain * __restrict__ chains)
   const SubpelChain *ch = chains + blockIdx.x;
   // the blocks whose origin lies inside the picture: the others are skipped, their records stay as they are
   const int cols = min (ch->nbx, (ch->w + ch->xb - 1) / ch->xb), rws = min (ch->nby, (ch->h + ch->yb - 1) / ch->yb);
-  for (int d = 0; d < cols + rws - 1; d++) {
-    const int jlo = max (0, d - (cols - 1)), jhi = min (d, rws - 1);
-    for (int j = jlo + (int) threadIdx.x; j <= jhi; j += (int) blockDim.x)
-      subpel_choose_block (ch, d - j, j);
-    __syncthreads ();           // the next diagonal reads this one's records
-  }
+  walk_diagonals (cols, rws, (int) threadIdx.x, (int) blockDim.x, [&](int i, int j) {
+        subpel_choose_block (ch, i, j);
+      });
 }
 
 int

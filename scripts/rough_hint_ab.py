@@ -169,7 +169,11 @@ def main():
     for k in range(0, len(scans), 997):
         i, j = blocks1[k]
         mv = f1[j * P["x_num_blocks"] + i]
-        assert (int(got[k][0]) << 1, int(got[k][1]) << 1, int(got[k][2])) == (int(mv["v"][0]), int(mv["v"][2]), int(mv["metric"])), ("scans", k)
+        # (the window lies around the winner, not around the chain's start vector: it holds positions the chain never saw,
+        # so the scan may find a smaller metric than the chain's -- never a larger one, the winner is its gravity position)
+        assert int(got[k][2]) <= int(mv["metric"]), ("scans", k)
+        if int(got[k][2]) == int(mv["metric"]):
+            assert (int(got[k][0]) << 1, int(got[k][1]) << 1) == (int(mv["v"][0]), int(mv["v"][2])), ("scans", k)
     med, spread = rounds_of(ctx, run, a)
     hmed, hlo, n = host_clock(ctx, run, a)
     lines.append("scans    level 1 through schro_hip_metric_scan_batch, %d pictures x %d scans in one call (descriptor table %.1f MB): %9.4f ms device  "
