@@ -1364,6 +1364,74 @@ typedef struct {
  * sub-bands contain records of no width or height, skips those: their summary is zero.) */
 int schro_hip_quantise_batch (SchroHipContext * ctx, const SchroHipQuantPlane * planes, int nplanes, int bytes_per_sample);
 
+/* ---- encoder: core-syntax transform data in the VLC parse codes, written on the device ---------
+ *
+ * schro_encoder_encode_transform_data (schroencoder.c:3462-3483) for params->is_noarith, that is
+ * schro_encoder_encode_subband_noarith (:4072-4192) over component 0 .. 2 and sub-band 0 .. 3 * depth, WITHOUT its
+ * quantiser call (:4100-4104): schro_hip_quantise_batch / schro_hipframe_quantise have run, the quant planes are the
+ * input.  The output is what the reference appends to frame->pack from a synchronised pack, up to and including one
+ * final schro_pack_sync.  Per sub-band: sync, uint (length); when length > 0, uint (quant index of codeblock (0, 0)),
+ * sync and `length` bytes of the flushed sub-pack -- per codeblock in raster order bit (zero) when there is more than one
+ * codeblock and index > 0, sint (0) when there is more than one codeblock and codeblock_mode_index == 1 (the ENCODER's
+ * rule; schro_decoder_setup_codeblocks ignores the count), then schro_pack_encode_sint of every value, rows top to
+ * bottom (schropack.c:148-178: 1 .. 32 bits on s16, up to 64 on s32).  Codeblock counts and rectangles are
+ * schro_hip_codeblock_layout's: sub-band 0 takes entry [0], every other one [SCHRO_SUBBAND_SHIFT (position) + 1].
+ *
+ * Three things of the reference's are kept as they are.
+ * (a) The zero test of s16 frames, schro_frame_data_is_zero (:4043-4070): true when the 16-bit wrapped sum of the 16-bit
+ *     abs of every row is 0 (abs (-32768) stays -32768).  A codeblock's flag applies it to the codeblock's row pieces, the
+ *     sub-band's flag to the sub-band's whole rows; each can be true over non-zero values, and the two can disagree in
+ *     both directions.  The bytes follow the reference; false_zero_* count what was called zero though it holds a
+ *     non-zero value -- codeblocks (of sub-bands that are written, where a flag is written) and sub-bands -- so that a
+ *     caller sees that the stream and its local decode have parted.  s32 frames take the true test.
+ *     SchroHipCodeblockSummary.nonzero keeps its true meaning; this call does not read the summaries.
+ * (b) subband_bits is frame->actual_subband_bits: 8 x the difference of whole-byte offsets after the leading sync and
+ *     before any trailing one -- 0 for a zero sub-band (its one bit is still in the accumulator), header + payload else.
+ * (c) The quant offset written is always 0, so the records of one sub-band must carry one quant index.
+ *
+ * INT_MIN in an s32 plane is undefined in the reference (-value overflows); here it takes the 64-bit code of magnitude
+ * 2^31 and stays inside the bound.  Bit positions are 32-bit: a picture whose schro_hip_noarith_encode_bound reaches 2^29
+ * bytes is refused.  `capacity` may be any size; only min (capacity, bytes) bytes of `out` are ever written. */
+#define SCHRO_HIP_NOARITH_MAX_SUBBANDS 19       /* 1 + 3 * SCHRO_HIP_LIMIT_TRANSFORM_DEPTH */
+typedef struct {
+  uint32_t bytes;               /* what the picture takes, whether or not it fitted */
+  uint32_t overrun;             /* 1: bytes > capacity, `out` holds the first `capacity` bytes */
+  uint32_t false_zero_codeblocks, false_zero_subbands;  /* (a) */
+  uint32_t subband_bits[3][SCHRO_HIP_NOARITH_MAX_SUBBANDS];     /* (b); entries past 3 * depth are 0 */
+} SchroHipNoarithResult;
+
+typedef struct {
+  const void *quant[3];         /* device: Y, U, V quant planes (s16 or s32); not written */
+  size_t bytes[3];              /* what each plane spans: no record may reach past it */
+  int stride[3];                /* bytes between rows of the plane */
+  int iwt_width[3], iwt_height[3];      /* the transform's size: positive multiples of 1 << transform_depth */
+  const SchroHipCodeblock *codeblocks[3];       /* HOST: schro_hip_codeblock_layout's records for `stride`; quant_index read */
+  int ncodeblocks[3];
+  int transform_depth;
+  int horiz_codeblocks[7], vert_codeblocks[7];  /* params->horiz_codeblocks / vert_codeblocks [0 .. depth] */
+  int codeblock_mode_index;
+  uint8_t *out;                 /* device: the bytes */
+  size_t capacity;              /* of out */
+  SchroHipNoarithResult *result;        /* device, 4-byte aligned: cleared and filled by the call */
+} SchroHipNoarithPicture;
+
+/* The capacity that always suffices: 4 bytes per s16 sample or 8 per s32 sample, two flag bits per codeblock and ten
+ * bytes of header and padding per sub-band.  Reads the sizes, the depth and the counts of `picture` only; < 0 on refusal. */
+int64_t schro_hip_noarith_encode_bound (const SchroHipNoarithPicture * picture, int bytes_per_sample);
+
+/* Pictures of unlike geometry in one call: a count launch over all row pieces (a codeblock's part of a sub-band row), a
+ * layout launch (a workgroup per picture), a clear of the bytes the picture takes and a pack launch.  Enqueues, does not
+ * synchronise.  Refused (SCHRO_HIP_EINVAL, nothing enqueued, the message naming picture, component and sub-band or
+ * record): bytes_per_sample not 2 or 4, a depth above 6, sizes that are no positive multiples of 1 << depth or reach
+ * 32768, codeblock counts outside 1 .. 32767, a codeblock_mode_index other than 0 / 1, a NULL or misaligned pointer, a
+ * stride shorter than a row or no multiple of the sample size, records that are not schro_hip_codeblock_layout's for the
+ * stated counts and stride, a record that reaches outside `bytes`, a quant index above 60, unlike quant indices in one
+ * sub-band, a bound of 2^29 bytes or more, an output that overlaps a quant plane. */
+int schro_hip_noarith_encode_batch (SchroHipContext * ctx, const SchroHipNoarithPicture * pictures, int npictures,
+    int bytes_per_sample);
+/* host only: the refusals of schro_hip_noarith_encode_batch without a context.  No pointer is dereferenced but the HOST arrays. */
+int schro_hip_noarith_encode_check (const SchroHipNoarithPicture * pictures, int npictures, int bytes_per_sample);
+
 /* ---- encoder: sub-band histograms on the device ----------------------------------------------
  *
  * The pass over the coefficients that every rate-controlled quantiser choice starts with
@@ -1801,6 +1869,18 @@ int schro_hip_decode_lowdelay_transform_data (SchroHipFrame * transform_frame,
  * first departure).  Copies back on the selected queue and waits for it. */
 int schro_hip_encode_lowdelay_transform_data (const SchroHipFrame * iwt_frame, void *slices, size_t slices_bytes,
     const SchroHipLowDelayParams * params, uint8_t * base_index, int *overruns);
+
+/* schro_encoder_encode_transform_data (frame) for params->is_noarith, schroencoder.c:3462-3483, with frame->quant_frame
+ * on the device (schro_hipframe_quantise has run): the bytes the reference appends to frame->pack arrive in the HOST
+ * buffer `out`, at most `capacity` of them; *bytes is what the picture takes.  quant_indices[k]: the quant index of every
+ * record of component k in schro_hip_codeblock_layout's order, as schro_hipframe_quantise takes them.  subband_bits (or
+ * NULL): frame->actual_subband_bits, [component][index]; false_zero (or NULL): the codeblocks and the sub-bands the s16
+ * zero test called zero over non-zero values (schro_hip_noarith_encode_batch (a)).  Returns 0, or SCHRO_HIP_ENOMEM with
+ * *bytes set when the picture takes more than `capacity` (schro_hip_noarith_encode_bound always suffices).  Copies back
+ * on the selected queue and waits for it. */
+int schro_hip_encode_transform_data_noarith (const SchroHipFrame * quant_frame, const SchroHipParams * params,
+    const int *const quant_indices[3], void *out, size_t capacity, size_t *bytes,
+    int subband_bits[3][SCHRO_HIP_NOARITH_MAX_SUBBANDS], int false_zero[2]);
 
 /* r05 -- the quantised hand-over behind the frame layer (VERDICT r04 "missing" 1): what a patched
  * schro_decoder_decode_subband (schrodecoder.c:3525-3640) leaves behind for one picture instead of a dense

@@ -251,6 +251,60 @@ def mode_check(pictures):
     check(_lib.load().schro_hip_mode_decision_check(mode_pictures(pictures), len(pictures)))
 
 
+def noarith_pictures(pictures):
+    """The SchroHipNoarithPicture array of [(planes, tables, depth, horiz_codeblocks, vert_codeblocks, codeblock_mode_index,
+    out, capacity, result)]: planes -- the Y, U, V quant planes at the transform's size (anything with ptr, stride, width,
+    height); tables -- per component the C table of Context.codeblock_layout for that plane's stride with the quant
+    indices filled in (or a list of record tuples); out, result -- device memory (anything with ptr) or None.  Returns
+    (array, what it points to)."""
+    arr = (_lib.NoarithPicture * len(pictures))()
+    keep = []
+    for a, (planes, tables, depth, hc, vc, mode, out, capacity, result) in zip(arr, pictures):
+        for k in range(3):
+            tab = tables[k] if isinstance(tables[k], C.Array) else Context.codeblock_table(tables[k])
+            keep.append(tab)
+            a.quant[k], a.stride[k] = planes[k].ptr, planes[k].stride
+            a.iwt_width[k], a.iwt_height[k] = planes[k].width, planes[k].height
+            a.bytes[k] = planes[k].stride * planes[k].height
+            a.codeblocks[k], a.ncodeblocks[k] = tab, len(tab)
+        a.transform_depth, a.codeblock_mode_index = depth, mode
+        for l in range(min(len(hc), 7)):
+            a.horiz_codeblocks[l], a.vert_codeblocks[l] = hc[l], vc[l]
+        a.out = out.ptr if out is not None else None
+        a.capacity = capacity
+        a.result = result.ptr if result is not None else None
+    return arr, keep
+
+
+def noarith_encode_check(pictures, bpp):
+    """The refusals of Context.noarith_encode_batch on the host, without a context (schro_hip_noarith_encode_check)."""
+    arr, keep = noarith_pictures(pictures)
+    check(_lib.load().schro_hip_noarith_encode_check(arr, len(pictures), bpp))
+
+
+def noarith_encode_bound(sizes, depth, horiz_codeblocks, vert_codeblocks, bpp):
+    """schro_hip_noarith_encode_bound: the output capacity that always suffices for a picture whose components are
+    sizes = [(width, height)] * 3 at the transform's size."""
+    a = _lib.NoarithPicture()
+    for k, (w, h) in enumerate(sizes):
+        a.iwt_width[k], a.iwt_height[k] = w, h
+    a.transform_depth = depth
+    for l in range(min(len(horiz_codeblocks), 7)):
+        a.horiz_codeblocks[l], a.vert_codeblocks[l] = horiz_codeblocks[l], vert_codeblocks[l]
+    n = _lib.load().schro_hip_noarith_encode_bound(C.byref(a), bpp)
+    if n < 0:
+        check(int(n))
+    return int(n)
+
+
+def noarith_result(words):
+    """A downloaded SchroHipNoarithResult (uint32 words) as a dict: bytes, overrun, false_zero (codeblocks, sub-bands),
+    subband_bits (3 x 19)."""
+    w = np.asarray(words, np.uint32).ravel()
+    return {"bytes": int(w[0]), "overrun": int(w[1]), "false_zero": (int(w[2]), int(w[3])),
+            "subband_bits": w[4:4 + 3 * _lib.NOARITH_MAX_SUBBANDS].astype(np.int64).reshape(3, _lib.NOARITH_MAX_SUBBANDS)}
+
+
 QUANTISE_DC_THREADS = 256       # SCHRO_HIP_QUANTISE_DC_THREADS (include/schro_hip.h): the DC recurrence's workgroup size
 
 
@@ -1095,6 +1149,59 @@ class Context:
         check(self.lib.schro_hip_encode_lowdelay_transform_data(iwt_frame.ptr(), data.ctypes.data, nbytes,
                                                                 C.byref(self.lowdelay_params(P)), idx.ctypes.data, C.byref(ovr)))
         return data[:nbytes], idx, int(ovr.value)
+
+    def noarith_encode_batch(self, pictures, capacity=None):
+        """schro_hip_noarith_encode_batch.  pictures: per picture (planes, tables, depth, horiz_codeblocks, vert_codeblocks,
+        codeblock_mode_index) -- as noarith_pictures takes them -- or the same followed by (out, capacity, result) with
+        caller-owned device buffers (a u8 DevicePlane, its capacity in bytes, a DevicePlane of a SchroHipNoarithResult).
+        Mirrors schro_encoder_encode_transform_data for is_noarith without its quantiser call.  Where the buffers are the
+        call's own -- `capacity` bytes each, or noarith_encode_bound -- waits and returns per picture (bytes uint8 array
+        cut at the capacity, noarith_result dict); with caller-owned buffers the call is asynchronous and returns None."""
+        bpp = pictures[0][0][0].dtype.itemsize
+        own, full = [], []
+        words = C.sizeof(_lib.NoarithResult) // 4
+        for pic in pictures:
+            if len(pic) == 9:
+                full.append(tuple(pic))
+                continue
+            planes, tables, depth, hc, vc, mode = pic
+            cap = capacity if capacity is not None else noarith_encode_bound([(p.width, p.height) for p in planes], depth, hc, vc, bpp)
+            out = DevicePlane(self, 1, max(cap, 1), np.uint8)
+            res = DevicePlane(self, 1, words, np.uint32)
+            own.append((out, res, cap))
+            full.append((planes, tables, depth, hc, vc, mode, out, cap, res))
+        try:
+            arr, keep = noarith_pictures(full)
+            check(self.lib.schro_hip_noarith_encode_batch(self.h, arr, len(full), bpp))
+            if not own:
+                return None
+            got = []
+            for out, res, cap in own:
+                r = noarith_result(res.download())
+                got.append((out.download()[0, :min(cap, r["bytes"])].copy(), r))
+            return got
+        finally:
+            for out, res, cap in own:
+                out.free()
+                res.free()
+
+    def encode_transform_data_noarith(self, quant_frame, params, quant_indices, capacity):
+        """schro_hip_encode_transform_data_noarith on a device frame (frames.DeviceFrame, s16 / s32) that
+        schro_hipframe_quantise filled: (bytes uint8 array, bytes the picture takes, subband_bits (3 x 19), false_zero
+        (codeblocks, sub-bands), status) -- status 0, or SCHRO_HIP_ENOMEM (-3) when the picture takes more than
+        `capacity`; any other status raises.  quant_indices: per component the quant index of every record."""
+        idx = [np.ascontiguousarray(q, np.int32) for q in quant_indices]
+        qi = (C.POINTER(C.c_int) * 3)(*[q.ctypes.data_as(C.POINTER(C.c_int)) for q in idx])
+        data = np.zeros(max(capacity, 1), np.uint8)
+        nbytes = C.c_size_t(0)
+        bits = ((C.c_int * _lib.NOARITH_MAX_SUBBANDS) * 3)()
+        fz = (C.c_int * 2)()
+        rc = self.lib.schro_hip_encode_transform_data_noarith(quant_frame.ptr(), C.byref(params), qi, data.ctypes.data, capacity,
+                                                              C.byref(nbytes), bits, fz)
+        if rc not in (0, -3) or (rc == -3 and nbytes.value <= capacity):
+            check(rc)
+        return (data[:min(capacity, nbytes.value)], int(nbytes.value), np.array([list(b) for b in bits], np.int64),
+                (int(fz[0]), int(fz[1])), rc)
 
     @staticmethod
     def codeblock_table(cbs):

@@ -54,6 +54,8 @@ EXPORTED_SYMBOLS = [
     "schro_hipframe_shift_right", "schro_hip_add_batch", "schro_hipframe_add",
     "schro_hip_lowdelay_arith", "schro_hip_lowdelay_batch", "schro_hip_dc_predict_batch",
     "schro_hip_lowdelay_encode_batch", "schro_hip_encode_lowdelay_transform_data",
+    "schro_hip_noarith_encode_bound", "schro_hip_noarith_encode_batch", "schro_hip_noarith_encode_check",
+    "schro_hip_encode_transform_data_noarith",
     "schro_hip_dequant_batch", "schro_hip_quantise_batch", "schro_hip_subtract_batch", "schro_hipframe_subtract",
     "schro_hipframe_quantise", "schro_hip_histogram_batch", "schro_hipframe_subband_histograms",
     "schro_hip_decode_lowdelay_transform_data", "schro_hipframe_dequantise",
@@ -243,6 +245,23 @@ class QuantPlane(C.Structure):
     _fields_ = [("coeffs", C.c_void_p), ("quant", C.c_void_p), ("bytes", C.c_size_t), ("codeblocks", C.POINTER(Codeblock)),
                 ("ncodeblocks", C.c_int), ("is_intra", C.c_int), ("dc_predict_first", C.c_int), ("dc_width", C.c_int),
                 ("dc_height", C.c_int), ("summary", C.c_void_p)]
+
+
+NOARITH_MAX_SUBBANDS = 19       # SCHRO_HIP_NOARITH_MAX_SUBBANDS (include/schro_hip.h)
+
+
+class NoarithResult(C.Structure):
+    """SchroHipNoarithResult: what schro_hip_noarith_encode_batch leaves on the device per picture."""
+    _fields_ = [("bytes", C.c_uint32), ("overrun", C.c_uint32), ("false_zero_codeblocks", C.c_uint32),
+                ("false_zero_subbands", C.c_uint32), ("subband_bits", (C.c_uint32 * NOARITH_MAX_SUBBANDS) * 3)]
+
+
+class NoarithPicture(C.Structure):
+    """SchroHipNoarithPicture (include/schro_hip.h): one picture of schro_hip_noarith_encode_batch."""
+    _fields_ = [("quant", C.c_void_p * 3), ("bytes", C.c_size_t * 3), ("stride", C.c_int * 3), ("iwt_width", C.c_int * 3),
+                ("iwt_height", C.c_int * 3), ("codeblocks", C.POINTER(Codeblock) * 3), ("ncodeblocks", C.c_int * 3),
+                ("transform_depth", C.c_int), ("horiz_codeblocks", C.c_int * 7), ("vert_codeblocks", C.c_int * 7),
+                ("codeblock_mode_index", C.c_int), ("out", C.c_void_p), ("capacity", C.c_size_t), ("result", C.c_void_p)]
 
 
 HISTOGRAM_BINS = 104            # SCHRO_HIP_HISTOGRAM_BINS (include/schro_hip.h)
@@ -608,6 +627,16 @@ def load():
     L.schro_hip_encode_lowdelay_transform_data.argtypes = [C.POINTER(Frame), vp, C.c_size_t, C.POINTER(LowDelayParams),
                                                            vp, C.POINTER(C.c_int)]
     L.schro_hip_encode_lowdelay_transform_data.restype = i
+    L.schro_hip_noarith_encode_bound.argtypes = [C.POINTER(NoarithPicture), i]
+    L.schro_hip_noarith_encode_bound.restype = C.c_int64
+    L.schro_hip_noarith_encode_batch.argtypes = [vp, C.POINTER(NoarithPicture), i, i]
+    L.schro_hip_noarith_encode_batch.restype = i
+    L.schro_hip_noarith_encode_check.argtypes = [C.POINTER(NoarithPicture), i, i]
+    L.schro_hip_noarith_encode_check.restype = i
+    L.schro_hip_encode_transform_data_noarith.argtypes = [C.POINTER(Frame), C.POINTER(Params), C.POINTER(C.POINTER(C.c_int)), vp,
+                                                          C.c_size_t, C.POINTER(C.c_size_t),
+                                                          C.POINTER(C.c_int * NOARITH_MAX_SUBBANDS), C.POINTER(C.c_int)]
+    L.schro_hip_encode_transform_data_noarith.restype = i
     L.schro_hip_dc_predict_batch.argtypes = [vp, C.POINTER(DcPlane), i, i]
     L.schro_hip_dc_predict_batch.restype = i
     L.schro_hip_shift_right_batch.argtypes = [vp, C.POINTER(DcPlane), i, i, i]

@@ -660,6 +660,93 @@ schro_hip_encode_lowdelay_transform_data (const SchroHipFrame * iwt_frame, void 
   return r ? r : rs;
 }
 
+// schro_encoder_encode_transform_data (schroencoder.c:3462-3483) for params->is_noarith with frame->quant_frame on the
+// device: the bytes the reference appends to frame->pack come back to the host instead of the quant frame.
+int
+schro_hip_encode_transform_data_noarith (const SchroHipFrame * quant_frame, const SchroHipParams * params,
+    const int *const quant_indices[3], void *out, size_t capacity, size_t *bytes,
+    int subband_bits[3][SCHRO_HIP_NOARITH_MAX_SUBBANDS], int false_zero[2])
+{
+  const char *who = "encode_transform_data_noarith";
+  SCHRO_HIP_REQUIRE (quant_frame && frame_ctx (quant_frame) && params && quant_indices && bytes && (out || capacity == 0),
+      "%s: bad arguments (the quant frame must be a device frame)", who);
+  SchroHipContext *ctx = frame_ctx (quant_frame);
+  const int bpp = format_bpp (quant_frame->format);
+  SCHRO_HIP_REQUIRE ((bpp == 2 || bpp == 4) && !(quant_frame->format & 0x100), "%s: the frame must be a planar s16 or s32 frame", who);
+  const int depth = params->transform_depth;
+  SCHRO_HIP_REQUIRE (depth >= 0 && depth <= 6, "%s: transform_depth %d", who, depth);
+  SchroHipNoarithPicture pic;
+  memset (&pic, 0, sizeof (pic));
+  pic.transform_depth = depth;
+  pic.codeblock_mode_index = params->codeblock_mode_index;
+  for (int l = 0; l <= depth; l++) {
+    pic.horiz_codeblocks[l] = params->horiz_codeblocks[l];
+    pic.vert_codeblocks[l] = params->vert_codeblocks[l];
+  }
+  std::vector < SchroHipCodeblock > recs[3];
+  for (int k = 0; k < 3; k++) {
+    const SchroHipFrameData & q = quant_frame->components[k];
+    const int w = k ? params->iwt_chroma_width : params->iwt_luma_width, h = k ? params->iwt_chroma_height : params->iwt_luma_height;
+    SCHRO_HIP_REQUIRE (quant_indices[k], "%s: component %d has no quant indices", who, k);
+    SCHRO_HIP_REQUIRE (w > 0 && h > 0 && q.width >= w && q.height >= h && (long long) q.stride >= (long long) w * bpp,
+        "%s: component %d (%d x %d, stride %d) does not hold the %d x %d transform", who, k, q.width, q.height, q.stride, w, h);
+    const int n = schro_hip_codeblock_layout (w, h, depth, params->horiz_codeblocks, params->vert_codeblocks, q.stride, bpp, nullptr, 0);
+    if (n <= 0)
+      return n < 0 ? n : set_error (SCHRO_HIP_EINVAL, "%s: component %d has no codeblocks", who, k);
+    recs[k].resize (n);
+    (void) schro_hip_codeblock_layout (w, h, depth, params->horiz_codeblocks, params->vert_codeblocks, q.stride, bpp, recs[k].data (), n);
+    for (int c = 0; c < n; c++) {
+      SCHRO_HIP_REQUIRE (quant_indices[k][c] >= 0 && quant_indices[k][c] <= 60, "%s: component %d, codeblock %d: quant index %d", who, k,
+          c, quant_indices[k][c]);
+      recs[k][c].quant_index = (unsigned char) quant_indices[k][c];
+    }
+    pic.quant[k] = q.data;
+    pic.bytes[k] = (size_t) q.stride * (size_t) h;
+    pic.stride[k] = q.stride;
+    pic.iwt_width[k] = w;
+    pic.iwt_height[k] = h;
+    pic.codeblocks[k] = recs[k].data ();
+    pic.ncodeblocks[k] = n;
+  }
+  // one allocation: the result, the bytes
+  char *d = (char *) schro_hip_domain_alloc (ctx, 256 + (capacity ? capacity : 1));
+  if (!d)
+    return SCHRO_HIP_ENOMEM;
+  pic.result = (SchroHipNoarithResult *) d;
+  pic.out = (uint8_t *) d + 256;
+  pic.capacity = capacity;
+  static_assert (sizeof (SchroHipNoarithResult) <= 256, "the result sits in front of the bytes");
+  int r = schro_hip_noarith_encode_batch (ctx, &pic, 1, bpp);
+  SchroHipNoarithResult res;
+  memset (&res, 0, sizeof (res));
+  if (!r && hipMemcpyAsync (&res, d, sizeof (res), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+    r = set_error (SCHRO_HIP_EDEVICE, "%s: copy of the result failed", who);
+  int rs = r ? 0 : schro_hip_synchronize (ctx);
+  const size_t take = std::min ((size_t) res.bytes, capacity);
+  if (!r && !rs && take) {
+    if (hipMemcpyAsync (out, d + 256, take, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+      r = set_error (SCHRO_HIP_EDEVICE, "%s: copy of %zu bytes failed", who, take);
+    rs = schro_hip_synchronize (ctx);   // the host buffer is filled, d is free again
+  } else if (r) {
+    rs = schro_hip_synchronize (ctx);
+  }
+  schro_hip_domain_free (ctx, d);
+  if (r || rs)
+    return r ? r : rs;
+  *bytes = res.bytes;
+  if (subband_bits)
+    for (int k = 0; k < 3; k++)
+      for (int i = 0; i < SCHRO_HIP_NOARITH_MAX_SUBBANDS; i++)
+        subband_bits[k][i] = (int) res.subband_bits[k][i];
+  if (false_zero) {
+    false_zero[0] = (int) res.false_zero_codeblocks;
+    false_zero[1] = (int) res.false_zero_subbands;
+  }
+  if (res.overrun)
+    return set_status (SCHRO_HIP_ENOMEM, "%s: the picture takes %u bytes, the buffer holds %zu", who, res.bytes, capacity);
+  return 0;
+}
+
 // r05 -- schro_decoder_decode_subband's data-parallel half on the device, behind the frame layer: the picture arrives
 // as codeblock records + quantised values (include/schro_hip.h), leaves as the dense transform frame x_wavelet_transform
 // reads.  Reference: schrodecoder.c:3525-3640 (the codeblock loop), :3311-3322 (zero codeblocks), :3060-3083 / :3400-3451

@@ -859,6 +859,43 @@ int launch_quantise_dc (hipStream_t stream, const QuantDcJob * d_jobs, int njobs
 // lowdelay_enc.hip; stages: 1 estimate, 2 choose, 4 pack
 int launch_lowdelay_encode (hipStream_t stream, const EncJob * d_jobs, int njobs, const SliceParams & P,
     const EncChooseLayout & L, int stages);
+// noarith_enc.hip: one sub-band of one component of one picture.  Its pieces are (band row r, codeblock column x), piece
+// r * hc + x; its codeblocks (y, x) in raster order -- schro_hip_codeblock_layout's, by the closed forms xmin = x bw / hc,
+// ymin = y bh / vc, which plane_noarith_enc.cpp holds the caller's records against
+struct NaSubband {
+  const void *base;             // sample (0, 0) of the band in the quant plane
+  int stride;                   // bytes between band rows
+  int bw, bh, hc, vc;
+  int piece_base;               // first of its bh * hc pieces in the call's piece arrays
+  int cb_base;                  // first of its hc * vc codeblocks in the call's codeblock arrays
+  int row_base;                 // band rows of the picture's sub-bands before it
+  int flags;                    // 1: have_zero_flags, 2: have_quant_offset
+  int quant_index;              // of codeblock (0, 0)
+  int comp, index;
+  int pad[2];
+};
+static_assert (sizeof (NaSubband) == 64, "NaSubband is copied to LDS as 16 words");
+struct NaPicture {
+  uint8_t *out;
+  SchroHipNoarithResult *result;
+  uint32_t capacity;            // min (capacity, 2^29): a picture takes less
+  int sb_first, nsb;            // its sub-bands in the call's table, stream order
+  int cb_first, ncb;            // its codeblocks
+  int rows;                     // band rows of all its sub-bands
+};
+constexpr int kNaMaxSubbands = 3 * SCHRO_HIP_NOARITH_MAX_SUBBANDS;
+constexpr int kNaLayoutThreads = 1024;  // the layout workgroup: a picture of more codeblocks is scanned in runs per thread
+constexpr int kNaGridX = 1024;  // workgroups per sub-band of the count and pack launches: more pieces are walked in strides
+constexpr uint32_t kNaNone = 0xffffffffu;       // a piece or sub-band that is not written
+struct NaScratch {              // the selected queue's, per call
+  uint32_t *bits, *info, *start;        // per piece: bits of its codes; row sum (16 bits) | non-zero << 16; first bit
+  uint32_t *cb_bits, *cb_flags, *cb_pos, *cb_at;        // per codeblock: bits of its values; 1 zero test fails, 2 truly non-zero;
+  // payload bits of the picture before it; its first bit in the picture
+  uint32_t *sb_at, *sb_len;     // per sub-band: first bit of its header; payload bytes (0: the zero form)
+};
+// stages: 1 count, 2 layout, 4 clear + pack
+int launch_noarith_encode (hipStream_t stream, const NaSubband * d_sbs, int nsbs, const NaPicture * d_pics, int npics,
+    const NaScratch & S, int bpp, int grid_x, int clear_x, int stages);
 // hist.hip
 void hist_tile_geometry (int *group_bytes, int *groups_per_tile, int *groups_per_step);
 int launch_histogram (hipStream_t stream, const HistJob * d_jobs, int njobs, int total_tiles, int bpp);
