@@ -335,8 +335,18 @@ def new_stats(stats=None):
     return st
 
 
-def choose(table, params, width, height, lam, fields, order="raster", fused=False, stats=None):
-    """(motion as MV_DTYPE, the superblock table as SB_DTYPE) from the metric table and the sub-pel fields."""
+def _stale_get(get, stale, x, y):
+    """`get` for block (x, y), with the neighbours the predicate names read as they were before the call."""
+    if stale is None:
+        return get
+    return lambda nx, ny: bytearray(20) if stale(x, y, nx, ny) else get(nx, ny)
+
+
+def choose(table, params, width, height, lam, fields, order="raster", fused=False, stats=None, stale=None):
+    """(motion as MV_DTYPE, the superblock table as SB_DTYPE) from the metric table and the sub-pel fields.  `stale` exists
+    only for the CPU assertions of tests/long_diagonal_cases.py: a predicate (x, y, nx, ny) that makes neighbour (nx, ny) of
+    block (x, y), where it says so, the record as it was before the call (20 zero bytes), as a device that missed the
+    neighbour's stores would read it."""
     nbx, nby, blocks, _ = geometry(params, width, height)
     assert nbx % 4 == 0 and nby % 4 == 0
     num_refs = len(fields)
@@ -364,7 +374,8 @@ def choose(table, params, width, height, lam, fields, order="raster", fused=Fals
                                 same = (nx >> 2, ny >> 2) == (x >> 2, y >> 2)
                                 st["inside_with_outside_neighbour"] += int(inside(x, y))
                                 st["same_sb_outside_neighbour" if same else "other_sb_outside_neighbour"] += 1
-                        work, final, e, h = choose_block(get, x, y, inside(x, y), num_refs, lam, fields, table[y * nbx + x], y * nbx + x, fused, st)
+                        work, final, e, h = choose_block(_stale_get(get, stale, x, y), x, y, inside(x, y), num_refs, lam, fields, table[y * nbx + x],
+                                                         y * nbx + x, fused, st)
                         motion[y * nbx + x] = work
                         block[jj, ii] = final
                         error[(j // 4) * sbx + i // 4] += e
@@ -383,7 +394,8 @@ def choose(table, params, width, height, lam, fields, order="raster", fused=Fals
 
                 def get(nx, ny, x=x, y=y):
                     return (working if (nx >> 2, ny >> 2) == (x >> 2, y >> 2) else final)[ny * nbx + nx]
-                done[x, y] = choose_block(get, x, y, inside(x, y), num_refs, lam, fields, table[y * nbx + x], y * nbx + x, fused, st)
+                done[x, y] = choose_block(_stale_get(get, stale, x, y), x, y, inside(x, y), num_refs, lam, fields, table[y * nbx + x], y * nbx + x,
+                                          fused, st)
             for (x, y), (work, fin, e, h) in done.items():      # (a diagonal's blocks do not see one another)
                 working[y * nbx + x], final[y * nbx + x] = work, fin
                 error[(y // 4) * sbx + x // 4] += e

@@ -7,9 +7,12 @@ edge extensions): every edge extension also overwrites the last column, or the b
 tests/test_subpel_ref.py compares the planes with oracle_lib.UpComp.get sample for sample.  Every read asserts that it
 stays inside the aprons.
 
-Two switches exist only for the CPU assertions of tests/subpel_cases.py: `stale_neighbours` predicts from the vectors
+Switches that exist only for CPU assertions.  tests/subpel_cases.py: `stale_neighbours=True` predicts from the vectors
 as they were at the start of the pass (doubled), and `fused` scores as the correctly rounded lambda * error + entropy (what
-a fused multiply-add would give)."""
+a fused multiply-add would give).  tests/long_diagonal_cases.py: `stale_neighbours` as a predicate (i, j, ni, nj) makes
+neighbour (ni, nj) of block (i, j), where it says so, the record as it was before the pass -- NOT doubled: what a device
+that missed the neighbour's stores would read -- and `order="diagonal"` walks the anti-diagonals i + j, each from the
+bottom row up (the opposite of raster), in place: a block reads only blocks of earlier diagonals."""
 from fractions import Fraction
 
 import numpy as np
@@ -134,8 +137,16 @@ def _score(entropy, lam, error, fused):
     return entropy + lam * float(error)                 # a rounded product, then a rounded sum
 
 
+def block_order(nbx, nby, order):
+    """The blocks (i, j) line by line: the rows of the C loops, or the anti-diagonals."""
+    if order == "raster":
+        return [[(i, j) for i in range(nbx)] for j in range(nby)]
+    assert order == "diagonal"
+    return [[(d - j, j) for j in range(min(d, nby - 1), max(0, d - (nbx - 1)) - 1, -1)] for d in range(nbx + nby - 1)]
+
+
 def subpel_deep(src, ref, params, mv_precision, ref_index, lam, field, extension, tables=None, stale_neighbours=False,
-                fused=False, stats=None):
+                fused=False, stats=None, order="raster"):
     """(field, [the int32 (records, 8) error table of pass 1, 2, ..]).  src, ref: the luma planes (ref may be None with
     `tables`); field: the MV_DTYPE source field (not changed); tables: the error tables to choose from instead of the
     pictures (-1: inadmissible), one per pass."""
@@ -158,8 +169,8 @@ def subpel_deep(src, ref, params, mv_precision, ref_index, lam, field, extension
         x_max, y_max = (width << mvprec) + extension, (height << mvprec) + extension
         table = np.full((nbx * nby, 8), -1, np.int32)
         start = v.copy()
-        for j in range(nby):
-            for i in range(nbx):
+        for line in block_order(nbx, nby, order):
+            for i, j in line:
                 n = j * nbx + i
                 # schro_frame_get_data (orig_frame, &orig, 0, i * xblen, j * yblen)
                 if i * xblen >= width or j * yblen >= height:
@@ -171,7 +182,16 @@ def subpel_deep(src, ref, params, mv_precision, ref_index, lam, field, extension
                 v[n][2 + ref_index] = _int16(int(v[n][2 + ref_index]) << 1)
                 st["shifted"] += 1
                 mvx, mvy = int(v[n][ref_index]), int(v[n][2 + ref_index])
-                if stale_neighbours:
+                if callable(stale_neighbours):
+                    vx, vy = [], []
+                    for cond, ni, nj in ((i > 0, i - 1, j), (j > 0, i, j - 1), (i > 0 and j > 0, i - 1, j - 1)):
+                        if cond:
+                            rec = (start if stale_neighbours(i, j, ni, nj) else v)[nj * nbx + ni]
+                            vx.append(int(rec[ref_index]))
+                            vy.append(int(rec[2 + ref_index]))
+                    pred_x, pred_y = ((0, 0) if not vx else (vx[0], vy[0]) if len(vx) == 1 else
+                                      ((vx[0] + vx[1] + 1) >> 1, (vy[0] + vy[1] + 1) >> 1) if len(vx) == 2 else (_median3(*vx), _median3(*vy)))
+                elif stale_neighbours:
                     stale = np.array([[_int16(int(a) << 1) for a in rec] for rec in start[[max(n - 1, 0), max(n - nbx, 0), max(n - nbx - 1, 0)]]])
                     vx, vy = [], []
                     for cond, k in ((i > 0, 0), (j > 0, 1), (i > 0 and j > 0, 2)):
