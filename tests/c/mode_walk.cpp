@@ -3,7 +3,12 @@
 // objects of the library's device-free sanitizer build (make -C schroedinger_amd/csrc dry_asan).  Launches are dropped
 // there, so what runs is every refusal, the table and scratch arithmetic and the job records of the three batch calls, over
 // pictures of every geometry class: three chroma formats, one and two references, separations from 4 to 32, clipped and
-// padded grids, one to eight pictures per call.  tests/test_mode_host_sanitized.py builds and runs it.
+// padded grids, one to eight pictures per call.  Then, on a context of its own, the frame-layer runs of the motion stages
+// -- sub-pel refinement, split 2, the whole mode decision, the block-matching chain, the rough chain -- in small, large,
+// small order with plane-layer calls between them: every one of them sizes the queue's scratch itself, carves fields and
+// outputs out of it behind the tables and copies to and from host arrays of the exact size, so a copy out of a block
+// that the batch call reallocated, or past a host field, is a report here (the CPU-side twin of
+// tests/test_gpu_encoder_pipeline.py::test_scratch_sequences).  tests/test_mode_host_sanitized.py builds and runs it.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -116,6 +121,161 @@ refusals (const SchroHipModePicture & good)
   EXPECT (schro_hip_mode_decision_check (&good, 1 << 20) == SCHRO_HIP_EINVAL, "2^20 pictures pass");
 }
 
+// ---- the frame-layer runs on a fresh context: small, large, small ---------------------------------------------------------
+
+struct HostFields {
+  std::vector < void *>owned;
+  void *take (size_t bytes)
+  {
+    void *m = calloc (bytes ? bytes : 1, 1);    // (the exact size: a copy past it is a report)
+    if (!m)
+      exit (2);
+    owned.push_back (m);
+    return m;
+  }
+   ~HostFields ()
+  {
+    for (void *m:owned)
+      free (m);
+  }
+};
+
+static void
+plain_frame (SchroHipContext * ctx, SchroHipFrame * f, int format, int w, int h, int ext, int upsampled)
+{
+  memset (f, 0, sizeof (*f));
+  f->refcount = 1;
+  f->domain = schro_hip_context_domain (ctx);
+  f->format = format, f->width = w, f->height = h, f->extension = ext, f->is_upsampled = upsampled;
+}
+
+// the picture of `pic` as the frame layer takes it: a planar u8 frame and one upsampled frame per reference (plane images)
+static void
+frames_of (SchroHipContext * ctx, const Geometry & g, const Picture & pic, SchroHipFrame * src, SchroHipFrame * ups)
+{
+  const SchroHipSplit2Picture & s = pic.p.split2;
+  const int format = g.hs | (g.vs << 1);
+  plain_frame (ctx, src, format, g.w, g.h, g.ext, 0);
+  for (int r = 0; r < g.refs; r++)
+    plain_frame (ctx, &ups[r], format, g.w, g.h, g.ext, 1);
+  for (int k = 0; k < 3; k++) {
+    const int w = k ? (g.w + (1 << g.hs) - 1) >> g.hs : g.w, h = k ? (g.h + (1 << g.vs) - 1) >> g.vs : g.h;
+    SchroHipFrameData d;
+    memset (&d, 0, sizeof (d));
+    d.format = format, d.width = w, d.height = h, d.h_shift = k ? g.hs : 0, d.v_shift = k ? g.vs : 0;
+    d.data = (void *) s.src[k], d.stride = s.src_stride[k], d.length = s.src_stride[k] * h;
+    src->components[k] = d;
+    for (int r = 0; r < g.refs; r++) {
+      d.data = (void *) s.ref_up[r][k], d.stride = s.ref_up_stride[k], d.length = 0;
+      ups[r].components[k] = d;
+    }
+  }
+}
+
+static void
+frame_layer_motion (SchroHipContext * ctx, const Geometry & g, const char *what)
+{
+  Picture pic;
+  make (ctx, g, pic);
+  SchroHipFrame src, ups[2], *up_ptrs[2] = { &ups[0], &ups[1] };
+  frames_of (ctx, g, pic, &src, ups);
+  const SchroHipSplit2Picture & s = pic.p.split2;
+  const size_t records = (size_t) s.x_num_blocks * s.y_num_blocks;
+  SchroHipParams P;
+  memset (&P, 0, sizeof (P));
+  P.x_num_blocks = s.x_num_blocks, P.y_num_blocks = s.y_num_blocks, P.xbsep_luma = g.xb, P.ybsep_luma = g.yb;
+  P.mv_precision = g.prec, P.num_refs = g.refs;
+  HostFields host;
+  void *fields[2] = { nullptr, nullptr };
+  const void *cfields[2], *hbm[4] = { nullptr, nullptr, nullptr, nullptr };
+  for (int r = 0; r < g.refs; r++) {
+    fields[r] = host.take (records * 20);
+    hbm[2 * r] = host.take (records * 20);
+    hbm[2 * r + 1] = host.take (records * 20);
+  }
+  cfields[0] = fields[0], cfields[1] = fields[1];
+  void *motion = host.take (records * 20), *sb = host.take (records / 16 * 16), *trials = host.take (records / 16 * 4 * sizeof (SchroHipModeTrial));
+  double stats[3];
+  EXPECT (schro_encoder_motion_predict_subpel_deep_hip (&src, up_ptrs, &P, 0.1, fields) == 0, "frame-layer sub-pel refinement, %s", what);
+  EXPECT (schro_mode_decision_split2_hip (&src, up_ptrs, &P, 0.1, cfields, motion, sb) == 0, "frame-layer split 2, %s", what);
+  EXPECT (schro_mode_decision_hip (&src, up_ptrs, &P, 0.1, cfields, hbm, motion, sb, trials, stats) == 0, "frame-layer mode decision, %s", what);
+  // the plane-layer stage behind them, on the scratch they sized
+  EXPECT (schro_hip_mode_decision_batch (ctx, &pic.p, 1) == 0, "stage behind the frame-layer runs, %s", what);
+  EXPECT (schro_hip_synchronize (ctx) == 0, "synchronize");
+  for (void *m:pic.owned)
+    schro_hip_domain_free (ctx, m);
+}
+
+// the pyramids of a w x h 4:2:0 picture and of its reference as frames with aprons, and the two chains on them
+static void
+frame_layer_search (SchroHipContext * ctx, int w, int h, int ext, const char *what)
+{
+  const int n_levels = 3;
+  std::vector < void *>owned;
+  std::vector < SchroHipFrame > frames (2 * (n_levels + 1));
+  SchroHipFrame *fp[n_levels + 1], *rp[n_levels + 1];
+  int lw = w, lh = h;
+  for (int k = 0; k <= n_levels; k++) {
+    for (int side = 0; side < 2; side++) {
+      SchroHipFrame *f = &frames[2 * k + side];
+      plain_frame (ctx, f, 3, lw, lh, ext, 0);
+      for (int c = 0; c < 3; c++) {
+        const int cw = c ? (lw + 1) >> 1 : lw, ch = c ? (lh + 1) >> 1 : lh, stride = cw + 2 * ext;
+        void *m = schro_hip_domain_alloc (ctx, (size_t) stride * (ch + 2 * ext));
+        if (!m)
+          exit (2);
+        owned.push_back (m);
+        SchroHipFrameData & d = f->components[c];
+        d.format = 3, d.width = cw, d.height = ch, d.stride = stride, d.length = stride * (ch + 2 * ext), d.h_shift = d.v_shift = c ? 1 : 0;
+        d.data = (char *) m + (size_t) ext * stride + ext;
+      }
+      (side ? rp : fp)[k] = f;
+    }
+    lw = (lw + 1) / 2, lh = (lh + 1) / 2;
+  }
+  SchroHipParams P;
+  memset (&P, 0, sizeof (P));
+  P.x_num_blocks = grid (w, 8), P.y_num_blocks = grid (h, 8), P.xbsep_luma = P.ybsep_luma = 8;
+  const size_t records = (size_t) P.x_num_blocks * P.y_num_blocks;
+  HostFields host;
+  void *fields[n_levels + 1];
+  for (int k = 0; k <= n_levels; k++)
+    fields[k] = host.take (records * 20);
+  EXPECT (schro_hbm_scan_hip (fp, rp, &P, n_levels, 1, 1, fields) == 0, "frame-layer block matching, %s", what);
+  EXPECT (schro_hbm_scan_hip (fp, rp, &P, n_levels, 0, 0, fields) == 0, "frame-layer block matching without level 0, %s", what);
+  EXPECT (schro_rough_me_heirarchical_scan_hip (fp, rp, &P, n_levels, 0, fields) == 0, "frame-layer rough chain, %s", what);
+  EXPECT (schro_hierarchical_bm_scan_hint_hip (fp[1], rp[1], &P, 1, 5, 0, fields[2], fields[1]) == 0, "frame-layer block matching level, %s", what);
+  EXPECT (schro_hip_synchronize (ctx) == 0, "synchronize");
+  for (void *m:owned)
+    schro_hip_domain_free (ctx, m);
+}
+
+static int
+frame_layer_walk ()
+{
+  // 16 records, then 32640, then 64: the scratch allocated from empty, grown, and reused stale by a smaller picture
+  static const Geometry order[] = { {100, 75, 32, 32, 0, 0, 2, 2, 32}, {3840, 2160, 16, 16, 1, 1, 2, 2, 32}, {17, 17, 4, 4, 0, 0, 1, 1, 8} };
+  static const char *const names[] = { "small", "large", "small again" };
+  for (int queue = 0; queue < 2; queue++) {
+    SchroHipContext *ctx = schro_hip_context_new (0);
+    if (!ctx)
+      return 0;
+    EXPECT (schro_hip_context_select_queue (ctx, queue) == 0, "select_queue");
+    for (int n = 0; n < 3; n++)
+      frame_layer_motion (ctx, order[n], names[n]);
+    schro_hip_context_free (ctx);
+    ctx = schro_hip_context_new (0);
+    if (!ctx)
+      return 0;
+    EXPECT (schro_hip_context_select_queue (ctx, queue) == 0, "select_queue");
+    frame_layer_search (ctx, 40, 30, 32, names[0]);
+    frame_layer_search (ctx, 1920, 1080, 32, names[1]);
+    frame_layer_search (ctx, 64, 48, 32, names[2]);
+    schro_hip_context_free (ctx);
+  }
+  return 3;
+}
+
 int
 main ()
 {
@@ -163,6 +323,8 @@ main ()
     for (void *m:pic.owned)
       schro_hip_domain_free (ctx, m);
   schro_hip_context_free (ctx);
+  const int walked = frame_layer_walk ();
+  printf ("mode_walk: frame layer small, large, small: %d pictures on each queue, %s\n", walked, failures || !walked ? "FAILED" : "ok");
   printf ("mode_walk: %zu pictures, %s\n", pictures.size (), failures ? "FAILED" : "ok");
   return failures ? 1 : 0;
 }
