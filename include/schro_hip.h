@@ -1432,6 +1432,67 @@ int schro_hip_noarith_encode_batch (SchroHipContext * ctx, const SchroHipNoarith
 /* host only: the refusals of schro_hip_noarith_encode_batch without a context.  No pointer is dereferenced but the HOST arrays. */
 int schro_hip_noarith_encode_check (const SchroHipNoarithPicture * pictures, int npictures, int bytes_per_sample);
 
+/* ---- encoder: the motion data of a noarith (VLC) picture, written on the device ----------------
+ *
+ * What schro_encoder_encode_picture appends to frame->pack between the prediction parameters and the transform
+ * parameters (schroencoder.c:2505-2515) for params->is_noarith, from a synchronised pack: the sections superblock split,
+ * prediction modes, ref-1 x, ref-1 y, with two references ref-2 x and ref-2 y, and the DC of Y, U, V
+ * (schro_encoder_encode_superblock_split, _prediction_modes, _vector_data, _dc_data, :2841-3142) -- 7 or 9 of them, each
+ * sync, uint (payload bytes), sync, the flushed sub-pack; an empty section is the one byte 0x80.  Section indices are
+ * always 0 split, 1 modes, 2 / 3 ref-1 x / y, 4 / 5 ref-2 x / y, 6 .. 8 DC; with one reference 4 and 5 are absent.
+ *
+ * `motion` is a field of SchroMotionVector records (20 bytes: pred_mode : 2, using_global : 1, split : 2 in the first
+ * word; dx[2], dy[2] -- or dc[3] -- at byte 12), x_num_blocks * y_num_blocks of them in raster order: what
+ * schro_hip_mode_decision_batch leaves in its `motion`.  Superblocks go in raster order, the units of one in steps of
+ * 4 >> split of its top-left record.  The predictions (schromotion.c:163-430) read the neighbours' records as they are:
+ * nothing checks that a split-0 or split-1 superblock carries the copies schro_motion_verify (:441-525) demands, and a
+ * field without them codes to bytes that decode to another field.  `unverified` counts the blocks schro_motion_verify
+ * would reject -- a split unlike the superblock's, a copy of a split-0 / split-1 superblock that is not byte-equal to its
+ * origin, a DC outside -128 .. 127, pred_mode >= 2 with one reference, using_global without have_global_motion --
+ * and first_unverified is the raster index of the first one (-1: none).  `asserted` counts where the reference asserts:
+ * a superblock of split 3 (coded as split 2 here: the reference would not terminate) and a coded unit with using_global
+ * though have_global_motion is 0.  When it is not 0 the bytes are unspecified; the call still ends inside its buffers. */
+#define SCHRO_HIP_MOTION_SECTIONS 9
+typedef struct {
+  uint32_t bytes;               /* what the picture takes, whether or not it fitted */
+  uint32_t overrun;             /* 1: bytes > capacity, `out` holds the first `capacity` bytes */
+  uint32_t section_bytes[SCHRO_HIP_MOTION_SECTIONS];    /* the payload of each section; absent and empty ones 0 */
+  uint32_t section_units[SCHRO_HIP_MOTION_SECTIONS];    /* the units each section codes (modes: every coded unit) */
+  uint32_t asserted;
+  uint32_t unverified;
+  int32_t first_unverified;
+} SchroHipMotionEncodeResult;
+
+typedef struct {
+  const void *motion;           /* device, 4-byte aligned: the records; not written */
+  int x_num_blocks, y_num_blocks;       /* positive multiples of 4, at most 16384 */
+  int num_refs;                 /* 1 or 2 */
+  int have_global_motion;
+  uint8_t *out;                 /* device: the bytes */
+  size_t capacity;              /* of out */
+  SchroHipMotionEncodeResult *result;   /* device, 4-byte aligned: every word written by the call */
+} SchroHipMotionEncodePicture;
+
+/* The capacity that always suffices.  A vector or DC difference of two int16 takes at most 34 bits (magnitude <= 65535:
+ * 33 bits of uint code and a sign); a block carries four of them with two references, or three DCs -- and with one
+ * reference two vector components or three DCs: 136 or 102 bits; its mode takes 1 + (num_refs > 1) + (have_global_motion
+ * != 0) bits; a superblock's split residual (0 .. 2) at most 3 bits.  A section adds less than a byte of padding behind
+ * its payload and at most 8 bytes of length code (59 bits below 2^29) with its padding: 9 bytes for each of the 7 or 9.
+ *   bound = (blocks * (136 | 102 + mode bits) + superblocks * 3 + 7) / 8 + 9 * sections
+ * < 0 on refusal (block counts, num_refs). */
+int64_t schro_hip_motion_encode_bound (int x_num_blocks, int y_num_blocks, int num_refs, int have_global_motion);
+
+/* Pictures of unlike geometry and num_refs in one call: a count launch (a lane per block, the 16 lanes of a row one
+ * superblock), a layout launch (a workgroup per picture), a clear of the bytes the picture takes and a pack launch.
+ * Enqueues, does not synchronise; the tables come from the queue's grow-only scratch.  Behind
+ * schro_hip_mode_decision_batch on the same queue it takes that call's `motion` as it is.  Refused (SCHRO_HIP_EINVAL,
+ * nothing enqueued, the message naming the picture): block counts that are no positive multiples of 4 or above 16384,
+ * num_refs other than 1 / 2, a NULL or misaligned pointer, an output or result that overlaps the field or another
+ * picture's buffers, a bound of 2^29 bytes or more.  Only min (capacity, bytes) bytes of `out` are ever written. */
+int schro_hip_motion_encode_batch (SchroHipContext * ctx, const SchroHipMotionEncodePicture * pictures, int npictures);
+/* host only: the refusals of schro_hip_motion_encode_batch without a context.  No pointer is dereferenced. */
+int schro_hip_motion_encode_check (const SchroHipMotionEncodePicture * pictures, int npictures);
+
 /* ---- encoder: sub-band histograms on the device ----------------------------------------------
  *
  * The pass over the coefficients that every rate-controlled quantiser choice starts with
@@ -1719,6 +1780,13 @@ SCHRO_HIP_SIZE (SchroHipModePicture, 232);
 SCHRO_HIP_LAYOUT (SchroHipModePicture, hbm_fields, 184);
 SCHRO_HIP_LAYOUT (SchroHipModePicture, trials, 216);
 SCHRO_HIP_LAYOUT (SchroHipModePicture, stats, 224);
+SCHRO_HIP_SIZE (SchroHipMotionEncodeResult, 92);
+SCHRO_HIP_LAYOUT (SchroHipMotionEncodeResult, section_units, 44);
+SCHRO_HIP_LAYOUT (SchroHipMotionEncodeResult, first_unverified, 88);
+SCHRO_HIP_SIZE (SchroHipMotionEncodePicture, 48);
+SCHRO_HIP_LAYOUT (SchroHipMotionEncodePicture, num_refs, 16);
+SCHRO_HIP_LAYOUT (SchroHipMotionEncodePicture, out, 24);
+SCHRO_HIP_LAYOUT (SchroHipMotionEncodePicture, result, 40);
 #endif
 
 /* schro_frame_new_and_alloc (schroframe.c:60-191) on the device domain:
@@ -1881,6 +1949,15 @@ int schro_hip_encode_lowdelay_transform_data (const SchroHipFrame * iwt_frame, v
 int schro_hip_encode_transform_data_noarith (const SchroHipFrame * quant_frame, const SchroHipParams * params,
     const int *const quant_indices[3], void *out, size_t capacity, size_t *bytes,
     int subband_bits[3][SCHRO_HIP_NOARITH_MAX_SUBBANDS], int false_zero[2]);
+
+/* The motion data of a noarith picture, schroencoder.c:2505-2515 with params->is_noarith: motion->motion_vectors is the
+ * HOST field of params->x_num_blocks * params->y_num_blocks records (no device frame comes with it, so the context is
+ * an argument); the bytes the reference appends to frame->pack arrive in the HOST buffer `out`, at most `capacity` of
+ * them; *bytes is what the picture takes, section_bytes (or NULL) the payload of each section, result (or NULL) the
+ * whole SchroHipMotionEncodeResult.  Returns 0, or SCHRO_HIP_ENOMEM with *bytes set when the picture takes more than
+ * `capacity` (schro_hip_motion_encode_bound always suffices).  Copies on the selected queue and waits for it. */
+int schro_hip_encode_motion_data_noarith (SchroHipContext * ctx, const SchroHipMotion * motion, const SchroHipParams * params,
+    void *out, size_t capacity, size_t *bytes, int section_bytes[SCHRO_HIP_MOTION_SECTIONS], SchroHipMotionEncodeResult * result);
 
 /* r05 -- the quantised hand-over behind the frame layer (VERDICT r04 "missing" 1): what a patched
  * schro_decoder_decode_subband (schrodecoder.c:3525-3640) leaves behind for one picture instead of a dense

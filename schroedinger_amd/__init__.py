@@ -305,6 +305,40 @@ def noarith_result(words):
             "subband_bits": w[4:4 + 3 * _lib.NOARITH_MAX_SUBBANDS].astype(np.int64).reshape(3, _lib.NOARITH_MAX_SUBBANDS)}
 
 
+def motion_encode_pictures(pictures):
+    """The SchroHipMotionEncodePicture array of [(motion, x_num_blocks, y_num_blocks, num_refs, have_global_motion, out,
+    capacity, result)]: motion, out, result -- device memory (anything with ptr, or an address) or None."""
+    arr = (_lib.MotionEncodePicture * len(pictures))()
+    addr = lambda m: None if m is None else getattr(m, "ptr", m)
+    for a, (motion, nbx, nby, num_refs, hg, out, capacity, result) in zip(arr, pictures):
+        a.motion, a.x_num_blocks, a.y_num_blocks, a.num_refs, a.have_global_motion = addr(motion), nbx, nby, num_refs, int(hg)
+        a.out, a.capacity, a.result = addr(out), capacity, addr(result)
+    return arr
+
+
+def motion_encode_check(pictures):
+    """The refusals of Context.motion_encode_batch on the host, without a context (schro_hip_motion_encode_check)."""
+    check(_lib.load().schro_hip_motion_encode_check(motion_encode_pictures(pictures), len(pictures)))
+
+
+def motion_encode_bound(x_num_blocks, y_num_blocks, num_refs, have_global_motion):
+    """schro_hip_motion_encode_bound: the output capacity that always suffices for a picture's motion data."""
+    n = _lib.load().schro_hip_motion_encode_bound(x_num_blocks, y_num_blocks, num_refs, int(have_global_motion))
+    if n < 0:
+        check(int(n))
+    return int(n)
+
+
+def motion_encode_result(words):
+    """A downloaded SchroHipMotionEncodeResult (uint32 words) as a dict: bytes, overrun, section_bytes (9), section_units
+    (9), asserted, unverified, first_unverified."""
+    w = np.asarray(words, np.uint32).ravel()
+    n = _lib.MOTION_SECTIONS
+    return {"bytes": int(w[0]), "overrun": int(w[1]), "section_bytes": [int(x) for x in w[2:2 + n]],
+            "section_units": [int(x) for x in w[2 + n:2 + 2 * n]], "asserted": int(w[2 + 2 * n]), "unverified": int(w[3 + 2 * n]),
+            "first_unverified": int(w[4 + 2 * n:5 + 2 * n].view(np.int32)[0])}
+
+
 QUANTISE_DC_THREADS = 256       # SCHRO_HIP_QUANTISE_DC_THREADS (include/schro_hip.h): the DC recurrence's workgroup size
 
 
@@ -1184,6 +1218,57 @@ class Context:
             for out, res, cap in own:
                 out.free()
                 res.free()
+
+    def motion_encode_batch(self, pictures, capacity=None):
+        """schro_hip_motion_encode_batch.  pictures: per picture (motion, x_num_blocks, y_num_blocks, num_refs,
+        have_global_motion) -- motion: the device field (anything with ptr) -- or the same followed by (out, capacity,
+        result) with caller-owned device buffers.  Mirrors schroencoder.c:2505-2515 for is_noarith.  Where the buffers
+        are the call's own -- `capacity` bytes each, or motion_encode_bound -- waits and returns per picture (bytes uint8
+        array cut at the capacity, motion_encode_result dict); with caller-owned buffers the call is asynchronous and
+        returns None."""
+        own, full = [], []
+        words = C.sizeof(_lib.MotionEncodeResult) // 4
+        try:
+            for pic in pictures:
+                if len(pic) == 8:
+                    full.append(tuple(pic))
+                    continue
+                motion, nbx, nby, num_refs, hg = pic
+                cap = capacity if capacity is not None else motion_encode_bound(nbx, nby, num_refs, hg)
+                out = DevicePlane(self, 1, max(cap, 1), np.uint8)
+                res = DevicePlane(self, 1, words, np.uint32)
+                own.append((out, res, cap))
+                full.append((motion, nbx, nby, num_refs, hg, out, cap, res))
+            check(self.lib.schro_hip_motion_encode_batch(self.h, motion_encode_pictures(full), len(full)))
+            if not own:
+                return None
+            got = []
+            for out, res, cap in own:
+                r = motion_encode_result(res.download())
+                got.append((out.download()[0, :min(cap, r["bytes"])].copy(), r))
+            return got
+        finally:
+            for out, res, cap in own:
+                out.free()
+                res.free()
+
+    def encode_motion_data_noarith(self, field, params, capacity):
+        """schro_hip_encode_motion_data_noarith on a HOST field (MV_DTYPE records, params.x_num_blocks x y_num_blocks):
+        (bytes uint8 array, bytes the picture takes, section_bytes (9), motion_encode_result dict, status) -- status 0, or
+        SCHRO_HIP_ENOMEM (-3) when the picture takes more than `capacity`; any other status raises."""
+        field = np.ascontiguousarray(field)
+        motion = _lib.Motion()
+        motion.motion_vectors = field.ctypes.data
+        data = np.zeros(max(capacity, 1), np.uint8)
+        nbytes = C.c_size_t(0)
+        sec = (C.c_int * _lib.MOTION_SECTIONS)()
+        res = _lib.MotionEncodeResult()
+        rc = self.lib.schro_hip_encode_motion_data_noarith(self.h, C.byref(motion), C.byref(params), data.ctypes.data, capacity,
+                                                           C.byref(nbytes), sec, C.byref(res))
+        if rc not in (0, -3) or (rc == -3 and nbytes.value <= capacity):
+            check(rc)
+        words = np.frombuffer(bytes(res), np.uint32)
+        return data[:min(capacity, nbytes.value)], int(nbytes.value), list(sec), motion_encode_result(words), rc
 
     def encode_transform_data_noarith(self, quant_frame, params, quant_indices, capacity):
         """schro_hip_encode_transform_data_noarith on a device frame (frames.DeviceFrame, s16 / s32) that

@@ -56,6 +56,8 @@ EXPORTED_SYMBOLS = [
     "schro_hip_lowdelay_encode_batch", "schro_hip_encode_lowdelay_transform_data",
     "schro_hip_noarith_encode_bound", "schro_hip_noarith_encode_batch", "schro_hip_noarith_encode_check",
     "schro_hip_encode_transform_data_noarith",
+    "schro_hip_motion_encode_bound", "schro_hip_motion_encode_batch", "schro_hip_motion_encode_check",
+    "schro_hip_encode_motion_data_noarith",
     "schro_hip_dequant_batch", "schro_hip_quantise_batch", "schro_hip_subtract_batch", "schro_hipframe_subtract",
     "schro_hipframe_quantise", "schro_hip_histogram_batch", "schro_hipframe_subband_histograms",
     "schro_hip_decode_lowdelay_transform_data", "schro_hipframe_dequantise",
@@ -262,6 +264,22 @@ class NoarithPicture(C.Structure):
                 ("iwt_height", C.c_int * 3), ("codeblocks", C.POINTER(Codeblock) * 3), ("ncodeblocks", C.c_int * 3),
                 ("transform_depth", C.c_int), ("horiz_codeblocks", C.c_int * 7), ("vert_codeblocks", C.c_int * 7),
                 ("codeblock_mode_index", C.c_int), ("out", C.c_void_p), ("capacity", C.c_size_t), ("result", C.c_void_p)]
+
+
+MOTION_SECTIONS = 9             # SCHRO_HIP_MOTION_SECTIONS (include/schro_hip.h)
+
+
+class MotionEncodeResult(C.Structure):
+    """SchroHipMotionEncodeResult: what schro_hip_motion_encode_batch leaves on the device per picture."""
+    _fields_ = [("bytes", C.c_uint32), ("overrun", C.c_uint32), ("section_bytes", C.c_uint32 * MOTION_SECTIONS),
+                ("section_units", C.c_uint32 * MOTION_SECTIONS), ("asserted", C.c_uint32), ("unverified", C.c_uint32),
+                ("first_unverified", C.c_int32)]
+
+
+class MotionEncodePicture(C.Structure):
+    """SchroHipMotionEncodePicture (include/schro_hip.h): one picture of schro_hip_motion_encode_batch."""
+    _fields_ = [("motion", C.c_void_p), ("x_num_blocks", C.c_int), ("y_num_blocks", C.c_int), ("num_refs", C.c_int),
+                ("have_global_motion", C.c_int), ("out", C.c_void_p), ("capacity", C.c_size_t), ("result", C.c_void_p)]
 
 
 HISTOGRAM_BINS = 104            # SCHRO_HIP_HISTOGRAM_BINS (include/schro_hip.h)
@@ -637,6 +655,15 @@ def load():
                                                           C.c_size_t, C.POINTER(C.c_size_t),
                                                           C.POINTER(C.c_int * NOARITH_MAX_SUBBANDS), C.POINTER(C.c_int)]
     L.schro_hip_encode_transform_data_noarith.restype = i
+    L.schro_hip_motion_encode_bound.argtypes = [i, i, i, i]
+    L.schro_hip_motion_encode_bound.restype = C.c_int64
+    L.schro_hip_motion_encode_batch.argtypes = [vp, C.POINTER(MotionEncodePicture), i]
+    L.schro_hip_motion_encode_batch.restype = i
+    L.schro_hip_motion_encode_check.argtypes = [C.POINTER(MotionEncodePicture), i]
+    L.schro_hip_motion_encode_check.restype = i
+    L.schro_hip_encode_motion_data_noarith.argtypes = [vp, C.POINTER(Motion), C.POINTER(Params), vp, C.c_size_t,
+                                                       C.POINTER(C.c_size_t), C.POINTER(C.c_int), C.POINTER(MotionEncodeResult)]
+    L.schro_hip_encode_motion_data_noarith.restype = i
     L.schro_hip_dc_predict_batch.argtypes = [vp, C.POINTER(DcPlane), i, i]
     L.schro_hip_dc_predict_batch.restype = i
     L.schro_hip_shift_right_batch.argtypes = [vp, C.POINTER(DcPlane), i, i, i]

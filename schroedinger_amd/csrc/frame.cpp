@@ -747,6 +747,68 @@ schro_hip_encode_transform_data_noarith (const SchroHipFrame * quant_frame, cons
   return 0;
 }
 
+// The motion data of a noarith picture (schroencoder.c:2505-2515): the host field goes up, the bytes the reference
+// appends to frame->pack come back.
+int
+schro_hip_encode_motion_data_noarith (SchroHipContext * ctx, const SchroHipMotion * motion, const SchroHipParams * params,
+    void *out, size_t capacity, size_t *bytes, int section_bytes[SCHRO_HIP_MOTION_SECTIONS], SchroHipMotionEncodeResult * result)
+{
+  const char *who = "encode_motion_data_noarith";
+  SCHRO_HIP_REQUIRE (ctx && motion && motion->motion_vectors && params && bytes && (out || capacity == 0), "%s: bad arguments", who);
+  const int64_t bound = schro_hip_motion_encode_bound (params->x_num_blocks, params->y_num_blocks, params->num_refs, params->have_global_motion);
+  if (bound < 0)
+    return (int) bound;
+  capacity = std::min (capacity, (size_t) bound);
+  const size_t field_bytes = (size_t) params->x_num_blocks * params->y_num_blocks * kMvBytes, field_at = 256;
+  const size_t out_at = field_at + round_up (field_bytes, 256);
+  // one allocation: the result, the field, the bytes
+  char *d = (char *) schro_hip_domain_alloc (ctx, out_at + (capacity ? capacity : 1));
+  if (!d)
+    return SCHRO_HIP_ENOMEM;
+  static_assert (sizeof (SchroHipMotionEncodeResult) <= 256, "the result sits in front of the field");
+  SchroHipMotionEncodePicture pic;
+  memset (&pic, 0, sizeof (pic));
+  pic.motion = d + field_at;
+  pic.x_num_blocks = params->x_num_blocks;
+  pic.y_num_blocks = params->y_num_blocks;
+  pic.num_refs = params->num_refs;
+  pic.have_global_motion = params->have_global_motion;
+  pic.out = (uint8_t *) d + out_at;
+  pic.capacity = capacity;
+  pic.result = (SchroHipMotionEncodeResult *) d;
+  int r = 0;
+  // (the batch call's layout launch writes every word of the result; cleared here so that a launch that did not run
+  // reports no bytes instead of what the allocation held)
+  if (hipMemsetAsync (d, 0, field_at, ctx->stream) != hipSuccess
+      || hipMemcpyAsync (d + field_at, motion->motion_vectors, field_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+    r = set_error (SCHRO_HIP_EDEVICE, "%s: copy of the field failed", who);
+  if (!r)
+    r = schro_hip_motion_encode_batch (ctx, &pic, 1);
+  SchroHipMotionEncodeResult res;
+  memset (&res, 0, sizeof (res));
+  if (!r && hipMemcpyAsync (&res, d, sizeof (res), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+    r = set_error (SCHRO_HIP_EDEVICE, "%s: copy of the result failed", who);
+  int rs = schro_hip_synchronize (ctx);
+  const size_t take = std::min ((size_t) res.bytes, capacity);
+  if (!r && !rs && take) {
+    if (hipMemcpyAsync (out, d + out_at, take, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+      r = set_error (SCHRO_HIP_EDEVICE, "%s: copy of %zu bytes failed", who, take);
+    rs = schro_hip_synchronize (ctx);   // the host buffer is filled, d is free again
+  }
+  schro_hip_domain_free (ctx, d);
+  if (r || rs)
+    return r ? r : rs;
+  *bytes = res.bytes;
+  if (section_bytes)
+    for (int s = 0; s < SCHRO_HIP_MOTION_SECTIONS; s++)
+      section_bytes[s] = (int) res.section_bytes[s];
+  if (result)
+    *result = res;
+  if (res.overrun)
+    return set_status (SCHRO_HIP_ENOMEM, "%s: the picture takes %u bytes, the buffer holds %zu", who, res.bytes, capacity);
+  return 0;
+}
+
 // r05 -- schro_decoder_decode_subband's data-parallel half on the device, behind the frame layer: the picture arrives
 // as codeblock records + quantised values (include/schro_hip.h), leaves as the dense transform frame x_wavelet_transform
 // reads.  Reference: schrodecoder.c:3525-3640 (the codeblock loop), :3311-3322 (zero codeblocks), :3060-3083 / :3400-3451

@@ -896,6 +896,25 @@ struct NaScratch {              // the selected queue's, per call
 // stages: 1 count, 2 layout, 4 clear + pack
 int launch_noarith_encode (hipStream_t stream, const NaSubband * d_sbs, int nsbs, const NaPicture * d_pics, int npics,
     const NaScratch & S, int bpp, int grid_x, int clear_x, int stages);
+// motion_enc.hip: one picture's motion data.  A superblock owns kMeSbWords words of the call's scratch: what the count
+// launch found in it and where the layout launch put it.
+struct MePicture {
+  const uint8_t *motion;
+  uint8_t *out;
+  SchroHipMotionEncodeResult *result;
+  uint32_t capacity;            // min (capacity, 2^29): a picture takes less
+  int nbx, nby;
+  int num_refs, have_global;
+  int sb_first;                 // its first superblock in the call's scratch
+  int pad;
+};
+constexpr int kMeSections = SCHRO_HIP_MOTION_SECTIONS;
+constexpr int kMeLayoutThreads = 256;   // the layout workgroup: a picture of more superblocks is scanned in runs per thread
+constexpr int kMeBits = 0, kMeUnits = 9, kMeUnverified = 18, kMeFirst = 19, kMeAsserted = 20, kMePos = 21, kMeSbWords = 32;
+// scratch: kMeSbWords words per superblock of the call, then 2 * kMeSections words per picture (each section's header
+// bit, its payload's first bit); stages: 1 count, 2 layout, 4 clear, 8 pack
+int launch_motion_encode (hipStream_t stream, const MePicture * d_pics, int npics, uint32_t * scratch, int total_sbs, int waves_x, int clear_x,
+    int stages);
 // hist.hip
 void hist_tile_geometry (int *group_bytes, int *groups_per_tile, int *groups_per_step);
 int launch_histogram (hipStream_t stream, const HistJob * d_jobs, int njobs, int total_tiles, int bpp);
