@@ -1432,6 +1432,89 @@ int schro_hip_noarith_encode_batch (SchroHipContext * ctx, const SchroHipNoarith
 /* host only: the refusals of schro_hip_noarith_encode_batch without a context.  No pointer is dereferenced but the HOST arrays. */
 int schro_hip_noarith_encode_check (const SchroHipNoarithPicture * pictures, int npictures, int bytes_per_sample);
 
+/* ---- decoder: core-syntax transform data in the VLC parse codes, read on the device ------------
+ *
+ * schro_decoder_parse_transform_data (schrodecoder.c:2939-2987) and schro_decoder_decode_transform_data (:2990-3015,
+ * :3279-3449, :3525-3625) for params->is_noarith: the picture's transform-data bytes go in, from a synchronised position;
+ * the completely filled, dequantised coefficient planes come out.  A sub-band of length 0 is zero-filled, a codeblock whose
+ * zero flag is set is zero-filled, every other sample is dequantised with the decoder's arithmetic (s16 planes: the 16-bit
+ * Orc program; s32 planes: C int -- the same two forms schro_hip_dequant_batch has).  The arithmetic decoder stays host code.
+ *
+ * These are the DECODER's rules; the encoder's (schro_hip_noarith_encode_batch above) differ.  Per component and sub-band
+ * the outer unpack reads: byte sync, uint (length); length 0: byte sync; else uint (quant index), byte sync and `length`
+ * bytes of payload, which its own unpack reads with guard bit 1 (bits past the payload's end read as 1, so every further
+ * value is 0).  have_zero_flags = more than one codeblock, for EVERY sub-band (the encoder writes none for sub-band 0);
+ * have_quant_offset = codeblock_mode_index == 1 && !(compat_quant_offset && one codeblock) (the encoder writes an offset
+ * only where there is more than one codeblock).  Per codeblock, in raster order over schro_hip_codeblock_layout's
+ * rectangles: bit (zero) when have_zero_flags; quant index += sint, clamped to 0 .. 60 (clamped_quant counts) and carried
+ * to the next codeblock, when have_quant_offset; width x height sints, rows top to bottom.  The two rule sets agree where
+ * sub-band 0 has one codeblock and either the mode is 0 or compat_quant_offset is set.
+ *
+ * schro_decoder_test_quant_offset_compat (:3324-3352): in sub-band 0 of each component, when it is coded, has one
+ * codeblock and have_quant_offset holds, quant index + (a peeked sint) outside 0 .. 60 sets the decoder INSTANCE's
+ * compat_quant_offset: from then on no sub-band of one codeblock has an offset, that one included, in later components and
+ * later pictures.  The call takes the state before the picture and reports the state after it.
+ *
+ * Where the reference is undefined the call is defined and bounded.  The input is fetched as the aligned dwords that hold
+ * its bytes (so up to 3 bytes in front of `data` and behind its end are loaded, masked and never used); nothing else is read:
+ *  - schro_unpack_decode_uint computes 1 << count, undefined from count 31 on.  Here v = 1; per data bit v = (v << 1 | b)
+ *    mod 2^32; the magnitude is v - 1 mod 2^32; a code with data bits always has a sign bit; then the sign, then truncation
+ *    to the sample type.  Equal to the reference for every code an encoder can write (count <= 30); the others are
+ *    counted in long_codes (headers, offsets and values; not the compat test's peek).
+ *  - a header quant index above 60 (picture->error, :2971): error = 1, first_error = component * 19 + index, NOTHING of the
+ *    picture's planes is written, compat_quant_offset is reported as it came in, the header fields stand as far as the
+ *    walk went.  Other pictures of the call are unaffected.
+ *  - a length that reaches past the input's end: the payload is cut there and decoded with guard bits; `truncated` counts
+ *    such sub-bands (the reference would read outside its buffer).
+ *  - what the reference only warns about (:3606-3622): sub-bands with bits_read / 8 < length - 1 count in not_consumed,
+ *    with bits_read / 8 > length in overran (length as stated). */
+typedef struct {
+  uint32_t bytes_read;          /* whole bytes the outer unpack consumed (rounded up; saturates at 2^32 - 1) */
+  uint32_t error, first_error;  /* quant index > 60 in a header: nothing written */
+  uint32_t compat_quant_offset; /* the instance's state after this picture */
+  uint32_t truncated, not_consumed, overran, long_codes, clamped_quant;
+  uint32_t subband_length[3][SCHRO_HIP_NOARITH_MAX_SUBBANDS];
+  uint8_t subband_quant_index[3][SCHRO_HIP_NOARITH_MAX_SUBBANDS];       /* of codeblock (0,0), as the header states it */
+} SchroHipNoarithDecodeResult;
+
+typedef struct {
+  const uint8_t *data;          /* device: the transform data, from a synchronised position */
+  size_t data_bytes;            /* host: at most this many bytes are ever used (below 2^29) */
+  const uint32_t *bytes_on_device;      /* optional, device, 4-byte aligned: min (*bytes_on_device, data_bytes) is the length --
+                                           e.g. &SchroHipNoarithResult.bytes of an encode on the same queue */
+  void *coeffs[3];              /* device: Y, U, V coefficient planes (s16 or s32) */
+  size_t bytes[3];              /* what each plane spans */
+  int stride[3];                /* bytes between rows, of coeffs and of quant */
+  void *quant[3];               /* optional, same layout: the values as read, not dequantised (all three or none) */
+  int iwt_width[3], iwt_height[3], transform_depth;
+  int horiz_codeblocks[7], vert_codeblocks[7], codeblock_mode_index;
+  int is_intra;                 /* num_refs == 0: offsets _1_2, else _3_8.  The LL bands are NOT DC-predicted here: an error
+                                   picture must stay untouched and the error is only known on the device, so the caller runs
+                                   schro_hip_dc_predict_batch once result->error is known (schro_hipframe_decode_transform_data_noarith does) */
+  int compat_quant_offset;      /* the instance's state before this picture */
+  SchroHipNoarithDecodeResult *result;  /* device, 4-byte aligned: cleared and filled by the call */
+} SchroHipNoarithDecodePicture;
+
+/* Pictures of unlike geometry and depth in one call: a header launch (the serial chain of at most 57 sub-band headers
+ * per picture), a summary launch (a lane per 64-bit chunk of every payload), a chain launch (a workgroup per coded
+ * sub-band finds every codeblock's first bit by composing the summaries), a decode launch (a lane per chunk decodes,
+ * dequantises and stores the codes that start in it) and a fill launch (zero sub-bands, zero codeblocks, values behind
+ * the payload's end).  Enqueues, does not synchronise; bytes between a row's width and the stride and everything outside
+ * the planes are not written.  Refused (SCHRO_HIP_EINVAL, nothing enqueued, the message naming picture and component):
+ * bytes_per_sample not 2 or 4, a depth above 6, sizes that are no positive multiples of 1 << depth or reach 32768,
+ * codeblock counts outside 1 .. 32767, a codeblock_mode_index other than 0 / 1, a NULL or misaligned pointer, a stride
+ * shorter than a row or no multiple of the sample size, a plane that does not hold its rows, `data` overlapping a plane,
+ * `quant` overlapping `coeffs`, `result` overlapping `data`, `bytes_on_device` or a plane, planes overlapping each other,
+ * anything one picture of the call writes (planes, result) overlapping what another reads or writes (the results are
+ * cleared in front of the first launch), data_bytes of 2^29 or more. */
+int schro_hip_noarith_decode_batch (SchroHipContext * ctx, const SchroHipNoarithDecodePicture * pictures, int npictures,
+    int bytes_per_sample);
+/* host only: the refusals of schro_hip_noarith_decode_batch without a context.  No pointer is dereferenced. */
+int schro_hip_noarith_decode_check (const SchroHipNoarithDecodePicture * pictures, int npictures, int bytes_per_sample);
+/* host only: the words of queue scratch the call takes for these pictures (5 per chunk slot -- data_bytes / 8 + sub-bands
+ * + 1 slots per picture --, 3 per codeblock, 8 per sub-band, 2 per picture), or < 0 on refusal. */
+int64_t schro_hip_noarith_decode_scratch_words (const SchroHipNoarithDecodePicture * pictures, int npictures, int bytes_per_sample);
+
 /* ---- encoder: the motion data of a noarith (VLC) picture, written on the device ----------------
  *
  * What schro_encoder_encode_picture appends to frame->pack between the prediction parameters and the transform
@@ -1984,6 +2067,15 @@ typedef struct {
  * Enqueued on the selected queue; complete on return unless stage completion is off. */
 int schro_hipframe_dequantise (SchroHipFrame * transform_frame, const SchroHipQuantisedPicture * quantised,
     SchroHipParams * params);
+
+/* schro_decoder_parse_transform_data + schro_decoder_decode_transform_data (frame) for params->is_noarith
+ * (schro_hip_noarith_decode_batch): `length` bytes of the picture's transform data, from a synchronised position on the
+ * HOST, go up; transform_frame (a device frame, s16 or s32) is filled as schro_hipframe_dequantise leaves it, the LL bands
+ * of an intra picture (params->num_refs == 0) DC-predicted.  *compat_quant_offset is the decoder instance's state: read,
+ * and updated when the picture decodes.  *result is always filled when the call reaches the device; picture->error
+ * (a header quant index above 60) returns SCHRO_HIP_EINVAL with the frame untouched.  Waits for the result. */
+int schro_hipframe_decode_transform_data_noarith (SchroHipFrame * transform_frame, const uint8_t * host_data, size_t length,
+    SchroHipParams * params, int *compat_quant_offset, SchroHipNoarithDecodeResult * result);
 
 /* schro_upsampled_gpuframe_upsample (schrogpuframe.h:27) replacement:
  * dest (device, is_upsampled) <- half-pel images of src (device u8). */

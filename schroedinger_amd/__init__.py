@@ -305,6 +305,49 @@ def noarith_result(words):
             "subband_bits": w[4:4 + 3 * _lib.NOARITH_MAX_SUBBANDS].astype(np.int64).reshape(3, _lib.NOARITH_MAX_SUBBANDS)}
 
 
+def noarith_decode_pictures(pictures):
+    """The SchroHipNoarithDecodePicture array of [(data, data_bytes, bytes_on_device, coeffs, quant, depth, horiz_codeblocks,
+    vert_codeblocks, codeblock_mode_index, is_intra, compat_quant_offset, result)]: data, bytes_on_device, result -- device
+    memory (anything with ptr, or an address) or None; coeffs -- the Y, U, V planes at the transform's size (anything with
+    ptr, stride, width, height); quant -- three planes of the same layout or None."""
+    arr = (_lib.NoarithDecodePicture * len(pictures))()
+    addr = lambda m: None if m is None else getattr(m, "ptr", m)
+    for a, (data, nbytes, on_device, coeffs, quant, depth, hc, vc, mode, is_intra, compat, result) in zip(arr, pictures):
+        a.data, a.data_bytes, a.bytes_on_device = addr(data), nbytes, addr(on_device)
+        for k in range(3):
+            a.coeffs[k], a.stride[k] = coeffs[k].ptr, coeffs[k].stride
+            a.iwt_width[k], a.iwt_height[k] = coeffs[k].width, coeffs[k].height
+            a.bytes[k] = coeffs[k].stride * coeffs[k].height
+            a.quant[k] = quant[k].ptr if quant is not None else None
+        a.transform_depth, a.codeblock_mode_index = depth, mode
+        for l in range(min(len(hc), 7)):
+            a.horiz_codeblocks[l], a.vert_codeblocks[l] = hc[l], vc[l]
+        a.is_intra, a.compat_quant_offset = int(bool(is_intra)), int(bool(compat))
+        a.result = addr(result)
+    return arr
+
+
+def noarith_decode_check(pictures, bpp):
+    """The refusals of Context.noarith_decode_batch on the host, without a context (schro_hip_noarith_decode_check)."""
+    check(_lib.load().schro_hip_noarith_decode_check(noarith_decode_pictures(pictures), len(pictures), bpp))
+
+
+def noarith_decode_result(words):
+    """A downloaded SchroHipNoarithDecodeResult (uint32 words, or the ctypes structure) as a dict: bytes_read, error,
+    first_error, compat_quant_offset, truncated, not_consumed, overran, long_codes, clamped_quant, subband_length (3 x 19),
+    subband_quant_index (3 x 19)."""
+    if isinstance(words, _lib.NoarithDecodeResult):
+        words = np.frombuffer(bytes(words), np.uint32)
+    w = np.ascontiguousarray(np.asarray(words, np.uint32).ravel()[:C.sizeof(_lib.NoarithDecodeResult) // 4])
+    n = 3 * _lib.NOARITH_MAX_SUBBANDS
+    names = ("bytes_read", "error", "first_error", "compat_quant_offset", "truncated", "not_consumed", "overran", "long_codes",
+             "clamped_quant")
+    out = {k: int(v) for k, v in zip(names, w[:9])}
+    out["subband_length"] = w[9:9 + n].astype(np.int64).reshape(3, _lib.NOARITH_MAX_SUBBANDS)
+    out["subband_quant_index"] = w[9 + n:].view(np.uint8)[:n].astype(np.int64).reshape(3, _lib.NOARITH_MAX_SUBBANDS)
+    return out
+
+
 def motion_encode_pictures(pictures):
     """The SchroHipMotionEncodePicture array of [(motion, x_num_blocks, y_num_blocks, num_refs, have_global_motion, out,
     capacity, result)]: motion, out, result -- device memory (anything with ptr, or an address) or None."""
@@ -1218,6 +1261,52 @@ class Context:
             for out, res, cap in own:
                 out.free()
                 res.free()
+
+    def noarith_decode_batch(self, pictures):
+        """schro_hip_noarith_decode_batch.  pictures: per picture (data, coeffs, quant, depth, horiz_codeblocks,
+        vert_codeblocks, codeblock_mode_index, is_intra, compat_quant_offset) -- data: the HOST bytes (uint8 array or bytes);
+        coeffs, quant as noarith_decode_pictures takes them -- or the twelve entries of noarith_decode_pictures with
+        caller-owned device buffers.  Mirrors schro_decoder_parse_transform_data + schro_decoder_decode_transform_data for
+        is_noarith.  Where the bytes and the result are the call's own, waits and returns a noarith_decode_result dict per
+        picture; with caller-owned buffers the call is asynchronous and returns None."""
+        bpp = np.dtype(pictures[0][3][0].dtype if len(pictures[0]) == 12 else pictures[0][1][0].dtype).itemsize
+        own, full = [], []
+        words = C.sizeof(_lib.NoarithDecodeResult) // 4
+        try:
+            for pic in pictures:
+                if len(pic) == 12:
+                    full.append(tuple(pic))
+                    continue
+                data, coeffs, quant, depth, hc, vc, mode, is_intra, compat = pic
+                raw = np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, np.uint8)
+                dev = DevicePlane(self, 1, max(raw.size, 1), np.uint8)
+                res = DevicePlane(self, 1, words, np.uint32)
+                own.append((dev, res))
+                if raw.size:
+                    dev.upload(raw.reshape(1, -1))
+                full.append((dev, int(raw.size), None, coeffs, quant, depth, hc, vc, mode, is_intra, compat, res))
+            check(self.lib.schro_hip_noarith_decode_batch(self.h, noarith_decode_pictures(full), len(full), bpp))
+            if not own:
+                return None
+            return [noarith_decode_result(res.download()) for dev, res in own]
+        finally:
+            for dev, res in own:
+                dev.free()
+                res.free()
+
+    def decode_transform_data_noarith(self, transform_frame, data, params, compat_quant_offset):
+        """schro_hipframe_decode_transform_data_noarith on a device frame (frames.DeviceFrame, s16 / s32): the HOST bytes go
+        up, the frame is filled as schro_hipframe_dequantise leaves it.  Returns (noarith_decode_result dict, the compat
+        state after the picture, status) -- status 0, or SCHRO_HIP_EINVAL (-1) with result["error"] set when a header holds
+        a quant index above 60 (the frame is untouched); any other status raises."""
+        raw = np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, np.uint8)
+        compat = C.c_int(int(bool(compat_quant_offset)))
+        res = _lib.NoarithDecodeResult()
+        rc = self.lib.schro_hipframe_decode_transform_data_noarith(transform_frame.ptr(), raw.ctypes.data if raw.size else None, raw.size,
+                                                                   C.byref(params), C.byref(compat), C.byref(res))
+        if rc != 0 and not (rc == -1 and res.error):
+            check(rc)
+        return noarith_decode_result(res), int(compat.value), rc
 
     def motion_encode_batch(self, pictures, capacity=None):
         """schro_hip_motion_encode_batch.  pictures: per picture (motion, x_num_blocks, y_num_blocks, num_refs,

@@ -56,6 +56,8 @@ EXPORTED_SYMBOLS = [
     "schro_hip_lowdelay_encode_batch", "schro_hip_encode_lowdelay_transform_data",
     "schro_hip_noarith_encode_bound", "schro_hip_noarith_encode_batch", "schro_hip_noarith_encode_check",
     "schro_hip_encode_transform_data_noarith",
+    "schro_hip_noarith_decode_batch", "schro_hip_noarith_decode_check", "schro_hip_noarith_decode_scratch_words",
+    "schro_hipframe_decode_transform_data_noarith",
     "schro_hip_motion_encode_bound", "schro_hip_motion_encode_batch", "schro_hip_motion_encode_check",
     "schro_hip_encode_motion_data_noarith",
     "schro_hip_dequant_batch", "schro_hip_quantise_batch", "schro_hip_subtract_batch", "schro_hipframe_subtract",
@@ -264,6 +266,23 @@ class NoarithPicture(C.Structure):
                 ("iwt_height", C.c_int * 3), ("codeblocks", C.POINTER(Codeblock) * 3), ("ncodeblocks", C.c_int * 3),
                 ("transform_depth", C.c_int), ("horiz_codeblocks", C.c_int * 7), ("vert_codeblocks", C.c_int * 7),
                 ("codeblock_mode_index", C.c_int), ("out", C.c_void_p), ("capacity", C.c_size_t), ("result", C.c_void_p)]
+
+
+class NoarithDecodeResult(C.Structure):
+    """SchroHipNoarithDecodeResult: what schro_hip_noarith_decode_batch leaves on the device per picture."""
+    _fields_ = [("bytes_read", C.c_uint32), ("error", C.c_uint32), ("first_error", C.c_uint32), ("compat_quant_offset", C.c_uint32),
+                ("truncated", C.c_uint32), ("not_consumed", C.c_uint32), ("overran", C.c_uint32), ("long_codes", C.c_uint32),
+                ("clamped_quant", C.c_uint32), ("subband_length", (C.c_uint32 * NOARITH_MAX_SUBBANDS) * 3),
+                ("subband_quant_index", (C.c_uint8 * NOARITH_MAX_SUBBANDS) * 3)]
+
+
+class NoarithDecodePicture(C.Structure):
+    """SchroHipNoarithDecodePicture (include/schro_hip.h): one picture of schro_hip_noarith_decode_batch."""
+    _fields_ = [("data", C.c_void_p), ("data_bytes", C.c_size_t), ("bytes_on_device", C.c_void_p), ("coeffs", C.c_void_p * 3),
+                ("bytes", C.c_size_t * 3), ("stride", C.c_int * 3), ("quant", C.c_void_p * 3), ("iwt_width", C.c_int * 3),
+                ("iwt_height", C.c_int * 3), ("transform_depth", C.c_int), ("horiz_codeblocks", C.c_int * 7),
+                ("vert_codeblocks", C.c_int * 7), ("codeblock_mode_index", C.c_int), ("is_intra", C.c_int),
+                ("compat_quant_offset", C.c_int), ("result", C.c_void_p)]
 
 
 MOTION_SECTIONS = 9             # SCHRO_HIP_MOTION_SECTIONS (include/schro_hip.h)
@@ -655,6 +674,15 @@ def load():
                                                           C.c_size_t, C.POINTER(C.c_size_t),
                                                           C.POINTER(C.c_int * NOARITH_MAX_SUBBANDS), C.POINTER(C.c_int)]
     L.schro_hip_encode_transform_data_noarith.restype = i
+    L.schro_hip_noarith_decode_batch.argtypes = [vp, C.POINTER(NoarithDecodePicture), i, i]
+    L.schro_hip_noarith_decode_batch.restype = i
+    L.schro_hip_noarith_decode_check.argtypes = [C.POINTER(NoarithDecodePicture), i, i]
+    L.schro_hip_noarith_decode_check.restype = i
+    L.schro_hip_noarith_decode_scratch_words.argtypes = [C.POINTER(NoarithDecodePicture), i, i]
+    L.schro_hip_noarith_decode_scratch_words.restype = C.c_int64
+    L.schro_hipframe_decode_transform_data_noarith.argtypes = [C.POINTER(Frame), vp, C.c_size_t, C.POINTER(Params), C.POINTER(C.c_int),
+                                                               C.POINTER(NoarithDecodeResult)]
+    L.schro_hipframe_decode_transform_data_noarith.restype = i
     L.schro_hip_motion_encode_bound.argtypes = [i, i, i, i]
     L.schro_hip_motion_encode_bound.restype = C.c_int64
     L.schro_hip_motion_encode_batch.argtypes = [vp, C.POINTER(MotionEncodePicture), i]

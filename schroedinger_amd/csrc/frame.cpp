@@ -912,6 +912,78 @@ schro_hipframe_dequantise (SchroHipFrame * transform_frame, const SchroHipQuanti
   return stage_done (ctx, r);
 }
 
+// schro_decoder_parse_transform_data + schro_decoder_decode_transform_data for params->is_noarith: the picture's bytes go
+// up instead of the entropy-decoded values; the frame is left as schro_hipframe_dequantise leaves it.
+int
+schro_hipframe_decode_transform_data_noarith (SchroHipFrame * transform_frame, const uint8_t * host_data, size_t length,
+    SchroHipParams * params, int *compat_quant_offset, SchroHipNoarithDecodeResult * result)
+{
+  const char *who = "hipframe_decode_transform_data_noarith";
+  SCHRO_HIP_REQUIRE (transform_frame && frame_ctx (transform_frame) && params && compat_quant_offset && result
+      && (host_data || length == 0), "%s: bad arguments (the transform frame must be a device frame)", who);
+  SchroHipContext *ctx = frame_ctx (transform_frame);
+  const int bpp = format_bpp (transform_frame->format);
+  SCHRO_HIP_REQUIRE ((bpp == 2 || bpp == 4) && !(transform_frame->format & 0x100), "%s: the frame must be a planar s16 or s32 frame", who);
+  const int depth = params->transform_depth;
+  SCHRO_HIP_REQUIRE (depth >= 0 && depth <= 6, "%s: transform_depth %d", who, depth);
+  SCHRO_HIP_REQUIRE (length < ((size_t) 1 << 29), "%s: %zu bytes (below 2^29)", who, length);
+  (void) hipSetDevice (ctx->device);
+  const int intra = params->num_refs == 0;
+  SchroHipNoarithDecodePicture pic;
+  memset (&pic, 0, sizeof (pic));
+  pic.transform_depth = depth;
+  pic.codeblock_mode_index = params->codeblock_mode_index;
+  pic.is_intra = intra;
+  pic.compat_quant_offset = *compat_quant_offset != 0;
+  for (int l = 0; l <= depth; l++) {
+    pic.horiz_codeblocks[l] = params->horiz_codeblocks[l];
+    pic.vert_codeblocks[l] = params->vert_codeblocks[l];
+  }
+  SchroHipDcPlane ll[3];
+  for (int k = 0; k < 3; k++) {
+    const SchroHipFrameData & c = transform_frame->components[k];
+    const int w = k ? params->iwt_chroma_width : params->iwt_luma_width, h = k ? params->iwt_chroma_height : params->iwt_luma_height;
+    SCHRO_HIP_REQUIRE (w > 0 && h > 0 && c.width >= w && c.height >= h && (long long) c.stride >= (long long) w * bpp,
+        "%s: component %d (%d x %d, stride %d) does not hold the %d x %d transform", who, k, c.width, c.height, c.stride, w, h);
+    pic.coeffs[k] = c.data;
+    pic.bytes[k] = (size_t) c.stride * (size_t) h;
+    pic.stride[k] = c.stride;
+    pic.iwt_width[k] = w;
+    pic.iwt_height[k] = h;
+    ll[k].data = c.data;
+    ll[k].stride = c.stride << depth;   // schro_subband_get_frame_data, schroparams.c:319-352
+    ll[k].width = w >> depth;
+    ll[k].height = h >> depth;
+  }
+  // one allocation: the result, the bytes
+  static_assert (sizeof (SchroHipNoarithDecodeResult) <= 512, "the result sits in front of the bytes");
+  char *d = (char *) schro_hip_domain_alloc (ctx, 512 + (length ? length : 1));
+  if (!d)
+    return SCHRO_HIP_ENOMEM;
+  pic.result = (SchroHipNoarithDecodeResult *) d;
+  pic.data = (const uint8_t *) d + 512;
+  pic.data_bytes = length;
+  int r = 0;
+  if (length && hipMemcpyAsync (d + 512, host_data, length, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+    r = set_error (SCHRO_HIP_EDEVICE, "%s: copy of %zu bytes failed", who, length);
+  if (!r)
+    r = schro_hip_noarith_decode_batch (ctx, &pic, 1, bpp);
+  memset (result, 0, sizeof (*result));
+  if (!r && hipMemcpyAsync (result, d, sizeof (*result), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+    r = set_error (SCHRO_HIP_EDEVICE, "%s: copy of the result failed", who);
+  const int rs = schro_hip_synchronize (ctx);   // the result is here, d is free again
+  schro_hip_domain_free (ctx, d);
+  if (r || rs)
+    return r ? r : rs;
+  if (result->error)
+    return set_status (SCHRO_HIP_EINVAL, "%s: quant index above 60 in the header of component %u, sub-band %u", who,
+        result->first_error / SCHRO_HIP_NOARITH_MAX_SUBBANDS, result->first_error % SCHRO_HIP_NOARITH_MAX_SUBBANDS);
+  *compat_quant_offset = (int) result->compat_quant_offset;
+  if (intra)
+    r = schro_hip_dc_predict_batch (ctx, ll, 3, bpp);
+  return stage_done (ctx, r);
+}
+
 int
 schro_upsampled_hipframe_upsample (SchroHipFrame * dest, SchroHipFrame * src)
 {

@@ -896,6 +896,58 @@ struct NaScratch {              // the selected queue's, per call
 // stages: 1 count, 2 layout, 4 clear + pack
 int launch_noarith_encode (hipStream_t stream, const NaSubband * d_sbs, int nsbs, const NaPicture * d_pics, int npics,
     const NaScratch & S, int bpp, int grid_x, int clear_x, int stages);
+// noarith_dec.hip: the same syntax read back.  One sub-band of one component of one picture, from the host: where its
+// samples go and how it is cut into codeblocks (schro_hip_codeblock_layout's closed forms, as above).
+struct NdSubband {
+  void *coeffs, *quant;         // sample (0, 0) of the band in each plane; quant may be NULL
+  int stride;                   // bytes between band rows, both planes
+  int bw, bh, hc, vc;
+  int cb_base;                  // first of its hc * vc codeblocks in the call's codeblock records
+  int pic, comp, index;
+  int pad;
+};
+struct NdPicture {
+  const uint8_t *data;
+  const uint32_t *bytes_on_device;      // NULL: data_bytes is the length
+  SchroHipNoarithDecodeResult *result;
+  uint32_t data_bytes;
+  int sb_first, nsb;            // its sub-bands in the call's table, stream order
+  uint32_t chunk_first, chunk_cap;      // its chunk slots in the call's arrays: data_bytes / 8 + nsb suffice
+  int mode, is_intra, compat;
+  int pad;
+};
+// what nd_header_kernel finds in the stream, per sub-band (8 words)
+struct NdBand {
+  uint32_t first_byte;          // of the payload, from `data`
+  uint32_t bytes;               // of the payload, cut at the input's end
+  uint32_t length;              // as stated
+  uint32_t chunk_base, nchunks; // its chunks among the picture's
+  uint32_t quant_index;
+  uint32_t flags;               // 1 coded, 2 have_zero_flags, 4 have_quant_offset
+  uint32_t pad;
+};
+constexpr int kNdChunkBits = 64;        // a lane's share of a payload
+constexpr int kNdChainThreads = 1024;   // chunks the chain workgroup composes per step
+constexpr int kNdLaneThreads = 256;     // workgroup of the chunk-per-lane launches
+constexpr int kNdFillGridX = 1024;      // workgroups per sub-band of the fill launch: more row pieces are walked in strides
+constexpr int kNdChunkWords = 5, kNdCbWords = 3, kNdBandWords = 8, kNdPicWords = 2;
+struct NdScratch {              // the selected queue's, per call
+  NdBand *bands;                // per sub-band
+  uint32_t *ptotal;             // per picture: chunks in use, spare
+  uint32_t *sum;                // per chunk, 2 words: per entry state A, D, F, S 16 bits: completions << 2 | exit state
+  uint32_t *rec;                // per chunk, 3 words: codeblock (kNaNone: no code starts here), index of the first code that
+                                // starts here, entry state | first bit << 2
+  uint32_t *cb;                 // per codeblock, 3 words: first value bit (zero: the flag's bit), quant index | zero << 8, codes that start in the payload
+};
+// the scratch the call takes, in words (plane_noarith_dec.cpp and its tests)
+static inline size_t
+nd_scratch_words (size_t chunks, size_t codeblocks, size_t subbands, size_t pictures)
+{
+  return kNdChunkWords * chunks + kNdCbWords * codeblocks + kNdBandWords * subbands + kNdPicWords * pictures;
+}
+// stages: 1 header, 2 summary, 4 chain, 8 decode + fill
+int launch_noarith_decode (hipStream_t stream, const NdSubband * d_sbs, int nsbs, const NdPicture * d_pics, int npics,
+    const NdScratch & S, int bpp, int lane_x, int fill_x, int stages);
 // motion_enc.hip: one picture's motion data.  A superblock owns kMeSbWords words of the call's scratch: what the count
 // launch found in it and where the layout launch put it.
 struct MePicture {
