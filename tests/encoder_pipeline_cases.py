@@ -1,14 +1,14 @@
 """The cases of tests/test_gpu_encoder_pipeline.py: which cases of the encoder's stages are enqueued in which order, the
 scratch each of them needs, and what every call must leave.  Nothing is restated here: the inputs and the expected values
 are the cached ones of the stages' own case modules (subpel_cases, split2_cases, mode_cases, hier_bm_cases,
-noarith_enc_cases, lowdelay_enc_cases, quant_cases) and of the rough chain of tests/test_gpu_rough_hint.py, whose
+noarith_enc_cases, noarith_dec_cases, motion_enc_cases, lowdelay_enc_cases, quant_cases) and of the rough chain of tests/test_gpu_rough_hint.py, whose
 witnesses the CPU walks of those modules assert.
 
 The scratch needs are the formulas of schroedinger_amd/csrc/plane_*.cpp.  The plane-layer batch call takes its tables
 from the START of the queue's grow-only block (`batch_need`; 0 where the call takes none: the block matching and the
 rough search keep everything in the caller's fields).  The frame-layer run sizes the block for those tables and, BEHIND
-them, the fields and outputs it copies in and out (`frame_need`; the two entropy coders' frame-layer runs allocate their
-outputs elsewhere and need what their batch call needs).  A sequence is (A, B, C): A small, B at least four times A -- the
+them, the fields and outputs it copies in and out (`frame_need`; the frame-layer runs of the entropy coders, of the VLC
+decoder and of the motion-data encoder allocate their inputs and outputs elsewhere and need what their batch call needs).  A sequence is (A, B, C): A small, B at least four times A -- the
 block is reallocated behind A's launches --, C smaller than B and unlike A -- its tables lie on what B left.
 tests/test_encoder_pipeline_cases.py asserts that order, so that a changed case cannot make a sequence monotone without a
 failure."""
@@ -19,6 +19,8 @@ import numpy as np
 import hier_bm_cases as HK
 import lowdelay_enc_cases as LC
 import mode_cases as MC
+import motion_enc_cases as ME
+import noarith_dec_cases as DC
 import noarith_enc_cases as NC
 import quant_cases as QC
 import split2_cases as S2
@@ -193,6 +195,60 @@ def _lowdelay_outputs(name):
     return {"slices": res["bytes"], "index": res["index"], "count": np.array([res["count"]], np.uint32)}
 
 
+# ---- the VLC decoder and the motion-data encoder ----------------------------------------------------------------------------
+
+ND_RESULT_WORDS = 9 + 3 * 19 + 15       # SchroHipNoarithDecodeResult: nine counters, 3 x 19 lengths, 3 x 19 index bytes and padding
+ME_SB_WORDS, ME_SECTIONS = 32, 9        # kMeSbWords, kMeSections (schro_hip_internal.h)
+
+
+def _noarith_dec_need(case):
+    # plane_noarith_dec.cpp: five words per chunk slot (data_bytes / 8 + sub-bands + 1), three per codeblock, eight per
+    # sub-band, two per picture
+    nsb = 3 * case.nsub
+    ncb = 3 * sum(case.counts(i)[0] * case.counts(i)[1] for i in range(case.nsub))
+    return (5 * (case.data_bytes // 8 + nsb + 1) + 3 * ncb + 8 * nsb + 2) * 4
+
+
+def noarith_dec_result_words(result):
+    """A result dict of tests/noarith_dec_ref.py (or of sa.noarith_decode_result) as the words of the device's block."""
+    head = [result[k] for k in ("bytes_read", "error", "first_error", "compat_quant_offset", "truncated", "not_consumed", "overran",
+                                "long_codes", "clamped_quant")]
+    index = np.zeros(4 * 15, np.uint8)
+    index[:3 * 19] = np.asarray(result["subband_quant_index"]).ravel()
+    words = np.concatenate([np.array(head, np.uint32), np.asarray(result["subband_length"]).ravel().astype(np.uint32), index.view(np.uint32)])
+    assert words.size == ND_RESULT_WORDS
+    return words
+
+
+def _noarith_dec_outputs(name):
+    coeffs, quant, result = DC.BY_NAME[name].expected()
+    flat = lambda planes: np.concatenate([p.ravel() for p in planes])
+    return {"coeffs": flat(coeffs), "quant": flat(quant), "result": noarith_dec_result_words(result)}
+
+
+@functools.lru_cache(maxsize=None)
+def _motion_cases():
+    return {c[0]: c for c in ME.all_cases()}
+
+
+def _motion_enc_need(case):
+    # plane_motion_enc.cpp: kMeSbWords words per superblock, each section's header bits and length per picture
+    name, field, nbx, nby, num_refs, hg, _ = case
+    return (nbx * nby // 16 * ME_SB_WORDS + 2 * ME_SECTIONS) * 4
+
+
+@functools.lru_cache(maxsize=None)
+def motion_enc_expected(name):
+    """(bytes, result) of tests/motion_enc_ref.py, once per case"""
+    import motion_enc_ref as MR
+    return MR.encode(*_motion_cases()[name][1:6])
+
+
+def _motion_enc_outputs(name):
+    data, result = motion_enc_expected(name)
+    return {"bytes": np.frombuffer(data, np.uint8), "sections": np.array(result["section_bytes"], np.int64)}
+
+
 # ---- the quantiser: three unlike planes of the codeblock-geometry case ------------------------------------------------
 
 QUANT_SPECS = {"88x72_inter": 0, "44x40_intra": 3, "two_codeblocks": 5}
@@ -229,6 +285,12 @@ STAGES = {
                     frame_need=_noarith_need, outputs=_noarith_outputs),
     "lowdelay": dict(cases=LC.CASES, sequence=("64x32_d3_420", "128x64_16x8_420", "72x40_5x3"), batch_need=_lowdelay_need,
                      frame_need=_lowdelay_need, outputs=_lowdelay_outputs),
+    # the decoder's C after B is the one to watch: its chunk and codeblock records lie on what B's 1027 chunks left
+    "noarith_dec": dict(cases=DC.BY_NAME, sequence=("s16-16x8-420-d2-three-m1-c1", "s16-chain-two-steps", "s16-32x16-420-d3-two-m0-c0"),
+                        batch_need=_noarith_dec_need, frame_need=_noarith_dec_need, outputs=_noarith_dec_outputs),
+    "motion_enc": dict(cases=_Lazy(lambda name: _motion_cases()[name]),
+                       sequence=("4x4 split 2 refs 2", "132x68: three superblocks per layout thread", "12x12 mixed refs 2"),
+                       batch_need=_motion_enc_need, frame_need=_motion_enc_need, outputs=_motion_enc_outputs),
 }
 # what only the nine calls run: the single launches of the sub-pel stage -- pass 1 of each case, from the field and the table
 # the restatement has there -- and the quantiser, which takes no scratch
@@ -237,8 +299,8 @@ LAUNCHES = {
     "subpel_choose": dict(STAGES["subpel"], outputs=_subpel_choose_outputs),
     "quantise": dict(cases=_Lazy(quant_spec), sequence=tuple(QUANT_SPECS), outputs=_quant_outputs),
 }
-SCRATCH_STAGES = ("rough", "hbm", "subpel", "split2", "mode", "noarith", "lowdelay")
-NINE_CALL_STAGES = ("subpel_error", "subpel_choose", "subpel", "split2", "mode", "hbm", "quantise")
+SCRATCH_STAGES = ("rough", "hbm", "subpel", "split2", "mode", "noarith", "lowdelay", "noarith_dec", "motion_enc")
+NINE_CALL_STAGES = ("subpel_error", "subpel_choose", "subpel", "split2", "mode", "hbm", "quantise", "noarith_dec", "motion_enc")
 BIG_TABLES = 4                  # SchroHipContext::kBigTables: the pinned mirrors and device buffers of a queue, used in turn
 NINE = 2 * BIG_TABLES + 1
 

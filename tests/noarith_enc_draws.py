@@ -14,8 +14,8 @@ MAX_ABS = 2047
 MAX_ROW = 32
 
 
-def _fill(case, rng):
-    density = rng.choice([0.0, 0.1, 0.5, 0.9])
+def _fill(case, rng, densities=(0.0, 0.1, 0.5, 0.9)):
+    density = rng.choice(densities)
     for p in case.planes:
         v = rng.integers(-MAX_ABS, MAX_ABS + 1, p.shape)
         p[...] = np.where(rng.random(p.shape) < density, v, 0)
@@ -42,4 +42,30 @@ def draws():
     return out
 
 
+DEEP_SEED = 20261020
+DEEP_DEPTHS = (4, 5, 6)
+
+
+def deep_draws():
+    """Depths 4, 5 and 6 for both sample sizes and both codeblock modes, from a generator of their own (DRAWS stay what
+    they were).  The transform's width is a multiple of 1 << depth, so the limit on rows is held where it matters: the
+    widest sub-band row -- half the plane -- has at most MAX_ROW samples.  At depth 6 the LL band of a 64 x 64 component is
+    one sample and most levels have more codeblocks than samples."""
+    rng = np.random.default_rng(DEEP_SEED)
+    out = []
+    for depth in DEEP_DEPTHS:
+        for dtype in (np.int16, np.int32):
+            for mode in (0, 1):
+                fmt = int(rng.choice([420, 422, 444]))
+                lw = int(rng.integers(1, 2 * MAX_ROW + 1))
+                lh = int(rng.integers(1, 2 * MAX_ROW + 1))
+                counts = [(int(rng.integers(1, 5)), int(rng.integers(1, 4))) for _ in range(depth + 1)]
+                name = "deep-d%d-%s-m%d" % (depth, "s16" if dtype == np.int16 else "s32", mode)
+                out.append(NC.Case(name, dtype, lw, lh, fmt, depth, counts, mode, lambda c, r: _fill(c, r, (0.1, 0.5, 0.9)),
+                                   seed=int(rng.integers(1 << 30)), qbase=int(rng.integers(0, 61))))
+                assert max(w for w, h in out[-1].sizes) // 2 <= MAX_ROW
+    return out
+
+
 DRAWS = draws()
+DEEP_DRAWS = deep_draws()

@@ -20,6 +20,46 @@ def test_scratch_needs_are_small_large_smaller(stage):
     assert len(set(P.stage(stage)["sequence"])) == 3
 
 
+def test_the_new_stages_are_in_both_lists():
+    for stage in ("noarith_dec", "motion_enc"):
+        assert stage in P.SCRATCH_STAGES and stage in P.NINE_CALL_STAGES and stage in P.STAGES
+
+
+def test_decoder_scratch_by_hand_is_the_librarys():
+    """The by-hand formula of the decoder's scratch against schro_hip_noarith_decode_scratch_words, for A, B and C and for
+    the three in one call; B is the picture of 1027 chunks."""
+    import schroedinger_amd as sa
+    from schroedinger_amd import _lib
+    from test_noarith_decode_api import fake_picture
+    lib = _lib.load()
+    s = P.stage("noarith_dec")
+    cases = [s["cases"][n] for n in s["sequence"]]
+    for case in cases:
+        assert case.dtype.itemsize == 2
+        assert 4 * lib.schro_hip_noarith_decode_scratch_words(sa.noarith_decode_pictures([fake_picture(case)]), 1, 2) == s["batch_need"](case), case.name
+    arr = sa.noarith_decode_pictures([fake_picture(c, n) for n, c in enumerate(cases)])
+    assert 4 * lib.schro_hip_noarith_decode_scratch_words(arr, 3, 2) == sum(s["batch_need"](c) for c in cases)
+    a, b, c = cases
+    assert a.sizes[0] == (16, 8) and c.sizes[0] == (32, 16) and c.depth == 3
+    assert -(-int(b.expected()[2]["subband_length"][0, 1]) // 8) == 1027
+    # A goes through the frame layer as an inter picture of a 4:2:0 frame
+    assert a.is_intra == 0 and a.sizes[1] == (8, 4) and all(x.expected()[2]["error"] == 0 for x in cases)
+    words = P.noarith_dec_result_words(a.expected()[2])
+    assert words.size * 4 == __import__("ctypes").sizeof(_lib.NoarithDecodeResult)
+    back = sa.noarith_decode_result(words)
+    assert all(np.array_equal(np.asarray(back[k]), np.asarray(v)) for k, v in a.expected()[2].items())
+
+
+def test_motion_encoder_scratch_constants_are_the_headers():
+    import os
+    text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "schroedinger_amd", "csrc", "schro_hip_internal.h")).read()
+    assert "kMeSbWords = %d" % P.ME_SB_WORDS in text and "kMeSections = SCHRO_HIP_MOTION_SECTIONS" in text
+    from schroedinger_amd import _lib
+    assert _lib.MOTION_SECTIONS == P.ME_SECTIONS
+    a, b, c = (P.case("motion_enc", n) for n in P.stage("motion_enc")["sequence"])
+    assert (a[2], a[3]) == (4, 4) and (b[2], b[3]) == (132, 68) and (c[2], c[3]) == (12, 12)
+
+
 @pytest.mark.parametrize("both_queues", [False, True])
 @pytest.mark.parametrize("stage", P.SCRATCH_STAGES)
 def test_scratch_sequence_order(stage, both_queues):

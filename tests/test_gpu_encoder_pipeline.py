@@ -20,12 +20,15 @@ import guard_lib as G
 import hier_bm_cases as HK
 import lowdelay_enc_cases as LC
 import mode_cases as MC
+import noarith_dec_cases as DC
 import noarith_enc_cases as NC
 import quant_cases as QC
 import schroedinger_amd as sa
 import split2_cases as S2
 import subpel_cases as SP
 import test_gpu_mode_decision as TM
+import test_gpu_motion_encode as TV
+import test_gpu_noarith_decode as TD
 import test_gpu_noarith_encode as TN
 import test_gpu_split2 as TS
 import test_gpu_subpel as TP
@@ -402,6 +405,110 @@ class Lowdelay:
             f.unref()
 
 
+class NoarithDec:
+    """schro_hip_noarith_decode_batch with caller-owned buffers: the input bytes, the coefficient and quant planes and the
+    result words of every entry in a guarded block.  The launches behind the header walk read the records -- bands, chunk
+    totals, chunk and codeblock records -- that earlier launches of the same call left in the scratch."""
+
+    def __init__(self, ctx):
+        self.ctx, self.keep = ctx, []
+
+    def setup(self, names, frame_name=None):
+        self.names = names
+        self.cases = [DC.BY_NAME[name] for name in names]
+        lay = G.Layout()
+        self.specs = []
+        for k, case in enumerate(self.cases):
+            b = case.dtype.itemsize
+            assert case.expected()[0] is not None
+            stride = lambda w: (w * b + 63) // 64 * 64 + (k % 3) * b
+            self.specs.append(dict(
+                data=lay.span(max(len(case.data), 1), align=64, skew=k % 4, footprint=None, name="data%d" % k),
+                coeffs=[lay.plane(h, w, case.dtype, stride=stride(w), skew=b * ((k + c) % 4), name="coeffs%d_%d" % (k, c))
+                        for c, (w, h) in enumerate(case.sizes)],
+                quant=[lay.plane(h, w, case.dtype, stride=stride(w), skew=b * ((k + c + 2) % 4), name="quant%d_%d" % (k, c))
+                       for c, (w, h) in enumerate(case.sizes)],
+                result=lay.plane(1, TD.WORDS, np.uint32, align=64, skew=4 * (k % 4), name="result%d" % k)))
+        self.block = G.GuardedBlock(self.ctx, lay, seed=len(names))
+        for case, s in zip(self.cases, self.specs):
+            self.block[s["data"]].upload(np.frombuffer(case.data, np.uint8).reshape(1, -1))
+        if frame_name:
+            case = self.frame_case = DC.BY_NAME[frame_name]
+            (w, h) = case.sizes[0]
+            assert case.sizes[1] == ((w + 1) // 2, (h + 1) // 2) and not case.is_intra
+            start = [np.full((hh, ww), 0x1234, case.dtype) for ww, hh in case.sizes]
+            self.frame = frames.DeviceFrame(self.ctx, frames.frame_format(case.dtype, 1, 1), w, h).upload(frames.HostFrame(start, 1, 1))
+            self.keep.append(self.frame)
+            self.params = frames.make_params(transform_depth=case.depth, num_refs=1, is_noarith=1, iwt_luma_width=w, iwt_luma_height=h,
+                                             iwt_chroma_width=case.sizes[1][0], iwt_chroma_height=case.sizes[1][1],
+                                             codeblock_mode_index=case.mode)
+            for l in range(case.depth + 1):
+                self.params.horiz_codeblocks[l], self.params.vert_codeblocks[l] = case.hc[l], case.vc[l]
+            want = P.outputs("noarith_dec", frame_name)
+            self.frame_want = {"coeffs": want["coeffs"], "result": want["result"]}
+        self.ctx.synchronize()
+
+    def call(self, k):
+        case, s, b = self.cases[k], self.specs[k], self.block
+        assert self.ctx.noarith_decode_batch([(b[s["data"]], case.data_bytes, None, [b[c] for c in s["coeffs"]], [b[c] for c in s["quant"]],
+                                               case.depth, case.hc, case.vc, case.mode, case.is_intra, case.compat, b[s["result"]])]) is None
+
+    def frame_call(self):
+        case = self.frame_case
+        result, compat, status = self.ctx.decode_transform_data_noarith(self.frame, case.data, self.params, case.compat)
+        assert status == 0 and compat == case.expected()[2]["compat_quant_offset"]
+        return {"coeffs": np.concatenate([p.ravel() for p in self.frame.download()]), "result": P.noarith_dec_result_words(result)}
+
+    def check(self):
+        want = {}
+        for case, s in zip(self.cases, self.specs):
+            coeffs, quant, result = case.expected()
+            want.update(zip(s["coeffs"], coeffs))
+            want.update(zip(s["quant"], quant))
+            want[s["result"]] = P.noarith_dec_result_words(result).reshape(1, -1)
+        self.block.check(want)
+
+    def free(self):
+        self.block.free()
+        for f in self.keep:
+            f.unref()
+
+
+class MotionEnc:
+    """schro_hip_motion_encode_batch with caller-owned buffers: the rig of its own test -- the fields, the bytes with the
+    bound's room and the result words of every entry in one guarded block."""
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+
+    def setup(self, names, frame_name=None):
+        self.names = names
+        cases = [P.case("motion_enc", name) for name in names]
+        self.rig = TV.Rig(self.ctx, cases, [sa.motion_encode_bound(*c[2:6]) for c in cases], [k % 4 for k in range(len(cases))], seed=len(names))
+        self.pictures = self.rig.pictures()
+        if frame_name:
+            self.frame_case = P.case("motion_enc", frame_name)
+            self.frame_want = P.outputs("motion_enc", frame_name)
+        self.ctx.synchronize()
+
+    def call(self, k):
+        assert self.ctx.motion_encode_batch([self.pictures[k]]) is None
+
+    def frame_call(self):
+        _, field, nbx, nby, num_refs, hg, _ = self.frame_case
+        params = frames.make_params(x_num_blocks=nbx, y_num_blocks=nby, num_refs=num_refs, have_global_motion=hg, **TV.PARAMS)
+        got, nbytes, sections, result, status = self.ctx.encode_motion_data_noarith(field, params, sa.motion_encode_bound(nbx, nby, num_refs, hg))
+        assert status == 0 and nbytes == len(got)
+        TV.same(got, result, self.frame_case)
+        return {"bytes": np.frombuffer(bytes(got), np.uint8), "sections": np.array(sections, np.int64)}
+
+    def check(self):
+        self.rig.check()
+
+    def free(self):
+        self.rig.free()
+
+
 class Quantise:
     """schro_hip_quantise_batch, one plane per call: coefficients, quantised values and summaries of every entry in a guarded
     block, the quant planes filled as tests/quant_cases.py fills them."""
@@ -460,7 +567,7 @@ def make_stage(ctx, stage):
         return ModeLike(ctx, stage)
     if stage in ("hbm", "rough"):
         return Chain(ctx, stage)
-    return {"noarith": Noarith, "lowdelay": Lowdelay, "quantise": Quantise}[stage](ctx)
+    return {"noarith": Noarith, "lowdelay": Lowdelay, "quantise": Quantise, "noarith_dec": NoarithDec, "motion_enc": MotionEnc}[stage](ctx)
 
 
 # ---- 1. scratch from empty, grown behind a running call, then reused stale -----------------------------------------------

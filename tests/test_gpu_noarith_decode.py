@@ -29,13 +29,25 @@ def same_result(got, want, what):
         assert np.array_equal(np.asarray(got[key]), np.asarray(value)), (what, key, got[key], value)
 
 
-def run_guarded(ctx, cases, skews, pad=0, with_quant=True):
-    """The cases (one sample size) in ONE call, everything in one guarded block; returns nothing, raises on any difference."""
+def expected_with_word(case, word):
+    """What the case must leave when the call takes its length from a word on the device: the restatement on the first
+    min(word, data_bytes) bytes."""
+    if word is None:
+        return case.expected()
+    return DC.Case(case.name, case.dtype, case.sizes, case.depth, case.hc, case.vc, case.mode, case.compat, case.is_intra, case.data,
+                   min(word, case.data_bytes)).expected()
+
+
+def run_guarded(ctx, cases, skews, pad=0, with_quant=True, words=None):
+    """The cases (one sample size) in ONE call, everything in one guarded block; returns nothing, raises on any difference.
+    words: per case None or the value of a bytes_on_device word of its own in the block, which must keep its value."""
     b = cases[0].dtype.itemsize
     lay = G.Layout()
     specs = []
+    words = [None] * len(cases) if words is None else words
+    wanted = [expected_with_word(case, word) for case, word in zip(cases, words)]
     for n, (case, skew) in enumerate(zip(cases, skews)):
-        coeffs_e, quant_e, result_e = case.expected()
+        coeffs_e, quant_e, result_e = wanted[n]
         fp = "rect" if coeffs_e is not None else None           # a picture with the error: nothing may change
         tag = "p%d-" % n
         data = lay.span(max(len(case.data), 1), align=64, skew=skew, footprint=None, name=tag + "data")
@@ -46,24 +58,29 @@ def run_guarded(ctx, cases, skews, pad=0, with_quant=True):
         quant = [lay.plane(h, w, case.dtype, stride=(w * b + 63) // 64 * 64 + pad * b, skew=b * ((skew + k + 2) % 4), footprint=fp,
                            name="%squant%d" % (tag, k)) for k, (w, h) in enumerate(case.sizes)] if with_quant else None
         res = lay.plane(1, WORDS, np.uint32, align=64, skew=4 * (skew % 4), footprint="rect", name=tag + "result")
-        specs.append((data, coeffs, quant, res))
+        word = lay.plane(1, 1, np.uint32, align=64, skew=4 * ((skew + 1) % 4), footprint=None, name=tag + "length word") \
+            if words[n] is not None else None
+        specs.append((data, coeffs, quant, res, word))
     block = G.GuardedBlock(ctx, lay, seed=len(cases) + pad)
     try:
         pics, expected = [], {}
-        for case, (data, coeffs, quant, res) in zip(cases, specs):
+        for n, (case, (data, coeffs, quant, res, word)) in enumerate(zip(cases, specs)):
             if case.data:
                 block[data].upload(np.frombuffer(case.data, np.uint8).reshape(1, -1))
-            pics.append((block[data], case.data_bytes, None, [block[s] for s in coeffs], [block[s] for s in quant] if quant else None,
-                         case.depth, case.hc, case.vc, case.mode, case.is_intra, case.compat, block[res]))
-            coeffs_e, quant_e, result_e = case.expected()
+            if word is not None:
+                block[word].upload(np.array([[words[n]]], np.uint32))
+            pics.append((block[data], case.data_bytes, block[word] if word is not None else None, [block[s] for s in coeffs],
+                         [block[s] for s in quant] if quant else None, case.depth, case.hc, case.vc, case.mode, case.is_intra, case.compat,
+                         block[res]))
+            coeffs_e, quant_e, result_e = wanted[n]
             if coeffs_e is not None:
                 expected.update(zip(coeffs, coeffs_e))
                 if quant:
                     expected.update(zip(quant, quant_e))
         assert ctx.noarith_decode_batch(pics) is None
         ctx.synchronize()
-        for case, (data, coeffs, quant, res) in zip(cases, specs):
-            same_result(sa.noarith_decode_result(block[res].download()), case.expected()[2], case.name)
+        for n, (case, (data, coeffs, quant, res, word)) in enumerate(zip(cases, specs)):
+            same_result(sa.noarith_decode_result(block[res].download()), wanted[n][2], case.name)
         block.check(expected)
     finally:
         block.free()
@@ -172,16 +189,15 @@ def test_own_buffers_return_the_result(ctx):
             p.free()
 
 
-@pytest.mark.parametrize("dtype", [np.int16, np.int32])
-def test_chain_quantise_encode_decode_without_a_host_wait(ctx, dtype):
-    """quantise_batch -> noarith_encode_batch -> noarith_decode_batch on one queue, nothing waited for in between: the
-    decoder takes its length from the encoder's result word on the device.  Its quant planes are the quantiser's and its
-    coefficient planes the reconstruction the quantiser left.  Two unlike pictures of geometries where the encoder's and
-    the decoder's rules agree (one codeblock in sub-band 0, compat on)."""
+def chain_round_trip(ctx, dtype, pics, seed=77):
+    """quantise_batch -> noarith_encode_batch -> noarith_decode_batch on one queue, nothing waited for in between, for
+    pics [(sizes, depth, hc, vc, mode)] where the encoder's and the decoder's rules agree (one codeblock in sub-band 0,
+    compat on): the decoder's quant planes are the quantiser's, its coefficient planes the reconstruction the quantiser
+    left, and it read the bytes the encoder reported."""
     dtype = np.dtype(dtype)
     b = dtype.itemsize
-    rng = np.random.default_rng(77)
-    pics = [(NC.iwt_sizes(32, 16, 420, 2), 2, [1, 2, 3], [1, 2, 2], 1), (NC.iwt_sizes(48, 24, 444, 1), 1, [1, 3], [1, 2], 0)]
+    rng = np.random.default_rng(seed)
+    assert all((hc[0], vc[0]) == (1, 1) for _, _, hc, vc, _ in pics)
     held, enc_pics, dec_pics, jobs = [], [], [], []
     words = C.sizeof(_lib.NoarithResult) // 4
     for sizes, depth, hc, vc, mode in pics:
@@ -198,7 +214,10 @@ def test_chain_quantise_encode_decode_without_a_host_wait(ctx, dtype):
                     n += 1
             src.append(c), quant.append(q), tabs.append(tab)
             dq.append(ctx.plane(h, w, dtype, stride=c.stride).fill(0x22)), dc.append(ctx.plane(h, w, dtype, stride=c.stride).fill(0x33))
-            jobs.append((c, q, tab, 0))
+            # (the plane-layer quantiser takes no record without samples -- a tiny sub-band cut into more codeblocks than it has
+            # columns or rows --; the encoder takes the whole table)
+            jobs.append((c, q, [(t.dst_offset, t.dst_stride, t.width, t.height, t.src_offset, t.src_bytes, t.quant_index)
+                                for t in tab if t.width and t.height], 0))
         cap = sa.noarith_encode_bound(sizes, depth, hc, vc, b)
         out = ctx.plane(1, cap, np.uint8)
         eres = ctx.plane(1, words, np.uint32)
@@ -228,3 +247,12 @@ def test_chain_quantise_encode_decode_without_a_host_wait(ctx, dtype):
             for item in group:
                 for p in (item if isinstance(item, list) else [item]):
                     p.free()
+
+
+@pytest.mark.parametrize("dtype", [np.int16, np.int32])
+def test_chain_quantise_encode_decode_without_a_host_wait(ctx, dtype):
+    """quantise_batch -> noarith_encode_batch -> noarith_decode_batch on one queue, nothing waited for in between: the
+    decoder takes its length from the encoder's result word on the device.  Its quant planes are the quantiser's and its
+    coefficient planes the reconstruction the quantiser left.  Two unlike pictures of geometries where the encoder's and
+    the decoder's rules agree (one codeblock in sub-band 0, compat on)."""
+    chain_round_trip(ctx, dtype, [(NC.iwt_sizes(32, 16, 420, 2), 2, [1, 2, 3], [1, 2, 2], 1), (NC.iwt_sizes(48, 24, 444, 1), 1, [1, 3], [1, 2], 0)])

@@ -118,6 +118,21 @@ def test_random_geometries(ctx, bpp):
             free(p)
 
 
+@pytest.mark.parametrize("bpp", [2, 4])
+def test_deep_random_geometries(ctx, bpp):
+    """The draws of depths 4, 5 and 6 of one sample size in one call: 57 sub-bands per picture at depth 6."""
+    cases = [c for c in ND.DEEP_DRAWS if c.dtype.itemsize == bpp]
+    assert sorted({c.depth for c in cases}) == [4, 5, 6] and {c.mode for c in cases} == {0, 1}
+    pics = [picture_of(ctx, c, pad=n % 3) for n, c in enumerate(cases)]
+    try:
+        for (got, result), case in zip(ctx.noarith_encode_batch(pics), cases):
+            same(got, result, case, case.name)
+            assert result["false_zero"] == (0, 0)
+    finally:
+        for p in pics:
+            free(p)
+
+
 @pytest.mark.parametrize("name,short,skew", [("s16-32x16-d3-mixed-m1", 0, 1), ("s16-32x16-d3-mixed-m1", 1, 3),
                                              ("s32-extremes-d1", 0, 2), ("s32-extremes-d1", 1, 0), ("s16-window-65", 1, 1)])
 def test_capacity_exact_and_one_byte_short(ctx, name, short, skew):

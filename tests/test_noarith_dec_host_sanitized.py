@@ -9,6 +9,7 @@ import subprocess
 import pytest
 
 import noarith_dec_cases as DC
+import noarith_dec_draws as DD
 from test_sanitizers import REPORT, clang_runtime
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,9 +30,13 @@ def scratch_words(case):
     return 5 * (case.data_bytes // 8 + nsb + 1) + 3 * ncb + 8 * nsb + 2
 
 
+# the named cases, and the drawn and scale ones: depths to 6, sizes the transform rounds up, inputs cut short
+GEOMETRIES = DC.CASES + DC.HOSTILE + DD.DRAWS + DD.SCALE
+
+
 def table_lines():
     out = []
-    for case in DC.CASES + DC.HOSTILE:
+    for case in GEOMETRIES:
         row = ["G", case.name] + _shape(case.dtype.itemsize, case.depth, case.mode, case.sizes, case.hc, case.vc)
         out.append(" ".join(str(v) for v in row + [case.data_bytes, scratch_words(case)]))
     for refused, table in ((1, DC.REFUSALS), (0, [(n, c, "") for n, c in DC.ACCEPTED])):
@@ -60,4 +65,4 @@ def test_the_noarith_decoder_host_code_under_asan_and_ubsan(tmp_path):
     text = r.stdout.decode(errors="replace")
     found = REPORT.search(text)
     assert not found and r.returncode == 0, text[-6000:]
-    assert "noarith_dec_walk: %d geometries, %d descriptions, ok" % (len(DC.CASES) + len(DC.HOSTILE), len(DC.REFUSALS) + len(DC.ACCEPTED)) in text
+    assert "noarith_dec_walk: %d geometries, %d descriptions, ok" % (len(GEOMETRIES), len(DC.REFUSALS) + len(DC.ACCEPTED)) in text

@@ -116,3 +116,18 @@ def test_round_trip_of_all_draws():
         assert max(int(np.abs(p.astype(np.int64)).max()) for p in case.planes) <= ND.MAX_ABS
         kinds.add((case.dtype.itemsize, case.depth > 0, case.mode))
     assert len(kinds) == 8      # both sample sizes, depth 0 and deeper, both codeblock modes
+
+
+def test_round_trip_of_the_deep_draws():
+    """Depths 4 .. 6: every (depth, sample size, codeblock mode) once, every one with coded sub-bands in every component."""
+    kinds = set()
+    for case in ND.DEEP_DRAWS:
+        data, bits, stats = case.expected()
+        assert stats == {"false_zero_codeblocks": 0, "false_zero_subbands": 0}, case.name
+        assert roundtrip(case), case.name
+        assert max(int(np.abs(p.astype(np.int64)).max()) for p in case.planes) <= ND.MAX_ABS
+        assert all(np.asarray(bits)[k].any() for k in range(3)), case.name
+        kinds.add((case.depth, case.dtype.itemsize, case.mode))
+    assert kinds == {(d, b, m) for d in ND.DEEP_DEPTHS for b in (2, 4) for m in (0, 1)} and len(ND.DEEP_DRAWS) == len(kinds)
+    # the first 24 draws are what they were before the deep ones came
+    assert [c.depth for c in ND.DRAWS] == [(n >> 2) % 4 for n in range(ND.NDRAWS)]
