@@ -809,6 +809,52 @@ schro_hip_encode_motion_data_noarith (SchroHipContext * ctx, const SchroHipMotio
   return 0;
 }
 
+// The way back (schrodecoder.c:2531-2814): the host bytes go up, the host field and the result come back.
+int
+schro_hip_decode_motion_data_noarith (SchroHipContext * ctx, const void *data, size_t length, const SchroHipParams * params,
+    SchroHipMotion * motion, SchroHipMotionDecodeResult * result)
+{
+  const char *who = "decode_motion_data_noarith";
+  SCHRO_HIP_REQUIRE (ctx && (data || length == 0) && params && motion && motion->motion_vectors, "%s: bad arguments", who);
+  SCHRO_HIP_REQUIRE (params->x_num_blocks > 0 && params->y_num_blocks > 0 && params->x_num_blocks <= kMaxMotionBlocks
+      && params->y_num_blocks <= kMaxMotionBlocks, "%s: %d x %d blocks", who, params->x_num_blocks, params->y_num_blocks);
+  SCHRO_HIP_REQUIRE (length < ((size_t) 1 << 29), "%s: %zu bytes (below 2^29)", who, length);
+  const size_t field_bytes = (size_t) params->x_num_blocks * params->y_num_blocks * kMvBytes, field_at = 256;
+  const size_t data_at = field_at + round_up (field_bytes, 256);
+  // one allocation: the result, the field, the bytes
+  char *d = (char *) schro_hip_domain_alloc (ctx, data_at + (length ? length : 1));
+  if (!d)
+    return SCHRO_HIP_ENOMEM;
+  static_assert (sizeof (SchroHipMotionDecodeResult) <= 256, "the result sits in front of the field");
+  SchroHipMotionDecodePicture pic;
+  memset (&pic, 0, sizeof (pic));
+  pic.data = (const uint8_t *) d + data_at;
+  pic.data_bytes = length;
+  pic.x_num_blocks = params->x_num_blocks;
+  pic.y_num_blocks = params->y_num_blocks;
+  pic.num_refs = params->num_refs;
+  pic.have_global_motion = params->have_global_motion;
+  pic.motion = d + field_at;
+  pic.result = (SchroHipMotionDecodeResult *) d;
+  int r = 0;
+  if (length && hipMemcpyAsync (d + data_at, data, length, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+    r = set_error (SCHRO_HIP_EDEVICE, "%s: copy of the bytes failed", who);
+  if (!r)
+    r = schro_hip_motion_decode_batch (ctx, &pic, 1);
+  SchroHipMotionDecodeResult res;
+  memset (&res, 0, sizeof (res));
+  if (!r && (hipMemcpyAsync (&res, d, sizeof (res), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess
+          || hipMemcpyAsync (motion->motion_vectors, d + field_at, field_bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess))
+    r = set_error (SCHRO_HIP_EDEVICE, "%s: copy of the field failed", who);
+  int rs = schro_hip_synchronize (ctx);
+  schro_hip_domain_free (ctx, d);
+  if (r || rs)
+    return r ? r : rs;
+  if (result)
+    *result = res;
+  return 0;
+}
+
 // r05 -- schro_decoder_decode_subband's data-parallel half on the device, behind the frame layer: the picture arrives
 // as codeblock records + quantised values (include/schro_hip.h), leaves as the dense transform frame x_wavelet_transform
 // reads.  Reference: schrodecoder.c:3525-3640 (the codeblock loop), :3311-3322 (zero codeblocks), :3060-3083 / :3400-3451

@@ -967,6 +967,39 @@ constexpr int kMeBits = 0, kMeUnits = 9, kMeUnverified = 18, kMeFirst = 19, kMeA
 // bit, its payload's first bit); stages: 1 count, 2 layout, 4 clear, 8 pack
 int launch_motion_encode (hipStream_t stream, const MePicture * d_pics, int npics, uint32_t * scratch, int total_sbs, int waves_x, int clear_x,
     int stages);
+// motion_dec.hip: the same sections read back.  A picture owns md_picture_words words of the call's scratch, from
+// scratch_first on: the sections (kMdSecWords each), per chunk slot the summary (2 words: per entry state A, D, F, S 16
+// bits, completions << 2 | exit state) and the entry (2 words: the index of the first code that starts there, the entry
+// state), per superblock the split residual, the split and the first unit (the three together padded to an even count),
+// per block seven residuals (sections 2 .. 8), the flags and two code indices (ref-1 or DC, ref-2).
+struct MdPicture {
+  const uint8_t *data;
+  const uint32_t *bytes_on_device;      // NULL: data_bytes is the length
+  uint8_t *motion;
+  SchroHipMotionDecodeResult *result;
+  uint64_t scratch_first;
+  uint32_t data_bytes, chunk_cap;       // chunk_cap slots: (data_bytes + 7) / 8 + 8 suffice
+  int nbx, nby;
+  int num_refs, have_global;
+};
+constexpr int kMdSections = SCHRO_HIP_MOTION_SECTIONS, kMdSecWords = 8;
+constexpr int kMdLaneThreads = 256;     // workgroup of the chunk-per-lane launches
+constexpr int kMdScanThreads = 256;     // the scan workgroup: a section of more chunks is composed in runs per thread
+constexpr int kMdSplitThreads = 64;     // the split walk: a diagonal of superblocks is short (135 at 2160p with 8 x 8 blocks)
+constexpr int kMdWalkThreads = 256;     // the mode and value walks
+static inline uint32_t
+md_chunk_cap (size_t data_bytes)
+{
+  return (uint32_t) ((data_bytes + 7) / 8 + 8);
+}
+static inline uint64_t
+md_picture_words (size_t data_bytes, uint64_t blocks)
+{
+  const uint64_t nsb = blocks / 16;
+  return (uint64_t) kMdSections * kMdSecWords + 4ull * md_chunk_cap (data_bytes) + ((3 * nsb + 1) & ~1ull) + 10 * blocks;
+}
+// stages: 1 header, 2 summary, 4 scan, 8 extract, 16 split walk, 32 mode walk, 64 value walk
+int launch_motion_decode (hipStream_t stream, const MdPicture * d_pics, int npics, uint32_t * scratch, int lane_x, int stages);
 // hist.hip
 void hist_tile_geometry (int *group_bytes, int *groups_per_tile, int *groups_per_step);
 int launch_histogram (hipStream_t stream, const HistJob * d_jobs, int njobs, int total_tiles, int bpp);
