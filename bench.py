@@ -12,9 +12,15 @@ resident in HBM.  Frames shard across GPUs (one process per GPU, no data-path
 collective): weak scaling, value = pictures * 3840*2160 / max-over-ranks time.
 
 Prints ONE JSON line (rank 0).  The roofline block is the dominant kernel's
-algorithmic bytes / its HIP-event time, measured during the timed steps; the
-cpu_baseline block is the CPU oracle (a port of the reference algorithm, see
-oracle/) timed on a bounded sample of the same workload, rank 0, N=1 only.
+algorithmic bytes / its HIP-event time, measured during the timed steps.
+
+A plain run does what that line's headline needs and nothing else: set-up,
+warm-up, the timed steps, --dump-outputs, the line.  --full adds every other
+leg, each outside the timed region with runs of its own: the cpu_baseline block
+(the CPU oracle, a port of the reference algorithm, see oracle/, timed on a
+bounded sample of the same workload and compared with the device's pictures:
+`parity`; rank 0, N=1 only), the transforms by themselves, the other picture
+kinds, the PCIe-inclusive pipelines, the frame layer and the low-delay path.
 """
 import argparse
 import json
@@ -1204,10 +1210,14 @@ def main():
                     help="picture batches in flight per GPU (2: OBMC of one beside the wavelet of the next)")
     ap.add_argument("--prewarm-ms", type=float, default=300.0,
                     help="untimed steps for this long before the warm-up steps (GPU clocks / caches in their steady state)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg (CPU baseline and parity against the oracle, the "
+                         "transforms by themselves, other picture kinds, PCIe-inclusive pipelines, frame layer, low delay): "
+                         "minutes; without it the run ends with the headline's line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline and its parity check")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the timed workload: no CPU baseline, no 1080p / PCIe-inclusive extras "
-                         "(profiler runs: every launch in the trace is a launch of the headline step)")
+                    help="what a run without --full is anyway: only the timed workload (profiler runs: every launch in the "
+                         "trace is a launch of the headline step); kept for command lines that carry it, and wins over --full")
     ap.add_argument("--cpu-cores", type=int, default=0, help="threads for the CPU baseline (0: auto)")
     ap.add_argument("--profile-steps", type=int, default=-1,
                     help="time the launches of the LAST n timed steps with HIP events (default: max (3, steps / 8)); "
@@ -1223,6 +1233,7 @@ def main():
         ap.error("--steps must be at least 1")
     if args.gpus is None:           # under a launcher the world size is the number of GPUs
         args.gpus = int(os.environ.get("WORLD_SIZE", "1"))
+    extras = args.full and not args.headline_only       # every leg but the headline's own
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: this process becomes the launcher.
@@ -1309,7 +1320,7 @@ def main():
     # r05: at N > 1 the host hand-over runs on every rank at once -- SURVEY 8(e): "expected scaling limit = host entropy
     # decode and PCIe, not the kernels" -- and rank 0 reports the slowest rank's step (outside the timed region)
     pcie_all = None
-    if world > 1 and not args.headline_only:
+    if world > 1 and extras:
         import torch
         legs = {}
         for name, quantised in (("pcie_inclusive", False), ("pcie_inclusive_quantised", True)):
@@ -1425,7 +1436,7 @@ def main():
             out["host_affinity"] = affinity
         if pcie_all:
             out.update(pcie_all)
-        if world == 1 and not args.headline_only:
+        if world == 1 and extras:
             # not part of the timed region: the other sizes / views SURVEY 8(d) asks for
             out["iiwt_2160p"] = iiwt_2160p(wl)
             out["iiwt_s32_2160p"] = iiwt_s32_2160p(ctx.device)
@@ -1451,7 +1462,7 @@ def main():
                 ts.append(ctx.timer_end())
             out["one_batch_in_flight"] = {"median_ms_per_step": round(float(np.median(ts)), 4),
                                           "Mpix_per_s": round(args.frames * W * H / float(np.median(ts)) / 1e3, 1)}
-        if world == 1 and not args.headline_only:
+        if world == 1 and extras:
             wl.queues = args.queues
             out["coherent_motion"] = coherent_motion(wl)
             # r06: the other pictures a decoder meets, each through the whole path: full-pel
@@ -1472,7 +1483,7 @@ def main():
             if any(str(out[k].get("parity", "")).startswith("MISMATCH") for k in
                    ("fullpel_2160p", "eighthpel_2160p", "blocks_24_16_2160p", "encoder_default_2160p", "weighted_2160p", "decode_1080p")):
                 out["parity_variants"] = "MISMATCH"
-        if world == 1 and not args.no_cpu_baseline and not args.headline_only:
+        if world == 1 and extras and not args.no_cpu_baseline:
             cores = args.cpu_cores or min(16, os.cpu_count() or 1)      # a one-GPU box's CPU share
             v, checked, equal, single = cpu_baseline(wl, cores)
             out["cpu_baseline"] = {"value": round(v, 2), "unit": "Mpix/s", "cores": cores,
@@ -1507,7 +1518,7 @@ def main():
             want = len(wl.sets) * wl.frames
             out["parity"] = ("bit-exact vs oracle on %d / %d pictures" % (equal, want) if equal == checked == want
                              else "MISMATCH vs oracle: %d of %d pictures equal (%d of %d checked)" % (equal, checked, checked, want))
-        if world == 1 and not args.headline_only:
+        if world == 1 and extras:
             wl.queues = 2
             out["pcie_inclusive_quantised"] = pcie_pipeline(wl, quantised=True)
             # the two other forms beside it: the r03 form -- the same queues and marks, the host never waits on

@@ -3,8 +3,11 @@
 # form, rocprofv3 kernel stats of the headline (two batches in flight / one), the counter passes, the config-5 leg's stats and
 # counters.  Copy the summaries into profiles/ (profiles/rNN_*) afterwards.
 set -e
-python3 bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err
-python3 bench.py --steps 20 --warmup 5 > gpurun_out/bench_steps20.json 2> gpurun_out/bench_steps20.err
+# (--full: the lines kept under profiles/ carry every leg, not the headline alone; PROFILE_OUT: where the two lines go)
+out=${PROFILE_OUT:-profile_out}
+mkdir -p $out
+python3 bench.py --full > $out/bench_default.json 2> $out/bench_default.err
+python3 bench.py --full --steps 20 --warmup 5 > $out/bench_steps20.json 2> $out/bench_steps20.err
 scripts/profile_round.sh > gpurun_out/profile_round.log 2>&1
 scripts/profile_one_batch.sh > gpurun_out/profile_one_batch.log 2>&1
 scripts/pmc_obmc_mix.sh > gpurun_out/pmc_mix.log 2>&1

@@ -57,6 +57,12 @@ def test_gpus_2_fails_loudly_without_devices():
     assert p.stderr.count("needs a HIP device") >= 2 or p.stderr.count("rank") >= 2, p.stderr
 
 
+def test_full_is_an_option_and_off_by_default():
+    """Every leg but the headline's own runs behind --full (tests/test_gpu_bench_plain.py: what a run without it prints)."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and "[--full]" in p.stdout, p.stdout + p.stderr
+
+
 def _fake_sysfs(root, cards, nodes):
     """cards: [(card name, pci address, vendor, numa_node)]; nodes: {node: cpulist text}."""
     for name, pci, vendor, node in cards:
