@@ -1689,6 +1689,102 @@ typedef struct {
  * counts are complete once that queue has passed the call. */
 int schro_hip_histogram_batch (SchroHipContext * ctx, const SchroHipHistogramPlane * planes, int nplanes, int bytes_per_sample);
 
+/* ---- encoder: the quantiser choice on the device ------------------------------------------------
+ *
+ * What every rate-controlled engine of the reference does with the histograms above, without a host step:
+ * schro_encoder_calc_estimates (schroquantiser.c:688-732) and then schro_encoder_lambda_to_entropy (:838-885) once
+ * (rdo_lambda, rdo_cbr: :758-782), under schro_encoder_entropy_to_lambda's search and once more at its answer
+ * (rdo_bit_allocation, :738-756, :887-969), or schro_encoder_lambda_to_error under schro_encoder_error_to_lambda's
+ * search (constant_error, :971-1119).  The input is the three components' SchroHipHistogramCounts arrays as
+ * schro_hip_histogram_batch leaves them, on the same queue; the output is a device record whose quant_index rows
+ * schro_hip_quantise_chosen_batch reads.
+ *
+ * Estimates: per (component, sub-band, index j < 60) est_entropy = schro_histogram_estimate_entropy (hist, j, is_noarith)
+ * * context_ratio and est_error = schro_histogram_apply_table (hist, error table j) (schrohistogram.c:42-104, :266-343,
+ * schroutils.c:309-327), on bins = counts * skip as doubles, in the reference's evaluation order, nothing fused.  What no
+ * transcendental touches is the reference's bit for bit: est_error, the twelve ranges, the sub-band lambdas, frame_lambda.
+ * The device's exp and log are within 1 ulp, as the host's are: est_entropy agrees with a host's to parts in 10^16 (the
+ * noarith branch: |d (1 - exp (-12.5 r))| < 4e-16 is a relative 3e-17 / r of the estimate, r = bin[1] / bin[0] >= 2^-32)
+ * and is not promised as bits.  The premise of the exact part: a sub-band's counts sum to less than 2^32 (as
+ * schro_hip_histogram_batch guarantees) and skip <= 1024, so that every sum inside get_range is exact in a double.
+ *
+ * The reference's behaviour, kept: all 104 bins zero (every sampled value in `overflow`, or an empty band) makes the
+ * noarith estimate 0 / 0 = NaN for every index, and index 0 is chosen (NaN never satisfies x < min); the first minimum
+ * wins; the sub-band lambda is frame lambda, *= subband0 scale, *= chroma scale, *= diagonal scale, /= weight * weight
+ * in that order, the error path without the diagonal scale; constant_error leaves the indices of its LAST evaluation and
+ * never evaluates at the lambda it returns, bit allocation evaluates once more at its answer; lo == hi after the steps
+ * returns sqrt (lo * hi) at once.  not_bracketed is the condition of the reference's "not bracketed" message; its own
+ * control flow never makes it true (a search that runs out of steps ends in lo == hi, or in NaN sums that compare false).
+ *
+ * The tables are encoder state and the caller's: encoder->intra_hist_tables (60 x 104 weights) and, for pictures that
+ * are not noarith, the one-bits / zero-bits tables of the same shape.  The sub-band weights
+ * (encoder->intra_ / inter_subband_weights [filter][MAX (0, depth - 1)]), the arith context ratios and the three
+ * magic_*_lambda_scale travel with each picture. */
+#define SCHRO_HIP_QUANT_CHOOSE_INDICES 60
+#define SCHRO_HIP_QUANT_ENGINE_LAMBDA 0           /* target: the frame lambda (rdo_lambda, rdo_cbr) */
+#define SCHRO_HIP_QUANT_ENGINE_BIT_ALLOCATION 1   /* target: frame->allocated_residual_bits */
+#define SCHRO_HIP_QUANT_ENGINE_CONSTANT_ERROR 2   /* target: the error, 255 * 0.1 ^ (0.05 noise_threshold) * width * height */
+typedef struct {
+  double frame_lambda;          /* the lambda engine's target, or what the search returned */
+  double sum;                   /* what the last evaluation returned: entropy, or (constant error) error */
+  double chosen_entropy[3][SCHRO_HIP_NOARITH_MAX_SUBBANDS];     /* the estimates at quant_index; a host forms */
+  double chosen_error[3][SCHRO_HIP_NOARITH_MAX_SUBBANDS];       /* estimated_residual_bits from them (:785-798) */
+  int32_t quant_index[3][SCHRO_HIP_NOARITH_MAX_SUBBANDS];       /* what the engine leaves; entries past 3 * depth are 0 */
+  int32_t evaluations;          /* lambda_to_entropy / _error calls made */
+  int32_t not_bracketed;
+  int32_t reserved;
+} SchroHipQuantChoice;
+
+typedef struct {
+  const SchroHipHistogramCounts *counts[3];     /* device: 1 + 3 * transform_depth entries per component; not written */
+  int skip[SCHRO_HIP_NOARITH_MAX_SUBBANDS];     /* per sub-band, what the histogram call sampled with: 1 .. 1024, a power of two */
+  int transform_depth;          /* 0 .. 6 */
+  int is_intra;                 /* 0 / 1; the tables the reference picks by it are the caller's: weights and ratios below */
+  int is_noarith;               /* which branch of the entropy estimate */
+  int engine;                   /* SCHRO_HIP_QUANT_ENGINE_* */
+  double subband_weight[SCHRO_HIP_NOARITH_MAX_SUBBANDS];        /* finite, positive */
+  double context_ratio[3][SCHRO_HIP_NOARITH_MAX_SUBBANDS];
+  double subband0_lambda_scale, chroma_lambda_scale, diagonal_lambda_scale;
+  double target;
+  SchroHipQuantChoice *result;  /* device, 8-byte aligned: every byte written */
+  double *est_entropy, *est_error;      /* device or NULL: [3][19][60] doubles each, the rows of sub-bands past 3 * depth untouched */
+} SchroHipQuantChoosePicture;
+
+/* The tables into device memory of the context (stored [104][60]: the 60 lanes of an estimate read neighbours).
+ * error: 60 x 104 doubles; onebits, zerobits: the same shape, or both NULL.  Calling it again replaces them; it waits for
+ * the context's queues first. */
+int schro_hip_quant_choose_tables (SchroHipContext * ctx, const double *error, const double *onebits, const double *zerobits);
+/* Pictures of unlike depth, form and engine in one call, two launches: the estimates (a wave per component and sub-band,
+ * lane j owns index j) and the choice (a workgroup per picture runs the whole engine, search included).  Enqueues, does
+ * not synchronise; the estimates go through the queue's grow-only scratch.  Refused (SCHRO_HIP_EINVAL, nothing enqueued,
+ * the message naming the picture and the field): what schro_hip_quant_choose_check refuses, no tables, more than 65535
+ * pictures. */
+int schro_hip_quant_choose_batch (SchroHipContext * ctx, const SchroHipQuantChoosePicture * pictures, int npictures);
+/* host only: a depth outside 0 .. 6, a skip that is no power of two in 1 .. 1024, a weight that is not finite and
+ * positive, a non-finite ratio, scale or target, an unknown engine, is_intra / is_noarith other than 0 / 1, NULL or
+ * misaligned pointers, a picture that is not noarith when have_bit_tables is 0.  No pointer is dereferenced. */
+int schro_hip_quant_choose_check (const SchroHipQuantChoosePicture * pictures, int npictures, int have_bit_tables);
+
+/* The two consumers with the indices taken from device memory, so that histograms -> choice -> quantise -> bytes is one
+ * run of enqueued calls.  Everything is schro_hip_quantise_batch's / schro_hip_noarith_encode_batch's -- structs,
+ * refusals, kernels, results bit for bit -- but for this: a codeblock record's quant_index holds its SUB-BAND number
+ * (0 .. 3 * depth), and the index comes from chosen[plane][sub-band] (the quantiser: a device row of 19 int32 per plane,
+ * SchroHipQuantChoice.quant_index[component]) or chosen[picture][component][sub-band] (the VLC encoder: a device block
+ * of 3 x 19 int32 per picture, SchroHipQuantChoice.quant_index).  `chosen` itself is a HOST array of device pointers.  A
+ * small resolve launch behind the job table's upload writes the constants the host would have written.  A value outside
+ * 0 .. 60 -- it can only come from a table of the caller's own making -- is clamped into range and counted: *clamped, a
+ * device word the caller has cleared, is added to once per record (quantiser) or sub-band (VLC encoder) that read one.
+ * One index per sub-band: the VLC encoder's refusal of unlike indices in a sub-band cannot arise.  Refused in addition:
+ * a NULL or misaligned chosen[.] or clamped, a record whose quant_index is not a sub-band (above 18; the VLC encoder: not
+ * the sub-band its place in the layout says). */
+int schro_hip_quantise_chosen_batch (SchroHipContext * ctx, const SchroHipQuantPlane * planes, const int32_t * const *chosen, int nplanes,
+    int bytes_per_sample, uint32_t * clamped);
+int schro_hip_noarith_encode_chosen_batch (SchroHipContext * ctx, const SchroHipNoarithPicture * pictures, const int32_t * const *chosen,
+    int npictures, int bytes_per_sample, uint32_t * clamped);
+/* host only: the refusals of schro_hip_noarith_encode_chosen_batch without a context.  No pointer is dereferenced but the HOST arrays. */
+int schro_hip_noarith_encode_chosen_check (const SchroHipNoarithPicture * pictures, const int32_t * const *chosen, int npictures,
+    int bytes_per_sample, const uint32_t * clamped);
+
 /* ---- frame layer: the reference's stage boundary ------------------------- */
 
 /* The structs of this layer are LAYOUT-IDENTICAL to the reference's (same members, same
@@ -2213,7 +2309,8 @@ int schro_hipframe_quantise (SchroHipFrame * quant_frame, SchroHipFrame * iwt_fr
 /* schro_encoder_generate_subband_histograms (schroquantiser.c:618-637) with frame->iwt_frame on the device: what it
  * leaves in frame->subband_hists.  SchroHipHistogram is LAYOUT-IDENTICAL to SchroHistogram (schrohistogram.h:16-20), so
  * the reference's estimate and choice code (schro_histogram_estimate_entropy, schro_histogram_apply_table, ...) runs on
- * the result unchanged.  hists: 3 * (1 + 3 * transform_depth) HOST entries, component-major, sub-band index minor;
+ * the result unchanged (on the host; schro_hip_quant_choose_batch is that code on the device, behind
+ * schro_hip_histogram_batch).  hists: 3 * (1 + 3 * transform_depth) HOST entries, component-major, sub-band index minor;
  * bins[k] = counts * skip and n = sampled values * skip, skip = 1 << max (0, SCHRO_SUBBAND_SHIFT (position) - 1).  The
  * sub-band rectangles are schro_hip_codeblock_layout's with 1 x 1 codeblocks; sub-band 0 takes the DC-predict form when
  * params->num_refs == 0; a sub-band of no width or height gives an all-zero histogram.  overflow (may be NULL): as many
@@ -2230,6 +2327,23 @@ typedef struct {
 } SchroHipHistogram;            /* layout-identical to SchroHistogram */
 int schro_hipframe_subband_histograms (SchroHipFrame * iwt_frame, const SchroHipParams * params,
     SchroHipHistogram * hists, uint32_t * overflow /* may be NULL */);
+
+/* schro_encoder_choose_quantisers (schroquantiser.c:288-316) for the engines rdo_bit_allocation, rdo_lambda, rdo_cbr and
+ * constant_error with frame->iwt_frame on the device, SYNCHRONOUS: the histograms as above (is_intra and the DC form from
+ * params->num_refs == 0), schro_hip_quant_choose_batch on their device counts, and the SchroHipQuantChoice in `result`
+ * (HOST memory) on return: quant_index is frame->quant_indices, frame_lambda frame->frame_lambda; estimated_residual_bits
+ * is the truncating int sum of chosen_entropy (:785-798).  schro_hip_quant_choose_tables comes first.  Refusals: those of
+ * the two calls (the settings' after the histograms have run); waits for the selected queue whatever the stage setting. */
+typedef struct {
+  int is_noarith;               /* params->is_noarith */
+  int engine;                   /* SCHRO_HIP_QUANT_ENGINE_* */
+  double target;                /* the frame lambda, the bits, or the error */
+  double subband_weight[SCHRO_HIP_NOARITH_MAX_SUBBANDS];
+  double context_ratio[3][SCHRO_HIP_NOARITH_MAX_SUBBANDS];
+  double subband0_lambda_scale, chroma_lambda_scale, diagonal_lambda_scale;
+} SchroHipQuantChooseSettings;
+int schro_encoder_choose_quantisers_hip (SchroHipFrame * iwt_frame, const SchroHipParams * params,
+    const SchroHipQuantChooseSettings * settings, SchroHipQuantChoice * result);
 
 /* schro_gpuframe_convert (schrogpuframe.h:20) replacement for the conversions the decode path
  * performs: s16/s32 -> u8 (+128, clamp, crop), u8 -> u8 copy, planar -> packed (YUYV, UYVY,

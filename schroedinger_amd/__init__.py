@@ -282,6 +282,13 @@ def noarith_encode_check(pictures, bpp):
     check(_lib.load().schro_hip_noarith_encode_check(arr, len(pictures), bpp))
 
 
+def noarith_encode_chosen_check(pictures, chosen, clamped, bpp):
+    """The refusals of Context.noarith_encode_chosen_batch on the host, without a context."""
+    arr, keep = noarith_pictures(pictures)
+    ptrs = (C.c_void_p * max(len(chosen), 1))(*[getattr(c, "ptr", c) for c in chosen])
+    check(_lib.load().schro_hip_noarith_encode_chosen_check(arr, ptrs, len(pictures), bpp, getattr(clamped, "ptr", clamped)))
+
+
 def noarith_encode_bound(sizes, depth, horiz_codeblocks, vert_codeblocks, bpp):
     """schro_hip_noarith_encode_bound: the output capacity that always suffices for a picture whose components are
     sizes = [(width, height)] * 3 at the transform's size."""
@@ -417,6 +424,42 @@ def motion_decode_result(words):
             "section_bits": [int(x) for x in w[1 + 2 * n:1 + 3 * n]], "truncated": int(w[1 + 3 * n]), "overran": int(w[2 + 3 * n]),
             "not_consumed": int(w[3 + 3 * n]), "long_codes": int(w[4 + 3 * n]), "unverified": int(w[5 + 3 * n]),
             "first_unverified": int(w[6 + 3 * n:7 + 3 * n].view(np.int32)[0])}
+
+
+# SchroHipQuantChoice (include/schro_hip.h) as a numpy record
+QUANT_CHOICE_DTYPE = np.dtype([("frame_lambda", "<f8"), ("sum", "<f8"), ("chosen_entropy", "<f8", (3, _lib.QUANT_CHOOSE_BANDS)),
+                               ("chosen_error", "<f8", (3, _lib.QUANT_CHOOSE_BANDS)), ("quant_index", "<i4", (3, _lib.QUANT_CHOOSE_BANDS)),
+                               ("evaluations", "<i4"), ("not_bracketed", "<i4"), ("reserved", "<i4")])
+QUANT_ENGINE_LAMBDA, QUANT_ENGINE_BIT_ALLOCATION, QUANT_ENGINE_CONSTANT_ERROR = 0, 1, 2
+
+
+def quant_choose_pictures(pictures):
+    """The SchroHipQuantChoosePicture array of a list of dicts: counts (three device arrays of SchroHipHistogramCounts:
+    anything with ptr, or an address), skip (per sub-band), depth, is_intra, is_noarith, engine, weight (per sub-band),
+    ratio ([3][sub-bands]), scales (sub-band 0, chroma, diagonal), target, result and optionally est_entropy, est_error
+    (device memory, as counts)."""
+    arr = (_lib.QuantChoosePicture * len(pictures))()
+    addr = lambda m: None if m is None else getattr(m, "ptr", m)
+    for a, p in zip(arr, pictures):
+        for c in range(3):
+            a.counts[c] = addr(p["counts"][c])
+        for i, s in enumerate(p["skip"]):
+            a.skip[i] = int(s)
+        a.transform_depth, a.is_intra, a.is_noarith, a.engine = int(p["depth"]), int(p["is_intra"]), int(p["is_noarith"]), int(p["engine"])
+        for i, w in enumerate(list(p["weight"])[:_lib.QUANT_CHOOSE_BANDS]):
+            a.subband_weight[i] = float(w)
+        for c in range(3):
+            for i, r in enumerate(list(p["ratio"][c])[:_lib.QUANT_CHOOSE_BANDS]):
+                a.context_ratio[c][i] = float(r)
+        a.subband0_lambda_scale, a.chroma_lambda_scale, a.diagonal_lambda_scale = (float(s) for s in p["scales"])
+        a.target = float(p["target"])
+        a.result, a.est_entropy, a.est_error = addr(p["result"]), addr(p.get("est_entropy")), addr(p.get("est_error"))
+    return arr
+
+
+def quant_choose_check(pictures, have_bit_tables=True):
+    """The refusals of Context.quant_choose_batch on the host, without a context (schro_hip_quant_choose_check)."""
+    check(_lib.load().schro_hip_quant_choose_check(quant_choose_pictures(pictures), len(pictures), 1 if have_bit_tables else 0))
 
 
 QUANTISE_DC_THREADS = 256      # SCHRO_HIP_QUANTISE_DC_THREADS (include/schro_hip.h): the DC recurrence's workgroup size
@@ -1271,6 +1314,20 @@ class Context:
         Mirrors schro_encoder_encode_transform_data for is_noarith without its quantiser call.  Where the buffers are the
         call's own -- `capacity` bytes each, or noarith_encode_bound -- waits and returns per picture (bytes uint8 array
         cut at the capacity, noarith_result dict); with caller-owned buffers the call is asynchronous and returns None."""
+        return self._noarith_encode(pictures, capacity, lambda arr, n, bpp: self.lib.schro_hip_noarith_encode_batch(self.h, arr, n, bpp))
+
+    def noarith_encode_chosen_batch(self, pictures, chosen, clamped, capacity=None):
+        """schro_hip_noarith_encode_chosen_batch: noarith_encode_batch with the quant indices taken from device memory.
+        The records' quant_index holds their sub-band; chosen: per picture the device address of its 3 x 19 int32 chosen
+        indices (SchroHipQuantChoice.quant_index: anything with ptr, or an address); clamped: a device word the caller has
+        cleared (anything with ptr, or an address), added to for every sub-band whose index lay outside 0 .. 60."""
+        addr = lambda m: getattr(m, "ptr", m)
+        ptrs = (C.c_void_p * len(chosen))(*[addr(c) for c in chosen])
+        assert len(chosen) == len(pictures)
+        return self._noarith_encode(pictures, capacity, lambda arr, n, bpp: self.lib.schro_hip_noarith_encode_chosen_batch(
+            self.h, arr, ptrs, n, bpp, addr(clamped)))
+
+    def _noarith_encode(self, pictures, capacity, call):
         bpp = pictures[0][0][0].dtype.itemsize
         own, full = [], []
         words = C.sizeof(_lib.NoarithResult) // 4
@@ -1286,7 +1343,7 @@ class Context:
             full.append((planes, tables, depth, hc, vc, mode, out, cap, res))
         try:
             arr, keep = noarith_pictures(full)
-            check(self.lib.schro_hip_noarith_encode_batch(self.h, arr, len(full), bpp))
+            check(call(arr, len(full), bpp))
             if not own:
                 return None
             got = []
@@ -1550,6 +1607,9 @@ class Context:
         quant_index) --, is_intra[, (dc_predict_first, dc_width, dc_height)]).  The coefficient planes receive the
         reconstruction, the quant planes the quantised values.  Returns one DevicePlane per component holding its
         SchroHipCodeblockSummary entries (download (): an (ncodeblocks, 2) uint32 array of nonzero, max_abs)."""
+        return self._quantise(jobs, lambda arr, n, bpp: self.lib.schro_hip_quantise_batch(self.h, arr, n, bpp))
+
+    def _quantise(self, jobs, call):
         n = len(jobs)
         arr = (_lib.QuantPlane * n)()
         keep, summaries = [], []
@@ -1565,8 +1625,19 @@ class Context:
             a.codeblocks, a.ncodeblocks, a.is_intra = tab, len(tab), 1 if intra else 0
             a.dc_predict_first, a.dc_width, a.dc_height = dc
             a.summary = summ.ptr
-        check(self.lib.schro_hip_quantise_batch(self.h, arr, n, jobs[0][0].dtype.itemsize))
+        check(call(arr, n, jobs[0][0].dtype.itemsize))
         return summaries
+
+    def quantise_chosen_batch(self, jobs, chosen, clamped):
+        """schro_hip_quantise_chosen_batch: quantise_batch with the quant indices taken from device memory.  jobs: as
+        quantise_batch takes them, the records' quant_index holding their sub-band; chosen: per job the device address of
+        its component's row of 19 int32 chosen indices (SchroHipQuantChoice.quant_index[component]: anything with ptr, or
+        an address); clamped: a device word the caller has cleared, added to for every record whose index lay outside
+        0 .. 60.  Enqueued, not waited for.  Returns the summaries as quantise_batch does."""
+        addr = lambda m: getattr(m, "ptr", m)
+        assert len(chosen) == len(jobs)
+        ptrs = (C.c_void_p * len(chosen))(*[addr(c) for c in chosen])
+        return self._quantise(jobs, lambda arr, n, bpp: self.lib.schro_hip_quantise_chosen_batch(self.h, arr, ptrs, n, bpp, addr(clamped)))
 
     def histogram_planes(self, jobs):
         """The C table of a schro_hip_histogram_batch call and its device counts.  jobs: per component (coeffs DevicePlane
@@ -1607,6 +1678,51 @@ class Context:
         check(self.lib.schro_hipframe_subband_histograms(iwt_frame.ptr(), C.byref(params), hists, ovf))
         return (np.array([h.n for h in hists], np.int64), np.array([list(h.bins) for h in hists], np.float64).reshape(nh, -1),
                 np.array(list(ovf), np.uint32))
+
+    def quant_choose_tables(self, error, onebits=None, zerobits=None):
+        """schro_hip_quant_choose_tables: the encoder's error table (60 x 104 doubles) and, for pictures that are not
+        noarith, its one-bits / zero-bits tables, into the context's device memory.  Replaces earlier ones."""
+        tabs = [None if t is None else np.ascontiguousarray(t, np.float64) for t in (error, onebits, zerobits)]
+        for t in tabs:
+            assert t is None or t.shape == (_lib.QUANT_CHOOSE_INDICES, _lib.HISTOGRAM_BINS), t.shape
+        dp = C.POINTER(C.c_double)
+        check(self.lib.schro_hip_quant_choose_tables(self.h, *[None if t is None else t.ctypes.data_as(dp) for t in tabs]))
+
+    def quant_choose_batch(self, pictures, estimates=False):
+        """schro_hip_quant_choose_batch over `pictures` (quant_choose_pictures' dicts; `result` may be left out: one
+        DevicePlane of QUANT_CHOICE_DTYPE rows is made for the call).  Enqueued, not waited for.  Returns the results'
+        DevicePlane (download ().view (QUANT_CHOICE_DTYPE): a row per picture; row p's quant_index starts
+        QUANT_CHOICE_DTYPE.fields["quant_index"][1] bytes into it) and, with estimates=True, a DevicePlane of
+        2 x len (pictures) rows of 3 x 19 x 60 doubles: est_entropy, then est_error, per picture."""
+        n = len(pictures)
+        size = QUANT_CHOICE_DTYPE.itemsize
+        res = DevicePlane(self, n, size, np.uint8, stride=size)
+        est = DevicePlane(self, 2 * n, 3 * _lib.QUANT_CHOOSE_BANDS * _lib.QUANT_CHOOSE_INDICES, np.float64) if estimates else None
+        full = []
+        for k, p in enumerate(pictures):
+            p = dict(p)
+            p.setdefault("result", res.ptr + k * size)
+            if est is not None:
+                p["est_entropy"], p["est_error"] = est.ptr + 2 * k * est.stride, est.ptr + (2 * k + 1) * est.stride
+            full.append(p)
+        check(self.lib.schro_hip_quant_choose_batch(self.h, quant_choose_pictures(full), n))
+        return (res, est) if estimates else res
+
+    def choose_quantisers(self, iwt_frame, params, is_noarith, engine, target, weight, ratio, scales):
+        """schro_encoder_choose_quantisers_hip on a device frame (frames.DeviceFrame / PlaneFrame): the histograms, the
+        choice, and the SchroHipQuantChoice on the host -- a QUANT_CHOICE_DTYPE record.  Waits.  weight: per sub-band;
+        ratio: [3][sub-bands]; scales: (sub-band 0, chroma, diagonal)."""
+        s = _lib.QuantChooseSettings()
+        s.is_noarith, s.engine, s.target = int(is_noarith), int(engine), float(target)
+        for i, w in enumerate(list(weight)[:_lib.QUANT_CHOOSE_BANDS]):
+            s.subband_weight[i] = float(w)
+        for c in range(3):
+            for i, r in enumerate(list(ratio[c])[:_lib.QUANT_CHOOSE_BANDS]):
+                s.context_ratio[c][i] = float(r)
+        s.subband0_lambda_scale, s.chroma_lambda_scale, s.diagonal_lambda_scale = (float(v) for v in scales)
+        out = np.zeros(1, QUANT_CHOICE_DTYPE)
+        check(self.lib.schro_encoder_choose_quantisers_hip(iwt_frame.ptr(), C.byref(params), C.byref(s), out.ctypes.data_as(C.c_void_p)))
+        return out[0]
 
     def upsample_batch(self, pairs):
         """pairs: [(src u8 plane h x w, dst HpPlane)] or [((src U, src V), dst pair HpPlane)]."""

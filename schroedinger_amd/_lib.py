@@ -64,6 +64,9 @@ EXPORTED_SYMBOLS = [
     "schro_hip_decode_motion_data_noarith",
     "schro_hip_dequant_batch", "schro_hip_quantise_batch", "schro_hip_subtract_batch", "schro_hipframe_subtract",
     "schro_hipframe_quantise", "schro_hip_histogram_batch", "schro_hipframe_subband_histograms",
+    "schro_hip_quant_choose_tables", "schro_hip_quant_choose_batch", "schro_hip_quant_choose_check",
+    "schro_hip_quantise_chosen_batch", "schro_hip_noarith_encode_chosen_batch", "schro_hip_noarith_encode_chosen_check",
+    "schro_encoder_choose_quantisers_hip",
     "schro_hip_decode_lowdelay_transform_data", "schro_hipframe_dequantise",
     "schro_hip_obmc_batch", "schro_hip_obmc_prediction_epoch", "schro_hip_obmc_overflowed",
     "schro_hip_frame_new_and_alloc", "schro_hip_frame_ref", "schro_hip_frame_unref",
@@ -340,6 +343,35 @@ class HistogramPlane(C.Structure):
 class Histogram(C.Structure):
     """SchroHipHistogram: layout-identical to the reference's SchroHistogram."""
     _fields_ = [("n", C.c_int), ("bins", C.c_double * HISTOGRAM_BINS)]
+
+
+QUANT_CHOOSE_INDICES = 60      # SCHRO_HIP_QUANT_CHOOSE_INDICES
+QUANT_CHOOSE_BANDS = 19        # SCHRO_HIP_NOARITH_MAX_SUBBANDS
+QUANT_ENGINE_LAMBDA, QUANT_ENGINE_BIT_ALLOCATION, QUANT_ENGINE_CONSTANT_ERROR = 0, 1, 2
+
+
+class QuantChoice(C.Structure):
+    """SchroHipQuantChoice (include/schro_hip.h): what schro_hip_quant_choose_batch leaves per picture, on the device."""
+    _fields_ = [("frame_lambda", C.c_double), ("sum", C.c_double),
+                ("chosen_entropy", C.c_double * QUANT_CHOOSE_BANDS * 3), ("chosen_error", C.c_double * QUANT_CHOOSE_BANDS * 3),
+                ("quant_index", C.c_int32 * QUANT_CHOOSE_BANDS * 3), ("evaluations", C.c_int32), ("not_bracketed", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+class QuantChoosePicture(C.Structure):
+    """SchroHipQuantChoosePicture (include/schro_hip.h): one picture of schro_hip_quant_choose_batch."""
+    _fields_ = [("counts", C.c_void_p * 3), ("skip", C.c_int * QUANT_CHOOSE_BANDS), ("transform_depth", C.c_int),
+                ("is_intra", C.c_int), ("is_noarith", C.c_int), ("engine", C.c_int),
+                ("subband_weight", C.c_double * QUANT_CHOOSE_BANDS), ("context_ratio", C.c_double * QUANT_CHOOSE_BANDS * 3),
+                ("subband0_lambda_scale", C.c_double), ("chroma_lambda_scale", C.c_double), ("diagonal_lambda_scale", C.c_double),
+                ("target", C.c_double), ("result", C.c_void_p), ("est_entropy", C.c_void_p), ("est_error", C.c_void_p)]
+
+
+class QuantChooseSettings(C.Structure):
+    """SchroHipQuantChooseSettings (include/schro_hip.h): what schro_encoder_choose_quantisers_hip takes beside frame and params."""
+    _fields_ = [("is_noarith", C.c_int), ("engine", C.c_int), ("target", C.c_double),
+                ("subband_weight", C.c_double * QUANT_CHOOSE_BANDS), ("context_ratio", C.c_double * QUANT_CHOOSE_BANDS * 3),
+                ("subband0_lambda_scale", C.c_double), ("chroma_lambda_scale", C.c_double), ("diagonal_lambda_scale", C.c_double)]
 
 
 class QuantisedPicture(C.Structure):
@@ -745,6 +777,21 @@ def load():
     L.schro_hip_histogram_batch.restype = i
     L.schro_hipframe_subband_histograms.argtypes = [C.POINTER(Frame), C.POINTER(Params), C.POINTER(Histogram), C.POINTER(C.c_uint32)]
     L.schro_hipframe_subband_histograms.restype = i
+    dp = C.POINTER(C.c_double)
+    L.schro_hip_quant_choose_tables.argtypes = [vp, dp, dp, dp]
+    L.schro_hip_quant_choose_tables.restype = i
+    L.schro_hip_quant_choose_batch.argtypes = [vp, C.POINTER(QuantChoosePicture), i]
+    L.schro_hip_quant_choose_batch.restype = i
+    L.schro_hip_quant_choose_check.argtypes = [C.POINTER(QuantChoosePicture), i, i]
+    L.schro_hip_quant_choose_check.restype = i
+    L.schro_hip_quantise_chosen_batch.argtypes = [vp, C.POINTER(QuantPlane), C.POINTER(C.c_void_p), i, i, vp]
+    L.schro_hip_quantise_chosen_batch.restype = i
+    L.schro_hip_noarith_encode_chosen_batch.argtypes = [vp, C.POINTER(NoarithPicture), C.POINTER(C.c_void_p), i, i, vp]
+    L.schro_hip_noarith_encode_chosen_batch.restype = i
+    L.schro_hip_noarith_encode_chosen_check.argtypes = [C.POINTER(NoarithPicture), C.POINTER(C.c_void_p), i, i, vp]
+    L.schro_hip_noarith_encode_chosen_check.restype = i
+    L.schro_encoder_choose_quantisers_hip.argtypes = [C.POINTER(Frame), C.POINTER(Params), C.POINTER(QuantChooseSettings), vp]
+    L.schro_encoder_choose_quantisers_hip.restype = i
     L.schro_hip_upsampled_bytes.argtypes = [i, i, C.POINTER(C.c_int)]
     L.schro_hip_upsampled_bytes.restype = C.c_size_t
     L.schro_hip_upsampled_download.argtypes = [vp, vp, i, vp, i, i, i]

@@ -690,6 +690,7 @@ schro_hip_context_free (SchroHipContext * ctx)
   }
   frame_quant_table_free (ctx);
   frame_hist_table_free (ctx);
+  quant_choose_tables_free (ctx);
   for (auto & s : ctx->slots)
     (void) hipFree (s.ptr);
   if (ctx->dc_gave_up)

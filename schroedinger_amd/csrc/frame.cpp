@@ -1500,6 +1500,55 @@ schro_hipframe_subband_histograms (SchroHipFrame * iwt_frame, const SchroHipPara
   return stage_done (ctx, 0);
 }
 
+// schro_encoder_choose_quantisers for the four rate-controlled engines, synchronous: the histograms as above (their counts
+// stay on the device, in the context's table for the selected queue), schro_hip_quant_choose_batch on them, the record on
+// the host.  It sizes nothing itself but the device record, one per queue, the context's.
+int
+schro_encoder_choose_quantisers_hip (SchroHipFrame * iwt_frame, const SchroHipParams * params, const SchroHipQuantChooseSettings * settings,
+    SchroHipQuantChoice * result)
+{
+  SCHRO_HIP_REQUIRE (iwt_frame && params && settings && result && frame_ctx (iwt_frame),
+      "encoder_choose_quantisers_hip: needs a device frame, the parameters, the settings and the result");
+  SchroHipContext *ctx = frame_ctx (iwt_frame);
+  SCHRO_HIP_REQUIRE (ctx->qc_tables, "encoder_choose_quantisers_hip: no tables (schro_hip_quant_choose_tables comes first)");
+  const int depth = params->transform_depth;
+  SCHRO_HIP_REQUIRE (depth >= 0 && depth <= 6, "encoder_choose_quantisers_hip: transform_depth %d", depth);
+  const int nb = 1 + 3 * depth;
+  SchroHipQuantChoosePicture pic;
+  memset (&pic, 0, sizeof (pic));
+  pic.transform_depth = depth;
+  pic.is_intra = params->num_refs == 0;
+  pic.is_noarith = settings->is_noarith;
+  pic.engine = settings->engine;
+  memcpy (pic.subband_weight, settings->subband_weight, sizeof (pic.subband_weight));
+  memcpy (pic.context_ratio, settings->context_ratio, sizeof (pic.context_ratio));
+  pic.subband0_lambda_scale = settings->subband0_lambda_scale;
+  pic.chroma_lambda_scale = settings->chroma_lambda_scale;
+  pic.diagonal_lambda_scale = settings->diagonal_lambda_scale;
+  pic.target = settings->target;
+  (void) hipSetDevice (ctx->device);
+  if (!ctx->qc_frame_choice)
+    SCHRO_HIP_CHECK (hipMalloc ((void **) &ctx->qc_frame_choice, SchroHipContext::kQueues * sizeof (SchroHipQuantChoice)));
+  // (the settings are the choice call's to refuse: a refusal comes after the histograms have run, before the choice is launched)
+  std::vector < SchroHipHistogram > hists ((size_t) 3 * nb);
+  int r = schro_hipframe_subband_histograms (iwt_frame, params, hists.data (), nullptr);
+  if (r)
+    return r;
+  const FrameHistTable *t = ctx->frame_h_table;
+  const SchroHipHistogramCounts *d_counts = t->d_counts + (size_t) ctx->cur * t->total;
+  for (int k = 0; k < 3; k++)
+    pic.counts[k] = d_counts + (size_t) k * nb;
+  for (int i = 0; i < nb; i++)
+    pic.skip[i] = t->bands[0][i].skip;
+  pic.result = ctx->qc_frame_choice + ctx->cur;
+  r = schro_hip_quant_choose_batch (ctx, &pic, 1);
+  if (r)
+    return r;
+  SCHRO_HIP_CHECK (hipMemcpyAsync (result, pic.result, sizeof (SchroHipQuantChoice), hipMemcpyDeviceToHost, ctx->stream));
+  SCHRO_HIP_CHECK (hipStreamSynchronize (ctx->stream));
+  return stage_done (ctx, 0);
+}
+
 int
 schro_hipframe_shift_right (SchroHipFrame * frame, int shift)
 {

@@ -403,7 +403,32 @@ void na_pack_kernel (const NaSubband * __restrict__ sbs, const NaPicture * __res
   }
 }
 
+// schro_hip_noarith_encode_chosen_batch: the quant index of every sub-band's header from the picture's chosen indices on
+// the device ([3][19] int32); a value outside 0 .. 60 is clamped into range and counted
+__global__ __launch_bounds__ (64)
+void na_resolve_kernel (NaSubband * __restrict__ sbs, int nsbs, const int *__restrict__ sb_pic, const int32_t * const *__restrict__ chosen,
+    uint32_t * clamped)
+{
+  const int t = blockIdx.x * 64 + threadIdx.x;
+  if (t >= nsbs)
+    return;
+  const int32_t q = chosen[sb_pic[t]][sbs[t].comp * SCHRO_HIP_NOARITH_MAX_SUBBANDS + sbs[t].index];
+  if (q < 0 || q > 60)
+    __hip_atomic_fetch_add (clamped, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  sbs[t].quant_index = q < 0 ? 0 : (q > 60 ? 60 : q);
+}
+
 }                               // namespace
+
+int
+launch_noarith_resolve (hipStream_t stream, NaSubband * d_sbs, int nsbs, const int *d_sb_pic, const int32_t * const *d_chosen, uint32_t * clamped)
+{
+  SCHRO_LAUNCH (na_resolve_kernel, dim3 (div_up (nsbs, 64)), dim3 (64), 0, stream, d_sbs, nsbs, d_sb_pic, d_chosen, clamped);
+  hipError_t e = hipGetLastError ();
+  if (e != hipSuccess)
+    return set_error (SCHRO_HIP_EDEVICE, "noarith resolve launch: %s", hipGetErrorString (e));
+  return 0;
+}
 
 int
 launch_noarith_encode (hipStream_t stream, const NaSubband * d_sbs, int nsbs, const NaPicture * d_pics, int npics,

@@ -72,8 +72,19 @@ struct NaPlan {
 };
 
 int
-na_build (const char *who, const SchroHipNoarithPicture * pictures, int npictures, int bpp, NaPlan & plan)
+na_build (const char *who, const SchroHipNoarithPicture * pictures, int npictures, int bpp, NaPlan & plan,
+    const int32_t * const *chosen = nullptr, const uint32_t * clamped = nullptr, bool chosen_form = false)
 {
+  // the chosen form (schro_hip_noarith_encode_chosen_batch): a record's quant_index is its SUB-BAND, the index written
+  // into the sub-band's header comes from chosen[picture][component][sub-band] on the device -- one per sub-band, so the
+  // records of a sub-band cannot disagree; the sub-band records are completed by a resolve launch
+  if (chosen_form) {
+    SCHRO_HIP_REQUIRE (chosen && clamped && (uintptr_t) clamped % sizeof (uint32_t) == 0, "%s: chosen is NULL, or clamped is NULL or not "
+        "4-byte aligned", who);
+    for (int p = 0; pictures && p < npictures; p++)
+      SCHRO_HIP_REQUIRE (chosen[p] && (uintptr_t) chosen[p] % sizeof (int32_t) == 0, "%s: picture %d: chosen is NULL or not 4-byte aligned",
+          who, p);
+  }
   SCHRO_HIP_REQUIRE (pictures && npictures > 0 && npictures <= kMaxJobs, "%s: bad arguments", who);
   SCHRO_HIP_REQUIRE (bpp == 2 || bpp == 4, "%s: bytes_per_sample must be 2 or 4", who);
   for (int p = 0; p < npictures; p++) {
@@ -133,6 +144,11 @@ na_build (const char *who, const SchroHipNoarithPicture * pictures, int npicture
                 "%s: picture %d, component %d, sub-band %d, record %d (%d x %d at byte %d, pitch %d) is not schro_hip_codeblock_layout's "
                 "(%d x %d at byte %d, pitch %d)", who, p, k, i, n, cb.width, cb.height, cb.dst_offset, cb.dst_stride, xmax - xmin,
                 ymax - ymin, base + ymin * bstride + xmin * bpp, bstride);
+            if (chosen_form) {
+              SCHRO_HIP_REQUIRE (cb.quant_index == i, "%s: picture %d, component %d, sub-band %d, record %d: quant_index %d is not the "
+                  "sub-band", who, p, k, i, n, cb.quant_index);
+              continue;
+            }
             SCHRO_HIP_REQUIRE (cb.quant_index <= 60, "%s: picture %d, component %d, sub-band %d, record %d: quant_index %d", who, p, k, i,
                 n, cb.quant_index);
             // the quant offset written is always 0 (schroencoder.c:4148-4150): unlike indices would decode wrongly
@@ -153,7 +169,7 @@ na_build (const char *who, const SchroHipNoarithPicture * pictures, int npicture
         s.row_base = rows;
         const bool many = b.hc > 1 || b.vc > 1;
         s.flags = (many && i > 0 ? 1 : 0) | (many && pic.codeblock_mode_index == 1 ? 2 : 0);
-        s.quant_index = qi;
+        s.quant_index = chosen_form ? 0 : qi;
         s.comp = k;
         s.index = i;
         plan.sbs.push_back (s);
@@ -198,13 +214,15 @@ schro_hip_noarith_encode_check (const SchroHipNoarithPicture * pictures, int npi
   return na_build ("noarith_encode_batch", pictures, npictures, bytes_per_sample, plan);
 }
 
-int
-schro_hip_noarith_encode_batch (SchroHipContext * ctx, const SchroHipNoarithPicture * pictures, int npictures, int bytes_per_sample)
+}                               // extern "C"
+
+static int
+na_encode_run (const char *who, SchroHipContext * ctx, const SchroHipNoarithPicture * pictures, int npictures, int bytes_per_sample,
+    const int32_t * const *chosen, uint32_t * clamped, bool chosen_form)
 {
-  const char *who = "noarith_encode_batch";
   SCHRO_HIP_REQUIRE (ctx, "%s: bad arguments", who);
   NaPlan plan;
-  int r = na_build (who, pictures, npictures, bytes_per_sample, plan);
+  int r = na_build (who, pictures, npictures, bytes_per_sample, plan, chosen, clamped, chosen_form);
   if (r)
     return r;
   (void) hipSetDevice (ctx->device);
@@ -230,7 +248,8 @@ schro_hip_noarith_encode_batch (SchroHipContext * ctx, const SchroHipNoarithPict
 
   // one table: the sub-bands, the pictures, the picture of every sub-band
   const size_t sb_bytes = ns * sizeof (NaSubband), pic_bytes = plan.pics.size () * sizeof (NaPicture);
-  const size_t bytes = sb_bytes + pic_bytes + ns * sizeof (int);
+  const size_t index_bytes = round_up (ns * sizeof (int), sizeof (void *));
+  const size_t bytes = sb_bytes + pic_bytes + index_bytes + (chosen_form ? (size_t) npictures * sizeof (void *) : 0);
   void *host, *dev;
   r = big_table_begin (ctx, bytes, &host, &dev);
   if (r)
@@ -238,9 +257,17 @@ schro_hip_noarith_encode_batch (SchroHipContext * ctx, const SchroHipNoarithPict
   memcpy (host, plan.sbs.data (), sb_bytes);
   memcpy ((char *) host + sb_bytes, plan.pics.data (), pic_bytes);
   memcpy ((char *) host + sb_bytes + pic_bytes, plan.sb_pic.data (), ns * sizeof (int));
+  if (chosen_form)
+    memcpy ((char *) host + sb_bytes + pic_bytes + index_bytes, chosen, (size_t) npictures * sizeof (void *));
   r = big_table_commit (ctx, bytes);
   if (r)
     return r;
+  if (chosen_form) {
+    r = launch_noarith_resolve (ctx->stream, (NaSubband *) dev, (int) ns, (const int *) ((const char *) dev + sb_bytes + pic_bytes),
+        (const int32_t * const *) ((const char *) dev + sb_bytes + pic_bytes + index_bytes), clamped);
+    if (r)
+      return r;
+  }
   // (A/B runs, scripts/noarith_encode_ab.py: one launch at a time on the tables the call before left)
   const char *env = SCHRO_ENV ("SCHRO_HIP_NAENC_STAGES");
   const int stages = env && atoi (env) > 0 ? atoi (env) & 7 : 7;
@@ -249,6 +276,29 @@ schro_hip_noarith_encode_batch (SchroHipContext * ctx, const SchroHipNoarithPict
       SCHRO_HIP_CHECK (hipMemsetAsync (pictures[p].result, 0, sizeof (SchroHipNoarithResult), ctx->stream));
   return launch_noarith_encode (ctx->stream, (const NaSubband *) dev, (int) ns, (const NaPicture *) ((const char *) dev + sb_bytes),
       npictures, S, bytes_per_sample, plan.grid_x, plan.clear_x, stages);
+}
+
+extern "C" {
+
+int
+schro_hip_noarith_encode_batch (SchroHipContext * ctx, const SchroHipNoarithPicture * pictures, int npictures, int bytes_per_sample)
+{
+  return na_encode_run ("noarith_encode_batch", ctx, pictures, npictures, bytes_per_sample, nullptr, nullptr, false);
+}
+
+int
+schro_hip_noarith_encode_chosen_batch (SchroHipContext * ctx, const SchroHipNoarithPicture * pictures, const int32_t * const *chosen,
+    int npictures, int bytes_per_sample, uint32_t * clamped)
+{
+  return na_encode_run ("noarith_encode_chosen_batch", ctx, pictures, npictures, bytes_per_sample, chosen, clamped, true);
+}
+
+int
+schro_hip_noarith_encode_chosen_check (const SchroHipNoarithPicture * pictures, const int32_t * const *chosen, int npictures,
+    int bytes_per_sample, const uint32_t * clamped)
+{
+  NaPlan plan;
+  return na_build ("noarith_encode_chosen_batch", pictures, npictures, bytes_per_sample, plan, chosen, clamped, true);
 }
 
 }                               // extern "C"

@@ -13,9 +13,19 @@ using namespace schro;
 namespace schro {
 
 int
-quantise_batch_run (SchroHipContext * ctx, const SchroHipQuantPlane * planes, int nplanes, int bpp, bool allow_empty)
+quantise_batch_run (SchroHipContext * ctx, const SchroHipQuantPlane * planes, int nplanes, int bpp, bool allow_empty,
+    const int32_t * const *chosen, uint32_t * clamped)
 {
   SCHRO_HIP_REQUIRE (ctx && planes && nplanes > 0, "quantise_batch: bad arguments");
+  // the chosen form (schro_hip_quantise_chosen_batch): a record's quant_index is its SUB-BAND, the index comes from
+  // chosen[plane][sub-band] on the device -- the constants are left to a resolve launch behind the table's upload
+  if (chosen) {
+    SCHRO_HIP_REQUIRE (clamped && (uintptr_t) clamped % sizeof (uint32_t) == 0, "quantise_chosen_batch: clamped is NULL or not 4-byte aligned");
+    for (int p = 0; p < nplanes; p++)
+      SCHRO_HIP_REQUIRE (chosen[p] && (uintptr_t) chosen[p] % sizeof (int32_t) == 0,
+          "quantise_chosen_batch: plane %d: chosen is NULL or not 4-byte aligned", p);
+  }
+  std::vector < QuantChosen > job_runs, dc_runs;
   SCHRO_HIP_REQUIRE (bpp == 2 || bpp == 4, "quantise_batch: bytes_per_sample must be 2 or 4");
   (void) hipSetDevice (ctx->device);
   int tw, th;
@@ -41,14 +51,18 @@ quantise_batch_run (SchroHipContext * ctx, const SchroHipQuantPlane * planes, in
           "quantise_batch: plane %d: a DC band of %d x %d (1 .. %d rows)", p, pl.dc_width, pl.dc_height, SCHRO_HIP_QUANTISE_DC_MAX_ROWS);
     long long dc_area = 0;
     int dc_stride = 0;
-    const size_t dc_rec_base = dc_recs.size ();
+    const size_t dc_rec_base = dc_recs.size (), job_base = jobs.size ();
     for (int c = 0; c < pl.ncodeblocks; c++) {
       const SchroHipCodeblock & cb = pl.codeblocks[c];
       SCHRO_HIP_REQUIRE (cb.width >= 0 && cb.height >= 0 && (allow_empty || (cb.width > 0 && cb.height > 0)),
           "quantise_batch: plane %d codeblock %d: %d x %d samples", p, c, cb.width, cb.height);
       if (cb.width == 0 || cb.height == 0)
         continue;
-      SCHRO_HIP_REQUIRE (cb.quant_index <= 60, "quantise_batch: plane %d codeblock %d: quant_index %d", p, c, cb.quant_index);
+      if (chosen)
+        SCHRO_HIP_REQUIRE (cb.quant_index < SCHRO_HIP_NOARITH_MAX_SUBBANDS,
+            "quantise_chosen_batch: plane %d codeblock %d: quant_index %d is no sub-band (0 .. 18)", p, c, cb.quant_index);
+      else
+        SCHRO_HIP_REQUIRE (cb.quant_index <= 60, "quantise_batch: plane %d codeblock %d: quant_index %d", p, c, cb.quant_index);
       SCHRO_HIP_REQUIRE (cb.dst_stride > 0 && cb.dst_stride % bpp == 0 && (long long) cb.dst_stride >= (long long) cb.width * bpp,
           "quantise_batch: plane %d codeblock %d: a stride of %d bytes for rows of %d samples of %d bytes", p, c, cb.dst_stride,
           cb.width, bpp);
@@ -79,6 +93,10 @@ quantise_batch_run (SchroHipContext * ctx, const SchroHipQuantPlane * planes, in
         r.offset = j.offset;
         r.index = c;
         r.pad = 0;
+        if (chosen) {
+          r.factor = r.offset = 0;
+          r.pad = cb.quant_index;
+        }
         dc_recs.push_back (r);
         dc_area += (long long) cb.width * cb.height;
         continue;
@@ -91,10 +109,21 @@ quantise_batch_run (SchroHipContext * ctx, const SchroHipQuantPlane * planes, in
       j.stride = cb.dst_stride;
       j.w = cb.width;
       j.h = cb.height;
-      quant_job_constants (&j, cb.quant_index, pl.is_intra, bpp);
+      if (chosen)
+        j.pad = cb.quant_index;
+      else
+        quant_job_constants (&j, cb.quant_index, pl.is_intra, bpp);
       j.tiles_x = div_up (cb.width, tw);
       total_tiles += (long long) j.tiles_x * div_up (cb.height, th);
       jobs.push_back (j);
+    }
+    if (chosen) {
+      const QuantChosen jr = { chosen[p], (int) job_base, (int) (jobs.size () - job_base), pl.is_intra, 0 };
+      const QuantChosen dr = { chosen[p], (int) dc_rec_base, (int) (dc_recs.size () - dc_rec_base), pl.is_intra, 0 };
+      if (jr.count)
+        job_runs.push_back (jr);
+      if (dr.count)
+        dc_runs.push_back (dr);
     }
     if (ndc > 0) {
       SCHRO_HIP_REQUIRE (dc_area == (long long) pl.dc_width * pl.dc_height,
@@ -124,6 +153,21 @@ quantise_batch_run (SchroHipContext * ctx, const SchroHipQuantPlane * planes, in
   // one launch per 2^18 codeblocks (find_dequant_job's three probes), the table behind the jobs as dequant_batch builds it
   const size_t kPerLaunch = (size_t) 1 << 18;
   std::vector < char >table;
+  const QuantChosen *d_job_runs = nullptr, *d_dc_runs = nullptr;
+  if (chosen) {
+    SCHRO_HIP_REQUIRE ((job_runs.size () + dc_runs.size ()) * sizeof (QuantChosen) <= SchroHipContext::kArgSlotBytes,
+        "quantise_chosen_batch: %d planes are too many for one call", nplanes);
+    std::vector < QuantChosen > runs (job_runs);
+    runs.insert (runs.end (), dc_runs.begin (), dc_runs.end ());
+    void *d_runs = nullptr;
+    if (!runs.empty ()) {
+      int r = push_args (ctx, runs.data (), runs.size () * sizeof (QuantChosen), &d_runs);
+      if (r)
+        return r;
+    }
+    d_job_runs = (const QuantChosen *) d_runs;
+    d_dc_runs = d_job_runs + job_runs.size ();
+  }
   for (size_t first = 0; first < jobs.size (); first += kPerLaunch) {
     const size_t n = std::min (kPerLaunch, jobs.size () - first), n64 = (n + 63) / 64, n4096 = (n + 4095) / 4096;
     long long tiles = 0;
@@ -147,6 +191,11 @@ quantise_batch_run (SchroHipContext * ctx, const SchroHipQuantPlane * planes, in
         : push_big_table (ctx, table.data (), bytes, &d_jobs);
     if (r)
       return r;
+    if (chosen) {
+      r = launch_quantise_resolve (ctx->stream, (QuantJob *) d_jobs, (int) n, (int) first, d_job_runs, (int) job_runs.size (), bpp, clamped);
+      if (r)
+        return r;
+    }
     ProfileScope ps (ctx, SCHRO_HIP_KERNEL_QUANTISE);
     r = launch_quantise (ctx->stream, (const QuantJob *) d_jobs, (int) n, (int) tiles, bpp);
     if (r)
@@ -163,6 +212,12 @@ quantise_batch_run (SchroHipContext * ctx, const SchroHipQuantPlane * planes, in
         : push_big_table (ctx, table.data (), bytes, &d_tab);
     if (r)
       return r;
+    if (chosen) {
+      r = launch_quantise_resolve_dc (ctx->stream, (QuantDcRec *) ((char *) d_tab + job_bytes), (int) dc_recs.size (), d_dc_runs,
+          (int) dc_runs.size (), clamped);
+      if (r)
+        return r;
+    }
     ProfileScope ps (ctx, SCHRO_HIP_KERNEL_QUANTISE_DC);
     return launch_quantise_dc (ctx->stream, (const QuantDcJob *) d_tab, (int) dc_jobs.size (),
         (const QuantDcRec *) ((const char *) d_tab + job_bytes), dc_max_rows, bpp);
@@ -193,7 +248,15 @@ extern "C" {
 int
 schro_hip_quantise_batch (SchroHipContext * ctx, const SchroHipQuantPlane * planes, int nplanes, int bytes_per_sample)
 {
-  return quantise_batch_run (ctx, planes, nplanes, bytes_per_sample, false);
+  return quantise_batch_run (ctx, planes, nplanes, bytes_per_sample, false, nullptr, nullptr);
+}
+
+int
+schro_hip_quantise_chosen_batch (SchroHipContext * ctx, const SchroHipQuantPlane * planes, const int32_t * const *chosen, int nplanes,
+    int bytes_per_sample, uint32_t * clamped)
+{
+  SCHRO_HIP_REQUIRE (chosen, "quantise_chosen_batch: chosen is NULL");
+  return quantise_batch_run (ctx, planes, nplanes, bytes_per_sample, false, chosen, clamped);
 }
 
 }                               // extern "C"

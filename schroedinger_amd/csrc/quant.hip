@@ -59,6 +59,37 @@ make_quant_tables4 ()
   return t;
 }
 constexpr QuantTables4 kQuantTab = make_quant_tables4 ();
+static __device__ const QuantTables4 kDevQuantTab = make_quant_tables4 ();      // (the resolve launch looks the quantiser up)
+
+// form, factor, both offsets, shift and inverse of a codeblock, as schro_frame_data_quantise sets them up
+// (schroencoder.c:3492-3504, :3543-3544); s32 and the DC band: schro_quantise's offset - factor / 2
+__host__ __device__ __forceinline__ void
+quant_constants (const QuantTables4 & tab, QuantJob * job, int quant_index, int is_intra, int bpp)
+{
+  const int q = quant_index < 0 ? 0 : (quant_index > 60 ? 60 : quant_index);
+  job->factor = tab.factor[q];
+  job->offset = is_intra ? tab.off12[q] : tab.off38[q];
+  job->inverse = tab.inverse[q];
+  job->shift = (q >> 2) + 2;
+  if (bpp == 4) {
+    job->form = kQuantDivide;
+    job->qoff = (int32_t) job->offset - (int32_t) (job->factor / 2);
+    return;
+  }
+  job->qoff = (int32_t) job->offset - (int32_t) (job->factor >> 1);
+  if (q == 0) {
+    job->form = kQuantCopy;
+  } else if ((q & 3) == 0) {
+    job->form = kQuantShift;
+  } else if (q == 3) {
+    job->form = kQuantRecip32;
+    job->shift += 16;
+  } else {
+    job->form = kQuantRecip16;
+    if (q > 8)
+      job->qoff--;
+  }
+}
 
 // schro_quantise / schro_dequantise (schroutils.c:179-235), C int arithmetic (wrapping where C's would overflow)
 __device__ __forceinline__ int32_t
@@ -326,7 +357,70 @@ void quantise_dc_kernel (const QuantDcJob * __restrict__ jobs, const QuantDcRec 
     summary_add (job.summary + rec.index, cnt, mx);
 }
 
+// schro_hip_quantise_chosen_batch: the constants the host would have put into the records, from quant indices that are
+// on the device.  A record's `pad` holds its sub-band; the run it lies in names its plane's row of chosen indices.  A value
+// outside 0 .. 60 is clamped into range and counted.
+__device__ __forceinline__ int
+chosen_index (const QuantChosen * __restrict__ runs, int nruns, int t, int subband, uint32_t * clamped, int *is_intra)
+{
+  int r = 0;
+  while (r + 1 < nruns && t >= runs[r].first + runs[r].count)
+    r++;
+  *is_intra = runs[r].is_intra;
+  const int32_t q = runs[r].chosen[subband];
+  if (q < 0 || q > 60)
+    __hip_atomic_fetch_add (clamped, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return q < 0 ? 0 : (q > 60 ? 60 : q);
+}
+
+__global__ __launch_bounds__ (256)
+void quantise_resolve_kernel (QuantJob * __restrict__ jobs, int njobs, int first, const QuantChosen * __restrict__ runs, int nruns, int bpp,
+    uint32_t * clamped)
+{
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= njobs)
+    return;
+  int is_intra;
+  const int q = chosen_index (runs, nruns, first + t, jobs[t].pad, clamped, &is_intra);
+  quant_constants (kDevQuantTab, jobs + t, q, is_intra, bpp);
+}
+
+__global__ __launch_bounds__ (256)
+void quantise_resolve_dc_kernel (QuantDcRec * __restrict__ recs, int nrecs, const QuantChosen * __restrict__ runs, int nruns, uint32_t * clamped)
+{
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= nrecs)
+    return;
+  int is_intra;
+  const int q = chosen_index (runs, nruns, t, recs[t].pad, clamped, &is_intra);
+  QuantJob j;
+  quant_constants (kDevQuantTab, &j, q, is_intra, 4);   // (C schro_quantise at both depths)
+  recs[t].factor = j.factor;
+  recs[t].offset = j.offset;
+}
+
 }                               // namespace
+
+int
+launch_quantise_resolve (hipStream_t stream, QuantJob * d_jobs, int njobs, int first, const QuantChosen * d_runs, int nruns, int bpp,
+    uint32_t * clamped)
+{
+  SCHRO_LAUNCH (quantise_resolve_kernel, dim3 (div_up (njobs, 256)), dim3 (256), 0, stream, d_jobs, njobs, first, d_runs, nruns, bpp, clamped);
+  hipError_t e = hipGetLastError ();
+  if (e != hipSuccess)
+    return set_error (SCHRO_HIP_EDEVICE, "quantise resolve launch: %s", hipGetErrorString (e));
+  return 0;
+}
+
+int
+launch_quantise_resolve_dc (hipStream_t stream, QuantDcRec * d_recs, int nrecs, const QuantChosen * d_runs, int nruns, uint32_t * clamped)
+{
+  SCHRO_LAUNCH (quantise_resolve_dc_kernel, dim3 (div_up (nrecs, 256)), dim3 (256), 0, stream, d_recs, nrecs, d_runs, nruns, clamped);
+  hipError_t e = hipGetLastError ();
+  if (e != hipSuccess)
+    return set_error (SCHRO_HIP_EDEVICE, "quantise resolve (DC) launch: %s", hipGetErrorString (e));
+  return 0;
+}
 
 void
 quant_tile_geometry (int *tw, int *th)
@@ -335,34 +429,10 @@ quant_tile_geometry (int *tw, int *th)
   *th = kQTH;
 }
 
-// form, factor, both offsets, shift and inverse of a codeblock, as schro_frame_data_quantise sets them up
-// (schroencoder.c:3492-3504, :3543-3544); s32 and the DC band: schro_quantise's offset - factor / 2
 void
 quant_job_constants (QuantJob * job, int quant_index, int is_intra, int bpp)
 {
-  const int q = quant_index < 0 ? 0 : (quant_index > 60 ? 60 : quant_index);
-  job->factor = kQuantTab.factor[q];
-  job->offset = is_intra ? kQuantTab.off12[q] : kQuantTab.off38[q];
-  job->inverse = kQuantTab.inverse[q];
-  job->shift = (q >> 2) + 2;
-  if (bpp == 4) {
-    job->form = kQuantDivide;
-    job->qoff = (int32_t) job->offset - (int32_t) (job->factor / 2);
-    return;
-  }
-  job->qoff = (int32_t) job->offset - (int32_t) (job->factor >> 1);
-  if (q == 0) {
-    job->form = kQuantCopy;
-  } else if ((q & 3) == 0) {
-    job->form = kQuantShift;
-  } else if (q == 3) {
-    job->form = kQuantRecip32;
-    job->shift += 16;
-  } else {
-    job->form = kQuantRecip16;
-    if (q > 8)
-      job->qoff--;
-  }
+  quant_constants (kQuantTab, job, quant_index, is_intra, bpp);
 }
 
 int

@@ -856,6 +856,17 @@ void quant_tile_geometry (int *tw, int *th);
 void quant_job_constants (QuantJob * job, int quant_index, int is_intra, int bpp);
 int launch_quantise (hipStream_t stream, const QuantJob * d_jobs, int njobs, int total_tiles, int bpp);
 int launch_quantise_dc (hipStream_t stream, const QuantDcJob * d_jobs, int njobs, const QuantDcRec * d_recs, int max_rows, int bpp);
+// schro_hip_quantise_chosen_batch: a run of a call's QuantJobs (or of its QuantDcRecs) that belong to one plane, and the
+// plane's row of chosen quant indices on the device; the records' `pad` holds their sub-band.  The resolve launches write
+// what quant_job_constants would have (jobs: table entries first .. of the call's jobs; recs: all of the call's)
+struct QuantChosen {
+  const int32_t *chosen;
+  int first, count;
+  int is_intra, pad;
+};
+int launch_quantise_resolve (hipStream_t stream, QuantJob * d_jobs, int njobs, int first, const QuantChosen * d_runs, int nruns, int bpp,
+    uint32_t * clamped);
+int launch_quantise_resolve_dc (hipStream_t stream, QuantDcRec * d_recs, int nrecs, const QuantChosen * d_runs, int nruns, uint32_t * clamped);
 // lowdelay_enc.hip; stages: 1 estimate, 2 choose, 4 pack
 int launch_lowdelay_encode (hipStream_t stream, const EncJob * d_jobs, int njobs, const SliceParams & P,
     const EncChooseLayout & L, int stages);
@@ -896,6 +907,9 @@ struct NaScratch {              // the selected queue's, per call
 // stages: 1 count, 2 layout, 4 clear + pack
 int launch_noarith_encode (hipStream_t stream, const NaSubband * d_sbs, int nsbs, const NaPicture * d_pics, int npics,
     const NaScratch & S, int bpp, int grid_x, int clear_x, int stages);
+// schro_hip_noarith_encode_chosen_batch: NaSubband::quant_index from d_chosen[picture][comp][index] (device, [3][19])
+int launch_noarith_resolve (hipStream_t stream, NaSubband * d_sbs, int nsbs, const int *d_sb_pic, const int32_t * const *d_chosen,
+    uint32_t * clamped);
 // noarith_dec.hip: the same syntax read back.  One sub-band of one component of one picture, from the host: where its
 // samples go and how it is cut into codeblocks (schro_hip_codeblock_layout's closed forms, as above).
 struct NdSubband {
@@ -1000,6 +1014,24 @@ md_picture_words (size_t data_bytes, uint64_t blocks)
 }
 // stages: 1 header, 2 summary, 4 scan, 8 extract, 16 split walk, 32 mode walk, 64 value walk
 int launch_motion_decode (hipStream_t stream, const MdPicture * d_pics, int npics, uint32_t * scratch, int lane_x, int stages);
+// quant_choose.hip: one picture of the quantiser choice.  Its estimates live in the call's scratch: picture p owns
+// 2 * kQcEstimates doubles from p * 2 * kQcEstimates on -- est_entropy [3][19][60], then est_error.
+constexpr int kQcBands = SCHRO_HIP_NOARITH_MAX_SUBBANDS, kQcIndices = SCHRO_HIP_QUANT_CHOOSE_INDICES;
+constexpr int kQcEstimates = 3 * kQcBands * kQcIndices;
+constexpr int kQcTableDoubles = SCHRO_HIP_HISTOGRAM_BINS * kQcIndices;  // one table, stored [104][60]
+struct QcPicture {
+  const uint32_t *counts[3];    // SchroHipHistogramCounts arrays: 105 words per sub-band
+  SchroHipQuantChoice *result;
+  double *est_entropy, *est_error;      // the caller's copies, or NULL
+  double weight[kQcBands];
+  double ratio[3][kQcBands];
+  double scale[3];              // sub-band 0, chroma, diagonal
+  double target;
+  int skip[kQcBands];
+  int depth, noarith, engine;
+};
+// tables: error, then (have_bits) onebits, zerobits, kQcTableDoubles each
+int launch_quant_choose (hipStream_t stream, const QcPicture * d_pics, int npics, const double *tables, int have_bits, double *scratch);
 // hist.hip
 void hist_tile_geometry (int *group_bytes, int *groups_per_tile, int *groups_per_step);
 int launch_histogram (hipStream_t stream, const HistJob * d_jobs, int njobs, int total_tiles, int bpp);
@@ -1197,6 +1229,11 @@ struct SchroHipContext {
   // ... and its histogram table (schro_hipframe_subband_histograms): the sub-band records of one picture geometry, the
   // device counts and their pinned host mirror
   struct schro::FrameHistTable *frame_h_table = nullptr;
+  // the tables of the quantiser choice (schro_hip_quant_choose_tables): error, onebits, zerobits, transposed
+  double *qc_tables = nullptr;
+  bool qc_have_bits = false;
+  // ... and the device records of its frame-layer call (schro_encoder_choose_quantisers_hip), one per queue
+  SchroHipQuantChoice *qc_frame_choice = nullptr;
 };
 
 namespace schro {
@@ -1281,7 +1318,8 @@ int mode_host_run (SchroHipContext * ctx, SchroHipModePicture * pic, void *motio
 bool is_wide_format (int format);
 // plane_quant.cpp: schro_hip_quantise_batch; allow_empty: records of no width or height are skipped (the frame layer's
 // layouts of tiny sub-bands have them), not refused
-int quantise_batch_run (SchroHipContext * ctx, const SchroHipQuantPlane * planes, int nplanes, int bpp, bool allow_empty);
+int quantise_batch_run (SchroHipContext * ctx, const SchroHipQuantPlane * planes, int nplanes, int bpp, bool allow_empty,
+    const int32_t * const *chosen = nullptr, uint32_t * clamped = nullptr);
 struct FrameQuantTable {
   std::vector < int >key;       // what the records were laid out for
   std::vector < SchroHipCodeblock > recs[3];
@@ -1306,6 +1344,8 @@ struct FrameHistTable {
   SchroHipHistogramCounts *d_counts, *h_counts;
 };
 void frame_hist_table_free (SchroHipContext * ctx);
+// plane_quant_choose.cpp
+void quant_choose_tables_free (SchroHipContext * ctx);
 // the launches made while a scope is open are timed under its kernel class (when profiling is on)
 struct ProfileScope {
   ProfileScope (SchroHipContext * c, int cls);
