@@ -735,15 +735,18 @@ class Context:
             out[name] = (ms.value, n.value)
         return out
 
+    def _routes(self, read, names, reset):
+        counts = (C.c_longlong * len(names))()
+        check(read(self.h, counts, 1 if reset else 0))
+        return dict(zip(names, (int(n) for n in counts)))
+
     OBMC_ROUTES = ("row", "item", "general", "strip")       # SCHRO_HIP_OBMC_ROUTE_* (include/schro_hip.h)
 
     def obmc_routes(self, reset=False):
         """{route: planes} this context's OBMC calls have handed to the launches of each route (schro_hip_obmc_routes):
         "row" obmc_row*.hip, "item" / "general" obmc.hip's item / per-pixel kernel, "strip" obmc_strip.hip; reset: start
         the counts again from zero after reading them."""
-        counts = (C.c_longlong * len(self.OBMC_ROUTES))()
-        check(self.lib.schro_hip_obmc_routes(self.h, counts, 1 if reset else 0))
-        return dict(zip(self.OBMC_ROUTES, (int(n) for n in counts)))
+        return self._routes(self.lib.schro_hip_obmc_routes, self.OBMC_ROUTES, reset)
 
     V210_ROUTES = ("haar3", "level", "two_pass")             # SCHRO_HIP_V210_ROUTE_* (include/schro_hip.h)
 
@@ -751,9 +754,7 @@ class Context:
         """{route: pictures} this context's iiwt_pack_v210 calls have handed to each route (schro_hip_v210_routes): "haar3"
         the three-level s32 Haar kernel with the copy-out, "level" the finest level writing v210 (iiwt_v210_kernel), "two_pass"
         the pixel frame in a scratch block and the pack; reset: start the counts again from zero after reading them."""
-        counts = (C.c_longlong * len(self.V210_ROUTES))()
-        check(self.lib.schro_hip_v210_routes(self.h, counts, 1 if reset else 0))
-        return dict(zip(self.V210_ROUTES, (int(n) for n in counts)))
+        return self._routes(self.lib.schro_hip_v210_routes, self.V210_ROUTES, reset)
 
     PACK8_ROUTES = ("level", "two_pass")                     # SCHRO_HIP_PACK8_ROUTE_* (include/schro_hip.h)
 
@@ -761,9 +762,7 @@ class Context:
         """{route: pictures} this context's iiwt_pack_u8 calls have handed to each route (schro_hip_pack8_routes): "level" the
         finest level writing the packed rows (iiwt_pack8_kernel), "two_pass" the planar picture in a scratch block and the
         pack; reset: start the counts again from zero after reading them."""
-        counts = (C.c_longlong * len(self.PACK8_ROUTES))()
-        check(self.lib.schro_hip_pack8_routes(self.h, counts, 1 if reset else 0))
-        return dict(zip(self.PACK8_ROUTES, (int(n) for n in counts)))
+        return self._routes(self.lib.schro_hip_pack8_routes, self.PACK8_ROUTES, reset)
 
     WIDE_ROUTES = ("level", "two_pass")                      # SCHRO_HIP_WIDE_ROUTE_* (include/schro_hip.h)
 
@@ -771,9 +770,7 @@ class Context:
         """{route: pictures} this context's iiwt_pack_wide calls have handed to each route (schro_hip_wide_routes): "level" the
         finest level shifting, converting and writing the packed rows (iiwt_wide_kernel), "two_pass" the pixel frame in a
         scratch block, the shift and the pack; reset: start the counts again from zero after reading them."""
-        counts = (C.c_longlong * len(self.WIDE_ROUTES))()
-        check(self.lib.schro_hip_wide_routes(self.h, counts, 1 if reset else 0))
-        return dict(zip(self.WIDE_ROUTES, (int(n) for n in counts)))
+        return self._routes(self.lib.schro_hip_wide_routes, self.WIDE_ROUTES, reset)
 
     def plane(self, height, width, dtype, stride=None):
         return DevicePlane(self, height, width, dtype, stride)
@@ -1141,21 +1138,26 @@ class Context:
             a.width, a.height, a.format = w, h, FORMAT_V210
         check(self.lib.schro_hip_pack_v210_batch(self.h, arr, n, bpp))
 
+    @staticmethod
+    def _iiwt_pack_picture(a, bpp, planes, hs, vs, dst, w, h):
+        """The fields the pictures of the three iiwt_pack_*_batch calls have in common."""
+        for k in range(3):
+            assert planes[k].dtype.itemsize == bpp
+            a.src[k] = planes[k].ptr
+            a.src_stride[k] = planes[k].stride
+        a.width, a.height = planes[0].width, planes[0].height
+        a.h_shift, a.v_shift = hs, vs
+        a.dst, a.dst_stride = dst.ptr, dst.stride
+        a.out_width, a.out_height = w, h
+
     def iiwt_pack_v210_batch(self, jobs, depth, filt):
         """r05: the inverse wavelet and the v210 copy-out in one call.  jobs: (coefficient planes [Y, U, V] DevicePlanes of one
         dtype, h_shift, v_shift, dst DevicePlane of bytes, picture width, picture height) per picture."""
         n = len(jobs)
         arr = (_lib.IwtPackPicture * n)()
         bpp = jobs[0][0][0].dtype.itemsize
-        for a, (planes, hs, vs, dst, w, h) in zip(arr, jobs):
-            for k in range(3):
-                assert planes[k].dtype.itemsize == bpp
-                a.src[k] = planes[k].ptr
-                a.src_stride[k] = planes[k].stride
-            a.width, a.height = planes[0].width, planes[0].height
-            a.h_shift, a.v_shift = hs, vs
-            a.dst, a.dst_stride = dst.ptr, dst.stride
-            a.out_width, a.out_height = w, h
+        for a, job in zip(arr, jobs):
+            self._iiwt_pack_picture(a, bpp, *job)
         check(self.lib.schro_hip_iiwt_pack_v210_batch(self.h, arr, n, depth, filt, bpp))
 
     def iiwt_pack_u8_batch(self, jobs, depth, filt):
@@ -1167,18 +1169,12 @@ class Context:
         arr = (_lib.IwtPack8Picture * n)()
         bpp = jobs[0][0][0].dtype.itemsize
         for a, (planes, hs, vs, preds, dst, w, h, fmt) in zip(arr, jobs):
-            for k in range(3):
-                assert planes[k].dtype.itemsize == bpp
-                a.src[k] = planes[k].ptr
-                a.src_stride[k] = planes[k].stride
-                if preds is not None:
-                    assert preds[k].dtype == np.uint8
-                    a.pred[k] = preds[k].ptr
-                    a.pred_stride[k] = preds[k].stride
-            a.width, a.height = planes[0].width, planes[0].height
-            a.h_shift, a.v_shift = hs, vs
-            a.dst, a.dst_stride = dst.ptr, dst.stride
-            a.out_width, a.out_height, a.format = w, h, fmt
+            self._iiwt_pack_picture(a, bpp, planes, hs, vs, dst, w, h)
+            for k in range(3 if preds is not None else 0):
+                assert preds[k].dtype == np.uint8
+                a.pred[k] = preds[k].ptr
+                a.pred_stride[k] = preds[k].stride
+            a.format = fmt
         check(self.lib.schro_hip_iiwt_pack_u8_batch(self.h, arr, n, depth, filt, bpp))
 
     def iiwt_pack_wide_batch(self, jobs, depth, filt):
@@ -1188,15 +1184,9 @@ class Context:
         n = len(jobs)
         arr = (_lib.IwtPackWidePicture * n)()
         bpp = jobs[0][0][0].dtype.itemsize
-        for a, (planes, hs, vs, dst, w, h, fmt, shift) in zip(arr, jobs):
-            for k in range(3):
-                assert planes[k].dtype.itemsize == bpp
-                a.src[k] = planes[k].ptr
-                a.src_stride[k] = planes[k].stride
-            a.width, a.height = planes[0].width, planes[0].height
-            a.h_shift, a.v_shift = hs, vs
-            a.dst, a.dst_stride = dst.ptr, dst.stride
-            a.out_width, a.out_height, a.format, a.shift = w, h, fmt, shift
+        for a, (*common, fmt, shift) in zip(arr, jobs):
+            self._iiwt_pack_picture(a, bpp, *common)
+            a.format, a.shift = fmt, shift
         check(self.lib.schro_hip_iiwt_pack_wide_batch(self.h, arr, n, depth, filt, bpp))
 
     def pack_wide_batch(self, jobs):

@@ -151,21 +151,25 @@ push_big_table (SchroHipContext * ctx, const void *host, size_t bytes, void **de
 }
 
 int
-ensure_scratch (SchroHipContext * ctx, size_t bytes)
+grow_block (SchroHipContext * ctx, void *&block, size_t & size, size_t bytes)
 {
-  void *&scratch = ctx->scratch_q[ctx->cur];
-  size_t & size = ctx->scratch_size_q[ctx->cur];
   if (bytes <= size)
     return 0;
-  if (scratch) {
+  if (block) {
     SCHRO_HIP_CHECK (hipStreamSynchronize (ctx->stream));
-    SCHRO_HIP_CHECK (hipFree (scratch));
-    scratch = nullptr;
+    SCHRO_HIP_CHECK (hipFree (block));
+    block = nullptr;
     size = 0;
   }
-  SCHRO_HIP_CHECK (hipMalloc (&scratch, bytes));
+  SCHRO_HIP_CHECK (hipMalloc (&block, bytes));
   size = bytes;
   return 0;
+}
+
+int
+ensure_scratch (SchroHipContext * ctx, size_t bytes)
+{
+  return grow_block (ctx, ctx->scratch_q[ctx->cur], ctx->scratch_size_q[ctx->cur], bytes);
 }
 
 // Reported ONCE, by the first call that looks (the launch's epoch names the batch it belongs to); the word is

@@ -23,6 +23,11 @@
 //             Every filter measured faster on LEVEL than on two passes (Fidelity too: 0.291 against 0.336 ms per 8K picture),
 //             so no filter is sent to two passes; nor is a plane narrower than one tile (the tile clamps to the picture).
 // The bytes out are the same on every route.
+//
+// The 8-bit (YUYV / UYVY / AYUV) and the > 8-bit (v216 / ARGB / AY64) calls below have the LEVEL and TWO_PASS routes too.
+// What the three share exists once, in front of them: the refusals, what LEVEL asks of every picture, the layout of the
+// queue's block, the fields the three level jobs have in common, a TWO_PASS picture's planes.  None of it knows which call
+// it serves: what differs comes in as an argument or stays with its call.
 #include "schro_hip_internal.h"
 
 #include <cstdlib>
@@ -31,31 +36,262 @@
 
 using namespace schro;
 
+// A plane of the queue's block
+struct Slot {
+  size_t at;
+  int stride;
+};
+
+// The fields the three calls' pictures have in common, and what a call decided about the picture
+struct PackPic {
+  const void *src[3];
+  int src_stride[3];
+  int width, height, h_shift, v_shift;
+  uint8_t *dst;
+  int dst_stride;
+  int out_width, out_height;
+  bool level;                   // its route: LEVEL, else TWO_PASS
+  int px_row_bytes[3], px_rows[3];      // the planes a TWO_PASS picture's transform writes and its pack reads
+  Slot slot[3];                 // LEVEL (depth > 1): its compact LL planes; TWO_PASS: those planes
+
+  int cw (int c) const { return c ? width >> h_shift : width; }
+  int ch (int c) const { return c ? height >> v_shift : height; }
+};
+
+template < class Picture > static PackPic
+common_fields (const Picture & pic)
+{
+  PackPic k;
+  memset (&k, 0, sizeof (k));
+  for (int c = 0; c < 3; c++) {
+    k.src[c] = pic.src[c];
+    k.src_stride[c] = pic.src_stride[c];
+  }
+  k.width = pic.width;
+  k.height = pic.height;
+  k.h_shift = pic.h_shift;
+  k.v_shift = pic.v_shift;
+  k.dst = pic.dst;
+  k.dst_stride = pic.dst_stride;
+  k.out_width = pic.out_width;
+  k.out_height = pic.out_height;
+  return k;
+}
+
+static bool
+env_on (const char *value)
+{
+  return value && atoi (value) != 0;
+}
+
+// ---- the refusals (who: the call's name, as in motion_check_*) ------------------------------------------------------
+static int
+check_call (const char *who, const void *ctx, const void *pictures, int npictures, int njobs, int depth, int filter, int bps)
+{
+  SCHRO_HIP_REQUIRE (ctx && pictures && npictures > 0 && njobs <= kMaxJobs, "%s: bad arguments", who);
+  SCHRO_HIP_REQUIRE (depth >= 1 && depth <= 6 && filter >= 0 && filter <= 6 && (bps == 2 || bps == 4),
+      "%s: depth %d, filter %d, %d bytes per sample", who, depth, filter, bps);
+  return 0;
+}
+
+static int
+check_geometry (const char *who, int p, const PackPic & pic, int row_bytes)
+{
+  SCHRO_HIP_REQUIRE (pic.src[0] && pic.src[1] && pic.src[2] && pic.dst && pic.width > 0 && pic.height > 0
+      && pic.out_width > 0 && pic.out_height > 0 && pic.out_width <= pic.width && pic.out_height <= pic.height
+      && pic.dst_stride >= row_bytes, "%s: picture %d: bad geometry", who, p);
+  return 0;
+}
+
+// What schro_hip_iiwt_batch asks of every component: whole transform levels, rows that hold the component.  (Behind the
+// call's own check of h_shift and v_shift.  The v210 call's source is 4:2:2, and the wide call's v_shift is 0: there the
+// terms that compare the shifted size with the picture's cannot fire, for luma is refused first and its width is even at
+// depth >= 1.)
+static int
+check_component (const char *who, int p, int c, const PackPic & pic, int depth, int bps)
+{
+  const int w = pic.cw (c), h = pic.ch (c);
+  SCHRO_HIP_REQUIRE (w % (1 << depth) == 0 && h % (1 << depth) == 0 && w > 0 && h > 0 && (w << (c ? pic.h_shift : 0)) == pic.width
+      && (h << (c ? pic.v_shift : 0)) == pic.height, "%s: picture %d component %d: size %dx%d is not a multiple of 2^depth", who, p, c, w, h);
+  SCHRO_HIP_REQUIRE (pic.src_stride[c] >= w * bps, "%s: picture %d component %d: stride %d does not hold %d samples", who, p, c,
+      pic.src_stride[c], w);
+  return 0;
+}
+
+// ---- the LEVEL route ------------------------------------------------------------------------------------------------
+static bool
+apart (const void *a, size_t an, const void *b, size_t bn)
+{
+  const char *a0 = (const char *) a, *b0 = (const char *) b;
+  return a0 + an <= b0 || b0 + bn <= a0;
+}
+
+// What the finest level's kernels ask of every picture, whatever they pack: a 16-byte aligned destination (their stores
+// are whole 16-byte groups), sample-aligned coefficient rows, a dst apart from every coefficient plane (the two passes
+// read every coefficient before the pack writes dst; one launch does not)
+static bool
+level_fits (const PackPic & pic, int bps)
+{
+  bool fits = (((uintptr_t) pic.dst | (uintptr_t) pic.dst_stride) & 15) == 0;
+  for (int c = 0; c < 3; c++)
+    fits = fits && ((((uintptr_t) pic.src[c] | (uintptr_t) pic.src_stride[c]) & (bps - 1)) == 0)
+        && apart (pic.dst, (size_t) pic.dst_stride * pic.out_height, pic.src[c], (size_t) pic.src_stride[c] * pic.ch (c));
+  return fits;
+}
+
+// The queue's grow-only block for one call (the three calls share it: in-order reuse on the queue): the LEVEL pictures
+// first -- per picture the three compact LL planes of level 0 (depth > 1: the coarser levels' output, a quarter of the
+// component) --, then per TWO_PASS picture its three planes.  What takes a plane moves the block's end, so the size is
+// the end of the last plane.
+// r06: nothing is allocated, freed or waited for per call; a block that must grow waits for the queue once
+static int
+lay_out_block (SchroHipContext * ctx, std::vector < PackPic > &pics, int depth, int bps, char **block)
+{
+  size_t end = 0;
+  auto take = [&end] (size_t row_bytes, size_t row_align, int rows) {
+    const Slot s = { end, (int) round_up (row_bytes, row_align) };
+    end += round_up ((size_t) s.stride * (size_t) rows, 256);
+    return s;
+  };
+  for (PackPic & pic : pics)
+    for (int c = 0; c < 3 && pic.level && depth > 1; c++)
+      pic.slot[c] = take ((size_t) (pic.cw (c) >> 1) * bps, 128, pic.ch (c) >> 1);
+  for (PackPic & pic : pics)
+    for (int c = 0; c < 3 && !pic.level; c++)
+      pic.slot[c] = take ((size_t) pic.px_row_bytes[c], 64, pic.px_rows[c]);
+  const int q = ctx->cur;
+  int r = grow_block (ctx, ctx->pack_tmp_q[q], ctx->pack_tmp_size_q[q], end);
+  *block = (char *) ctx->pack_tmp_q[q];
+  return r;
+}
+
+// What V210Job, Pack8Job and WideJob have in common, and the picture's planes of levels depth-1 .. 1 for the level loop.
+// tiled_width: the columns that tiles of cols x rows cover; tiles: the launch's count so far.
+template < class Job > static Job
+level_job (const PackPic & pic, char *block, int depth, int bps, int tiled_width, int cols, int rows, int &tiles,
+    std::vector < SchroHipIwtPlane > &coarse)
+{
+  Job j;
+  memset (&j, 0, sizeof (j));
+  for (int c = 0; c < 3; c++) {
+    j.src[c] = pic.src[c];
+    j.src_stride[c] = pic.src_stride[c];
+    if (depth > 1) {
+      // the level-1 view of the coefficient frame {w / 2, h / 2, stride x 2} (schroparams.c:319-352), depth - 1 levels
+      SchroHipIwtPlane pl;
+      memset (&pl, 0, sizeof (pl));
+      pl.src = pic.src[c];
+      pl.src_stride = 2 * pic.src_stride[c];
+      pl.dst = block + pic.slot[c].at;
+      pl.dst_stride = pic.slot[c].stride;
+      pl.width = pic.cw (c) >> 1;
+      pl.height = pic.ch (c) >> 1;
+      coarse.push_back (pl);
+      j.ll[c] = pl.dst;
+      j.ll_stride[c] = pl.dst_stride;
+    } else {
+      j.ll[c] = pic.src[c];     // (the frame's LL quadrant)
+      j.ll_stride[c] = 2 * pic.src_stride[c];
+    }
+    // 8-byte loads of the four bands: whole groups of samples per row, 8-byte aligned rows and band origins
+    const int nc = pic.cw (c) >> 1, vl = 8 / bps;
+    const uintptr_t bits = (uintptr_t) j.ll[c] | (uintptr_t) j.ll_stride[c] | (uintptr_t) pic.src[c] | (uintptr_t) pic.src_stride[c]
+        | (uintptr_t) nc * bps;
+    if (nc % vl == 0 && nc >= vl && (bits & 7) == 0)
+      j.flags |= 1 << c;
+  }
+  j.w = pic.width;
+  j.h = pic.height;
+  j.out_w = pic.out_width;
+  j.out_h = pic.out_height;
+  j.dst = pic.dst;
+  j.dst_stride = pic.dst_stride;
+  j.tiles_x = div_up (tiled_width, cols);
+  j.tile_base = tiles;
+  tiles += j.tiles_x * div_up (pic.out_height, rows);
+  return j;
+}
+
+static int
+coarse_levels (SchroHipContext * ctx, const std::vector < SchroHipIwtPlane > &coarse, int depth, int filter, int bps)
+{
+  return coarse.empty () ? 0 : schro_hip_iiwt_batch (ctx, coarse.data (), (int) coarse.size (), depth - 1, filter, bps);
+}
+
+// One launch of a finest-level kernel for its jobs of the call, if it has any: launch (device jobs, their number)
+template < class Job, class Launch > static int
+finest_level (SchroHipContext * ctx, const std::vector < Job > &jobs, Launch launch)
+{
+  if (jobs.empty ())
+    return 0;
+  void *d_jobs = nullptr;
+  int r = push_args (ctx, jobs.data (), sizeof (Job) * jobs.size (), &d_jobs);
+  if (r)
+    return r;
+  ProfileScope ps (ctx, SCHRO_HIP_KERNEL_IIWT_FINEST);
+  return launch ((const Job *) d_jobs, (int) jobs.size ());
+}
+
+// ---- the two passes (the general form) ------------------------------------------------------------------------------
+// A picture's three transform planes into the block, and the pack that reads them
+static void
+two_pass_picture (const PackPic & pic, char *block, int format, std::vector < SchroHipIwtPlane > &planes,
+    std::vector < SchroHipPackPlane > &packs)
+{
+  SchroHipPackPlane pk;
+  memset (&pk, 0, sizeof (pk));
+  for (int c = 0; c < 3; c++) {
+    SchroHipIwtPlane pl;
+    memset (&pl, 0, sizeof (pl));
+    pl.src = pic.src[c];
+    pl.src_stride = pic.src_stride[c];
+    pl.dst = block + pic.slot[c].at;
+    pl.dst_stride = pic.slot[c].stride;
+    pl.width = pic.cw (c);
+    pl.height = pic.ch (c);
+    planes.push_back (pl);
+    pk.src[c] = (const uint8_t *) pl.dst;
+    pk.src_stride[c] = pl.dst_stride;
+  }
+  pk.src_width = pic.out_width; // (the picture inside the transform's padded size: crop, schrovirtframe.c:1823-1853)
+  pk.src_height = pic.out_height;
+  pk.src_h_shift = pic.h_shift;
+  pk.src_v_shift = pic.v_shift;
+  pk.dst = pic.dst;
+  pk.dst_stride = pic.dst_stride;
+  pk.width = pic.out_width;
+  pk.height = pic.out_height;
+  pk.format = format;
+  packs.push_back (pk);
+}
+
+// ---- v210 -----------------------------------------------------------------------------------------------------------
 extern "C" int
 schro_hip_iiwt_pack_v210_batch (SchroHipContext * ctx, const SchroHipIwtPackPicture * pictures, int npictures, int depth, int filter,
     int bytes_per_sample)
 {
-  SCHRO_HIP_REQUIRE (ctx && pictures && npictures > 0 && npictures <= kMaxJobs, "iiwt_pack_v210_batch: bad arguments");
-  SCHRO_HIP_REQUIRE (depth >= 1 && depth <= 6 && filter >= 0 && filter <= 6 && (bytes_per_sample == 2 || bytes_per_sample == 4),
-      "iiwt_pack_v210_batch: depth %d, filter %d, %d bytes per sample", depth, filter, bytes_per_sample);
+  const char *who = "iiwt_pack_v210_batch";
+  const int bps = bytes_per_sample;
+  if (int r = check_call (who, ctx, pictures, npictures, npictures, depth, filter, bps))
+    return r;
   (void) hipSetDevice (ctx->device);
-  bool fused = depth == 3 && (filter == 3 || filter == 4) && bytes_per_sample == 4;
+  // (experiments: SCHRO_HIP_V210_TWO_PASS=1 sends every picture the Haar kernel does not take to the two passes, for A/B runs)
+  const bool level_on = !env_on (SCHRO_ENV ("SCHRO_HIP_V210_TWO_PASS"));
+  bool fused = depth == 3 && (filter == 3 || filter == 4) && bps == 4;
   std::vector < HaarPackJob > jobs ((size_t) npictures);
-  int tile_base = 0;
+  std::vector < PackPic > pics;
+  int tile_base = 0, nlevel = 0;
   for (int p = 0; p < npictures; p++) {
-    const SchroHipIwtPackPicture & pic = pictures[p];
-    SCHRO_HIP_REQUIRE (pic.src[0] && pic.src[1] && pic.src[2] && pic.dst && pic.width > 0 && pic.height > 0
-        && pic.out_width > 0 && pic.out_height > 0 && pic.out_width <= pic.width && pic.out_height <= pic.height
-        && pic.dst_stride >= 16 * ((pic.out_width + 5) / 6), "iiwt_pack_v210_batch: picture %d: bad geometry", p);
+    PackPic pic = common_fields (pictures[p]);
+    if (int r = check_geometry (who, p, pic, 16 * ((pic.out_width + 5) / 6)))
+      return r;
     // (convert_4xx_422 of s16 / s32 frames is not on the reference's path either: schro_frame_convert finds no match, schroframe.c:869-979)
-    SCHRO_HIP_REQUIRE (pic.h_shift == 1 && pic.v_shift == 0, "iiwt_pack_v210_batch: picture %d: v210 from s16 / s32 frames needs a 4:2:2 frame", p);
-    // (what schro_hip_iiwt_batch asks of every component: whole transform levels, rows that hold the component)
+    SCHRO_HIP_REQUIRE (pic.h_shift == 1 && pic.v_shift == 0, "%s: picture %d: v210 from s16 / s32 frames needs a 4:2:2 frame", who, p);
     for (int c = 0; c < 3; c++) {
-      const int w = c ? pic.width >> pic.h_shift : pic.width, h = c ? pic.height >> pic.v_shift : pic.height;
-      SCHRO_HIP_REQUIRE (w % (1 << depth) == 0 && h % (1 << depth) == 0 && w > 0 && h > 0,
-          "iiwt_pack_v210_batch: picture %d component %d: size %dx%d is not a multiple of 2^depth", p, c, w, h);
-      SCHRO_HIP_REQUIRE (pic.src_stride[c] >= w * bytes_per_sample,
-          "iiwt_pack_v210_batch: picture %d component %d: stride %d does not hold %d samples", p, c, pic.src_stride[c], w);
+      if (int r = check_component (who, p, c, pic, depth, bps))
+        return r;
+      pic.px_row_bytes[c] = pic.cw (c) * bps;
+      pic.px_rows[c] = pic.ch (c);
     }
     HaarPackJob & j = jobs[(size_t) p];
     for (int c = 0; c < 3; c++) {
@@ -69,134 +305,33 @@ schro_hip_iiwt_pack_v210_batch (SchroHipContext * ctx, const SchroHipIwtPackPict
     j.tiles_x = div_up (pic.width, iiwt_haar3_v210_strip_width ());
     j.tile_base = tile_base;
     tile_base += j.tiles_x * (pic.height / 8);
-    fused = fused && pic.h_shift == 1 && pic.v_shift == 0 && pic.out_width == pic.width && pic.out_height == pic.height
-        && iiwt_haar3_v210_ok (j);
+    fused = fused && pic.out_width == pic.width && pic.out_height == pic.height && iiwt_haar3_v210_ok (j);
+    pic.level = level_on && level_fits (pic, bps);
+    nlevel += pic.level;
+    pics.push_back (pic);
   }
   if (fused) {
-    void *d_jobs;
-    int r = push_args (ctx, jobs.data (), sizeof (HaarPackJob) * jobs.size (), &d_jobs);
-    if (r)
-      return r;
-    ProfileScope ps (ctx, SCHRO_HIP_KERNEL_IIWT_FINEST);
-    r = launch_iiwt_haar3_v210 (ctx->stream, (const HaarPackJob *) d_jobs, npictures, tile_base, filter);
+    int r = finest_level (ctx, jobs, [&](const HaarPackJob * d, int n) { return launch_iiwt_haar3_v210 (ctx->stream, d, n, tile_base, filter); });
     if (!r)
       ctx->v210_routes[SCHRO_HIP_V210_ROUTE_HAAR3] += npictures;
     return r;
   }
-  // which pictures the finest level's v210 kernel takes (the rest: the two passes); a 16-byte aligned destination (its
-  // stores are whole v210 groups), sample-aligned coefficient rows
-  // (experiments: SCHRO_HIP_V210_TWO_PASS=1 sends every picture the Haar kernel does not take to the two passes, for A/B runs)
-  const bool level_on = !(SCHRO_ENV ("SCHRO_HIP_V210_TWO_PASS") && atoi (SCHRO_ENV ("SCHRO_HIP_V210_TWO_PASS")) != 0);
-  std::vector < char >level ((size_t) npictures, 0);
-  int nlevel = 0;
-  for (int p = 0; p < npictures; p++) {
-    const SchroHipIwtPackPicture & pic = pictures[p];
-    uintptr_t src_bits = 0;
-    bool apart = true;          // (the two passes read every coefficient before the pack writes dst; one launch does not)
-    const char *d0 = (const char *) pic.dst, *d1 = d0 + (size_t) pic.dst_stride * pic.out_height;
-    for (int c = 0; c < 3; c++) {
-      src_bits |= (uintptr_t) pic.src[c] | (uintptr_t) pic.src_stride[c];
-      const char *s0 = (const char *) pic.src[c], *s1 = s0 + (size_t) pic.src_stride[c] * (c ? pic.height >> pic.v_shift : pic.height);
-      apart = apart && (s1 <= d0 || d1 <= s0);
-    }
-    level[(size_t) p] = level_on && ((((uintptr_t) pic.dst | (uintptr_t) pic.dst_stride) & 15) == 0)
-        && (src_bits & (bytes_per_sample - 1)) == 0 && apart;
-    nlevel += level[(size_t) p];
-  }
-  // the queue's grow-only block: per level picture the three compact LL planes of level 0 (depth > 1: the coarser levels'
-  // output, a quarter of the component), per two-pass picture its three pixel planes
-  // r06: nothing is allocated, freed or waited for per call; a block that must grow waits for the queue once
-  auto ll_stride = [&](int w) { return (int) round_up ((size_t) (w >> 1) * bytes_per_sample, 128); };
-  size_t need = 0;
-  for (int p = 0; p < npictures; p++)
-    for (int c = 0; c < 3; c++) {
-      const SchroHipIwtPackPicture & pic = pictures[p];
-      const int w = c ? pic.width >> pic.h_shift : pic.width, h = c ? pic.height >> pic.v_shift : pic.height;
-      if (!level[(size_t) p])
-        need += round_up (round_up ((size_t) w * bytes_per_sample, 64) * (size_t) h, 256);
-      else if (depth > 1)
-        need += round_up ((size_t) ll_stride (w) * (size_t) (h >> 1), 256);
-    }
-  const int q = ctx->cur;
-  if (ctx->pack_tmp_size_q[q] < need) {
-    if (ctx->pack_tmp_q[q]) {
-      SCHRO_HIP_CHECK (hipStreamSynchronize (ctx->stream));
-      SCHRO_HIP_CHECK (hipFree (ctx->pack_tmp_q[q]));
-      ctx->pack_tmp_q[q] = nullptr;
-      ctx->pack_tmp_size_q[q] = 0;
-    }
-    SCHRO_HIP_CHECK (hipMalloc (&ctx->pack_tmp_q[q], need));
-    ctx->pack_tmp_size_q[q] = need;
-  }
-  size_t at = 0;
-  int r = 0;
+  char *block;
+  int r = lay_out_block (ctx, pics, depth, bps, &block);
+  if (r)
+    return r;
 
-  // ---- the level route: levels depth-1 .. 1 by the level loop into the LL planes, then the finest level + v210 ----
   if (nlevel) {
     std::vector < SchroHipIwtPlane > coarse;
     std::vector < V210Job > vj;
-    int cols, rows;
-    iiwt_v210_geometry (filter, bytes_per_sample, &cols, &rows);
-    const int vl = 8 / bytes_per_sample;
-    int vtiles = 0;
-    for (int p = 0; p < npictures; p++) {
-      if (!level[(size_t) p])
-        continue;
-      const SchroHipIwtPackPicture & pic = pictures[p];
-      V210Job j;
-      memset (&j, 0, sizeof (j));
-      for (int c = 0; c < 3; c++) {
-        const int w = c ? pic.width >> pic.h_shift : pic.width, h = pic.height;
-        j.src[c] = pic.src[c];
-        j.src_stride[c] = pic.src_stride[c];
-        if (depth > 1) {
-          // the level-1 view of the coefficient frame {w / 2, h / 2, stride x 2} (schroparams.c:319-352), depth - 1 levels
-          void *t = (char *) ctx->pack_tmp_q[q] + at;
-          at += round_up ((size_t) ll_stride (w) * (size_t) (h >> 1), 256);
-          SchroHipIwtPlane pl;
-          memset (&pl, 0, sizeof (pl));
-          pl.src = pic.src[c];
-          pl.src_stride = 2 * pic.src_stride[c];
-          pl.dst = t;
-          pl.dst_stride = ll_stride (w);
-          pl.width = w >> 1;
-          pl.height = h >> 1;
-          coarse.push_back (pl);
-          j.ll[c] = t;
-          j.ll_stride[c] = ll_stride (w);
-        } else {
-          j.ll[c] = pic.src[c];             // (the frame's LL quadrant)
-          j.ll_stride[c] = 2 * pic.src_stride[c];
-        }
-        // 8-byte loads of the four bands: whole groups of samples per row, 8-byte aligned rows and band origins
-        const int nc = w >> 1;
-        const uintptr_t bits = (uintptr_t) j.ll[c] | (uintptr_t) j.ll_stride[c] | (uintptr_t) pic.src[c] | (uintptr_t) pic.src_stride[c]
-            | (uintptr_t) nc * bytes_per_sample;
-        if (nc % vl == 0 && nc >= vl && (bits & 7) == 0)
-          j.flags |= 1 << c;
-      }
-      j.w = pic.width;
-      j.h = pic.height;
-      j.out_w = pic.out_width;
-      j.out_h = pic.out_height;
-      j.dst = pic.dst;
-      j.dst_stride = pic.dst_stride;
-      j.tiles_x = div_up (pic.out_width, cols);
-      j.tile_base = vtiles;
-      vtiles += j.tiles_x * div_up (pic.out_height, rows);
-      vj.push_back (j);
-    }
-    if (!coarse.empty ())
-      r = schro_hip_iiwt_batch (ctx, coarse.data (), (int) coarse.size (), depth - 1, filter, bytes_per_sample);
-    void *d_vj = nullptr;
+    int cols, rows, tiles = 0;
+    iiwt_v210_geometry (filter, bps, &cols, &rows);
+    for (const PackPic & pic : pics)
+      if (pic.level)
+        vj.push_back (level_job < V210Job > (pic, block, depth, bps, pic.out_width, cols, rows, tiles, coarse));
+    r = coarse_levels (ctx, coarse, depth, filter, bps);
     if (!r)
-      r = push_args (ctx, vj.data (), sizeof (V210Job) * vj.size (), &d_vj);
-    if (r)
-      return r;
-    {
-      ProfileScope ps (ctx, SCHRO_HIP_KERNEL_IIWT_FINEST);
-      r = launch_iiwt_v210 (ctx->stream, (const V210Job *) d_vj, (int) vj.size (), vtiles, filter, bytes_per_sample);
-    }
+      r = finest_level (ctx, vj, [&](const V210Job * d, int n) { return launch_iiwt_v210 (ctx->stream, d, n, tiles, filter, bps); });
     if (r)
       return r;
     ctx->v210_routes[SCHRO_HIP_V210_ROUTE_LEVEL] += nlevel;
@@ -204,46 +339,14 @@ schro_hip_iiwt_pack_v210_batch (SchroHipContext * ctx, const SchroHipIwtPackPict
       return 0;
   }
 
-  // ---- the two passes (the general form): transform into pixel planes, then the pack ----
   std::vector < SchroHipIwtPlane > planes;
   std::vector < SchroHipPackPlane > packs;
-  for (int p = 0; p < npictures; p++) {
-    if (level[(size_t) p])
-      continue;
-    const SchroHipIwtPackPicture & pic = pictures[p];
-    SchroHipPackPlane pk;
-    memset (&pk, 0, sizeof (pk));
-    for (int c = 0; c < 3; c++) {
-      const int w = c ? pic.width >> pic.h_shift : pic.width, h = c ? pic.height >> pic.v_shift : pic.height;
-      const int stride = (int) round_up ((size_t) w * bytes_per_sample, 64);
-      void *t = (char *) ctx->pack_tmp_q[q] + at;
-      at += round_up ((size_t) stride * (size_t) h, 256);
-      SchroHipIwtPlane pl;
-      memset (&pl, 0, sizeof (pl));
-      pl.src = pic.src[c];
-      pl.src_stride = pic.src_stride[c];
-      pl.dst = t;
-      pl.dst_stride = stride;
-      pl.width = w;
-      pl.height = h;
-      planes.push_back (pl);
-      pk.src[c] = (const uint8_t *) t;
-      pk.src_stride[c] = stride;
-    }
-    pk.src_width = pic.out_width;       // (the picture inside the transform's padded size: crop, schrovirtframe.c:1823-1853)
-    pk.src_height = pic.out_height;
-    pk.src_h_shift = pic.h_shift;
-    pk.src_v_shift = pic.v_shift;
-    pk.dst = pic.dst;
-    pk.dst_stride = pic.dst_stride;
-    pk.width = pic.out_width;
-    pk.height = pic.out_height;
-    pk.format = SCHRO_HIP_FORMAT_v210;
-    packs.push_back (pk);
-  }
-  r = schro_hip_iiwt_batch (ctx, planes.data (), (int) planes.size (), depth, filter, bytes_per_sample);
+  for (const PackPic & pic : pics)
+    if (!pic.level)
+      two_pass_picture (pic, block, SCHRO_HIP_FORMAT_v210, planes, packs);
+  r = schro_hip_iiwt_batch (ctx, planes.data (), (int) planes.size (), depth, filter, bps);
   if (!r)
-    r = schro_hip_pack_v210_batch (ctx, packs.data (), (int) packs.size (), bytes_per_sample);
+    r = schro_hip_pack_v210_batch (ctx, packs.data (), (int) packs.size (), bps);
   if (!r)
     ctx->v210_routes[SCHRO_HIP_V210_ROUTE_TWO_PASS] += (long long) packs.size ();
   return r;
@@ -252,13 +355,7 @@ schro_hip_iiwt_pack_v210_batch (SchroHipContext * ctx, const SchroHipIwtPackPict
 extern "C" int
 schro_hip_v210_routes (SchroHipContext * ctx, long long counts[SCHRO_HIP_V210_ROUTES], int reset)
 {
-  SCHRO_HIP_REQUIRE (ctx && counts, "v210_routes: bad arguments");
-  for (int k = 0; k < SCHRO_HIP_V210_ROUTES; k++) {
-    counts[k] = ctx->v210_routes[k];
-    if (reset)
-      ctx->v210_routes[k] = 0;
-  }
-  return 0;
+  return read_routes ("v210_routes", ctx, &SchroHipContext::v210_routes, counts, reset);
 }
 
 // ---- 8-bit packed output: YUYV / UYVY / AYUV (schro_hip.h: schro_hip_iiwt_pack_u8_batch) ---------------------------
@@ -286,161 +383,79 @@ pack8_level_filter (int filter, bool ayuv)
   return ayuv ? (filter == 1 || (filter >= 3 && filter <= 5)) : (filter >= 3 && filter <= 5);
 }
 
-static bool
-pack8_apart (const void *a, size_t an, const void *b, size_t bn)
-{
-  const char *a0 = (const char *) a, *b0 = (const char *) b;
-  return a0 + an <= b0 || b0 + bn <= a0;
-}
-
 extern "C" int
 schro_hip_iiwt_pack_u8_batch (SchroHipContext * ctx, const SchroHipIwtPack8Picture * pictures, int npictures, int depth, int filter,
     int bytes_per_sample)
 {
-  SCHRO_HIP_REQUIRE (ctx && pictures && npictures > 0 && 3 * npictures <= kMaxJobs, "iiwt_pack_u8_batch: bad arguments");
-  SCHRO_HIP_REQUIRE (depth >= 1 && depth <= 6 && filter >= 0 && filter <= 6 && (bytes_per_sample == 2 || bytes_per_sample == 4),
-      "iiwt_pack_u8_batch: depth %d, filter %d, %d bytes per sample", depth, filter, bytes_per_sample);
-  (void) hipSetDevice (ctx->device);
+  const char *who = "iiwt_pack_u8_batch";
   const int bps = bytes_per_sample;
-  const bool level_on = !(SCHRO_ENV ("SCHRO_HIP_PACK8_TWO_PASS") && atoi (SCHRO_ENV ("SCHRO_HIP_PACK8_TWO_PASS")) != 0);
-  const bool level_all = SCHRO_ENV ("SCHRO_HIP_PACK8_LEVEL") && atoi (SCHRO_ENV ("SCHRO_HIP_PACK8_LEVEL")) != 0;
-  auto comp_w = [](const SchroHipIwtPack8Picture & pic, int c, int w) { return c ? (w + pic.h_shift) >> pic.h_shift : w; };
-  auto comp_h = [](const SchroHipIwtPack8Picture & pic, int c, int h) { return c ? (h + pic.v_shift) >> pic.v_shift : h; };
-  std::vector < char >level ((size_t) npictures, 0);
+  if (int r = check_call (who, ctx, pictures, npictures, 3 * npictures, depth, filter, bps))
+    return r;
+  (void) hipSetDevice (ctx->device);
+  const bool level_on = !env_on (SCHRO_ENV ("SCHRO_HIP_PACK8_TWO_PASS")), level_all = env_on (SCHRO_ENV ("SCHRO_HIP_PACK8_LEVEL"));
+  std::vector < PackPic > pics;
   int nlevel = 0;
   for (int p = 0; p < npictures; p++) {
-    const SchroHipIwtPack8Picture & pic = pictures[p];
-    SCHRO_HIP_REQUIRE (pic.format == SCHRO_HIP_FORMAT_YUYV || pic.format == SCHRO_HIP_FORMAT_UYVY || pic.format == SCHRO_HIP_FORMAT_AYUV,
-        "iiwt_pack_u8_batch: picture %d: format 0x%x is not YUYV / UYVY / AYUV", p, pic.format);
-    const bool ayuv = pic.format == SCHRO_HIP_FORMAT_AYUV;
-    SCHRO_HIP_REQUIRE (pic.src[0] && pic.src[1] && pic.src[2] && pic.dst && pic.width > 0 && pic.height > 0
-        && pic.out_width > 0 && pic.out_height > 0 && pic.out_width <= pic.width && pic.out_height <= pic.height
-        && pic.dst_stride >= (ayuv ? 4 * pic.out_width : 4 * (pic.out_width / 2)), "iiwt_pack_u8_batch: picture %d: bad geometry", p);
+    const SchroHipIwtPack8Picture & in = pictures[p];
+    PackPic pic = common_fields (in);
+    SCHRO_HIP_REQUIRE (in.format == SCHRO_HIP_FORMAT_YUYV || in.format == SCHRO_HIP_FORMAT_UYVY || in.format == SCHRO_HIP_FORMAT_AYUV,
+        "%s: picture %d: format 0x%x is not YUYV / UYVY / AYUV", who, p, in.format);
+    const bool ayuv = in.format == SCHRO_HIP_FORMAT_AYUV;
+    if (int r = check_geometry (who, p, pic, ayuv ? 4 * pic.out_width : 4 * (pic.out_width / 2)))
+      return r;
     SCHRO_HIP_REQUIRE ((pic.h_shift == 0 || pic.h_shift == 1) && (pic.v_shift == 0 || pic.v_shift == 1) && !(pic.v_shift && !pic.h_shift),
-        "iiwt_pack_u8_batch: picture %d: chroma format not 4:4:4 / 4:2:2 / 4:2:0", p);
-    const bool has_pred = pic.pred[0] != nullptr;
-    SCHRO_HIP_REQUIRE ((pic.pred[1] != nullptr) == has_pred && (pic.pred[2] != nullptr) == has_pred,
-        "iiwt_pack_u8_batch: picture %d: a prediction for some components and not for others", p);
+        "%s: picture %d: chroma format not 4:4:4 / 4:2:2 / 4:2:0", who, p);
+    const bool has_pred = in.pred[0] != nullptr;
+    SCHRO_HIP_REQUIRE ((in.pred[1] != nullptr) == has_pred && (in.pred[2] != nullptr) == has_pred,
+        "%s: picture %d: a prediction for some components and not for others", who, p);
     bool fits = bps == 2 && level_on && (level_all || pack8_level_filter (filter, ayuv)) && pic.v_shift == 0 && pic.h_shift == (ayuv ? 0 : 1)
-        && ((((uintptr_t) pic.dst | (uintptr_t) pic.dst_stride) & 15) == 0);
-    const size_t dst_bytes = (size_t) pic.dst_stride * pic.out_height;
+        && level_fits (pic, bps);
     for (int c = 0; c < 3; c++) {
-      // (what schro_hip_iiwt_batch asks of every component: whole transform levels, rows that hold the component)
-      const int w = c ? pic.width >> pic.h_shift : pic.width, h = c ? pic.height >> pic.v_shift : pic.height;
-      SCHRO_HIP_REQUIRE (w % (1 << depth) == 0 && h % (1 << depth) == 0 && w > 0 && h > 0 && (w << (c ? pic.h_shift : 0)) == pic.width
-          && (h << (c ? pic.v_shift : 0)) == pic.height,
-          "iiwt_pack_u8_batch: picture %d component %d: size %dx%d is not a multiple of 2^depth", p, c, w, h);
-      SCHRO_HIP_REQUIRE (pic.src_stride[c] >= w * bps,
-          "iiwt_pack_u8_batch: picture %d component %d: stride %d does not hold %d samples", p, c, pic.src_stride[c], w);
-      const int ow = comp_w (pic, c, pic.out_width), oh = comp_h (pic, c, pic.out_height);
-      SCHRO_HIP_REQUIRE (!has_pred || pic.pred_stride[c] >= ow,
-          "iiwt_pack_u8_batch: picture %d component %d: prediction stride %d does not hold %d samples", p, c, pic.pred_stride[c], ow);
-      fits = fits && ((((uintptr_t) pic.src[c] | (uintptr_t) pic.src_stride[c]) & (bps - 1)) == 0)
-          && pack8_apart (pic.dst, dst_bytes, pic.src[c], (size_t) pic.src_stride[c] * h);
+      if (int r = check_component (who, p, c, pic, depth, bps))
+        return r;
+      // the planar picture of the two passes: u8, the output's size, chroma rounded up
+      const int ow = c ? (pic.out_width + pic.h_shift) >> pic.h_shift : pic.out_width;
+      const int oh = c ? (pic.out_height + pic.v_shift) >> pic.v_shift : pic.out_height;
+      pic.px_row_bytes[c] = ow;
+      pic.px_rows[c] = oh;
+      SCHRO_HIP_REQUIRE (!has_pred || in.pred_stride[c] >= ow,
+          "%s: picture %d component %d: prediction stride %d does not hold %d samples", who, p, c, in.pred_stride[c], ow);
       if (has_pred)
-        fits = fits && ((((uintptr_t) pic.pred[c] | (uintptr_t) pic.pred_stride[c]) & 7) == 0) && pic.pred_stride[c] >= ((ow + 7) & ~7)
-            && pack8_apart (pic.dst, dst_bytes, pic.pred[c], (size_t) pic.pred_stride[c] * oh);
+        fits = fits && ((((uintptr_t) in.pred[c] | (uintptr_t) in.pred_stride[c]) & 7) == 0) && in.pred_stride[c] >= ((ow + 7) & ~7)
+            && apart (pic.dst, (size_t) pic.dst_stride * pic.out_height, in.pred[c], (size_t) in.pred_stride[c] * oh);
     }
-    level[(size_t) p] = fits;
+    pic.level = fits;
     nlevel += fits;
+    pics.push_back (pic);
   }
-  // the queue's grow-only block (shared with the v210 call: in-order reuse on the queue): per level picture the three
-  // compact LL planes of level 0 (depth > 1), per two-pass picture its three u8 planes
-  auto ll_stride = [&](int w) { return (int) round_up ((size_t) (w >> 1) * bps, 128); };
-  size_t need = 0;
-  for (int p = 0; p < npictures; p++)
-    for (int c = 0; c < 3; c++) {
-      const SchroHipIwtPack8Picture & pic = pictures[p];
-      if (!level[(size_t) p])
-        need += round_up (round_up ((size_t) comp_w (pic, c, pic.out_width), 64) * (size_t) comp_h (pic, c, pic.out_height), 256);
-      else if (depth > 1)
-        need += round_up ((size_t) ll_stride (c ? pic.width >> pic.h_shift : pic.width) * (size_t) (pic.height >> 1), 256);
-    }
-  const int q = ctx->cur;
-  if (ctx->pack_tmp_size_q[q] < need) {
-    if (ctx->pack_tmp_q[q]) {
-      SCHRO_HIP_CHECK (hipStreamSynchronize (ctx->stream));
-      SCHRO_HIP_CHECK (hipFree (ctx->pack_tmp_q[q]));
-      ctx->pack_tmp_q[q] = nullptr;
-      ctx->pack_tmp_size_q[q] = 0;
-    }
-    SCHRO_HIP_CHECK (hipMalloc (&ctx->pack_tmp_q[q], need));
-    ctx->pack_tmp_size_q[q] = need;
-  }
-  size_t at = 0;
-  int r = 0;
+  char *block;
+  int r = lay_out_block (ctx, pics, depth, bps, &block);
+  if (r)
+    return r;
 
-  // ---- the level route: levels depth-1 .. 1 by the level loop into the LL planes, then the finest level + pack ----
   if (nlevel) {
     std::vector < SchroHipIwtPlane > coarse;
     std::vector < Pack8Job > pj[2];     // [0] YUYV / UYVY, [1] AYUV: one launch each
     int tiles[2] = { 0, 0 };
     for (int p = 0; p < npictures; p++) {
-      if (!level[(size_t) p])
+      if (!pics[(size_t) p].level)
         continue;
-      const SchroHipIwtPack8Picture & pic = pictures[p];
-      const int ayuv = pic.format == SCHRO_HIP_FORMAT_AYUV;
+      const SchroHipIwtPack8Picture & in = pictures[p];
+      const int ayuv = in.format == SCHRO_HIP_FORMAT_AYUV;
       int cols, rows;
       iiwt_pack8_geometry (filter, ayuv, &cols, &rows);
-      Pack8Job j;
-      memset (&j, 0, sizeof (j));
+      Pack8Job j = level_job < Pack8Job > (pics[(size_t) p], block, depth, bps, in.out_width, cols, rows, tiles[ayuv], coarse);
       for (int c = 0; c < 3; c++) {
-        const int w = c ? pic.width >> pic.h_shift : pic.width, h = pic.height;
-        j.src[c] = pic.src[c];
-        j.src_stride[c] = pic.src_stride[c];
-        j.pred[c] = pic.pred[c];
-        j.pred_stride[c] = pic.pred_stride[c];
-        if (depth > 1) {
-          // the level-1 view of the coefficient frame {w / 2, h / 2, stride x 2} (schroparams.c:319-352), depth - 1 levels
-          void *t = (char *) ctx->pack_tmp_q[q] + at;
-          at += round_up ((size_t) ll_stride (w) * (size_t) (h >> 1), 256);
-          SchroHipIwtPlane pl;
-          memset (&pl, 0, sizeof (pl));
-          pl.src = pic.src[c];
-          pl.src_stride = 2 * pic.src_stride[c];
-          pl.dst = t;
-          pl.dst_stride = ll_stride (w);
-          pl.width = w >> 1;
-          pl.height = h >> 1;
-          coarse.push_back (pl);
-          j.ll[c] = t;
-          j.ll_stride[c] = ll_stride (w);
-        } else {
-          j.ll[c] = pic.src[c];             // (the frame's LL quadrant)
-          j.ll_stride[c] = 2 * pic.src_stride[c];
-        }
-        // 8-byte loads of the four bands: whole groups of samples per row, 8-byte aligned rows and band origins
-        const int nc = w >> 1, vl = 8 / bps;
-        const uintptr_t bits = (uintptr_t) j.ll[c] | (uintptr_t) j.ll_stride[c] | (uintptr_t) pic.src[c] | (uintptr_t) pic.src_stride[c]
-            | (uintptr_t) nc * bps;
-        if (nc % vl == 0 && nc >= vl && (bits & 7) == 0)
-          j.flags |= 1 << c;
+        j.pred[c] = in.pred[c];
+        j.pred_stride[c] = in.pred_stride[c];
       }
-      if (pic.format == SCHRO_HIP_FORMAT_UYVY)
+      if (in.format == SCHRO_HIP_FORMAT_UYVY)
         j.flags |= 8;
-      j.w = pic.width;
-      j.h = pic.height;
-      j.out_w = pic.out_width;
-      j.out_h = pic.out_height;
-      j.dst = pic.dst;
-      j.dst_stride = pic.dst_stride;
-      j.tiles_x = div_up (pic.out_width, cols);
-      j.tile_base = tiles[ayuv];
-      tiles[ayuv] += j.tiles_x * div_up (pic.out_height, rows);
       pj[ayuv].push_back (j);
     }
-    if (!coarse.empty ())
-      r = schro_hip_iiwt_batch (ctx, coarse.data (), (int) coarse.size (), depth - 1, filter, bps);
-    for (int ayuv = 0; ayuv < 2 && !r; ayuv++) {
-      if (pj[ayuv].empty ())
-        continue;
-      void *d_pj = nullptr;
-      r = push_args (ctx, pj[ayuv].data (), sizeof (Pack8Job) * pj[ayuv].size (), &d_pj);
-      if (r)
-        break;
-      ProfileScope ps (ctx, SCHRO_HIP_KERNEL_IIWT_FINEST);
-      r = launch_iiwt_pack8 (ctx->stream, (const Pack8Job *) d_pj, (int) pj[ayuv].size (), tiles[ayuv], filter, ayuv);
-    }
+    r = coarse_levels (ctx, coarse, depth, filter, bps);
+    for (int ayuv = 0; ayuv < 2 && !r; ayuv++)
+      r = finest_level (ctx, pj[ayuv], [&](const Pack8Job * d, int n) { return launch_iiwt_pack8 (ctx->stream, d, n, tiles[ayuv], filter, ayuv); });
     if (r)
       return r;
     ctx->pack8_routes[SCHRO_HIP_PACK8_ROUTE_LEVEL] += nlevel;
@@ -448,47 +463,23 @@ schro_hip_iiwt_pack_u8_batch (SchroHipContext * ctx, const SchroHipIwtPack8Pictu
       return 0;
   }
 
-  // ---- the two passes (the general form): the combine form into planar u8 planes, then the pack ----
+  // the combine form into planar u8 planes, then the pack
   std::vector < SchroHipIwtPlane > planes;
   std::vector < SchroHipPackPlane > packs;
   for (int p = 0; p < npictures; p++) {
-    if (level[(size_t) p])
+    const PackPic & pic = pics[(size_t) p];
+    if (pic.level)
       continue;
-    const SchroHipIwtPack8Picture & pic = pictures[p];
-    SchroHipPackPlane pk;
-    memset (&pk, 0, sizeof (pk));
+    const SchroHipIwtPack8Picture & in = pictures[p];
+    two_pass_picture (pic, block, in.format, planes, packs);
     for (int c = 0; c < 3; c++) {
-      const int ow = comp_w (pic, c, pic.out_width), oh = comp_h (pic, c, pic.out_height);
-      const int stride = (int) round_up ((size_t) ow, 64);
-      void *t = (char *) ctx->pack_tmp_q[q] + at;
-      at += round_up ((size_t) stride * (size_t) oh, 256);
-      SchroHipIwtPlane pl;
-      memset (&pl, 0, sizeof (pl));
-      pl.src = pic.src[c];
-      pl.src_stride = pic.src_stride[c];
-      pl.dst = t;
-      pl.dst_stride = stride;
-      pl.width = c ? pic.width >> pic.h_shift : pic.width;
-      pl.height = c ? pic.height >> pic.v_shift : pic.height;
-      pl.combine = pic.pred[0] ? 1 : 2;
-      pl.pred = pic.pred[c];
-      pl.pred_stride = pic.pred_stride[c];
-      pl.out_width = ow;
-      pl.out_height = oh;
-      planes.push_back (pl);
-      pk.src[c] = (const uint8_t *) t;
-      pk.src_stride[c] = stride;
+      SchroHipIwtPlane & pl = planes[planes.size () - 3 + (size_t) c];
+      pl.combine = in.pred[0] ? 1 : 2;
+      pl.pred = in.pred[c];
+      pl.pred_stride = in.pred_stride[c];
+      pl.out_width = pic.px_row_bytes[c];
+      pl.out_height = pic.px_rows[c];
     }
-    pk.src_width = pic.out_width;
-    pk.src_height = pic.out_height;
-    pk.src_h_shift = pic.h_shift;
-    pk.src_v_shift = pic.v_shift;
-    pk.dst = pic.dst;
-    pk.dst_stride = pic.dst_stride;
-    pk.width = pic.out_width;
-    pk.height = pic.out_height;
-    pk.format = pic.format;
-    packs.push_back (pk);
   }
   r = schro_hip_iiwt_batch (ctx, planes.data (), (int) planes.size (), depth, filter, bps);
   if (!r)
@@ -501,13 +492,7 @@ schro_hip_iiwt_pack_u8_batch (SchroHipContext * ctx, const SchroHipIwtPack8Pictu
 extern "C" int
 schro_hip_pack8_routes (SchroHipContext * ctx, long long counts[SCHRO_HIP_PACK8_ROUTES], int reset)
 {
-  SCHRO_HIP_REQUIRE (ctx && counts, "pack8_routes: bad arguments");
-  for (int k = 0; k < SCHRO_HIP_PACK8_ROUTES; k++) {
-    counts[k] = ctx->pack8_routes[k];
-    if (reset)
-      ctx->pack8_routes[k] = 0;
-  }
-  return 0;
+  return read_routes ("pack8_routes", ctx, &SchroHipContext::pack8_routes, counts, reset);
 }
 
 // ---- > 8-bit packed output: v216 / ARGB / AY64 (schro_hip.h: schro_hip_iiwt_pack_wide_batch) -----------------------
@@ -552,141 +537,63 @@ extern "C" int
 schro_hip_iiwt_pack_wide_batch (SchroHipContext * ctx, const SchroHipIwtPackWidePicture * pictures, int npictures, int depth, int filter,
     int bytes_per_sample)
 {
-  SCHRO_HIP_REQUIRE (ctx && pictures && npictures > 0 && 3 * npictures <= kMaxJobs, "iiwt_pack_wide_batch: bad arguments");
-  SCHRO_HIP_REQUIRE (depth >= 1 && depth <= 6 && filter >= 0 && filter <= 6 && (bytes_per_sample == 2 || bytes_per_sample == 4),
-      "iiwt_pack_wide_batch: depth %d, filter %d, %d bytes per sample", depth, filter, bytes_per_sample);
-  (void) hipSetDevice (ctx->device);
+  const char *who = "iiwt_pack_wide_batch";
   const int bps = bytes_per_sample;
-  const bool level_on = !(SCHRO_ENV ("SCHRO_HIP_WIDE_TWO_PASS") && atoi (SCHRO_ENV ("SCHRO_HIP_WIDE_TWO_PASS")) != 0);
-  const bool level_all = SCHRO_ENV ("SCHRO_HIP_WIDE_LEVEL") && atoi (SCHRO_ENV ("SCHRO_HIP_WIDE_LEVEL")) != 0;
-  std::vector < char >level ((size_t) npictures, 0);
+  if (int r = check_call (who, ctx, pictures, npictures, 3 * npictures, depth, filter, bps))
+    return r;
+  (void) hipSetDevice (ctx->device);
+  const bool level_on = !env_on (SCHRO_ENV ("SCHRO_HIP_WIDE_TWO_PASS")), level_all = env_on (SCHRO_ENV ("SCHRO_HIP_WIDE_LEVEL"));
+  std::vector < PackPic > pics;
   int nlevel = 0;
   for (int p = 0; p < npictures; p++) {
-    const SchroHipIwtPackWidePicture & pic = pictures[p];
-    SCHRO_HIP_REQUIRE (is_wide_format (pic.format), "iiwt_pack_wide_batch: picture %d: format 0x%x is not v216 / ARGB / AY64", p, pic.format);
-    const bool v216 = pic.format == SCHRO_HIP_FORMAT_v216;
-    const int row_bytes = v216 ? 8 * (pic.out_width / 2) : pic.format == SCHRO_HIP_FORMAT_ARGB ? 4 * pic.out_width : 8 * pic.out_width;
-    SCHRO_HIP_REQUIRE (pic.src[0] && pic.src[1] && pic.src[2] && pic.dst && pic.width > 0 && pic.height > 0
-        && pic.out_width > 0 && pic.out_height > 0 && pic.out_width <= pic.width && pic.out_height <= pic.height
-        && pic.dst_stride >= row_bytes, "iiwt_pack_wide_batch: picture %d: bad geometry", p);
+    const SchroHipIwtPackWidePicture & in = pictures[p];
+    PackPic pic = common_fields (in);
+    SCHRO_HIP_REQUIRE (is_wide_format (in.format), "%s: picture %d: format 0x%x is not v216 / ARGB / AY64", who, p, in.format);
+    const bool v216 = in.format == SCHRO_HIP_FORMAT_v216;
+    const int row_bytes = v216 ? 8 * (pic.out_width / 2) : in.format == SCHRO_HIP_FORMAT_ARGB ? 4 * pic.out_width : 8 * pic.out_width;
+    if (int r = check_geometry (who, p, pic, row_bytes))
+      return r;
     // (no chroma resampling of s16 / s32 frames on the reference's path: as schro_hip_pack_wide_batch)
-    SCHRO_HIP_REQUIRE (pic.v_shift == 0 && pic.h_shift == (v216 ? 1 : 0), "iiwt_pack_wide_batch: picture %d: the source must be %s", p,
+    SCHRO_HIP_REQUIRE (pic.v_shift == 0 && pic.h_shift == (v216 ? 1 : 0), "%s: picture %d: the source must be %s", who, p,
         v216 ? "4:2:2" : "4:4:4");
-    SCHRO_HIP_REQUIRE (pic.shift >= 0 && pic.shift < 8 * bps, "iiwt_pack_wide_batch: picture %d: shift %d", p, pic.shift);
-    bool fits = level_on && (level_all || wide_level_combination (pic.format, filter, bps)) && row_bytes > 0
-        && ((((uintptr_t) pic.dst | (uintptr_t) pic.dst_stride) & 15) == 0);
-    const size_t dst_bytes = (size_t) pic.dst_stride * pic.out_height;
+    SCHRO_HIP_REQUIRE (in.shift >= 0 && in.shift < 8 * bps, "%s: picture %d: shift %d", who, p, in.shift);
     for (int c = 0; c < 3; c++) {
-      // (what schro_hip_iiwt_batch asks of every component: whole transform levels, rows that hold the component)
-      const int w = c ? pic.width >> pic.h_shift : pic.width, h = pic.height;
-      SCHRO_HIP_REQUIRE (w % (1 << depth) == 0 && h % (1 << depth) == 0 && w > 0 && (w << (c ? pic.h_shift : 0)) == pic.width,
-          "iiwt_pack_wide_batch: picture %d component %d: size %dx%d is not a multiple of 2^depth", p, c, w, h);
-      SCHRO_HIP_REQUIRE (pic.src_stride[c] >= w * bps,
-          "iiwt_pack_wide_batch: picture %d component %d: stride %d does not hold %d samples", p, c, pic.src_stride[c], w);
-      fits = fits && ((((uintptr_t) pic.src[c] | (uintptr_t) pic.src_stride[c]) & (bps - 1)) == 0)
-          && pack8_apart (pic.dst, dst_bytes, pic.src[c], (size_t) pic.src_stride[c] * h);
+      if (int r = check_component (who, p, c, pic, depth, bps))
+        return r;
+      pic.px_row_bytes[c] = pic.cw (c) * bps;
+      pic.px_rows[c] = pic.ch (c);
     }
-    level[(size_t) p] = fits;
-    nlevel += fits;
+    pic.level = level_on && (level_all || wide_level_combination (in.format, filter, bps)) && row_bytes > 0 && level_fits (pic, bps);
+    nlevel += pic.level;
+    pics.push_back (pic);
   }
-  // the queue's grow-only block (shared with the v210 and the 8-bit calls: in-order reuse on the queue): per level picture
-  // the three compact LL planes of level 0 (depth > 1), per two-pass picture its three pixel planes
-  auto ll_stride = [&](int w) { return (int) round_up ((size_t) (w >> 1) * bps, 128); };
-  size_t need = 0;
-  for (int p = 0; p < npictures; p++)
-    for (int c = 0; c < 3; c++) {
-      const SchroHipIwtPackWidePicture & pic = pictures[p];
-      const int w = c ? pic.width >> pic.h_shift : pic.width, h = pic.height;
-      if (!level[(size_t) p])
-        need += round_up (round_up ((size_t) w * bps, 64) * (size_t) h, 256);
-      else if (depth > 1)
-        need += round_up ((size_t) ll_stride (w) * (size_t) (h >> 1), 256);
-    }
-  const int q = ctx->cur;
-  if (ctx->pack_tmp_size_q[q] < need) {
-    if (ctx->pack_tmp_q[q]) {
-      SCHRO_HIP_CHECK (hipStreamSynchronize (ctx->stream));
-      SCHRO_HIP_CHECK (hipFree (ctx->pack_tmp_q[q]));
-      ctx->pack_tmp_q[q] = nullptr;
-      ctx->pack_tmp_size_q[q] = 0;
-    }
-    SCHRO_HIP_CHECK (hipMalloc (&ctx->pack_tmp_q[q], need));
-    ctx->pack_tmp_size_q[q] = need;
-  }
-  size_t at = 0;
-  int r = 0;
+  char *block;
+  int r = lay_out_block (ctx, pics, depth, bps, &block);
+  if (r)
+    return r;
 
-  // ---- the level route: levels depth-1 .. 1 by the level loop into the LL planes, then the finest level + pack ----
   if (nlevel) {
     std::vector < SchroHipIwtPlane > coarse;
     std::vector < WideJob > wj[2];      // [0] ARGB / AY64, [1] v216: one launch each
     int tiles[2] = { 0, 0 };
     for (int p = 0; p < npictures; p++) {
-      if (!level[(size_t) p])
+      if (!pics[(size_t) p].level)
         continue;
-      const SchroHipIwtPackWidePicture & pic = pictures[p];
-      const int v216 = pic.format == SCHRO_HIP_FORMAT_v216;
+      const SchroHipIwtPackWidePicture & in = pictures[p];
+      const int v216 = in.format == SCHRO_HIP_FORMAT_v216;
       int cols, rows;
       iiwt_wide_geometry (filter, v216, &cols, &rows);
-      WideJob j;
-      memset (&j, 0, sizeof (j));
-      for (int c = 0; c < 3; c++) {
-        const int w = c ? pic.width >> pic.h_shift : pic.width, h = pic.height;
-        j.src[c] = pic.src[c];
-        j.src_stride[c] = pic.src_stride[c];
-        if (depth > 1) {
-          // the level-1 view of the coefficient frame {w / 2, h / 2, stride x 2} (schroparams.c:319-352), depth - 1 levels
-          void *t = (char *) ctx->pack_tmp_q[q] + at;
-          at += round_up ((size_t) ll_stride (w) * (size_t) (h >> 1), 256);
-          SchroHipIwtPlane pl;
-          memset (&pl, 0, sizeof (pl));
-          pl.src = pic.src[c];
-          pl.src_stride = 2 * pic.src_stride[c];
-          pl.dst = t;
-          pl.dst_stride = ll_stride (w);
-          pl.width = w >> 1;
-          pl.height = h >> 1;
-          coarse.push_back (pl);
-          j.ll[c] = t;
-          j.ll_stride[c] = ll_stride (w);
-        } else {
-          j.ll[c] = pic.src[c];             // (the frame's LL quadrant)
-          j.ll_stride[c] = 2 * pic.src_stride[c];
-        }
-        // 8-byte loads of the four bands: whole groups of samples per row, 8-byte aligned rows and band origins
-        const int nc = w >> 1, vl = 8 / bps;
-        const uintptr_t bits = (uintptr_t) j.ll[c] | (uintptr_t) j.ll_stride[c] | (uintptr_t) pic.src[c] | (uintptr_t) pic.src_stride[c]
-            | (uintptr_t) nc * bps;
-        if (nc % vl == 0 && nc >= vl && (bits & 7) == 0)
-          j.flags |= 1 << c;
-      }
-      if (pic.format == SCHRO_HIP_FORMAT_AY64)
-        j.flags |= 8;
-      j.w = pic.width;
-      j.h = pic.height;
-      j.out_w = pic.out_width;
-      j.out_h = pic.out_height;
-      j.dst = pic.dst;
-      j.dst_stride = pic.dst_stride;
-      j.shift = pic.shift;
       // (v216: a tile is `cols` output pairs = luma columns; the luma columns from out_width / 2 on are never lifted)
-      j.tiles_x = div_up (v216 ? pic.out_width / 2 : pic.out_width, cols);
-      j.tile_base = tiles[v216];
-      tiles[v216] += j.tiles_x * div_up (pic.out_height, rows);
+      WideJob j = level_job < WideJob > (pics[(size_t) p], block, depth, bps, v216 ? in.out_width / 2 : in.out_width, cols, rows,
+          tiles[v216], coarse);
+      if (in.format == SCHRO_HIP_FORMAT_AY64)
+        j.flags |= 8;
+      j.shift = in.shift;
       wj[v216].push_back (j);
     }
-    if (!coarse.empty ())
-      r = schro_hip_iiwt_batch (ctx, coarse.data (), (int) coarse.size (), depth - 1, filter, bps);
-    for (int v216 = 0; v216 < 2 && !r; v216++) {
-      if (wj[v216].empty ())
-        continue;
-      void *d_wj = nullptr;
-      r = push_args (ctx, wj[v216].data (), sizeof (WideJob) * wj[v216].size (), &d_wj);
-      if (r)
-        break;
-      ProfileScope ps (ctx, SCHRO_HIP_KERNEL_IIWT_FINEST);
-      r = launch_iiwt_wide (ctx->stream, (const WideJob *) d_wj, (int) wj[v216].size (), tiles[v216], filter, bps, v216);
-    }
+    r = coarse_levels (ctx, coarse, depth, filter, bps);
+    for (int v216 = 0; v216 < 2 && !r; v216++)
+      r = finest_level (ctx, wj[v216], [&](const WideJob * d, int n) { return launch_iiwt_wide (ctx->stream, d, n, tiles[v216], filter, bps, v216); });
     if (r)
       return r;
     ctx->wide_routes[SCHRO_HIP_WIDE_ROUTE_LEVEL] += nlevel;
@@ -694,48 +601,19 @@ schro_hip_iiwt_pack_wide_batch (SchroHipContext * ctx, const SchroHipIwtPackWide
       return 0;
   }
 
-  // ---- the two passes (the general form): transform into pixel planes, the shift, then the pack ----
+  // transform into pixel planes, the shift, then the pack
   std::vector < SchroHipIwtPlane > planes;
   std::vector < SchroHipPackPlane > packs;
   std::vector < int >shifts;            // the distinct non-zero shifts of the call
   for (int p = 0; p < npictures; p++) {
-    if (level[(size_t) p])
+    if (pics[(size_t) p].level)
       continue;
-    const SchroHipIwtPackWidePicture & pic = pictures[p];
-    SchroHipPackPlane pk;
-    memset (&pk, 0, sizeof (pk));
-    for (int c = 0; c < 3; c++) {
-      const int w = c ? pic.width >> pic.h_shift : pic.width, h = pic.height;
-      const int stride = (int) round_up ((size_t) w * bps, 64);
-      void *t = (char *) ctx->pack_tmp_q[q] + at;
-      at += round_up ((size_t) stride * (size_t) h, 256);
-      SchroHipIwtPlane pl;
-      memset (&pl, 0, sizeof (pl));
-      pl.src = pic.src[c];
-      pl.src_stride = pic.src_stride[c];
-      pl.dst = t;
-      pl.dst_stride = stride;
-      pl.width = w;
-      pl.height = h;
-      planes.push_back (pl);
-      pk.src[c] = (const uint8_t *) t;
-      pk.src_stride[c] = stride;
-    }
-    pk.src_width = pic.out_width;       // (the picture inside the transform's padded size: crop, schrovirtframe.c:1823-1853)
-    pk.src_height = pic.out_height;
-    pk.src_h_shift = pic.h_shift;
-    pk.src_v_shift = pic.v_shift;
-    pk.dst = pic.dst;
-    pk.dst_stride = pic.dst_stride;
-    pk.width = pic.out_width;
-    pk.height = pic.out_height;
-    pk.format = pic.format;
-    packs.push_back (pk);
-    bool seen = pic.shift == 0;
+    two_pass_picture (pics[(size_t) p], block, pictures[p].format, planes, packs);
+    bool seen = pictures[p].shift == 0;
     for (int s : shifts)
-      seen = seen || s == pic.shift;
+      seen = seen || s == pictures[p].shift;
     if (!seen)
-      shifts.push_back (pic.shift);
+      shifts.push_back (pictures[p].shift);
   }
   r = schro_hip_iiwt_batch (ctx, planes.data (), (int) planes.size (), depth, filter, bps);
   for (size_t n = 0; n < shifts.size () && !r; n++) {
@@ -743,11 +621,11 @@ schro_hip_iiwt_pack_wide_batch (SchroHipContext * ctx, const SchroHipIwtPackWide
     std::vector < SchroHipDcPlane > sp;
     size_t k = 0;
     for (int p = 0; p < npictures; p++) {
-      if (level[(size_t) p])
+      const PackPic & pic = pics[(size_t) p];
+      if (pic.level)
         continue;
-      const SchroHipIwtPackWidePicture & pic = pictures[p];
       for (int c = 0; c < 3; c++, k++) {
-        if (pic.shift != shifts[n])
+        if (pictures[p].shift != shifts[n])
           continue;
         SchroHipDcPlane d;
         d.data = planes[k].dst;
@@ -769,11 +647,5 @@ schro_hip_iiwt_pack_wide_batch (SchroHipContext * ctx, const SchroHipIwtPackWide
 extern "C" int
 schro_hip_wide_routes (SchroHipContext * ctx, long long counts[SCHRO_HIP_WIDE_ROUTES], int reset)
 {
-  SCHRO_HIP_REQUIRE (ctx && counts, "wide_routes: bad arguments");
-  for (int k = 0; k < SCHRO_HIP_WIDE_ROUTES; k++) {
-    counts[k] = ctx->wide_routes[k];
-    if (reset)
-      ctx->wide_routes[k] = 0;
-  }
-  return 0;
+  return read_routes ("wide_routes", ctx, &SchroHipContext::wide_routes, counts, reset);
 }

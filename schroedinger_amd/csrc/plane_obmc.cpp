@@ -639,13 +639,7 @@ schro_hip_obmc_prediction_epoch (SchroHipContext * ctx)
 int
 schro_hip_obmc_routes (SchroHipContext * ctx, long long counts[SCHRO_HIP_OBMC_ROUTES], int reset)
 {
-  SCHRO_HIP_REQUIRE (ctx && counts, "obmc_routes: bad arguments");
-  for (int k = 0; k < SCHRO_HIP_OBMC_ROUTES; k++) {
-    counts[k] = ctx->obmc_routes[k];
-    if (reset)
-      ctx->obmc_routes[k] = 0;
-  }
-  return 0;
+  return read_routes ("obmc_routes", ctx, &SchroHipContext::obmc_routes, counts, reset);
 }
 
 }                               // extern "C"

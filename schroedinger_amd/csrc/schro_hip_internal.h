@@ -1241,7 +1241,23 @@ namespace schro {
 // on the context's stream before the next 63 distinct tables
 int push_args (SchroHipContext * ctx, const void *host, size_t bytes,
     void **dev);
+// a grow-only device block of one queue (`block`, `size`: the context's members for the selected queue): nothing is
+// allocated, freed or waited for while it is large enough; a block that must grow waits for the queue once
+int grow_block (SchroHipContext * ctx, void *&block, size_t & size, size_t bytes);
 int ensure_scratch (SchroHipContext * ctx, size_t bytes);
+// schro_hip_obmc_routes / _v210_routes / _pack8_routes / _wide_routes, each on its array of the context
+template < int N > int
+read_routes (const char *who, SchroHipContext * ctx, long long (SchroHipContext::*routes)[N], long long *counts, int reset)
+{
+  SCHRO_HIP_REQUIRE (ctx && counts, "%s: bad arguments", who);
+  for (int k = 0; k < N; k++) {
+    counts[k] = (ctx->*routes)[k];
+    if (reset)
+      (ctx->*routes)[k] = 0;
+  }
+  return 0;
+}
+// a device copy
 // a device copy of a job table of any size, valid for the launches enqueued on the context's stream
 // before the fourth call from now on this queue
 int push_big_table (SchroHipContext * ctx, const void *host, size_t bytes, void **dev);
