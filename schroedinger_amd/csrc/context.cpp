@@ -285,14 +285,8 @@ dc_edge_for (SchroHipContext * ctx, int njobs, int max_rows, int max_w, unsigned
   // (8 words in front: the launch's ticket and finish counters)
   const size_t bytes = ((size_t) njobs * strips * max_w + 8) * sizeof (unsigned long long);
   if (bytes > size) {
-    if (buf) {
-      SCHRO_HIP_CHECK (hipStreamSynchronize (ctx->stream));
-      SCHRO_HIP_CHECK (hipFree (buf));
-      buf = nullptr;
-      size = 0;
-    }
-    SCHRO_HIP_CHECK (hipMalloc (&buf, bytes));
-    size = bytes;
+    if (const int r = grow_block (ctx, buf, size, bytes))
+      return r;
     // tag 0 = "never written": epochs start at 1
     SCHRO_HIP_CHECK (hipMemsetAsync (buf, 0, bytes, ctx->stream));
   }

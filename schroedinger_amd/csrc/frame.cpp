@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <algorithm>
+#include <memory>
 
 using namespace schro;
 
@@ -18,6 +19,212 @@ frame_ctx (const SchroHipFrame * f)
   if (!f || !f->domain || !(f->domain->flags & SCHRO_MEMORY_DOMAIN_HIP))
     return nullptr;
   return f->domain->ctx;
+}
+
+static int
+format_bpp (int format)
+{
+  switch (SCHRO_HIP_FORMAT_DEPTH (format)) {
+    case SCHRO_HIP_FORMAT_DEPTH_U8:
+      return 1;
+    case SCHRO_HIP_FORMAT_DEPTH_S16:
+      return 2;
+    case SCHRO_HIP_FORMAT_DEPTH_S32:
+      return 4;
+  }
+  return 0;
+}
+
+// ---- the pieces the transform-data calls stand on: each blind to its caller ----------------------
+
+// a refusal (or failure) of a piece is the call's
+#define SCHRO_HIP_TRY(call) do { if (const int r_ = (call)) return r_; } while (0)
+
+// The transform size of component k (SchroHipParams and SchroHipLowDelayParams name the four members alike).
+struct IwtSize {
+  int w, h;
+};
+template < typename Params > static IwtSize
+iwt_size (const Params * params, int k)
+{
+  if (k)
+    return { params->iwt_chroma_width, params->iwt_chroma_height };
+  return { params->iwt_luma_width, params->iwt_luma_height };
+}
+
+// a component holds that size; bpp != 0: the size is one, and the stride holds a row of it
+static bool
+holds (const SchroHipFrameData & c, IwtSize s, int bpp)
+{
+  return s.w <= c.width && s.h <= c.height && (!bpp || (s.w > 0 && s.h > 0 && (long long) c.stride >= (long long) s.w * bpp));
+}
+
+// ... said in the two wordings the calls have: bpp 0 the pixel path's and the slice calls', else the noarith calls'
+static int
+require_holds (const char *who, int k, const SchroHipFrameData & c, IwtSize s, int bpp)
+{
+  if (bpp)
+    SCHRO_HIP_REQUIRE (holds (c, s, bpp), "%s: component %d (%d x %d, stride %d) does not hold the %d x %d transform", who, k, c.width,
+        c.height, c.stride, s.w, s.h);
+  else
+    SCHRO_HIP_REQUIRE (holds (c, s, 0), "%s: component %d smaller than the iwt size", who, k);
+  return 0;
+}
+
+// The members the three fused-picture structs (include/schro_hip.h) share, and the refusals their calls share.  `v210`:
+// that call's refusals as they have been since r05 -- one text for "not shifted" and "smaller", of the components the luma
+// alone, the packed frame's size left to the plane layer; the others refuse each on its own.  `also (k)`: what a call
+// adds to component k, a refusal of its own included, in its place behind that component's.
+template < typename Picture, typename PerComponent > static int
+fill_fused_picture (Picture & pic, const SchroHipFrame * packed, const SchroHipFrame * transform_frame, const SchroHipParams * params,
+    bool v210, PerComponent also)
+{
+  const char *who = "inverse_iwt_transform_convert";
+  const IwtSize luma = iwt_size (params, 0), chroma = iwt_size (params, 1);
+  memset (&pic, 0, sizeof (pic));
+  pic.width = luma.w;
+  pic.height = luma.h;
+  pic.h_shift = SCHRO_HIP_FORMAT_H_SHIFT (transform_frame->format);
+  pic.v_shift = SCHRO_HIP_FORMAT_V_SHIFT (transform_frame->format);
+  const bool shifted = (chroma.w << pic.h_shift) == luma.w && (chroma.h << pic.v_shift) == luma.h;
+  if (v210) {
+    SCHRO_HIP_REQUIRE (holds (transform_frame->components[0], luma, 0) && shifted,
+        "%s: the frame is smaller than params' transform size (or the chroma size is not the luma size shifted)", who);
+  } else {
+    SCHRO_HIP_REQUIRE (shifted, "%s: params' chroma transform size is not the luma size shifted by the frame's chroma format", who);
+    SCHRO_HIP_REQUIRE (packed->width <= luma.w && packed->height <= luma.h, "%s: the packed frame is larger than the transform", who);
+  }
+  pic.dst = (uint8_t *) packed->components[0].data;
+  pic.dst_stride = packed->components[0].stride;
+  pic.out_width = packed->width;
+  pic.out_height = packed->height;
+  for (int k = 0; k < 3; k++) {
+    SCHRO_HIP_TRY (v210 ? 0 : require_holds (who, k, transform_frame->components[k], iwt_size (params, k), 0));
+    pic.src[k] = transform_frame->components[k].data;
+    pic.src_stride[k] = transform_frame->components[k].stride;
+    SCHRO_HIP_TRY (also (k));
+  }
+  return 0;
+}
+
+// One block of the domain for a call that copies up, runs its batch, copies down and waits for it: three parts one behind
+// the other, the second and third at multiples of `align` -- the result in front (kResultFront or kNoarithDecodeFront
+// bytes), then the field, then the bytes, for the calls that have a result.  The calls make their own copies; finish ()
+// waits (unless wait () already has, for the calls that fetch the bytes once the result has told how many), frees, and
+// gives r or else what the wait said.
+constexpr size_t kResultFront = 256, kNoarithDecodeFront = 512;
+static_assert (sizeof (SchroHipNoarithResult) <= kResultFront && sizeof (SchroHipMotionEncodeResult) <= kResultFront
+    && sizeof (SchroHipMotionDecodeResult) <= kResultFront, "the result sits in front of the field and the bytes");
+static_assert (sizeof (SchroHipNoarithDecodeResult) <= kNoarithDecodeFront, "the result sits in front of the bytes");
+
+enum { kFront, kField, kBytes };        // (the parts of a call with a result)
+struct SyncBlock {
+  SchroHipContext *ctx;
+  const size_t at[3];
+  char *d;                      // NULL: no memory (the allocation has said so)
+  int rs = 0;
+  bool waited = false;
+    SyncBlock (SchroHipContext * c, size_t first, size_t second, size_t third, size_t align = 256):ctx (c),
+      at { 0, round_up (first, align), round_up (first, align) + round_up (second, align) },
+      d ((char *) schro_hip_domain_alloc (c, at[2] + (third ? third : 1)))
+  {
+  }
+  ~SyncBlock ()
+  {
+    if (d)
+      schro_hip_domain_free (ctx, d);
+  }
+  char *part (int i) const
+  {
+    return d + at[i];
+  }
+  int wait ()
+  {
+    waited = true;
+    return rs = schro_hip_synchronize (ctx);
+  }
+  int finish (int r)
+  {
+    if (!waited)
+      wait ();                  // the host buffers are filled, d is free again
+    schro_hip_domain_free (ctx, d);
+    d = nullptr;
+    return r ? r : rs;
+  }
+};
+
+// the LL bands of an intra picture, for schro_hip_dc_predict_batch
+static void
+ll_planes (SchroHipDcPlane ll[3], const SchroHipFrame * transform_frame, const SchroHipParams * params)
+{
+  for (int k = 0; k < 3; k++) {
+    const SchroHipFrameData & c = transform_frame->components[k];
+    const IwtSize s = iwt_size (params, k);
+    ll[k].data = c.data;
+    ll[k].stride = c.stride << params->transform_depth; // schro_subband_get_frame_data, schroparams.c:319-352
+    ll[k].width = s.w >> params->transform_depth;
+    ll[k].height = s.h >> params->transform_depth;
+  }
+}
+
+// the codeblock records of component k, laid out for its stride
+static int
+layout_records (const char *who, int k, IwtSize s, const SchroHipParams * params, int stride, int bpp, std::vector < SchroHipCodeblock > &recs)
+{
+  const int depth = params->transform_depth;
+  const int n = schro_hip_codeblock_layout (s.w, s.h, depth, params->horiz_codeblocks, params->vert_codeblocks, stride, bpp, nullptr, 0);
+  if (n <= 0)
+    return n < 0 ? n : set_error (SCHRO_HIP_EINVAL, "%s: component %d has no codeblocks", who, k);
+  recs.resize (n);
+  (void) schro_hip_codeblock_layout (s.w, s.h, depth, params->horiz_codeblocks, params->vert_codeblocks, stride, bpp, recs.data (), n);
+  return 0;
+}
+
+// ... and a call's quant indices in them
+static int
+set_quant_indices (const char *who, int k, std::vector < SchroHipCodeblock > &recs, const int *quant_indices)
+{
+  for (size_t c = 0; c < recs.size (); c++) {
+    SCHRO_HIP_REQUIRE (quant_indices[c] >= 0 && quant_indices[c] <= 60, "%s: component %d, codeblock %d: quant index %d", who, k, (int) c,
+        quant_indices[c]);
+    recs[c].quant_index = (unsigned char) quant_indices[c];
+  }
+  return 0;
+}
+
+// the header fields of the two noarith picture structs
+template < typename Picture > static void
+fill_noarith_header (Picture & pic, const SchroHipParams * params)
+{
+  memset (&pic, 0, sizeof (pic));
+  pic.transform_depth = params->transform_depth;
+  pic.codeblock_mode_index = params->codeblock_mode_index;
+  for (int l = 0; l <= params->transform_depth; l++) {
+    pic.horiz_codeblocks[l] = params->horiz_codeblocks[l];
+    pic.vert_codeblocks[l] = params->vert_codeblocks[l];
+  }
+}
+
+// what the context's tables of a picture geometry (FrameQuantTable, FrameHistTable) were laid out for
+static std::vector < int >
+table_key (const SchroHipFrame * iwt_frame, const SchroHipParams * params, int bpp)
+{
+  return { bpp, params->transform_depth, params->iwt_luma_width, params->iwt_luma_height, params->iwt_chroma_width, params->iwt_chroma_height,
+    iwt_frame->components[0].stride, iwt_frame->components[1].stride, iwt_frame->components[2].stride };
+}
+
+// dest and src over the components' common size (schro_frame_add, _subtract, the s16 -> u8 convert)
+static void
+common_planes (SchroHipConvertPlane planes[3], const SchroHipFrame * dest, const SchroHipFrame * src)
+{
+  for (int k = 0; k < 3; k++) {
+    planes[k].src = src->components[k].data;
+    planes[k].src_stride = src->components[k].stride;
+    planes[k].dst = (uint8_t *) dest->components[k].data;
+    planes[k].dst_stride = dest->components[k].stride;
+    planes[k].width = std::min (dest->components[k].width, src->components[k].width);
+    planes[k].height = std::min (dest->components[k].height, src->components[k].height);
+  }
 }
 
 extern "C" {
@@ -44,20 +251,6 @@ schro_hip_context_set_stage_completion (SchroHipContext * ctx, int complete_on_r
 {
   SCHRO_HIP_REQUIRE (ctx, "set_stage_completion: no context");
   ctx->stage_complete = complete_on_return != 0;
-  return 0;
-}
-
-static int
-format_bpp (int format)
-{
-  switch (SCHRO_HIP_FORMAT_DEPTH (format)) {
-    case SCHRO_HIP_FORMAT_DEPTH_U8:
-      return 1;
-    case SCHRO_HIP_FORMAT_DEPTH_S16:
-      return 2;
-    case SCHRO_HIP_FORMAT_DEPTH_S32:
-      return 4;
-  }
   return 0;
 }
 
@@ -345,10 +538,10 @@ schro_hipframe_iwt_transform (SchroHipContext * ctx, SchroHipFrame * frame, cons
   for (int k = 0; k < 3; k++) {
     planes[k].src = planes[k].dst = frame->components[k].data;
     planes[k].src_stride = planes[k].dst_stride = frame->components[k].stride;
-    planes[k].width = k ? params->iwt_chroma_width : params->iwt_luma_width;
-    planes[k].height = k ? params->iwt_chroma_height : params->iwt_luma_height;
-    SCHRO_HIP_REQUIRE (planes[k].width <= frame->components[k].width && planes[k].height <= frame->components[k].height,
-        "hipframe_iwt_transform: component %d smaller than the iwt size", k);
+    const IwtSize s = iwt_size (params, k);
+    planes[k].width = s.w;
+    planes[k].height = s.h;
+    SCHRO_HIP_TRY (require_holds ("hipframe_iwt_transform", k, frame->components[k], s, 0));
   }
   return stage_done (ctx, iwt_batch_run (ctx, planes, 3, params->transform_depth, params->wavelet_filter_index, bpp, true));
 }
@@ -369,59 +562,47 @@ inverse_iwt_transform (SchroHipFrame * frame, SchroHipFrame * transform_frame, S
 
   // host coefficients are staged on the device first (the H2D step of
   // schro_frame_inverse_iwt_transform_cuda, schrogpuframe.c:584-599)
-  SchroHipFrame *staged = nullptr;
+  std::unique_ptr < SchroHipFrame, void (*)(SchroHipFrame *) > staged (nullptr, schro_hip_frame_unref);
   SchroHipFrame *src = transform_frame;
   SCHRO_HIP_REQUIRE (ctx->stage_complete || frame_ctx (transform_frame),
       "inverse_iwt_transform: with stage completion off the transform frame must be on the device "
       "(schro_frame_to_hip_async on the copy queue)");
   if (!frame_ctx (transform_frame)) {
-    staged = schro_hip_frame_new_and_alloc (ctx, transform_frame->format, transform_frame->width,
-        transform_frame->height, 0);
+    staged.reset (schro_hip_frame_new_and_alloc (ctx, transform_frame->format, transform_frame->width, transform_frame->height, 0));
     if (!staged)
       return SCHRO_HIP_ENOMEM;
-    int r = schro_frame_to_hip (staged, transform_frame);
-    if (r) {
-      schro_hip_frame_unref (staged);
-      return r;
-    }
-    src = staged;
+    SCHRO_HIP_TRY (schro_frame_to_hip (staged.get (), transform_frame));
+    src = staged.get ();
   }
+  const char *who = "inverse_iwt_transform";
   SchroHipIwtPlane planes[3];
   memset (planes, 0, sizeof (planes));
   for (int k = 0; k < 3; k++) {
+    const IwtSize s = iwt_size (params, k);
     planes[k].src = src->components[k].data;
     planes[k].src_stride = src->components[k].stride;
     planes[k].dst = frame->components[k].data;
     planes[k].dst_stride = frame->components[k].stride;
-    planes[k].width = k ? params->iwt_chroma_width : params->iwt_luma_width;
-    planes[k].height = k ? params->iwt_chroma_height : params->iwt_luma_height;
-    bool fits = planes[k].width <= src->components[k].width && planes[k].height <= src->components[k].height;
+    planes[k].width = s.w;
+    planes[k].height = s.h;
+    SCHRO_HIP_TRY (require_holds (who, k, src->components[k], s, 0));
     if (combine) {
       // the picture inside the transform's size (schrodecoder.c:1788-1790 converts with a crop; the render adds
       // over motion->width x height)
       planes[k].combine = combine;
-      planes[k].out_width = std::min (frame->components[k].width, planes[k].width);
-      planes[k].out_height = std::min (frame->components[k].height, planes[k].height);
+      planes[k].out_width = std::min (frame->components[k].width, s.w);
+      planes[k].out_height = std::min (frame->components[k].height, s.h);
       if (combine == 1) {
         planes[k].pred = (const uint8_t *) prediction->components[k].data;
         planes[k].pred_stride = prediction->components[k].stride;
-        fits = fits && prediction->components[k].width >= planes[k].out_width && prediction->components[k].height >= planes[k].out_height;
+        SCHRO_HIP_TRY (require_holds (who, k, prediction->components[k], { planes[k].out_width, planes[k].out_height }, 0));
       }
     } else {
-      fits = fits && planes[k].width <= frame->components[k].width && planes[k].height <= frame->components[k].height;
-    }
-    if (!fits) {
-      if (staged)
-        schro_hip_frame_unref (staged);
-      return set_error (SCHRO_HIP_EINVAL, "inverse_iwt_transform: component %d smaller than the iwt size", k);
+      SCHRO_HIP_TRY (require_holds (who, k, frame->components[k], s, 0));
     }
   }
-  int r = schro_hip_iiwt_batch (ctx, planes, 3, params->transform_depth,
-      params->wavelet_filter_index, bpp);
-  r = stage_done (ctx, r);
-  if (staged)
-    schro_hip_frame_unref (staged);
-  return r;
+  // (staged is released when the call returns: stage_done has waited for the queue -- it is a host frame's, above)
+  return stage_done (ctx, schro_hip_iiwt_batch (ctx, planes, 3, params->transform_depth, params->wavelet_filter_index, bpp));
 }
 
 int
@@ -450,42 +631,23 @@ schro_frame_inverse_iwt_transform_combine_hip (SchroHipFrame * output_frame, Sch
 // (prediction != NULL: the u8 frame schro_motion_render_hip (add = FALSE) wrote; x_combine's add, :1908-1921) or + 128:
 // schro_hip_iiwt_pack_u8_batch.  The planar picture is not written where its fused kernel applies.
 static int
-inverse_iwt_transform_pack8 (SchroHipFrame * packed, SchroHipFrame * transform_frame, SchroHipParams * params, SchroHipFrame * prediction)
+inverse_iwt_transform_pack8 (SchroHipFrame * packed, SchroHipFrame * transform_frame, SchroHipParams * params, SchroHipFrame * prediction, int bpp)
 {
   SchroHipContext *ctx = frame_ctx (packed);
-  const int bpp = format_bpp (transform_frame->format);
-  SCHRO_HIP_REQUIRE (bpp == 2 || bpp == 4, "inverse_iwt_transform_convert: the transform frame must be s16 or s32");
   SCHRO_HIP_REQUIRE (!prediction || (prediction->domain == packed->domain && format_bpp (prediction->format) == 1),
       "inverse_iwt_transform_combine_convert: the prediction must be the u8 frame of schro_motion_render_hip (add = FALSE) in the same domain");
   SchroHipIwtPack8Picture pic;
-  memset (&pic, 0, sizeof (pic));
-  pic.width = params->iwt_luma_width;
-  pic.height = params->iwt_luma_height;
-  pic.h_shift = SCHRO_HIP_FORMAT_H_SHIFT (transform_frame->format);
-  pic.v_shift = SCHRO_HIP_FORMAT_V_SHIFT (transform_frame->format);
-  SCHRO_HIP_REQUIRE ((params->iwt_chroma_width << pic.h_shift) == pic.width && (params->iwt_chroma_height << pic.v_shift) == pic.height,
-      "inverse_iwt_transform_convert: params' chroma transform size is not the luma size shifted by the frame's chroma format");
-  pic.out_width = std::min (packed->width, pic.width);
-  pic.out_height = std::min (packed->height, pic.height);
-  SCHRO_HIP_REQUIRE (pic.out_width == packed->width && pic.out_height == packed->height,
-      "inverse_iwt_transform_convert: the packed frame is larger than the transform");
-  for (int k = 0; k < 3; k++) {
-    pic.src[k] = transform_frame->components[k].data;
-    pic.src_stride[k] = transform_frame->components[k].stride;
-    const int w = k ? params->iwt_chroma_width : params->iwt_luma_width, h = k ? params->iwt_chroma_height : params->iwt_luma_height;
-    SCHRO_HIP_REQUIRE (w <= transform_frame->components[k].width && h <= transform_frame->components[k].height,
-        "inverse_iwt_transform_convert: component %d smaller than the iwt size", k);
-    if (prediction) {
-      const int ow = k ? (pic.out_width + pic.h_shift) >> pic.h_shift : pic.out_width;
-      const int oh = k ? (pic.out_height + pic.v_shift) >> pic.v_shift : pic.out_height;
-      SCHRO_HIP_REQUIRE (prediction->components[k].width >= ow && prediction->components[k].height >= oh,
-          "inverse_iwt_transform_combine_convert: component %d of the prediction is smaller than the picture", k);
-      pic.pred[k] = (const uint8_t *) prediction->components[k].data;
-      pic.pred_stride[k] = prediction->components[k].stride;
-    }
-  }
-  pic.dst = (uint8_t *) packed->components[0].data;
-  pic.dst_stride = packed->components[0].stride;
+  SCHRO_HIP_TRY (fill_fused_picture (pic, packed, transform_frame, params, false,[&](int k) {
+        if (!prediction)
+          return 0;
+        const int ow = k ? (pic.out_width + pic.h_shift) >> pic.h_shift : pic.out_width;
+        const int oh = k ? (pic.out_height + pic.v_shift) >> pic.v_shift : pic.out_height;
+        SCHRO_HIP_REQUIRE (prediction->components[k].width >= ow && prediction->components[k].height >= oh,
+            "inverse_iwt_transform_combine_convert: component %d of the prediction is smaller than the picture", k);
+        pic.pred[k] = (const uint8_t *) prediction->components[k].data;
+        pic.pred_stride[k] = prediction->components[k].stride;
+        return 0;
+      }));
   pic.format = packed->format;
   return stage_done (ctx, schro_hip_iiwt_pack_u8_batch (ctx, &pic, 1, params->transform_depth, params->wavelet_filter_index, bpp));
 }
@@ -493,35 +655,35 @@ inverse_iwt_transform_pack8 (SchroHipFrame * packed, SchroHipFrame * transform_f
 // ... and into a v216, ARGB or AY64 output picture -- the > 8-bit formats, no prediction (the reference has no > 8-bit inter
 // path) --, with x_combine's schro_frame_shift_right (schrodecoder.c:2013-2019) in the same call: schro_hip_iiwt_pack_wide_batch.
 static int
-inverse_iwt_transform_wide (SchroHipFrame * packed, SchroHipFrame * transform_frame, SchroHipParams * params, int shift)
+inverse_iwt_transform_wide (SchroHipFrame * packed, SchroHipFrame * transform_frame, SchroHipParams * params, int shift, int bpp)
 {
   SchroHipContext *ctx = frame_ctx (packed);
-  const int bpp = format_bpp (transform_frame->format);
-  SCHRO_HIP_REQUIRE (bpp == 2 || bpp == 4, "inverse_iwt_transform_convert: the transform frame must be s16 or s32");
   SchroHipIwtPackWidePicture pic;
-  memset (&pic, 0, sizeof (pic));
-  pic.width = params->iwt_luma_width;
-  pic.height = params->iwt_luma_height;
-  pic.h_shift = SCHRO_HIP_FORMAT_H_SHIFT (transform_frame->format);
-  pic.v_shift = SCHRO_HIP_FORMAT_V_SHIFT (transform_frame->format);
-  SCHRO_HIP_REQUIRE ((params->iwt_chroma_width << pic.h_shift) == pic.width && (params->iwt_chroma_height << pic.v_shift) == pic.height,
-      "inverse_iwt_transform_convert: params' chroma transform size is not the luma size shifted by the frame's chroma format");
-  SCHRO_HIP_REQUIRE (packed->width <= pic.width && packed->height <= pic.height,
-      "inverse_iwt_transform_convert: the packed frame is larger than the transform");
-  for (int k = 0; k < 3; k++) {
-    pic.src[k] = transform_frame->components[k].data;
-    pic.src_stride[k] = transform_frame->components[k].stride;
-    const int w = k ? params->iwt_chroma_width : params->iwt_luma_width, h = k ? params->iwt_chroma_height : params->iwt_luma_height;
-    SCHRO_HIP_REQUIRE (w <= transform_frame->components[k].width && h <= transform_frame->components[k].height,
-        "inverse_iwt_transform_convert: component %d smaller than the iwt size", k);
-  }
-  pic.dst = (uint8_t *) packed->components[0].data;
-  pic.dst_stride = packed->components[0].stride;
-  pic.out_width = packed->width;
-  pic.out_height = packed->height;
+  SCHRO_HIP_TRY (fill_fused_picture (pic, packed, transform_frame, params, false,[](int) { return 0; }));
   pic.format = packed->format;
   pic.shift = shift;
   return stage_done (ctx, schro_hip_iiwt_pack_wide_batch (ctx, &pic, 1, params->transform_depth, params->wavelet_filter_index, bpp));
+}
+
+// the three fused calls behind one door: the destination's format chooses (shift: the wide formats'; prediction: the 8-bit ones')
+static int
+inverse_iwt_transform_fused (SchroHipFrame * packed, SchroHipFrame * transform_frame, SchroHipParams * params, SchroHipFrame * prediction,
+    int shift)
+{
+  const bool pack8 = packed->format == SCHRO_HIP_FORMAT_YUYV || packed->format == SCHRO_HIP_FORMAT_UYVY || packed->format == SCHRO_HIP_FORMAT_AYUV;
+  SCHRO_HIP_REQUIRE (pack8 || ((packed->format == SCHRO_HIP_FORMAT_v210 || is_wide_format (packed->format)) && !prediction),
+      "inverse_iwt_transform_convert: the destination must be a YUYV, UYVY, AYUV or (without a prediction: the reference has no "
+      "> 8-bit inter path) v210, v216, ARGB or AY64 frame");
+  const int bpp = format_bpp (transform_frame->format);
+  SCHRO_HIP_REQUIRE (bpp == 2 || bpp == 4, "inverse_iwt_transform_convert: the transform frame must be s16 or s32");
+  if (pack8)
+    return inverse_iwt_transform_pack8 (packed, transform_frame, params, prediction, bpp);
+  if (is_wide_format (packed->format))
+    return inverse_iwt_transform_wide (packed, transform_frame, params, shift, bpp);
+  SchroHipContext *ctx = frame_ctx (packed);
+  SchroHipIwtPackPicture pic;
+  SCHRO_HIP_TRY (fill_fused_picture (pic, packed, transform_frame, params, true,[](int) { return 0; }));
+  return stage_done (ctx, schro_hip_iiwt_pack_v210_batch (ctx, &pic, 1, params->transform_depth, params->wavelet_filter_index, bpp));
 }
 
 int
@@ -530,33 +692,7 @@ schro_frame_inverse_iwt_transform_combine_convert_hip (SchroHipFrame * packed, S
 {
   SCHRO_HIP_REQUIRE (packed && transform_frame && params && frame_ctx (packed) && transform_frame->domain == packed->domain,
       "inverse_iwt_transform_convert: the packed frame and the transform frame must live in the same device domain");
-  if (packed->format == SCHRO_HIP_FORMAT_YUYV || packed->format == SCHRO_HIP_FORMAT_UYVY || packed->format == SCHRO_HIP_FORMAT_AYUV)
-    return inverse_iwt_transform_pack8 (packed, transform_frame, params, prediction);
-  SCHRO_HIP_REQUIRE ((packed->format == SCHRO_HIP_FORMAT_v210 || is_wide_format (packed->format)) && !prediction,
-      "inverse_iwt_transform_convert: the destination must be a YUYV, UYVY, AYUV or (without a prediction: the reference has no "
-      "> 8-bit inter path) v210, v216, ARGB or AY64 frame");
-  if (is_wide_format (packed->format))
-    return inverse_iwt_transform_wide (packed, transform_frame, params, 0);
-  SchroHipContext *ctx = frame_ctx (packed);
-  const int bpp = format_bpp (transform_frame->format);
-  SCHRO_HIP_REQUIRE (bpp == 2 || bpp == 4, "inverse_iwt_transform_convert: the transform frame must be s16 or s32");
-  SchroHipIwtPackPicture pic;
-  for (int k = 0; k < 3; k++) {
-    pic.src[k] = transform_frame->components[k].data;
-    pic.src_stride[k] = transform_frame->components[k].stride;
-  }
-  pic.width = params->iwt_luma_width;
-  pic.height = params->iwt_luma_height;
-  pic.h_shift = SCHRO_HIP_FORMAT_H_SHIFT (transform_frame->format);
-  pic.v_shift = SCHRO_HIP_FORMAT_V_SHIFT (transform_frame->format);
-  SCHRO_HIP_REQUIRE (pic.width <= transform_frame->components[0].width && pic.height <= transform_frame->components[0].height
-      && (params->iwt_chroma_width << pic.h_shift) == pic.width && (params->iwt_chroma_height << pic.v_shift) == pic.height,
-      "inverse_iwt_transform_convert: the frame is smaller than params' transform size (or the chroma size is not the luma size shifted)");
-  pic.dst = (uint8_t *) packed->components[0].data;
-  pic.dst_stride = packed->components[0].stride;
-  pic.out_width = packed->width;
-  pic.out_height = packed->height;
-  return stage_done (ctx, schro_hip_iiwt_pack_v210_batch (ctx, &pic, 1, params->transform_depth, params->wavelet_filter_index, bpp));
+  return inverse_iwt_transform_fused (packed, transform_frame, params, prediction, 0);
 }
 
 int
@@ -572,11 +708,9 @@ schro_frame_inverse_iwt_transform_shift_convert_hip (SchroHipFrame * packed, Sch
 {
   SCHRO_HIP_REQUIRE (packed && transform_frame && params && frame_ctx (packed) && transform_frame->domain == packed->domain,
       "inverse_iwt_transform_shift_convert: the packed frame and the transform frame must live in the same device domain");
-  if (is_wide_format (packed->format))
-    return inverse_iwt_transform_wide (packed, transform_frame, params, shift);
-  SCHRO_HIP_REQUIRE (shift == 0, "inverse_iwt_transform_shift_convert: a shift of %d with a format other than v216 / ARGB / AY64 "
-      "(schro_frame_inverse_iwt_transform_hip + schro_hipframe_shift_right + schro_hipframe_convert)", shift);
-  return schro_frame_inverse_iwt_transform_combine_convert_hip (packed, transform_frame, params, nullptr);
+  SCHRO_HIP_REQUIRE (shift == 0 || is_wide_format (packed->format), "inverse_iwt_transform_shift_convert: a shift of %d with a format "
+      "other than v216 / ARGB / AY64 (schro_frame_inverse_iwt_transform_hip + schro_hipframe_shift_right + schro_hipframe_convert)", shift);
+  return inverse_iwt_transform_fused (packed, transform_frame, params, nullptr, shift);
 }
 
 int
@@ -589,19 +723,17 @@ schro_hip_decode_lowdelay_transform_data (SchroHipFrame * transform_frame, const
   const int bpp = format_bpp (transform_frame->format);
   SCHRO_HIP_REQUIRE (bpp == 2 || bpp == 4, "decode_lowdelay_transform_data: the frame must be s16 or s32");
   for (int k = 0; k < 3; k++)
-    SCHRO_HIP_REQUIRE ((k ? params->iwt_chroma_width : params->iwt_luma_width) <= transform_frame->components[k].width
-        && (k ? params->iwt_chroma_height : params->iwt_luma_height) <= transform_frame->components[k].height,
-        "decode_lowdelay_transform_data: component %d smaller than the iwt size", k);
+    SCHRO_HIP_TRY (require_holds ("decode_lowdelay_transform_data", k, transform_frame->components[k], iwt_size (params, k), 0));
   // picture->lowdelay_buffer goes to the device as it is: compressed
-  void *d_slices = schro_hip_domain_alloc (ctx, slices_bytes ? slices_bytes : 1);
-  if (!d_slices)
+  SyncBlock blk (ctx, 0, 0, slices_bytes);
+  if (!blk.d)
     return SCHRO_HIP_ENOMEM;
   int r = 0;
-  if (hipMemcpyAsync (d_slices, slices, slices_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+  if (hipMemcpyAsync (blk.part (kBytes), slices, slices_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
     r = set_error (SCHRO_HIP_EDEVICE, "decode_lowdelay_transform_data: copy of %zu bytes failed", slices_bytes);
   if (!r) {
     SchroHipLowDelayPicture pic;
-    pic.slices = (const uint8_t *) d_slices;
+    pic.slices = (const uint8_t *) blk.part (kBytes);
     pic.slices_bytes = slices_bytes;
     for (int k = 0; k < 3; k++) {
       pic.comp[k] = transform_frame->components[k].data;
@@ -609,9 +741,7 @@ schro_hip_decode_lowdelay_transform_data (SchroHipFrame * transform_frame, const
     }
     r = schro_hip_lowdelay_batch (ctx, &pic, 1, params, bpp);
   }
-  const int rs = schro_hip_synchronize (ctx);   // the host buffer and d_slices are free again
-  schro_hip_domain_free (ctx, d_slices);
-  return r ? r : rs;
+  return blk.finish (r);
 }
 
 // schro_encoder_encode_lowdelay_transform_data (schrolowdelay.c:1150-1200) with frame->iwt_frame on the device: the bytes
@@ -627,37 +757,33 @@ schro_hip_encode_lowdelay_transform_data (const SchroHipFrame * iwt_frame, void 
   SCHRO_HIP_REQUIRE (bpp != 4, "encode_lowdelay_transform_data: s32 slices are not encoded (the reference's encoder is s16)");
   SCHRO_HIP_REQUIRE (bpp == 2, "encode_lowdelay_transform_data: the frame must be s16");
   for (int k = 0; k < 3; k++)
-    SCHRO_HIP_REQUIRE ((k ? params->iwt_chroma_width : params->iwt_luma_width) <= iwt_frame->components[k].width
-        && (k ? params->iwt_chroma_height : params->iwt_luma_height) <= iwt_frame->components[k].height,
-        "encode_lowdelay_transform_data: component %d smaller than the iwt size", k);
+    SCHRO_HIP_TRY (require_holds ("encode_lowdelay_transform_data", k, iwt_frame->components[k], iwt_size (params, k), 0));
   SCHRO_HIP_REQUIRE (params->n_horiz_slices > 0 && params->n_vert_slices > 0
       && (int64_t) params->n_horiz_slices * params->n_vert_slices < (1 << 24), "encode_lowdelay_transform_data: bad slice counts");
   const size_t nslices = (size_t) params->n_horiz_slices * params->n_vert_slices;
-  // one allocation: the slices, the base indices, the count
-  const size_t index_at = (slices_bytes + 15) & ~(size_t) 15, count_at = index_at + ((nslices + 15) & ~(size_t) 15);
-  char *d = (char *) schro_hip_domain_alloc (ctx, count_at + 16);
-  if (!d)
+  enum { kSlices, kIndex, kCount };
+  SyncBlock blk (ctx, slices_bytes, nslices, 16, 16);
+  if (!blk.d)
     return SCHRO_HIP_ENOMEM;
   SchroHipLowDelayEncodePicture pic;
   for (int k = 0; k < 3; k++) {
     pic.comp[k] = iwt_frame->components[k].data;
     pic.stride[k] = iwt_frame->components[k].stride;
   }
-  pic.slices = (uint8_t *) d;
+  pic.slices = (uint8_t *) blk.part (kSlices);
   pic.slices_bytes = slices_bytes;
-  pic.base_index = (uint8_t *) d + index_at;
-  pic.overruns = (uint32_t *) (d + count_at);
+  pic.base_index = (uint8_t *) blk.part (kIndex);
+  pic.overruns = (uint32_t *) blk.part (kCount);
   int r = schro_hip_lowdelay_encode_batch (ctx, &pic, 1, params, bpp);
   uint32_t count = 0;
-  if (!r && (hipMemcpyAsync (slices, d, slices_bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess
-          || (base_index && hipMemcpyAsync (base_index, d + index_at, nslices, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-          || hipMemcpyAsync (&count, d + count_at, sizeof (count), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess))
+  if (!r && (hipMemcpyAsync (slices, blk.part (kSlices), slices_bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess
+          || (base_index && hipMemcpyAsync (base_index, blk.part (kIndex), nslices, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+          || hipMemcpyAsync (&count, blk.part (kCount), sizeof (count), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess))
     r = set_error (SCHRO_HIP_EDEVICE, "encode_lowdelay_transform_data: copy of %zu bytes failed", slices_bytes);
-  const int rs = schro_hip_synchronize (ctx);   // the host buffers are filled, d is free again
-  schro_hip_domain_free (ctx, d);
-  if (!r && !rs && overruns)
+  r = blk.finish (r);
+  if (!r && overruns)
     *overruns = (int) count;
-  return r ? r : rs;
+  return r;
 }
 
 // schro_encoder_encode_transform_data (schroencoder.c:3462-3483) for params->is_noarith with frame->quant_frame on the
@@ -676,63 +802,42 @@ schro_hip_encode_transform_data_noarith (const SchroHipFrame * quant_frame, cons
   const int depth = params->transform_depth;
   SCHRO_HIP_REQUIRE (depth >= 0 && depth <= 6, "%s: transform_depth %d", who, depth);
   SchroHipNoarithPicture pic;
-  memset (&pic, 0, sizeof (pic));
-  pic.transform_depth = depth;
-  pic.codeblock_mode_index = params->codeblock_mode_index;
-  for (int l = 0; l <= depth; l++) {
-    pic.horiz_codeblocks[l] = params->horiz_codeblocks[l];
-    pic.vert_codeblocks[l] = params->vert_codeblocks[l];
-  }
+  fill_noarith_header (pic, params);
   std::vector < SchroHipCodeblock > recs[3];
   for (int k = 0; k < 3; k++) {
     const SchroHipFrameData & q = quant_frame->components[k];
-    const int w = k ? params->iwt_chroma_width : params->iwt_luma_width, h = k ? params->iwt_chroma_height : params->iwt_luma_height;
+    const IwtSize s = iwt_size (params, k);
     SCHRO_HIP_REQUIRE (quant_indices[k], "%s: component %d has no quant indices", who, k);
-    SCHRO_HIP_REQUIRE (w > 0 && h > 0 && q.width >= w && q.height >= h && (long long) q.stride >= (long long) w * bpp,
-        "%s: component %d (%d x %d, stride %d) does not hold the %d x %d transform", who, k, q.width, q.height, q.stride, w, h);
-    const int n = schro_hip_codeblock_layout (w, h, depth, params->horiz_codeblocks, params->vert_codeblocks, q.stride, bpp, nullptr, 0);
-    if (n <= 0)
-      return n < 0 ? n : set_error (SCHRO_HIP_EINVAL, "%s: component %d has no codeblocks", who, k);
-    recs[k].resize (n);
-    (void) schro_hip_codeblock_layout (w, h, depth, params->horiz_codeblocks, params->vert_codeblocks, q.stride, bpp, recs[k].data (), n);
-    for (int c = 0; c < n; c++) {
-      SCHRO_HIP_REQUIRE (quant_indices[k][c] >= 0 && quant_indices[k][c] <= 60, "%s: component %d, codeblock %d: quant index %d", who, k,
-          c, quant_indices[k][c]);
-      recs[k][c].quant_index = (unsigned char) quant_indices[k][c];
-    }
+    SCHRO_HIP_TRY (require_holds (who, k, q, s, bpp));
+    SCHRO_HIP_TRY (layout_records (who, k, s, params, q.stride, bpp, recs[k]));
+    SCHRO_HIP_TRY (set_quant_indices (who, k, recs[k], quant_indices[k]));
     pic.quant[k] = q.data;
-    pic.bytes[k] = (size_t) q.stride * (size_t) h;
+    pic.bytes[k] = (size_t) q.stride * (size_t) s.h;
     pic.stride[k] = q.stride;
-    pic.iwt_width[k] = w;
-    pic.iwt_height[k] = h;
+    pic.iwt_width[k] = s.w;
+    pic.iwt_height[k] = s.h;
     pic.codeblocks[k] = recs[k].data ();
-    pic.ncodeblocks[k] = n;
+    pic.ncodeblocks[k] = (int) recs[k].size ();
   }
-  // one allocation: the result, the bytes
-  char *d = (char *) schro_hip_domain_alloc (ctx, 256 + (capacity ? capacity : 1));
-  if (!d)
+  SyncBlock blk (ctx, kResultFront, 0, capacity);
+  if (!blk.d)
     return SCHRO_HIP_ENOMEM;
-  pic.result = (SchroHipNoarithResult *) d;
-  pic.out = (uint8_t *) d + 256;
+  pic.result = (SchroHipNoarithResult *) blk.part (kFront);
+  pic.out = (uint8_t *) blk.part (kBytes);
   pic.capacity = capacity;
-  static_assert (sizeof (SchroHipNoarithResult) <= 256, "the result sits in front of the bytes");
   int r = schro_hip_noarith_encode_batch (ctx, &pic, 1, bpp);
   SchroHipNoarithResult res;
   memset (&res, 0, sizeof (res));
-  if (!r && hipMemcpyAsync (&res, d, sizeof (res), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+  if (!r && hipMemcpyAsync (&res, blk.part (kFront), sizeof (res), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
     r = set_error (SCHRO_HIP_EDEVICE, "%s: copy of the result failed", who);
-  int rs = r ? 0 : schro_hip_synchronize (ctx);
-  const size_t take = std::min ((size_t) res.bytes, capacity);
-  if (!r && !rs && take) {
-    if (hipMemcpyAsync (out, d + 256, take, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+  const size_t take = blk.wait () ? 0 : std::min ((size_t) res.bytes, capacity);
+  if (!r && take) {
+    if (hipMemcpyAsync (out, blk.part (kBytes), take, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
       r = set_error (SCHRO_HIP_EDEVICE, "%s: copy of %zu bytes failed", who, take);
-    rs = schro_hip_synchronize (ctx);   // the host buffer is filled, d is free again
-  } else if (r) {
-    rs = schro_hip_synchronize (ctx);
+    blk.wait ();
   }
-  schro_hip_domain_free (ctx, d);
-  if (r || rs)
-    return r ? r : rs;
+  if ((r = blk.finish (r)))
+    return r;
   *bytes = res.bytes;
   if (subband_bits)
     for (int k = 0; k < 3; k++)
@@ -759,45 +864,40 @@ schro_hip_encode_motion_data_noarith (SchroHipContext * ctx, const SchroHipMotio
   if (bound < 0)
     return (int) bound;
   capacity = std::min (capacity, (size_t) bound);
-  const size_t field_bytes = (size_t) params->x_num_blocks * params->y_num_blocks * kMvBytes, field_at = 256;
-  const size_t out_at = field_at + round_up (field_bytes, 256);
-  // one allocation: the result, the field, the bytes
-  char *d = (char *) schro_hip_domain_alloc (ctx, out_at + (capacity ? capacity : 1));
-  if (!d)
+  const size_t field_bytes = (size_t) params->x_num_blocks * params->y_num_blocks * kMvBytes;
+  SyncBlock blk (ctx, kResultFront, field_bytes, capacity);
+  if (!blk.d)
     return SCHRO_HIP_ENOMEM;
-  static_assert (sizeof (SchroHipMotionEncodeResult) <= 256, "the result sits in front of the field");
   SchroHipMotionEncodePicture pic;
   memset (&pic, 0, sizeof (pic));
-  pic.motion = d + field_at;
+  pic.motion = blk.part (kField);
   pic.x_num_blocks = params->x_num_blocks;
   pic.y_num_blocks = params->y_num_blocks;
   pic.num_refs = params->num_refs;
   pic.have_global_motion = params->have_global_motion;
-  pic.out = (uint8_t *) d + out_at;
+  pic.out = (uint8_t *) blk.part (kBytes);
   pic.capacity = capacity;
-  pic.result = (SchroHipMotionEncodeResult *) d;
+  pic.result = (SchroHipMotionEncodeResult *) blk.part (kFront);
   int r = 0;
   // (the batch call's layout launch writes every word of the result; cleared here so that a launch that did not run
   // reports no bytes instead of what the allocation held)
-  if (hipMemsetAsync (d, 0, field_at, ctx->stream) != hipSuccess
-      || hipMemcpyAsync (d + field_at, motion->motion_vectors, field_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+  if (hipMemsetAsync (blk.part (kFront), 0, kResultFront, ctx->stream) != hipSuccess
+      || hipMemcpyAsync (blk.part (kField), motion->motion_vectors, field_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
     r = set_error (SCHRO_HIP_EDEVICE, "%s: copy of the field failed", who);
   if (!r)
     r = schro_hip_motion_encode_batch (ctx, &pic, 1);
   SchroHipMotionEncodeResult res;
   memset (&res, 0, sizeof (res));
-  if (!r && hipMemcpyAsync (&res, d, sizeof (res), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+  if (!r && hipMemcpyAsync (&res, blk.part (kFront), sizeof (res), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
     r = set_error (SCHRO_HIP_EDEVICE, "%s: copy of the result failed", who);
-  int rs = schro_hip_synchronize (ctx);
-  const size_t take = std::min ((size_t) res.bytes, capacity);
-  if (!r && !rs && take) {
-    if (hipMemcpyAsync (out, d + out_at, take, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+  const size_t take = blk.wait () ? 0 : std::min ((size_t) res.bytes, capacity);
+  if (!r && take) {
+    if (hipMemcpyAsync (out, blk.part (kBytes), take, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
       r = set_error (SCHRO_HIP_EDEVICE, "%s: copy of %zu bytes failed", who, take);
-    rs = schro_hip_synchronize (ctx);   // the host buffer is filled, d is free again
+    blk.wait ();
   }
-  schro_hip_domain_free (ctx, d);
-  if (r || rs)
-    return r ? r : rs;
+  if ((r = blk.finish (r)))
+    return r;
   *bytes = res.bytes;
   if (section_bytes)
     for (int s = 0; s < SCHRO_HIP_MOTION_SECTIONS; s++)
@@ -819,37 +919,32 @@ schro_hip_decode_motion_data_noarith (SchroHipContext * ctx, const void *data, s
   SCHRO_HIP_REQUIRE (params->x_num_blocks > 0 && params->y_num_blocks > 0 && params->x_num_blocks <= kMaxMotionBlocks
       && params->y_num_blocks <= kMaxMotionBlocks, "%s: %d x %d blocks", who, params->x_num_blocks, params->y_num_blocks);
   SCHRO_HIP_REQUIRE (length < ((size_t) 1 << 29), "%s: %zu bytes (below 2^29)", who, length);
-  const size_t field_bytes = (size_t) params->x_num_blocks * params->y_num_blocks * kMvBytes, field_at = 256;
-  const size_t data_at = field_at + round_up (field_bytes, 256);
-  // one allocation: the result, the field, the bytes
-  char *d = (char *) schro_hip_domain_alloc (ctx, data_at + (length ? length : 1));
-  if (!d)
+  const size_t field_bytes = (size_t) params->x_num_blocks * params->y_num_blocks * kMvBytes;
+  SyncBlock blk (ctx, kResultFront, field_bytes, length);
+  if (!blk.d)
     return SCHRO_HIP_ENOMEM;
-  static_assert (sizeof (SchroHipMotionDecodeResult) <= 256, "the result sits in front of the field");
   SchroHipMotionDecodePicture pic;
   memset (&pic, 0, sizeof (pic));
-  pic.data = (const uint8_t *) d + data_at;
+  pic.data = (const uint8_t *) blk.part (kBytes);
   pic.data_bytes = length;
   pic.x_num_blocks = params->x_num_blocks;
   pic.y_num_blocks = params->y_num_blocks;
   pic.num_refs = params->num_refs;
   pic.have_global_motion = params->have_global_motion;
-  pic.motion = d + field_at;
-  pic.result = (SchroHipMotionDecodeResult *) d;
+  pic.motion = blk.part (kField);
+  pic.result = (SchroHipMotionDecodeResult *) blk.part (kFront);
   int r = 0;
-  if (length && hipMemcpyAsync (d + data_at, data, length, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+  if (length && hipMemcpyAsync (blk.part (kBytes), data, length, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
     r = set_error (SCHRO_HIP_EDEVICE, "%s: copy of the bytes failed", who);
   if (!r)
     r = schro_hip_motion_decode_batch (ctx, &pic, 1);
   SchroHipMotionDecodeResult res;
   memset (&res, 0, sizeof (res));
-  if (!r && (hipMemcpyAsync (&res, d, sizeof (res), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess
-          || hipMemcpyAsync (motion->motion_vectors, d + field_at, field_bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess))
+  if (!r && (hipMemcpyAsync (&res, blk.part (kFront), sizeof (res), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess
+          || hipMemcpyAsync (motion->motion_vectors, blk.part (kField), field_bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess))
     r = set_error (SCHRO_HIP_EDEVICE, "%s: copy of the field failed", who);
-  int rs = schro_hip_synchronize (ctx);
-  schro_hip_domain_free (ctx, d);
-  if (r || rs)
-    return r ? r : rs;
+  if ((r = blk.finish (r)))
+    return r;
   if (result)
     *result = res;
   return 0;
@@ -904,16 +999,8 @@ schro_hipframe_dequantise (SchroHipFrame * transform_frame, const SchroHipQuanti
   if (!q->values_on_device && stage_bytes) {
     void *&buf = ctx->dq_stage_q[ctx->cur];
     size_t & size = ctx->dq_stage_size_q[ctx->cur];
-    if (size < stage_bytes) {
-      if (buf) {
-        SCHRO_HIP_CHECK (hipStreamSynchronize (ctx->stream));
-        SCHRO_HIP_CHECK (hipFree (buf));
-        buf = nullptr;
-        size = 0;
-      }
-      SCHRO_HIP_CHECK (hipMalloc (&buf, stage_bytes + stage_bytes / 4));
-      size = stage_bytes + stage_bytes / 4;
-    }
+    if (size < stage_bytes)     // (a quarter of headroom: pictures of one stream differ a little)
+      SCHRO_HIP_TRY (grow_block (ctx, buf, size, stage_bytes + stage_bytes / 4));
     stage = (char *) buf;
   }
   size_t off = 0;
@@ -945,14 +1032,7 @@ schro_hipframe_dequantise (SchroHipFrame * transform_frame, const SchroHipQuanti
   r = schro_hip_dequant_plan_run (ctx->frame_dq_plan, planes, 3);
   if (!r && intra) {
     SchroHipDcPlane ll[3];
-    for (int k = 0; k < 3; k++) {
-      const SchroHipFrameData & c = transform_frame->components[k];
-      const int w = k ? params->iwt_chroma_width : params->iwt_luma_width, h = k ? params->iwt_chroma_height : params->iwt_luma_height;
-      ll[k].data = c.data;
-      ll[k].stride = c.stride << params->transform_depth;        // schro_subband_get_frame_data, schroparams.c:319-352
-      ll[k].width = w >> params->transform_depth;
-      ll[k].height = h >> params->transform_depth;
-    }
+    ll_planes (ll, transform_frame, params);
     r = schro_hip_dc_predict_batch (ctx, ll, 3, bpp);
   }
   return stage_done (ctx, r);
@@ -976,57 +1056,44 @@ schro_hipframe_decode_transform_data_noarith (SchroHipFrame * transform_frame, c
   (void) hipSetDevice (ctx->device);
   const int intra = params->num_refs == 0;
   SchroHipNoarithDecodePicture pic;
-  memset (&pic, 0, sizeof (pic));
-  pic.transform_depth = depth;
-  pic.codeblock_mode_index = params->codeblock_mode_index;
+  fill_noarith_header (pic, params);
   pic.is_intra = intra;
   pic.compat_quant_offset = *compat_quant_offset != 0;
-  for (int l = 0; l <= depth; l++) {
-    pic.horiz_codeblocks[l] = params->horiz_codeblocks[l];
-    pic.vert_codeblocks[l] = params->vert_codeblocks[l];
-  }
-  SchroHipDcPlane ll[3];
   for (int k = 0; k < 3; k++) {
     const SchroHipFrameData & c = transform_frame->components[k];
-    const int w = k ? params->iwt_chroma_width : params->iwt_luma_width, h = k ? params->iwt_chroma_height : params->iwt_luma_height;
-    SCHRO_HIP_REQUIRE (w > 0 && h > 0 && c.width >= w && c.height >= h && (long long) c.stride >= (long long) w * bpp,
-        "%s: component %d (%d x %d, stride %d) does not hold the %d x %d transform", who, k, c.width, c.height, c.stride, w, h);
+    const IwtSize s = iwt_size (params, k);
+    SCHRO_HIP_TRY (require_holds (who, k, c, s, bpp));
     pic.coeffs[k] = c.data;
-    pic.bytes[k] = (size_t) c.stride * (size_t) h;
+    pic.bytes[k] = (size_t) c.stride * (size_t) s.h;
     pic.stride[k] = c.stride;
-    pic.iwt_width[k] = w;
-    pic.iwt_height[k] = h;
-    ll[k].data = c.data;
-    ll[k].stride = c.stride << depth;   // schro_subband_get_frame_data, schroparams.c:319-352
-    ll[k].width = w >> depth;
-    ll[k].height = h >> depth;
+    pic.iwt_width[k] = s.w;
+    pic.iwt_height[k] = s.h;
   }
-  // one allocation: the result, the bytes
-  static_assert (sizeof (SchroHipNoarithDecodeResult) <= 512, "the result sits in front of the bytes");
-  char *d = (char *) schro_hip_domain_alloc (ctx, 512 + (length ? length : 1));
-  if (!d)
+  SyncBlock blk (ctx, kNoarithDecodeFront, 0, length);
+  if (!blk.d)
     return SCHRO_HIP_ENOMEM;
-  pic.result = (SchroHipNoarithDecodeResult *) d;
-  pic.data = (const uint8_t *) d + 512;
+  pic.result = (SchroHipNoarithDecodeResult *) blk.part (kFront);
+  pic.data = (const uint8_t *) blk.part (kBytes);
   pic.data_bytes = length;
   int r = 0;
-  if (length && hipMemcpyAsync (d + 512, host_data, length, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+  if (length && hipMemcpyAsync (blk.part (kBytes), host_data, length, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
     r = set_error (SCHRO_HIP_EDEVICE, "%s: copy of %zu bytes failed", who, length);
   if (!r)
     r = schro_hip_noarith_decode_batch (ctx, &pic, 1, bpp);
   memset (result, 0, sizeof (*result));
-  if (!r && hipMemcpyAsync (result, d, sizeof (*result), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+  if (!r && hipMemcpyAsync (result, blk.part (kFront), sizeof (*result), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
     r = set_error (SCHRO_HIP_EDEVICE, "%s: copy of the result failed", who);
-  const int rs = schro_hip_synchronize (ctx);   // the result is here, d is free again
-  schro_hip_domain_free (ctx, d);
-  if (r || rs)
-    return r ? r : rs;
+  if ((r = blk.finish (r)))
+    return r;
   if (result->error)
     return set_status (SCHRO_HIP_EINVAL, "%s: quant index above 60 in the header of component %u, sub-band %u", who,
         result->first_error / SCHRO_HIP_NOARITH_MAX_SUBBANDS, result->first_error % SCHRO_HIP_NOARITH_MAX_SUBBANDS);
   *compat_quant_offset = (int) result->compat_quant_offset;
-  if (intra)
+  if (intra) {
+    SchroHipDcPlane ll[3];
+    ll_planes (ll, transform_frame, params);
     r = schro_hip_dc_predict_batch (ctx, ll, 3, bpp);
+  }
   return stage_done (ctx, r);
 }
 
@@ -1231,14 +1298,7 @@ schro_hipframe_convert (SchroHipFrame * dest, SchroHipFrame * src)
   int sb = format_bpp (src->format), db = format_bpp (dest->format);
   if (db == 1 && (sb == 2 || sb == 4)) {
     SchroHipConvertPlane planes[3];
-    for (int k = 0; k < 3; k++) {
-      planes[k].src = src->components[k].data;
-      planes[k].src_stride = src->components[k].stride;
-      planes[k].dst = (uint8_t *) dest->components[k].data;
-      planes[k].dst_stride = dest->components[k].stride;
-      planes[k].width = std::min (dest->components[k].width, src->components[k].width);
-      planes[k].height = std::min (dest->components[k].height, src->components[k].height);
-    }
+    common_planes (planes, dest, src);
     return stage_done (ctx, schro_hip_convert_u8_batch (ctx, planes, 3, sb));
   }
   if (db == sb) {
@@ -1257,50 +1317,37 @@ schro_hipframe_convert (SchroHipFrame * dest, SchroHipFrame * src)
 }
 
 // schro_gpuframe_add (dest, src) (schrogpuframe.h:18, call site schrodecoder.c:1908-1910) = schro_frame_add
-// (schroframe.c:1000-1029): dest (s16) += src (s16 | u8) over the components' common size
+// (schroframe.c:1000-1029), and schro_frame_subtract (dest, src) (schroframe.c:1031-1079): dest (s16) += or -= src (s16 | u8)
+// over the components' common size
+static int
+add_or_subtract (SchroHipFrame * dest, SchroHipFrame * src, bool subtract)
+{
+  const char *word = subtract ? "subtract" : "add";
+  SCHRO_HIP_REQUIRE (dest && src && frame_ctx (dest) && src->domain == dest->domain,
+      "hipframe_%s: both frames must live in the same device domain", word);
+  SCHRO_HIP_REQUIRE (!(dest->format & 0x100) && !(src->format & 0x100) && format_bpp (dest->format) == 2
+      && (format_bpp (src->format) == 1 || format_bpp (src->format) == 2)
+      && SCHRO_HIP_FORMAT_H_SHIFT (dest->format) == SCHRO_HIP_FORMAT_H_SHIFT (src->format)
+      && SCHRO_HIP_FORMAT_V_SHIFT (dest->format) == SCHRO_HIP_FORMAT_V_SHIFT (src->format),
+      "hipframe_%s: s16 %s s16 | u8 of the same chroma format (%s function unimplemented, schroframe.c:%d)", word,
+      subtract ? "-=" : "+=", word, subtract ? 1078 : 1027);
+  SchroHipConvertPlane planes[3];
+  common_planes (planes, dest, src);
+  SchroHipContext *ctx = frame_ctx (dest);
+  return stage_done (ctx, subtract ? schro_hip_subtract_batch (ctx, planes, 3, format_bpp (src->format) == 1)
+      : schro_hip_add_batch (ctx, planes, 3, format_bpp (src->format)));
+}
+
 int
 schro_hipframe_add (SchroHipFrame * dest, SchroHipFrame * src)
 {
-  SCHRO_HIP_REQUIRE (dest && src && frame_ctx (dest) && src->domain == dest->domain,
-      "hipframe_add: both frames must live in the same device domain");
-  SCHRO_HIP_REQUIRE (!(dest->format & 0x100) && !(src->format & 0x100) && format_bpp (dest->format) == 2
-      && (format_bpp (src->format) == 1 || format_bpp (src->format) == 2)
-      && SCHRO_HIP_FORMAT_H_SHIFT (dest->format) == SCHRO_HIP_FORMAT_H_SHIFT (src->format)
-      && SCHRO_HIP_FORMAT_V_SHIFT (dest->format) == SCHRO_HIP_FORMAT_V_SHIFT (src->format),
-      "hipframe_add: s16 += s16 | u8 of the same chroma format (add function unimplemented, schroframe.c:1027)");
-  SchroHipConvertPlane planes[3];
-  for (int k = 0; k < 3; k++) {
-    planes[k].src = src->components[k].data;
-    planes[k].src_stride = src->components[k].stride;
-    planes[k].dst = (uint8_t *) dest->components[k].data;
-    planes[k].dst_stride = dest->components[k].stride;
-    planes[k].width = std::min (dest->components[k].width, src->components[k].width);
-    planes[k].height = std::min (dest->components[k].height, src->components[k].height);
-  }
-  return stage_done (frame_ctx (dest), schro_hip_add_batch (frame_ctx (dest), planes, 3, format_bpp (src->format)));
+  return add_or_subtract (dest, src, false);
 }
 
-// schro_frame_subtract (dest, src) (schroframe.c:1031-1079): dest (s16) -= src (s16 | u8) over the components' common size
 int
 schro_hipframe_subtract (SchroHipFrame * dest, SchroHipFrame * src)
 {
-  SCHRO_HIP_REQUIRE (dest && src && frame_ctx (dest) && src->domain == dest->domain,
-      "hipframe_subtract: both frames must live in the same device domain");
-  SCHRO_HIP_REQUIRE (!(dest->format & 0x100) && !(src->format & 0x100) && format_bpp (dest->format) == 2
-      && (format_bpp (src->format) == 1 || format_bpp (src->format) == 2)
-      && SCHRO_HIP_FORMAT_H_SHIFT (dest->format) == SCHRO_HIP_FORMAT_H_SHIFT (src->format)
-      && SCHRO_HIP_FORMAT_V_SHIFT (dest->format) == SCHRO_HIP_FORMAT_V_SHIFT (src->format),
-      "hipframe_subtract: s16 -= s16 | u8 of the same chroma format (subtract function unimplemented, schroframe.c:1078)");
-  SchroHipConvertPlane planes[3];
-  for (int k = 0; k < 3; k++) {
-    planes[k].src = src->components[k].data;
-    planes[k].src_stride = src->components[k].stride;
-    planes[k].dst = (uint8_t *) dest->components[k].data;
-    planes[k].dst_stride = dest->components[k].stride;
-    planes[k].width = std::min (dest->components[k].width, src->components[k].width);
-    planes[k].height = std::min (dest->components[k].height, src->components[k].height);
-  }
-  return stage_done (frame_ctx (dest), schro_hip_subtract_batch (frame_ctx (dest), planes, 3, format_bpp (src->format) == 1));
+  return add_or_subtract (dest, src, true);
 }
 
 // schro_encoder_quantise_subband (schroencoder.c:3729-3785) over every sub-band of the three components, iwt_frame and
@@ -1320,19 +1367,16 @@ schro_hipframe_quantise (SchroHipFrame * quant_frame, SchroHipFrame * iwt_frame,
   const int depth = params->transform_depth;
   SCHRO_HIP_REQUIRE (depth >= 0 && depth <= 6, "hipframe_quantise: transform_depth %d", depth);
   (void) hipSetDevice (ctx->device);
-  std::vector < int >key = { bpp, depth, params->iwt_luma_width, params->iwt_luma_height, params->iwt_chroma_width,
-    params->iwt_chroma_height
-  };
+  const char *who = "hipframe_quantise";
   for (int k = 0; k < 3; k++) {
     const SchroHipFrameData & c = iwt_frame->components[k], &q = quant_frame->components[k];
-    const int w = k ? params->iwt_chroma_width : params->iwt_luma_width, h = k ? params->iwt_chroma_height : params->iwt_luma_height;
+    const IwtSize s = iwt_size (params, k);
     SCHRO_HIP_REQUIRE (quant_indices[k] && summary[k], "hipframe_quantise: component %d has no quant indices or no summary", k);
-    SCHRO_HIP_REQUIRE (w > 0 && h > 0 && c.width >= w && c.height >= h && q.stride == c.stride && q.height >= h
-        && (long long) c.stride >= (long long) w * bpp, "hipframe_quantise: component %d: the frames (%d x %d stride %d, %d x %d "
-        "stride %d) must both hold the %d x %d transform with one stride", k, c.width, c.height, c.stride, q.width, q.height,
-        q.stride, w, h);
-    key.push_back (c.stride);
+    SCHRO_HIP_REQUIRE (holds (c, s, bpp) && q.stride == c.stride && q.height >= s.h, "hipframe_quantise: component %d: the frames "
+        "(%d x %d stride %d, %d x %d stride %d) must both hold the %d x %d transform with one stride", k, c.width, c.height, c.stride,
+        q.width, q.height, q.stride, s.w, s.h);
   }
+  std::vector < int >key = table_key (iwt_frame, params, bpp);
   for (int l = 0; l <= depth; l++) {
     key.push_back (params->horiz_codeblocks[l]);
     key.push_back (params->vert_codeblocks[l]);
@@ -1340,29 +1384,18 @@ schro_hipframe_quantise (SchroHipFrame * quant_frame, SchroHipFrame * iwt_frame,
   FrameQuantTable *t = ctx->frame_q_table;
   if (!t || t->key != key) {
     frame_quant_table_free (ctx);
-    t = new FrameQuantTable ();
-    t->d_summary = nullptr;
-    size_t total = 0;
+    std::unique_ptr < FrameQuantTable > fresh (new FrameQuantTable ());
+    fresh->d_summary = nullptr;
+    fresh->total = 0;
     for (int k = 0; k < 3; k++) {
-      const int w = k ? params->iwt_chroma_width : params->iwt_luma_width, h = k ? params->iwt_chroma_height : params->iwt_luma_height;
-      const int stride = iwt_frame->components[k].stride;
-      const int n = schro_hip_codeblock_layout (w, h, depth, params->horiz_codeblocks, params->vert_codeblocks, stride, bpp, nullptr, 0);
-      if (n <= 0) {
-        delete t;
-        return n < 0 ? n : set_error (SCHRO_HIP_EINVAL, "hipframe_quantise: component %d has no codeblocks", k);
-      }
-      t->recs[k].resize (n);
-      (void) schro_hip_codeblock_layout (w, h, depth, params->horiz_codeblocks, params->vert_codeblocks, stride, bpp, t->recs[k].data (), n);
-      t->dc_first[k] = params->horiz_codeblocks[0] * params->vert_codeblocks[0];
-      total += (size_t) n;
+      SCHRO_HIP_TRY (layout_records (who, k, iwt_size (params, k), params, iwt_frame->components[k].stride, bpp, fresh->recs[k]));
+      fresh->dc_first[k] = params->horiz_codeblocks[0] * params->vert_codeblocks[0];
+      fresh->total += fresh->recs[k].size ();
     }
-    t->total = total;
-    if (hipMalloc ((void **) &t->d_summary, SchroHipContext::kQueues * total * sizeof (SchroHipCodeblockSummary)) != hipSuccess) {
-      delete t;
-      return set_error (SCHRO_HIP_ENOMEM, "hipframe_quantise: %zu summaries", total);
-    }
-    t->key = key;
-    ctx->frame_q_table = t;
+    if (hipMalloc ((void **) &fresh->d_summary, SchroHipContext::kQueues * fresh->total * sizeof (SchroHipCodeblockSummary)) != hipSuccess)
+      return set_error (SCHRO_HIP_ENOMEM, "hipframe_quantise: %zu summaries", fresh->total);
+    fresh->key = key;
+    ctx->frame_q_table = t = fresh.release ();
   }
   const int intra = params->num_refs == 0;
   SchroHipCodeblockSummary *const d_summary = t->d_summary + (size_t) ctx->cur * t->total;       // the selected queue's
@@ -1370,23 +1403,20 @@ schro_hipframe_quantise (SchroHipFrame * quant_frame, SchroHipFrame * iwt_frame,
   size_t first = 0;
   for (int k = 0; k < 3; k++) {
     const int n = (int) t->recs[k].size ();
-    for (int c = 0; c < n; c++) {
-      SCHRO_HIP_REQUIRE (quant_indices[k][c] >= 0 && quant_indices[k][c] <= 60, "hipframe_quantise: component %d, codeblock %d: "
-          "quant index %d", k, c, quant_indices[k][c]);
-      t->recs[k][c].quant_index = (unsigned char) quant_indices[k][c];
-    }
+    SCHRO_HIP_TRY (set_quant_indices (who, k, t->recs[k], quant_indices[k]));
     const SchroHipFrameData & c = iwt_frame->components[k];
+    const IwtSize s = iwt_size (params, k);
     SchroHipQuantPlane & pl = planes[k];
     memset (&pl, 0, sizeof (pl));
     pl.coeffs = c.data;
     pl.quant = quant_frame->components[k].data;
-    pl.bytes = (size_t) c.stride * (size_t) (k ? params->iwt_chroma_height : params->iwt_luma_height);
+    pl.bytes = (size_t) c.stride * (size_t) s.h;
     pl.codeblocks = t->recs[k].data ();
     pl.ncodeblocks = n;
     pl.is_intra = intra;
     pl.dc_predict_first = intra ? t->dc_first[k] : 0;
-    pl.dc_width = (k ? params->iwt_chroma_width : params->iwt_luma_width) >> depth;
-    pl.dc_height = (k ? params->iwt_chroma_height : params->iwt_luma_height) >> depth;
+    pl.dc_width = s.w >> depth;
+    pl.dc_height = s.h >> depth;
     pl.summary = d_summary + first;
     first += (size_t) n;
   }
@@ -1418,17 +1448,13 @@ schro_hipframe_subband_histograms (SchroHipFrame * iwt_frame, const SchroHipPara
   SCHRO_HIP_REQUIRE (depth >= 0 && depth <= 6, "hipframe_subband_histograms: transform_depth %d", depth);
   (void) hipSetDevice (ctx->device);
   const int nb = 1 + 3 * depth;
-  std::vector < int >key = { bpp, depth, params->iwt_luma_width, params->iwt_luma_height, params->iwt_chroma_width,
-    params->iwt_chroma_height
-  };
   for (int k = 0; k < 3; k++) {
     const SchroHipFrameData & c = iwt_frame->components[k];
-    const int w = k ? params->iwt_chroma_width : params->iwt_luma_width, h = k ? params->iwt_chroma_height : params->iwt_luma_height;
-    SCHRO_HIP_REQUIRE (w > 0 && h > 0 && c.width >= w && c.height >= h && (long long) c.stride >= (long long) w * bpp,
-        "hipframe_subband_histograms: component %d: the frame (%d x %d stride %d) must hold the %d x %d transform", k, c.width,
-        c.height, c.stride, w, h);
-    key.push_back (c.stride);
+    const IwtSize s = iwt_size (params, k);
+    SCHRO_HIP_REQUIRE (holds (c, s, bpp), "hipframe_subband_histograms: component %d: the frame (%d x %d stride %d) must hold the "
+        "%d x %d transform", k, c.width, c.height, c.stride, s.w, s.h);
   }
+  const std::vector < int >key = table_key (iwt_frame, params, bpp);
   FrameHistTable *t = ctx->frame_h_table;
   if (!t || t->key != key) {
     frame_hist_table_free (ctx);
@@ -1438,8 +1464,8 @@ schro_hipframe_subband_histograms (SchroHipFrame * iwt_frame, const SchroHipPara
     const int ones[7] = { 1, 1, 1, 1, 1, 1, 1 };
     std::vector < SchroHipCodeblock > recs (nb);
     for (int k = 0; k < 3; k++) {
-      const int w = k ? params->iwt_chroma_width : params->iwt_luma_width, h = k ? params->iwt_chroma_height : params->iwt_luma_height;
-      const int n = schro_hip_codeblock_layout (w, h, depth, ones, ones, iwt_frame->components[k].stride, bpp, recs.data (), nb);
+      const IwtSize s = iwt_size (params, k);
+      const int n = schro_hip_codeblock_layout (s.w, s.h, depth, ones, ones, iwt_frame->components[k].stride, bpp, recs.data (), nb);
       if (n != nb) {
         delete t;
         return n < 0 ? n : set_error (SCHRO_HIP_EINVAL, "hipframe_subband_histograms: component %d has %d sub-bands, not %d", k, n, nb);
@@ -1473,7 +1499,7 @@ schro_hipframe_subband_histograms (SchroHipFrame * iwt_frame, const SchroHipPara
     const SchroHipFrameData & c = iwt_frame->components[k];
     t->bands[k][0].dc_predict = params->num_refs == 0;
     planes[k].coeffs = c.data;
-    planes[k].bytes = (size_t) c.stride * (size_t) (k ? params->iwt_chroma_height : params->iwt_luma_height);
+    planes[k].bytes = (size_t) c.stride * (size_t) iwt_size (params, k).h;
     planes[k].bands = t->bands[k].data ();
     planes[k].nbands = nb;
     planes[k].counts = d_counts + (size_t) k * nb;
