@@ -241,6 +241,13 @@ int schro_hip_pack8_routes (SchroHipContext * ctx, long long counts[SCHRO_HIP_PA
 #define SCHRO_HIP_WIDE_ROUTES 2
 int schro_hip_wide_routes (SchroHipContext * ctx, long long counts[SCHRO_HIP_WIDE_ROUTES], int reset);
 
+/* The same for schro_hip_unpack_iwt_batch (and so for schro_hipframe_unpack_iwt_transform): pictures per route,
+ * counted on the host as the launches are enqueued, nothing for a call that fails validation. */
+#define SCHRO_HIP_UNPACK_ROUTE_FUSED 0  /* iwt_fwd.hip: the level-0 launch fetches the packed rows itself */
+#define SCHRO_HIP_UNPACK_ROUTE_TWO_PASS 1       /* schro_hip_unpack_batch twice through a scratch block, then schro_hip_iwt_batch */
+#define SCHRO_HIP_UNPACK_ROUTES 2
+int schro_hip_unpack_routes (SchroHipContext * ctx, long long counts[SCHRO_HIP_UNPACK_ROUTES], int reset);
+
 /* ---- plane layer: batched launches --------------------------------------- */
 
 /* One component of one picture for the inverse wavelet.
@@ -313,6 +320,87 @@ typedef struct {
  * a row or not a multiple of the sample size, dst overlapping src, a filter, depth or sample size out of range. */
 int schro_hip_iwt_batch (SchroHipContext * ctx, const SchroHipIwtFwdPlane * planes, int nplanes, int depth, int filter,
     int bytes_per_sample);
+
+/* ---- encoder input: packed pictures to planes and to wavelet coefficients ----
+ *
+ * One picture of the encoder-direction schro_frame_convert (schroframe.c:869-979; schro_encoder_push_frame_full,
+ * schroencoder.c:1048-1058, and the intra picture's convert into the transform frame, :2454): what the reference's chain
+ * of virtual frames renders, sample for sample.
+ *   source  format = SCHRO_HIP_FORMAT_YUYV / _UYVY / _AYUV / _v210 / _v216 / _AY64: the packed rows src[0] (src_stride[0]
+ *           bytes apart) of a src_width x src_height picture; src_bpp and the source shifts are not read.
+ *           format = 0: three planar planes of src_bpp 1 (u8) / 2 (s16) / 4 (s32) bytes per sample with the chroma shifts
+ *           src_h_shift, src_v_shift (the identity unpack, schrovirtframe.c:931-932).
+ *   unpack  (schrovirtframe.c:616-940) YUYV / UYVY -> u8 4:2:2, AYUV -> u8 4:4:4; v210 -> s16 4:2:2,
+ *           ((word >> s) & 0x3ff) - 512, a row's last partial group as :791-858; v216 -> s16 4:2:2, the HIGH BYTE of each
+ *           16-bit word and no offset (:876-888: restated, not repaired); AY64 -> s32 4:4:4, word - 32768.
+ *   depth   (schroframe.c:905-924, before the chroma step) u8 -> s16 / s32: x - 128; s16 -> s32: sign extension;
+ *           s32 -> s16: truncation; s16 -> u8: orc_offsetconvert_u8_s16; s32 -> u8: orc_offsetconvert_u8_s32.
+ *   chroma  (schrovirtframe.c:1438-1576) u8 frames only: decimation (every second sample / row) or repetition.
+ *   size    (schrovirtframe.c:1823-1960) crop or edge extension to width x height: destination sample (x, y) of a
+ *           component is source sample (min (x, w_src - 1), min (y, h_src - 1)) of it, component sizes rounded up after
+ *           the shifts.
+ * Refused (SCHRO_HIP_EINVAL, nothing launched, the message names the picture and the reference's line): an ARGB source
+ * (unpack_argb writes 16-bit samples into the lines of a frame it labels U8_444, schrovirtframe.c:693-732, 927-929);
+ * AY64 -> u8 (schroframe.c:908 tests the depth of the PACKED format code, 0x107 & 0xc = S16, and reads s32 lines as
+ * s16); an odd src_width for YUYV / UYVY / v216 (schrovirtframe.c:629, 881: width / 2 chroma samples of a
+ * (width + 1) / 2 wide component); a chroma change on a frame that is s16 / s32 after the depth step
+ * (schrovirtframe.c:1567-1569 asserts); a destination wider and shorter, or narrower and taller, than the source
+ * (schrovirtframe.c:1861-1862, 1939-1940 assert); strides below a row; planar pointers or strides that are no multiple
+ * of the sample size (AY64 rows: of 2); a destination plane overlapping a source of the call; sizes <= 0. */
+typedef struct {
+  const void *src[3];
+  int src_stride[3];            /* bytes */
+  int format;                   /* a packed SCHRO_HIP_FORMAT_*, or 0: planar */
+  int src_width, src_height;
+  int src_bpp;                  /* planar sources: 1, 2 or 4 */
+  int src_h_shift, src_v_shift; /* planar sources */
+  int reserved;
+  void *dst[3];
+  int dst_stride[3];            /* bytes */
+  int dst_bpp;                  /* 1, 2 or 4 */
+  int h_shift, v_shift;         /* the destination's chroma format */
+  int width, height;
+} SchroHipUnpackPicture;
+
+/* One launch for all pictures of the call (at most SCHRO_HIP_UNPACK_MAX_PICTURES); pictures of unlike size, format and
+ * depth mix freely.  Nothing outside the destination components' rectangles is written. */
+#define SCHRO_HIP_UNPACK_MAX_PICTURES 85
+int schro_hip_unpack_batch (SchroHipContext * ctx, const SchroHipUnpackPicture * pictures, int npictures);
+
+/* One intra picture from packed bytes to wavelet coefficients.  src: the packed rows of a src_width x src_height
+ * picture in `format`; width x height: the video format's picture size (the destination of the encoder's first
+ * schro_frame_convert); dst[k]: the coefficient plane of component k of an iwt_width x iwt_height frame (every
+ * component a multiple of 1 << depth and no smaller than the picture's), in schro_hip_iwt_batch's layout; h_shift,
+ * v_shift: the transform's chroma format.  Bit for bit the chain
+ *   schro_hip_unpack_batch into a width x height frame of the packed format's own depth (u8 for YUYV / UYVY / AYUV, s16
+ *   for v210 / v216, s32 for AY64) and the transform's chroma format,
+ *   schro_hip_unpack_batch (planar source) from that frame into an s16 / s32 frame of the transform size (the offset
+ *   removed, the edges extended: schroencoder.c:2454),
+ *   schro_hip_iwt_batch,
+ * and refused where the chain is.  Routes, per picture and mixed freely in a call (schro_hip_unpack_routes counts them):
+ *   FUSED     the level-0 launch of the forward wavelet fetches the packed rows itself (16-byte loads, the coordinate
+ *             clamped to the picture: the edge extension), extracts the component and removes the offset in registers;
+ *             levels 1 .. depth - 1 are schro_hip_iwt_batch's.  Needs the transform's chroma format to be the packed
+ *             format's own and src, src_stride to be multiples of 16.  Taken where it did not measure slower than the
+ *             chain (scripts/unpack_iwt_ab.py --sweep, profiles/unpack_iwt.txt: 8 x 2160p, depth 3):
+ *               s32 coefficients  every format with every filter but Fidelity; AY64 with Fidelity too
+ *               s16 coefficients  YUYV / UYVY / AYUV / v210 / v216 with Haar0 and Haar1; AY64 with every filter but Fidelity
+ *   TWO_PASS  everything else: the chain above through the queue's grow-only scratch. */
+typedef struct {
+  const void *src;
+  int src_stride;               /* bytes */
+  int format;                   /* SCHRO_HIP_FORMAT_YUYV / _UYVY / _AYUV / _v210 / _v216 / _AY64 */
+  int src_width, src_height;
+  int width, height;            /* the picture */
+  void *dst[3];
+  int dst_stride[3];            /* bytes */
+  int iwt_width, iwt_height;    /* the luma transform size; a chroma plane is that under the shifts, rounded up */
+  int h_shift, v_shift;
+  int reserved;
+} SchroHipUnpackIwtPicture;
+
+int schro_hip_unpack_iwt_batch (SchroHipContext * ctx, const SchroHipUnpackIwtPicture * pictures, int npictures, int depth,
+    int filter, int bytes_per_sample);
 
 /* ---- encoder analysis: the downsample pyramid and the SAD scan (schroanalysis.c:8-28, schrometric.c:31-214) ----
  *
@@ -2041,6 +2129,19 @@ SCHRO_HIP_LAYOUT (SchroHipMotionDecodePicture, bytes_on_device, 16);
 SCHRO_HIP_LAYOUT (SchroHipMotionDecodePicture, num_refs, 32);
 SCHRO_HIP_LAYOUT (SchroHipMotionDecodePicture, motion, 40);
 SCHRO_HIP_LAYOUT (SchroHipMotionDecodePicture, result, 48);
+SCHRO_HIP_SIZE (SchroHipUnpackPicture, 120);
+SCHRO_HIP_LAYOUT (SchroHipUnpackPicture, src_stride, 24);
+SCHRO_HIP_LAYOUT (SchroHipUnpackPicture, format, 36);
+SCHRO_HIP_LAYOUT (SchroHipUnpackPicture, src_bpp, 48);
+SCHRO_HIP_LAYOUT (SchroHipUnpackPicture, dst, 64);
+SCHRO_HIP_LAYOUT (SchroHipUnpackPicture, dst_bpp, 100);
+SCHRO_HIP_LAYOUT (SchroHipUnpackPicture, width, 112);
+SCHRO_HIP_SIZE (SchroHipUnpackIwtPicture, 88);
+SCHRO_HIP_LAYOUT (SchroHipUnpackIwtPicture, format, 12);
+SCHRO_HIP_LAYOUT (SchroHipUnpackIwtPicture, width, 24);
+SCHRO_HIP_LAYOUT (SchroHipUnpackIwtPicture, dst, 32);
+SCHRO_HIP_LAYOUT (SchroHipUnpackIwtPicture, iwt_width, 68);
+SCHRO_HIP_LAYOUT (SchroHipUnpackIwtPicture, h_shift, 76);
 #endif
 
 /* schro_frame_new_and_alloc (schroframe.c:60-191) on the device domain:
@@ -2349,6 +2450,18 @@ int schro_encoder_choose_quantisers_hip (SchroHipFrame * iwt_frame, const SchroH
  * performs: s16/s32 -> u8 (+128, clamp, crop), u8 -> u8 copy, planar -> packed (YUYV, UYVY,
  * AYUV from u8; v210, v216, ARGB, AY64 from u8 / s16 / s32). */
 int schro_hipframe_convert (SchroHipFrame * dest, SchroHipFrame * src);
+/* The ENCODER-direction schro_frame_convert (schro_encoder_push_frame_full, schroencoder.c:1048-1058, and the intra
+ * picture's convert into the transform frame, :2454) for two device frames of one domain: src a packed frame (YUYV, UYVY,
+ * AYUV, v210, v216, AY64) or a planar one, dest a planar u8 / s16 / s32 frame -- unpack, depth, u8 chroma decimation,
+ * crop or edge extension, as schro_hip_unpack_batch states and refuses them.  schro_hipframe_convert above keeps to the
+ * decode path. */
+int schro_hipframe_convert_input (SchroHipFrame * dest, SchroHipFrame * src);
+/* An intra picture from the packed device frame the application handed over to the coefficients in iwt_frame (s16 / s32,
+ * its components holding params->iwt_luma_* / iwt_chroma_*), picture_width x picture_height the video format's size:
+ * schro_hip_unpack_iwt_batch.  Same coefficients as schro_hipframe_convert_input into a picture-sized frame of the
+ * packed format's own depth, schro_hipframe_convert_input from that into iwt_frame, schro_hipframe_iwt_transform. */
+int schro_hipframe_unpack_iwt_transform (SchroHipFrame * iwt_frame, SchroHipFrame * packed, const SchroHipParams * params,
+    int picture_width, int picture_height);
 /* schro_frame_shift_right (schroframe.c:1265-1293) on a device s16 / s32 frame */
 int schro_hipframe_shift_right (SchroHipFrame * frame, int shift);
 

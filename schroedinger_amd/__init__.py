@@ -22,6 +22,15 @@ FORMAT_YUYV, FORMAT_UYVY, FORMAT_AYUV = 0x100, 0x101, 0x102       # packed, schr
 FORMAT_ARGB, FORMAT_V216, FORMAT_AY64 = 0x103, 0x105, 0x107
 FORMAT_V210 = 0x106
 
+
+
+def unpack_row_bytes(fmt, width):
+    """Bytes of a packed row the unpack reads (schrovirtframe.c:616-893): YUYV / UYVY width / 2 four-byte groups, AYUV 4
+    bytes per pixel, v216 8 bytes per pixel pair, v210 16 bytes per 6 pixels (the last group whole), AY64 8 per pixel."""
+    return {FORMAT_YUYV: 4 * (width // 2), FORMAT_UYVY: 4 * (width // 2), FORMAT_AYUV: 4 * width,
+            FORMAT_V216: 8 * (width // 2), FORMAT_V210: 16 * (-(-width // 6)), FORMAT_AY64: 8 * width}[fmt]
+
+
 # SchroMotionVector, schroedinger/schromotion.h:20-37 (20 bytes)
 MV_DTYPE = np.dtype([("flags", "<u4"), ("metric", "<u4"), ("chroma_metric", "<u4"),
                      ("v", "<i2", (4,))])
@@ -772,6 +781,14 @@ class Context:
         scratch block, the shift and the pack; reset: start the counts again from zero after reading them."""
         return self._routes(self.lib.schro_hip_wide_routes, self.WIDE_ROUTES, reset)
 
+    UNPACK_ROUTES = ("fused", "two_pass")                    # SCHRO_HIP_UNPACK_ROUTE_* (include/schro_hip.h)
+
+    def unpack_routes(self, reset=False):
+        """{route: pictures} this context's unpack_iwt calls have handed to each route (schro_hip_unpack_routes): "fused" the
+        forward wavelet's level-0 launch fetching the packed rows itself, "two_pass" the two converts through a scratch block
+        and the plane transform; reset: start the counts again from zero after reading them."""
+        return self._routes(self.lib.schro_hip_unpack_routes, self.UNPACK_ROUTES, reset)
+
     def plane(self, height, width, dtype, stride=None):
         return DevicePlane(self, height, width, dtype, stride)
 
@@ -828,6 +845,55 @@ class Context:
             assert s.dtype == d.dtype and s.dtype.itemsize == bpp and (s.height, s.width) == (d.height, d.width)
             arr[k] = _lib.IwtFwdPlane(s.ptr, s.stride, d.ptr, d.stride, s.width, s.height)
         check(self.lib.schro_hip_iwt_batch(self.h, arr, n, depth, filt, bpp))
+
+    def unpack_batch(self, jobs):
+        """The encoder-direction schro_frame_convert (schro_hip_unpack_batch).  jobs: (source, dst planes [Y, U, V] of one dtype
+        (u8 / s16 / s32), h_shift, v_shift, width, height) per picture; source: (packed plane of bytes, format, src_width,
+        src_height) or (planes [Y, U, V] of one dtype, h_shift, v_shift, src_width, src_height).  Pictures of unlike size,
+        format and depth mix freely; planes: DevicePlanes or anything with .ptr / .stride / .dtype."""
+        n = len(jobs)
+        arr = (_lib.UnpackPicture * n)()
+        for a, (source, dst, hs, vs, w, h) in zip(arr, jobs):
+            if len(source) == 4:
+                buf, a.format, a.src_width, a.src_height = source
+                a.src[0], a.src_stride[0] = buf.ptr, buf.stride
+            else:
+                planes, a.src_h_shift, a.src_v_shift, a.src_width, a.src_height = source
+                a.src_bpp = np.dtype(planes[0].dtype).itemsize
+                for k in range(3):
+                    assert np.dtype(planes[k].dtype).itemsize == a.src_bpp
+                    a.src[k], a.src_stride[k] = planes[k].ptr, planes[k].stride
+            a.dst_bpp = np.dtype(dst[0].dtype).itemsize
+            for k in range(3):
+                assert np.dtype(dst[k].dtype).itemsize == a.dst_bpp
+                a.dst[k], a.dst_stride[k] = dst[k].ptr, dst[k].stride
+            a.h_shift, a.v_shift, a.width, a.height = hs, vs, w, h
+        check(self.lib.schro_hip_unpack_batch(self.h, arr, n))
+
+    def unpack_iwt_batch(self, jobs, depth, filt):
+        """An intra picture from packed bytes to wavelet coefficients (schro_hip_unpack_iwt_batch).  jobs: (packed plane of
+        bytes, format, src_width, src_height, picture width, picture height, coefficient planes [Y, U, V] of one dtype (s16 /
+        s32), h_shift, v_shift, iwt_width, iwt_height) per picture."""
+        n = len(jobs)
+        arr = (_lib.UnpackIwtPicture * n)()
+        bpp = np.dtype(jobs[0][6][0].dtype).itemsize
+        for a, (buf, fmt, sw, sh, w, h, dst, hs, vs, iw, ih) in zip(arr, jobs):
+            a.src, a.src_stride, a.format, a.src_width, a.src_height = buf.ptr, buf.stride, fmt, sw, sh
+            a.width, a.height, a.h_shift, a.v_shift, a.iwt_width, a.iwt_height = w, h, hs, vs, iw, ih
+            for k in range(3):
+                assert np.dtype(dst[k].dtype).itemsize == bpp
+                a.dst[k], a.dst_stride[k] = dst[k].ptr, dst[k].stride
+        check(self.lib.schro_hip_unpack_iwt_batch(self.h, arr, n, depth, filt, bpp))
+
+    def convert_input(self, dest, src):
+        """schro_hipframe_convert_input: the encoder-direction schro_frame_convert between two device frames (frames.DeviceFrame):
+        src packed or planar, dest planar."""
+        check(self.lib.schro_hipframe_convert_input(dest.ptr(), src.ptr()))
+
+    def unpack_iwt_transform(self, iwt_frame, packed, params, picture_width, picture_height):
+        """schro_hipframe_unpack_iwt_transform: the packed device frame to the coefficients in iwt_frame (params: a
+        _lib.Params, frames.make_params)."""
+        check(self.lib.schro_hipframe_unpack_iwt_transform(iwt_frame.ptr(), packed.ptr(), C.byref(params), picture_width, picture_height))
 
     def downsample_batch(self, jobs):
         """One pyramid level (schro_frame_downsample + schro_frame_mc_edgeextend).  jobs: [(src, dst)] or [(src, dst, ext)],

@@ -33,7 +33,8 @@ EXPORTED_SYMBOLS = [
     "schro_hip_queue_mark", "schro_hip_queue_wait_mark",
     "schro_hip_timer_begin", "schro_hip_timer_end",
     "schro_hip_profile_enable", "schro_hip_profile_reset", "schro_hip_profile_read", "schro_hip_obmc_routes",
-    "schro_hip_v210_routes", "schro_hip_pack8_routes", "schro_hip_wide_routes",
+    "schro_hip_v210_routes", "schro_hip_pack8_routes", "schro_hip_wide_routes", "schro_hip_unpack_routes",
+    "schro_hip_unpack_batch", "schro_hip_unpack_iwt_batch",
     "schro_hip_iiwt_batch", "schro_hip_iwt_batch", "schro_hipframe_iwt_transform", "schro_hip_convert_u8_batch", "schro_hip_upsample_batch",
     "schro_hip_downsample_batch", "schro_hip_metric_scan_setup", "schro_hip_metric_scan_batch", "schro_hipframe_downsample",
     "schro_rough_me_heirarchical_scan_nohint_hip",
@@ -74,7 +75,7 @@ EXPORTED_SYMBOLS = [
     "schro_frame_inverse_iwt_transform_hip", "schro_frame_inverse_iwt_transform_combine_hip", "schro_frame_inverse_iwt_transform_convert_hip",
     "schro_frame_inverse_iwt_transform_combine_convert_hip", "schro_frame_inverse_iwt_transform_shift_convert_hip",
     "schro_upsampled_hipframe_upsample",
-    "schro_motion_render_hip", "schro_hipframe_convert",
+    "schro_motion_render_hip", "schro_hipframe_convert", "schro_hipframe_convert_input", "schro_hipframe_unpack_iwt_transform",
 ]
 
 
@@ -193,6 +194,23 @@ class PackPlane(C.Structure):
                 ("src_h_shift", C.c_int), ("src_v_shift", C.c_int),
                 ("dst", C.c_void_p), ("dst_stride", C.c_int),
                 ("width", C.c_int), ("height", C.c_int), ("format", C.c_int)]
+
+
+class UnpackPicture(C.Structure):
+    """SchroHipUnpackPicture (include/schro_hip.h): one picture of schro_hip_unpack_batch."""
+    _fields_ = [("src", C.c_void_p * 3), ("src_stride", C.c_int * 3), ("format", C.c_int),
+                ("src_width", C.c_int), ("src_height", C.c_int), ("src_bpp", C.c_int),
+                ("src_h_shift", C.c_int), ("src_v_shift", C.c_int), ("reserved", C.c_int),
+                ("dst", C.c_void_p * 3), ("dst_stride", C.c_int * 3), ("dst_bpp", C.c_int),
+                ("h_shift", C.c_int), ("v_shift", C.c_int), ("width", C.c_int), ("height", C.c_int)]
+
+
+class UnpackIwtPicture(C.Structure):
+    """SchroHipUnpackIwtPicture (include/schro_hip.h): one picture of schro_hip_unpack_iwt_batch."""
+    _fields_ = [("src", C.c_void_p), ("src_stride", C.c_int), ("format", C.c_int),
+                ("src_width", C.c_int), ("src_height", C.c_int), ("width", C.c_int), ("height", C.c_int),
+                ("dst", C.c_void_p * 3), ("dst_stride", C.c_int * 3), ("iwt_width", C.c_int), ("iwt_height", C.c_int),
+                ("h_shift", C.c_int), ("v_shift", C.c_int), ("reserved", C.c_int)]
 
 
 class IwtPackPicture(C.Structure):
@@ -615,6 +633,12 @@ def load():
     L.schro_hip_pack8_routes.restype = i
     L.schro_hip_wide_routes.argtypes = [vp, C.POINTER(C.c_longlong), i]
     L.schro_hip_wide_routes.restype = i
+    L.schro_hip_unpack_routes.argtypes = [vp, C.POINTER(C.c_longlong), i]
+    L.schro_hip_unpack_routes.restype = i
+    L.schro_hip_unpack_batch.argtypes = [vp, C.POINTER(UnpackPicture), i]
+    L.schro_hip_unpack_batch.restype = i
+    L.schro_hip_unpack_iwt_batch.argtypes = [vp, C.POINTER(UnpackIwtPicture), i, i, i, i]
+    L.schro_hip_unpack_iwt_batch.restype = i
     L.schro_hip_iiwt_batch.argtypes = [vp, C.POINTER(IwtPlane), i, i, i, i]
     L.schro_hip_iiwt_batch.restype = i
     L.schro_hip_iwt_batch.argtypes = [vp, C.POINTER(IwtFwdPlane), i, i, i, i]
@@ -838,6 +862,10 @@ def load():
     L.schro_motion_render_hip.restype = i
     L.schro_hipframe_convert.argtypes = [C.POINTER(Frame), C.POINTER(Frame)]
     L.schro_hipframe_convert.restype = i
+    L.schro_hipframe_convert_input.argtypes = [C.POINTER(Frame), C.POINTER(Frame)]
+    L.schro_hipframe_convert_input.restype = i
+    L.schro_hipframe_unpack_iwt_transform.argtypes = [C.POINTER(Frame), C.POINTER(Frame), C.POINTER(Params), i, i]
+    L.schro_hipframe_unpack_iwt_transform.restype = i
     _lib = L
     return L
 

@@ -1316,6 +1316,82 @@ schro_hipframe_convert (SchroHipFrame * dest, SchroHipFrame * src)
       sb, db);
 }
 
+// The encoder-direction schro_frame_convert (schroframe.c:869-979; schroencoder.c:1053-1055, 2454): `src` a packed or a
+// planar device frame, `dest` a planar one of any depth -- schro_hip_unpack_batch on the frames' components.
+int
+schro_hipframe_convert_input (SchroHipFrame * dest, SchroHipFrame * src)
+{
+  SCHRO_HIP_REQUIRE (dest && src && frame_ctx (dest) && src->domain == dest->domain,
+      "hipframe_convert_input: both frames must live in the same device domain");
+  SchroHipContext *ctx = frame_ctx (dest);
+  SCHRO_HIP_REQUIRE (!(dest->format & 0x100) && format_bpp (dest->format), "hipframe_convert_input: the destination must be planar");
+  SchroHipUnpackPicture pc;
+  memset (&pc, 0, sizeof (pc));
+  if (src->format & 0x100) {
+    pc.format = src->format;
+    pc.src[0] = src->components[0].data;
+    pc.src_stride[0] = src->components[0].stride;
+  } else {
+    pc.src_bpp = format_bpp (src->format);
+    pc.src_h_shift = SCHRO_HIP_FORMAT_H_SHIFT (src->format);
+    pc.src_v_shift = SCHRO_HIP_FORMAT_V_SHIFT (src->format);
+    for (int k = 0; k < 3; k++) {
+      pc.src[k] = src->components[k].data;
+      pc.src_stride[k] = src->components[k].stride;
+    }
+  }
+  pc.src_width = src->width;
+  pc.src_height = src->height;
+  for (int k = 0; k < 3; k++) {
+    pc.dst[k] = dest->components[k].data;
+    pc.dst_stride[k] = dest->components[k].stride;
+  }
+  pc.dst_bpp = format_bpp (dest->format);
+  pc.h_shift = SCHRO_HIP_FORMAT_H_SHIFT (dest->format);
+  pc.v_shift = SCHRO_HIP_FORMAT_V_SHIFT (dest->format);
+  pc.width = dest->width;
+  pc.height = dest->height;
+  return stage_done (ctx, schro_hip_unpack_batch (ctx, &pc, 1));
+}
+
+// An intra picture from the packed frame the application pushed to the coefficients in iwt_frame (s16 / s32, of the
+// transform size): schro_hip_unpack_iwt_batch on the frames' components.
+int
+schro_hipframe_unpack_iwt_transform (SchroHipFrame * iwt_frame, SchroHipFrame * packed, const SchroHipParams * params, int picture_width,
+    int picture_height)
+{
+  SCHRO_HIP_REQUIRE (iwt_frame && packed && params && frame_ctx (iwt_frame) && packed->domain == iwt_frame->domain,
+      "hipframe_unpack_iwt_transform: both frames must live in the same device domain");
+  SchroHipContext *ctx = frame_ctx (iwt_frame);
+  const int bpp = format_bpp (iwt_frame->format);
+  SCHRO_HIP_REQUIRE (!(iwt_frame->format & 0x100) && (bpp == 2 || bpp == 4), "hipframe_unpack_iwt_transform: the transform frame must be s16 or s32");
+  SCHRO_HIP_REQUIRE (packed->format & 0x100, "hipframe_unpack_iwt_transform: the source must be a packed frame");
+  SchroHipUnpackIwtPicture pc;
+  memset (&pc, 0, sizeof (pc));
+  pc.src = packed->components[0].data;
+  pc.src_stride = packed->components[0].stride;
+  pc.format = packed->format;
+  pc.src_width = packed->width;
+  pc.src_height = packed->height;
+  pc.width = picture_width;
+  pc.height = picture_height;
+  pc.h_shift = SCHRO_HIP_FORMAT_H_SHIFT (iwt_frame->format);
+  pc.v_shift = SCHRO_HIP_FORMAT_V_SHIFT (iwt_frame->format);
+  pc.iwt_width = params->iwt_luma_width;
+  pc.iwt_height = params->iwt_luma_height;
+  for (int k = 0; k < 3; k++) {
+    const IwtSize s = iwt_size (params, k);
+    SCHRO_HIP_TRY (require_holds ("hipframe_unpack_iwt_transform", k, iwt_frame->components[k], s, 0));
+    // (the plane layer's chroma planes are the luma size under the shifts, as the transform frame's components are)
+    SCHRO_HIP_REQUIRE (!k || (s.w == (params->iwt_luma_width + pc.h_shift) >> pc.h_shift && s.h == (params->iwt_luma_height + pc.v_shift) >> pc.v_shift),
+        "hipframe_unpack_iwt_transform: the chroma transform size %d x %d is not the luma size %d x %d under the frame's chroma shifts",
+        s.w, s.h, params->iwt_luma_width, params->iwt_luma_height);
+    pc.dst[k] = iwt_frame->components[k].data;
+    pc.dst_stride[k] = iwt_frame->components[k].stride;
+  }
+  return stage_done (ctx, schro_hip_unpack_iwt_batch (ctx, &pc, 1, params->transform_depth, params->wavelet_filter_index, bpp));
+}
+
 // schro_gpuframe_add (dest, src) (schrogpuframe.h:18, call site schrodecoder.c:1908-1910) = schro_frame_add
 // (schroframe.c:1000-1029), and schro_frame_subtract (dest, src) (schroframe.c:1031-1079): dest (s16) += or -= src (s16 | u8)
 // over the components' common size

@@ -23,11 +23,16 @@
 // in the scratch), writes its three detail bands into the coefficient frame and its LL band
 // into the scratch (the last level: into the frame): nothing is in place, so tiles never race.
 //
+// Level 0 of an intra picture can read a PACKED picture instead (iwt_fwd_packed_kernel, schro_hip_unpack_iwt_batch): the
+// same tile, LDS and lifting passes behind a staging stage that fetches the packed rows (unpack_fetch.h).  Measured it is
+// bound by that stage's per-sample extraction, not by bytes.
+//
 // Bound: HBM.  Algorithmic bytes per input sample per level: 2 * sizeof(T).
 // Open item: a register-tile form like iiwt_reg.hip's.
 
 #include "schro_hip_internal.h"
 #include "iiwt_steps.h"
+#include "unpack_fetch.h"
 
 namespace schro {
 namespace {
@@ -164,6 +169,41 @@ rows_load (uint2 * v, const void *base_, int stride, int tid, int r0, int c0, in
     const u32x2 q = gload < u32x2 > (base + (size_t) rr * stride + (size_t) c * 2 * sizeof (T));
     v[n] = make_uint2 (q.x, q.y);
   }
+}
+
+// the same region out of a packed picture's rows (unpack_fetch.h), in the layout an 8-byte load of the plane gives:
+// sample coordinates clamped to the picture (xmax, ymax: the edge extension), the component extracted, the format's
+// offset removed (u8: - 128; v210's - 512 and AY64's - 32768 are the unpack's own), the depth brought to T
+template < typename T, int RP, int RC, int NPS >
+__device__ __forceinline__ void
+rows_load_packed (uint2 * v, const IwtFwdPackedJob & job, int tid, int r0, int c0, int nr, int nc)
+{
+  constexpr int PL = 4 / sizeof (T), NG = RC / PL;
+  RowWords rw;
+  rw.row = nullptr;
+  rw.q = -1;
+  rw.w = (u32x4) { 0, 0, 0, 0 };
+  // (the source kind is uniform per workgroup: a scalar switch)
+  unpack_by_kind (job.s.kind, [&](auto kind) {
+#pragma unroll
+    for (int n = 0; n < NPS; n++) {
+      const int it = min (tid + n * kThreads, 2 * RP * NG - 1);
+      const int g = it % NG;
+      const int y = it / NG;
+      const int rr = min (clampi (2 * r0 + y, 0, 2 * nr - 1), job.ymax);
+      const uint8_t *row = job.s.base + (size_t) rr * job.s.stride;
+      uint32_t a[2 * PL];
+#pragma unroll
+      for (int i = 0; i < 2 * PL; i++) {
+        const int x = min (clampi (2 * (c0 + g * PL) + i, 0, 2 * nc - 1), job.xmax);
+        a[i] = (uint32_t) unpack_depth (unpack_sample < decltype (kind)::value > (rw, job.s, row, x), job.s.depth, (int) sizeof (T));
+      }
+      if constexpr (sizeof (T) == 2)
+        v[n] = make_uint2 ((a[0] & 0xffffu) | (a[1] << 16), (a[2] & 0xffffu) | (a[3] << 16));
+      else
+        v[n] = make_uint2 (a[0], a[1]);
+    }
+  });
 }
 
 // ... into LDS: even samples to the low half, odd samples to the high half, << 1 (wrapping: orc_deinterleave2_lshift1_*)
@@ -381,6 +421,36 @@ vertical_steps (T (*lds)[2 * RC], int tid, int vlo, int vhi, int r0, int cu0, co
   vertical_step < T, F, 0, RP, RC, H, HC, VCLAMP, true > (lds, tid, vlo, vhi, r0, cu0, sink);
 }
 
+// Everything behind the staging: the lifting passes of the staged region, the last one into the level's sub-bands.
+template < typename T, int F, int RC >
+__device__ __forceinline__ void
+lift_region (T (*lds)[2 * RC], int tid, const IwtFwdJob & job, int r0, int c0, int vlo, int vhi, int hlo, int hhi, int nc)
+{
+  typedef FwdGeo < T, F > G;
+  constexpr int RP = G::RP, H = G::H, HC = G::HC;
+  static_assert (RC == G::RC, "the region of the filter's tile");
+  if (hlo > 0 || hhi < RC - 1)  // the region sticks out of the picture: clamp columns
+    horizontal_steps < T, F, RP, RC, H, HC, true > (lds, tid, 2 * vlo, 2 * vhi + 1, hlo, hhi);
+  else
+    horizontal_steps < T, F, RP, RC, H, HC, false > (lds, tid, 2 * vlo, 2 * vhi + 1, hlo, hhi);
+
+  BandSink < T > sink;
+  sink.ll = (char *) job.band[0];
+  sink.hl = (char *) job.band[1];
+  sink.lh = (char *) job.band[2];
+  sink.hh = (char *) job.band[3];
+  sink.ll_stride = job.band_stride[0];
+  sink.hl_stride = job.band_stride[1];
+  sink.lh_stride = job.band_stride[2];
+  sink.hh_stride = job.band_stride[3];
+  sink.nc = nc;
+  sink.vec = (job.flags & 2) != 0;
+  if (vlo > 0 || vhi < RP - 1)  // ... clamp rows
+    vertical_steps < T, F, RP, RC, H, HC, true > (lds, tid, vlo, vhi, r0, c0 + HC, sink);
+  else
+    vertical_steps < T, F, RP, RC, H, HC, false > (lds, tid, vlo, vhi, r0, c0 + HC, sink);
+}
+
 }                               // namespace
 
 template < typename T, int F >
@@ -434,26 +504,42 @@ void iwt_fwd_level_kernel (const IwtFwdJob * __restrict__ jobs, int njobs)
   }
   __syncthreads ();
 
-  if (hlo > 0 || hhi < RC - 1)  // the region sticks out of the picture: clamp columns
-    horizontal_steps < T, F, RP, RC, H, HC, true > (lds, tid, 2 * vlo, 2 * vhi + 1, hlo, hhi);
-  else
-    horizontal_steps < T, F, RP, RC, H, HC, false > (lds, tid, 2 * vlo, 2 * vhi + 1, hlo, hhi);
+  lift_region < T, F, RC > (lds, tid, job, r0, c0, vlo, vhi, hlo, hhi, nc);
+}
 
-  BandSink < T > sink;
-  sink.ll = (char *) job.band[0];
-  sink.hl = (char *) job.band[1];
-  sink.lh = (char *) job.band[2];
-  sink.hh = (char *) job.band[3];
-  sink.ll_stride = job.band_stride[0];
-  sink.hl_stride = job.band_stride[1];
-  sink.lh_stride = job.band_stride[2];
-  sink.hh_stride = job.band_stride[3];
-  sink.nc = nc;
-  sink.vec = (job.flags & 2) != 0;
-  if (vlo > 0 || vhi < RP - 1)  // ... clamp rows
-    vertical_steps < T, F, RP, RC, H, HC, true > (lds, tid, vlo, vhi, r0, c0 + HC, sink);
-  else
-    vertical_steps < T, F, RP, RC, H, HC, false > (lds, tid, vlo, vhi, r0, c0 + HC, sink);
+// The same level whose staging reads a PACKED picture (schro_hip_unpack_iwt_batch, level 0): a region sample's
+// coordinate is clamped to the picture -- the edge extension of the encoder's converts (schroencoder.c:1053, 2454) --,
+// its bits come out of the packed row's 16-byte words (unpack_fetch.h), the component is extracted and the format's
+// offset removed in registers.  Everything behind the staging is the plane form's.
+template < typename T, int F >
+__global__ __launch_bounds__ (kThreads)
+void iwt_fwd_packed_kernel (const IwtFwdPackedJob * __restrict__ jobs, int njobs)
+{
+  typedef FwdGeo < T, F > G;
+  constexpr int RP = G::RP, RC = G::RC, H = G::H, HC = G::HC, UR = G::UR, UC = G::UC;
+  constexpr int NPS = rows_nps < T, RP, RC > ();
+  constexpr int SH = filter_shift (F);
+  __shared__ __attribute__ ((aligned (16))) T lds[2 * RP][2 * RC];
+
+  const int tid = threadIdx.x;
+  const int bid = xcd_tile_id (blockIdx.x, gridDim.x);
+  const IwtFwdPackedJob job = jobs[find_job (jobs, njobs, bid)];
+  const int t = bid - job.tile_base;
+  const int ty = mdiv (t, job.tiles_x, job.m_tiles_x);
+  const int tx = t - ty * job.tiles_x;
+  const int nr = job.h >> 1, nc = job.w >> 1;
+  const int r0 = ty * UR - H;
+  const int c0 = tx * UC - HC;
+  const int vlo = max (0, -r0), vhi = min (RP - 1, nr - 1 - r0);
+  const int hlo = max (0, -c0), hhi = min (RC - 1, nc - 1 - c0);
+
+  // all loads are issued before the first LDS write
+  uint2 v[NPS];
+  rows_load_packed < T, RP, RC, NPS > (v, job, tid, r0, c0, nr, nc);
+  rows_store < T, RP, RC, NPS, SH > (lds, v, tid);
+  __syncthreads ();
+
+  lift_region < T, F, RC > (lds, tid, job, r0, c0, vlo, vhi, hlo, hhi, nc);
 }
 
 namespace {
@@ -481,6 +567,33 @@ launch_filter (hipStream_t stream, const IwtFwdJob * d_jobs, int njobs, int tota
     case 4: return launch_one < T, 4 > (stream, d_jobs, njobs, total_tiles);
     case 5: return launch_one < T, 5 > (stream, d_jobs, njobs, total_tiles);
     case 6: return launch_one < T, 6 > (stream, d_jobs, njobs, total_tiles);
+  }
+  return set_error (SCHRO_HIP_EINVAL, "wavelet filter index %d out of range", filter);
+}
+
+template < typename T, int F >
+int
+launch_one_packed (hipStream_t stream, const IwtFwdPackedJob * d_jobs, int njobs, int total_tiles)
+{
+  SCHRO_LAUNCH ((iwt_fwd_packed_kernel < T, F >), dim3 (total_tiles), dim3 (kThreads), 0, stream, d_jobs, njobs);
+  hipError_t e = hipGetLastError ();
+  if (e != hipSuccess)
+    return set_error (SCHRO_HIP_EDEVICE, "forward iwt (packed) launch: %s", hipGetErrorString (e));
+  return 0;
+}
+
+template < typename T >
+int
+launch_filter_packed (hipStream_t stream, const IwtFwdPackedJob * d_jobs, int njobs, int total_tiles, int filter)
+{
+  switch (filter) {
+    case 0: return launch_one_packed < T, 0 > (stream, d_jobs, njobs, total_tiles);
+    case 1: return launch_one_packed < T, 1 > (stream, d_jobs, njobs, total_tiles);
+    case 2: return launch_one_packed < T, 2 > (stream, d_jobs, njobs, total_tiles);
+    case 3: return launch_one_packed < T, 3 > (stream, d_jobs, njobs, total_tiles);
+    case 4: return launch_one_packed < T, 4 > (stream, d_jobs, njobs, total_tiles);
+    case 5: return launch_one_packed < T, 5 > (stream, d_jobs, njobs, total_tiles);
+    case 6: return launch_one_packed < T, 6 > (stream, d_jobs, njobs, total_tiles);
   }
   return set_error (SCHRO_HIP_EINVAL, "wavelet filter index %d out of range", filter);
 }
@@ -517,6 +630,14 @@ launch_iwt_fwd_level (hipStream_t stream, const IwtFwdJob * d_jobs, int njobs, i
   if (bpp == 2)
     return launch_filter < int16_t > (stream, d_jobs, njobs, total_tiles, filter);
   return launch_filter < int32_t > (stream, d_jobs, njobs, total_tiles, filter);
+}
+
+int
+launch_iwt_fwd_packed (hipStream_t stream, const IwtFwdPackedJob * d_jobs, int njobs, int total_tiles, int filter, int bpp)
+{
+  if (bpp == 2)
+    return launch_filter_packed < int16_t > (stream, d_jobs, njobs, total_tiles, filter);
+  return launch_filter_packed < int32_t > (stream, d_jobs, njobs, total_tiles, filter);
 }
 
 }                               // namespace schro

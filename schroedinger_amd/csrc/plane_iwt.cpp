@@ -15,7 +15,7 @@ namespace schro {
 
 int
 iwt_batch_run (SchroHipContext * ctx, const SchroHipIwtFwdPlane * planes, int nplanes, int depth, int filter, int bpp,
-    bool in_place)
+    bool in_place, const IwtFwdPacked * packed)
 {
   SCHRO_HIP_REQUIRE (ctx && planes && nplanes > 0, "iwt_batch: bad arguments");
   SCHRO_HIP_REQUIRE (nplanes <= kMaxJobs, "iwt_batch: at most %d planes per call", kMaxJobs);
@@ -33,15 +33,19 @@ iwt_batch_run (SchroHipContext * ctx, const SchroHipIwtFwdPlane * planes, int np
   size_t total = 0;
   for (int p = 0; p < nplanes; p++) {
     const SchroHipIwtFwdPlane & pl = planes[p];
-    SCHRO_HIP_REQUIRE (pl.src && pl.dst, "iwt_batch: plane %d has a NULL pointer", p);
+    const bool from_packed = packed && packed[p].packed;        // level 0 reads packed rows: no source plane
+    SCHRO_HIP_REQUIRE ((pl.src || from_packed) && pl.dst, "iwt_batch: plane %d has a NULL pointer", p);
     SCHRO_HIP_REQUIRE (pl.width > 0 && pl.height > 0 && pl.width % (1 << depth) == 0 && pl.height % (1 << depth) == 0,
         "iwt_batch: plane %d size %dx%d is not a multiple of 2^depth", p, pl.width, pl.height);
     SCHRO_HIP_REQUIRE (pl.width <= (1 << 17) && pl.height <= (1 << 17), "iwt_batch: plane %d size %dx%d is too large", p, pl.width,
         pl.height);
-    SCHRO_HIP_REQUIRE (pl.src_stride >= pl.width * bpp && pl.dst_stride >= pl.width * bpp, "iwt_batch: plane %d stride too small", p);
-    SCHRO_HIP_REQUIRE (pl.src_stride % bpp == 0 && pl.dst_stride % bpp == 0 && (uintptr_t) pl.src % bpp == 0 && (uintptr_t) pl.dst % bpp == 0,
-        "iwt_batch: plane %d: pointers and strides must be multiples of the sample size %d", p, bpp);
-    if (!in_place) {
+    SCHRO_HIP_REQUIRE ((from_packed || pl.src_stride >= pl.width * bpp) && pl.dst_stride >= pl.width * bpp,
+        "iwt_batch: plane %d stride too small", p);
+    SCHRO_HIP_REQUIRE ((from_packed || (pl.src_stride % bpp == 0 && (uintptr_t) pl.src % bpp == 0)) && pl.dst_stride % bpp == 0
+        && (uintptr_t) pl.dst % bpp == 0, "iwt_batch: plane %d: pointers and strides must be multiples of the sample size %d", p, bpp);
+    if (from_packed) {
+      // (plane_unpack.cpp has checked the packed rows against dst)
+    } else if (!in_place) {
       const char *s0 = (const char *) pl.src, *s1 = s0 + (size_t) pl.src_stride * pl.height;
       const char *d0 = (const char *) pl.dst, *d1 = d0 + (size_t) pl.dst_stride * pl.height;
       SCHRO_HIP_REQUIRE (s1 <= d0 || d1 <= s0, "iwt_batch: plane %d src and dst overlap", p);
@@ -73,13 +77,20 @@ iwt_batch_run (SchroHipContext * ctx, const SchroHipIwtFwdPlane * planes, int np
         return r;
     }
 
-  std::vector < IwtFwdJob > jobs (nplanes);
+  // level 0 is two launches where planes read packed rows: theirs (pjobs) and the others'
+  std::vector < IwtFwdJob > jobs;
+  std::vector < IwtFwdPackedJob > pjobs;
   for (int level = 0; level < depth; level++) {
-    int tile_base = 0;
+    int tile_base = 0, ptile_base = 0;
+    jobs.clear ();
+    pjobs.clear ();
     for (int p = 0; p < nplanes; p++) {
       const SchroHipIwtFwdPlane & pl = planes[p];
-      IwtFwdJob & j = jobs[p];
-      memset (&j, 0, sizeof (j));
+      const bool from_packed = level == 0 && packed && packed[p].packed;
+      IwtFwdPackedJob pj;
+      memset (&pj, 0, sizeof (pj));
+      IwtFwdJob & j = pj;
+      int &tile_base_of = from_packed ? ptile_base : tile_base;
       const int w = pl.width >> level, h = pl.height >> level;
       if (level > 0) {
         j.src = scratch + ll_off[(size_t) p * depth + level - 1];
@@ -109,26 +120,44 @@ iwt_batch_run (SchroHipContext * ctx, const SchroHipIwtFwdPlane * planes, int np
       j.h = h;
       const int nc = w / 2, nr = h / 2;
       const int pl_pairs = 4 / bpp;     // column pairs per 8-byte load
-      const bool src_al = nc % pl_pairs == 0 && (((uintptr_t) j.src | (uintptr_t) j.src_stride) & 7) == 0;
+      const bool src_al = from_packed || (nc % pl_pairs == 0 && (((uintptr_t) j.src | (uintptr_t) j.src_stride) & 7) == 0);
       bool dst_al = nc % 4 == 0;
       for (int b = 0; b < 4; b++)
         dst_al = dst_al && (((uintptr_t) j.band[b] | (uintptr_t) j.band_stride[b]) & (size_t) (4 * bpp - 1)) == 0;
       j.flags = (src_al ? 1 : 0) | (dst_al ? 2 : 0);
       j.tiles_x = div_up (nc, uc);
       j.m_tiles_x = div_magic (j.tiles_x);
-      j.tile_base = tile_base;
+      j.tile_base = tile_base_of;
       // (the kernel's t / tiles_x is one multiply, schro_hip_internal.h mdiv: exact for tiles_x <= 1024 and fewer than
       // 2^22 tiles, which the size limit above keeps)
-      tile_base += j.tiles_x * div_up (nr, ur);
+      tile_base_of += j.tiles_x * div_up (nr, ur);
+      if (from_packed) {
+        pj.s = packed[p].s;
+        pj.xmax = packed[p].xmax;
+        pj.ymax = packed[p].ymax;
+        pjobs.push_back (pj);
+      } else {
+        jobs.push_back (j);
+      }
     }
-    void *d_jobs;
-    int r = push_args (ctx, jobs.data (), sizeof (IwtFwdJob) * jobs.size (), &d_jobs);
-    if (r)
-      return r;
     ProfileScope ps (ctx, level == 0 ? SCHRO_HIP_KERNEL_IIWT_FINEST : SCHRO_HIP_KERNEL_IIWT_COARSE);
-    r = launch_iwt_fwd_level (ctx->stream, (const IwtFwdJob *) d_jobs, nplanes, tile_base, filter, bpp);
-    if (r)
-      return r;
+    void *d_jobs;
+    if (!pjobs.empty ()) {
+      int r = push_args (ctx, pjobs.data (), sizeof (IwtFwdPackedJob) * pjobs.size (), &d_jobs);
+      if (r)
+        return r;
+      r = launch_iwt_fwd_packed (ctx->stream, (const IwtFwdPackedJob *) d_jobs, (int) pjobs.size (), ptile_base, filter, bpp);
+      if (r)
+        return r;
+    }
+    if (!jobs.empty ()) {
+      int r = push_args (ctx, jobs.data (), sizeof (IwtFwdJob) * jobs.size (), &d_jobs);
+      if (r)
+        return r;
+      r = launch_iwt_fwd_level (ctx->stream, (const IwtFwdJob *) d_jobs, (int) jobs.size (), tile_base, filter, bpp);
+      if (r)
+        return r;
+    }
   }
   return 0;
 }

@@ -127,6 +127,40 @@ struct IwtFwdJob {
   int pad;
 };
 
+// Where the samples of one component lie in a packed picture's rows or in a planar plane (unpack_fetch.h).
+enum { kUnpackU8 = 0, kUnpackS16 = 1, kUnpackS32 = 2, kUnpackV210 = 3, kUnpackU16 = 4 };
+struct UnpackSrc {
+  const uint8_t *base;          // row 0
+  int stride;                   // bytes
+  int row_bytes;                // the bytes of a row that exist
+  int kind;                     // kUnpack*
+  int xmul, xoff;               // sample x is at byte x * xmul + xoff of its row (not v210)
+  int comp;                     // v210: the component
+  int depth;                    // bytes per sample of the unpacked frame: 1 (u8), 2, 4
+};
+
+// One component of one picture of schro_hip_unpack_batch (unpack.hip).  A destination sample (x, y) comes from source
+// sample (min (x, xmax) shifted by xsh, min (y, ymax) shifted by ysh): crop / edge extension, then the u8 chroma
+// decimation (shift > 0: << 1) or repetition (shift < 0: >> 1).
+struct UnpackJob {
+  UnpackSrc s;
+  uint8_t *dst;
+  int dst_stride;
+  int w, h;                     // the destination component
+  int dst_bpp;
+  int xmax, ymax, xsh, ysh;
+  int vec;                      // dst and dst_stride are multiples of 16: whole 16-byte pieces
+  int tiles_x;
+  int tile_base;
+};
+
+// Level 0 of the forward wavelet reading a packed picture (iwt_fwd.hip): region sample (x, y) is source sample
+// (min (x, xmax), min (y, ymax)) less the format's offset.
+struct IwtFwdPackedJob:IwtFwdJob {
+  UnpackSrc s;
+  int xmax, ymax;
+};
+
 // One plane of the downsample (analysis.hip).  A tile is kDownTileCols x kDownTileRows samples of the destination
 // INCLUDING its apron: column xorg + 4 * group, row -ext + row.
 struct DownsampleJob {
@@ -771,6 +805,11 @@ void iiwt_tile_geometry (int filter, int bpp, int *useful_cols,
 // one level of the forward wavelet (iwt_fwd.hip)
 void iwt_fwd_tile_geometry (int filter, int bpp, int *useful_cols, int *useful_row_pairs);
 int launch_iwt_fwd_level (hipStream_t stream, const IwtFwdJob * d_jobs, int njobs, int total_tiles, int filter, int bpp);
+// ... level 0 with the packed fetch stage (the same tile geometry)
+int launch_iwt_fwd_packed (hipStream_t stream, const IwtFwdPackedJob * d_jobs, int njobs, int total_tiles, int filter, int bpp);
+// packed picture / planar frame -> planar frame (unpack.hip): a tile is pieces_x 16-byte pieces of `rows` destination rows
+void unpack_tile_geometry (int *pieces_x, int *rows);
+int launch_unpack (hipStream_t stream, const UnpackJob * d_jobs, int njobs, int total_tiles);
 // the downsample and the SAD scan (analysis.hip)
 void downsample_tile_geometry (int *cols, int *rows);
 int launch_downsample (hipStream_t stream, const DownsampleJob * d_jobs, int njobs, int total_tiles);
@@ -1222,7 +1261,9 @@ struct SchroHipContext {
   long long pack8_routes[SCHRO_HIP_PACK8_ROUTES] = {};
   // ... of schro_hip_iiwt_pack_wide_batch (schro_hip_wide_routes)
   long long wide_routes[SCHRO_HIP_WIDE_ROUTES] = {};
-  int cus;                      // compute units of the device (launch shaping)
+  // ... of schro_hip_unpack_iwt_batch (schro_hip_unpack_routes)
+  long long unpack_routes[SCHRO_HIP_UNPACK_ROUTES] = {};
+  int cus;                     // compute units of the device (launch shaping)
   // the frame layer's quantisation table (schro_hipframe_quantise): the codeblock records of one picture geometry and the
   // device summaries behind them
   struct schro::FrameQuantTable *frame_q_table = nullptr;
@@ -1269,8 +1310,15 @@ int copy_2d_async (SchroHipContext * ctx, void *dst, int dst_stride, const void 
     int height, hipMemcpyKind kind);
 // schro_hip_iwt_batch with src == dst allowed (plane_iwt.cpp): the source planes are copied into the queue's scratch
 // first, as the frame layer's in-place schro_hipframe_iwt_transform needs
+// packed (plane_unpack.cpp): per plane, where level 0 reads a packed picture's rows instead of planes[p].src (which is
+// then not looked at)
+struct IwtFwdPacked {
+  bool packed;
+  UnpackSrc s;
+  int xmax, ymax;               // the last source sample of the component along each axis: the edge extension's clamp
+};
 int iwt_batch_run (SchroHipContext * ctx, const SchroHipIwtFwdPlane * planes, int nplanes, int depth, int filter, int bpp,
-    bool in_place);
+    bool in_place, const IwtFwdPacked * packed = nullptr);
 // the loop of schro_rough_me_heirarchical_scan_nohint over schro_hip_metric_scan_batch (plane_analysis.cpp): fills the
 // host SchroMotionVector array and waits for the queue
 int rough_scan_nohint_run (SchroHipContext * ctx, const uint8_t * frame, int frame_stride, const uint8_t * ref, int ref_stride,
