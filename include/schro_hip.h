@@ -2465,6 +2465,118 @@ int schro_hipframe_unpack_iwt_transform (SchroHipFrame * iwt_frame, SchroHipFram
 /* schro_frame_shift_right (schroframe.c:1265-1293) on a device s16 / s32 frame */
 int schro_hipframe_shift_right (SchroHipFrame * frame, int shift);
 
+/* ---- picture statistics: average luma, squared error, SSIM, and the Gaussian low-pass under it ---------------
+ *
+ * The three measurements the reference's encoder takes of pictures this library keeps on the device:
+ * schro_frame_calculate_average_luma (schro_encoder_analyse_picture, schroencoder.c:2252-2261), schro_frame_mean_squared_error
+ * (schro_engine_get_scene_change_score, schroengine.c:304-345; enable_psnr, schroencoder.c:2728-2751) and schro_frame_ssim
+ * (enable_ssim; schrossim.c:64-149), and schro_frame_filter_lowpass2 (schrofilter.c:516-814), which SSIM runs five times
+ * and which is also the encoder's pre-filter `filtering = 2`.
+ *
+ * SUMS.  One job: the sum of plane `a` (u8: bytes_per_sample 1, s16: 2) and, when `b` is given (u8 against u8 only), the
+ * sum of (a - b)^2.  Per sample this is orc_sum_u8 / orc_sum_s16 / orc_sum_square_diff_u8 (schroorc-dist.c:9361-9548); the
+ * 16-bit mullw of the squared difference never loses a bit for u8 inputs (255^2 = 65025 < 65536).  The plane layer's sums
+ * are EXACT 64-bit integers, accumulated in integers only (the same bits on every run), and stay in device memory:
+ * result[0] the sum of a, result[1] the sum of squares (0 without b).  The call clears the two words and adds to them, all
+ * on the selected queue; nothing is waited for.  Jobs of unlike size and depth mix freely in one call; two jobs must not
+ * share a result. */
+typedef struct {
+  const void *a;                /* device */
+  int a_stride;                 /* bytes */
+  int bytes_per_sample;         /* 1: u8, 2: s16 */
+  int width, height;
+  const uint8_t *b;             /* device u8 plane, or NULL */
+  int b_stride;
+  int b_width, b_height;        /* must be width, height when b is given (schroanalysis.c:50-51) */
+  int64_t *result;              /* device, 8-byte aligned, two words */
+} SchroHipSumsJob;
+int schro_hip_plane_sums_batch (SchroHipContext * ctx, const SchroHipSumsJob * jobs, int njobs);
+/* host only: the refusals of schro_hip_plane_sums_batch without a context; no device pointer is dereferenced */
+int schro_hip_plane_sums_check (const SchroHipSumsJob * jobs, int njobs);
+
+/* LOW-PASS.  generate_coeff (schrofilter.c:666-689) on the host: the four doubles of one sigma. */
+void schro_hip_lowpass2_coeff (double sigma, double coeff[4]);
+/* schro_frame_component_filter_lowpass2_u8 / _s16 on one plane IN PLACE: every row forward then reverse with h_coeff, the
+ * columns forward, the columns reverse with v_coeff, each pass rounded to the sample type before the next reads it, with
+ * the reference's start states (s[0]; d[n - 1] after the forward pass; row 0 as the rows left it; the last row as the
+ * forward column pass left it).  A step is x = c0 * s + c1 * i0 + c2 * i1 + c3 * i2 in IEEE double, left to right, four
+ * rounded products and three rounded sums (no fused multiply-add), the stored sample rint (x).  Where rint (x) leaves the
+ * sample type's range the reference's x86-64 build stores the low 8 / 16 bits of the value converted to int32; so does
+ * this call, and it ADDS the number of such samples (of all four passes) to *out_of_range, which the caller clears.  For
+ * sigma below about 0.7 the filter sharpens and this happens on real pictures (the chroma of a 4:2:0 picture at
+ * filter_value 0.75); from sigma 0.75 up a 0 -> 255 step gives none.  Planes of unlike size, depth and coefficients mix in
+ * one call; several planes may share one counter.  No two planes may share a byte: planes whose byte extents (first sample
+ * to last) are apart pass, and so do windows of one buffer side by side -- equal strides, column ranges apart within the
+ * stride --; any other two planes whose extents meet are refused. */
+typedef struct {
+  void *data;                   /* device; 2-byte aligned with an even stride for s16 */
+  int stride;                   /* bytes */
+  int bytes_per_sample;         /* 1: u8, 2: s16 */
+  int width, height;
+  double h_coeff[4], v_coeff[4];        /* finite */
+  uint32_t *out_of_range;       /* device, 4-byte aligned; added to */
+} SchroHipLowpass2Plane;
+int schro_hip_lowpass2_batch (SchroHipContext * ctx, const SchroHipLowpass2Plane * planes, int nplanes);
+int schro_hip_lowpass2_check (const SchroHipLowpass2Plane * planes, int nplanes);
+
+/* SSIM.  What schro_frame_ssim reads, of the luma planes a and b (u8, one size): a_lowpass, b_lowpass the u8 low-pass at
+ * sigma = width / 256.0 * 1.5; a_hipass = (a - 128) - a_lowpass, b_hipass likewise (s16: schro_frame_dup16 converts u8 to s16 with
+ * the offset of orc_offsetconvert_s16_u8, so the values are -383 .. 127); the products ab, a^2, b^2 clamped to
+ * [-32768, 32767] (schrossim.c:49-50; they reach 146689, the clamp bites), each low-passed as s16; then per pixel
+ *   (2 mu_x mu_y + c1) (2 sigma_xy + c2) / ((mu_x^2 + mu_y^2 + c1) (sigma_x^2 + sigma_y^2 + c2)),
+ * the integer terms in int, the rest in double without contraction: every pixel's value is the reference's bit for bit
+ * and goes to `map` when one is given.  result->sum is their sum in a fixed order of this library's (rows of 8 within
+ * columns of 256, a fixed tree, the tiles in raster order), the same bits on every run but NOT the reference's raster-order
+ * accumulator's: two orders of adding the same n doubles differ by at most 2 (n - 1) 2^-53 sum |value|.  mssim = sum / (width * height) is the caller's (the
+ * frame layer's).  out_of_range[k]: the count of schro_hip_lowpass2_batch for a_lowpass, b_lowpass, ab, a^2, b^2.
+ * scratch: schro_hip_ssim_scratch_bytes (width, height) bytes of device memory, 16-byte aligned, the picture's own: what a
+ * picture writes (scratch, result, map) may share no byte with anything the call reads or writes, of this picture or of
+ * another (refused); a and b may be one plane, and pictures may share inputs. */
+typedef struct {
+  double sum;
+  uint32_t out_of_range[5];
+  uint32_t reserved;
+} SchroHipSsimResult;
+typedef struct {
+  const uint8_t *a;             /* device */
+  int a_stride;
+  int width, height;
+  const uint8_t *b;
+  int b_stride;
+  int b_width, b_height;        /* must be width, height */
+  void *scratch;
+  size_t scratch_bytes;
+  SchroHipSsimResult *result;   /* device, 8-byte aligned */
+  double *map;                  /* device, 8-byte aligned, or NULL */
+  int map_stride;               /* bytes, a multiple of 8 */
+} SchroHipSsimPicture;
+size_t schro_hip_ssim_scratch_bytes (int width, int height);
+int schro_hip_ssim_batch (SchroHipContext * ctx, const SchroHipSsimPicture * pictures, int npictures);
+int schro_hip_ssim_check (const SchroHipSsimPicture * pictures, int npictures);
+/* The tile and chunk lengths of the kernels above, for tests and tools that place planes around them: values[0 .. 7] =
+ * bytes and rows of a sums tile; rows of a row-pass workgroup, columns of a chunk it stages, columns of a column-pass
+ * workgroup, rows a column-pass lane loads at a time; columns and rows of an SSIM tile. */
+#define SCHRO_HIP_PICTURE_STATS_GEOMETRY 8
+void schro_hip_picture_stats_geometry (int values[SCHRO_HIP_PICTURE_STATS_GEOMETRY]);
+
+/* The frame layer, all synchronous, on device frames.
+ * schro_frame_calculate_average_luma (schroframe.c:1647-1680) of a u8 or s16 frame: the reference accumulates in an
+ * `int`, which a u8 plane of more than 8.42 M bright samples wraps (DCI 4K at level 255); this call returns the WRAPPED
+ * value the reference's build returns -- (double) (int32) sum / (width * height) --, the plane layer above always has the
+ * exact sum. */
+int schro_hipframe_calculate_average_luma (SchroHipFrame * frame, double *out);
+/* schro_frame_mean_squared_error (schroanalysis.c:44-84) of two u8 frames of one size and chroma format: the reference adds
+ * per-row int32 sums as doubles, exact below 2^53, so the device's integer sum converted once is the same double. */
+int schro_hipframe_mean_squared_error (SchroHipFrame * a, SchroHipFrame * b, double mse[3]);
+/* schro_frame_ssim: sum / (width * height) of schro_hip_ssim_batch over the luma planes of two u8 frames */
+int schro_hipframe_ssim (SchroHipFrame * a, SchroHipFrame * b, double *mssim);
+/* schro_frame_filter_lowpass2 (schrofilter.c:784-814) of a u8 or s16 frame in place, the chroma sigmas divided by 1 <<
+ * h_shift and 1 << v_shift of the format (:790-791); the out-of-range counts are dropped */
+int schro_hipframe_filter_lowpass2 (SchroHipFrame * frame, double sigma);
+/* schroengine.c:327-336 on the coarsest pyramid levels of a picture (frame1) and its predecessor (frame2): luma =
+ * average_luma - 16; the score is mse[0] / (luma * luma) when luma > 0.01, else 1.0 (then nothing is launched) */
+int schro_engine_get_scene_change_score_hip (SchroHipFrame * frame1, SchroHipFrame * frame2, double average_luma, double *score);
+
 /* diagnostics: with SCHRO_HIP_OBMC_STAMPS set, the row / staged OBMC kernels record cycle stamps
  * per phase and workgroup; this prints their medians to stderr (scratch runs only) */
 void schro_hip_obmc_stamps_dump (void);

@@ -51,6 +51,87 @@ def metric_scan_setup(x, y, block_width, block_height, frame_width, frame_height
     return s.ref_x, s.ref_y, s.scan_width, s.scan_height
 
 
+def lowpass2_coeff(sigma):
+    """generate_coeff (schrofilter.c:666-689) on the host (schro_hip_lowpass2_coeff): the four doubles of one sigma."""
+    c = (C.c_double * 4)()
+    _lib.load().schro_hip_lowpass2_coeff(float(sigma), c)
+    return [float(v) for v in c]
+
+
+PICTURE_STATS_GEOMETRY = ("sums_tile_bytes", "sums_tile_rows", "lowpass_rows", "lowpass_chunk", "lowpass_cols", "lowpass_col_rows",
+                          "ssim_tile_cols", "ssim_tile_rows")
+
+
+def picture_stats_geometry():
+    """{name: length} of the tiles and chunks of the picture-statistics kernels, from the library
+    (schro_hip_picture_stats_geometry): the sizes around which the tests place their planes."""
+    v = (C.c_int * len(PICTURE_STATS_GEOMETRY))()
+    _lib.load().schro_hip_picture_stats_geometry(v)
+    return dict(zip(PICTURE_STATS_GEOMETRY, (int(x) for x in v)))
+
+
+SSIM_RESULT_DTYPE = np.dtype([("sum", "<f8"), ("out_of_range", "<u4", (5,)), ("reserved", "<u4")])
+
+
+def _coeff4(v):
+    return lowpass2_coeff(v) if np.isscalar(v) else [float(x) for x in v]
+
+
+def sums_jobs(jobs):
+    """The SchroHipSumsJob array of Context.plane_sums_batch's jobs: (a, b or None, result) per job."""
+    arr = (_lib.SumsJob * len(jobs))()
+    for j, (a, b, result) in zip(arr, jobs):
+        j.a, j.a_stride, j.bytes_per_sample, j.width, j.height = a.ptr, a.stride, np.dtype(a.dtype).itemsize, a.width, a.height
+        if b is not None:
+            j.b, j.b_stride, j.b_width, j.b_height = b.ptr, b.stride, b.width, b.height
+        j.result = result.ptr
+    return arr
+
+
+def lowpass2_planes(planes):
+    """The SchroHipLowpass2Plane array of Context.lowpass2_batch's planes: (plane, h, v, counter) per plane -- h, v: a sigma
+    or four coefficients."""
+    arr = (_lib.Lowpass2Plane * len(planes))()
+    for p, (pl, h, v, counter) in zip(arr, planes):
+        p.data, p.stride, p.bytes_per_sample, p.width, p.height = pl.ptr, pl.stride, np.dtype(pl.dtype).itemsize, pl.width, pl.height
+        p.h_coeff[:], p.v_coeff[:] = _coeff4(h), _coeff4(v)
+        p.out_of_range = counter.ptr
+    return arr
+
+
+def ssim_pictures(pictures):
+    """The SchroHipSsimPicture array of Context.ssim_batch's pictures: (a, b, map or None, scratch, result) per picture --
+    scratch: a span of bytes (.ptr, .width bytes)."""
+    arr = (_lib.SsimPicture * len(pictures))()
+    for p, (a, b, m, scratch, result) in zip(arr, pictures):
+        p.a, p.a_stride, p.width, p.height = a.ptr, a.stride, a.width, a.height
+        p.b, p.b_stride, p.b_width, p.b_height = b.ptr, b.stride, b.width, b.height
+        p.scratch, p.scratch_bytes, p.result = scratch.ptr, scratch.width * np.dtype(scratch.dtype).itemsize, result.ptr
+        if m is not None:
+            p.map, p.map_stride = m.ptr, m.stride
+    return arr
+
+
+def plane_sums_check(jobs):
+    """The refusals of Context.plane_sums_batch on the host, without a context (schro_hip_plane_sums_check)."""
+    check(_lib.load().schro_hip_plane_sums_check(sums_jobs(jobs), len(jobs)))
+
+
+def lowpass2_check(planes):
+    """... of Context.lowpass2_batch (schro_hip_lowpass2_check)."""
+    check(_lib.load().schro_hip_lowpass2_check(lowpass2_planes(planes), len(planes)))
+
+
+def ssim_check(pictures):
+    """... of Context.ssim_batch (schro_hip_ssim_check)."""
+    check(_lib.load().schro_hip_ssim_check(ssim_pictures(pictures), len(pictures)))
+
+
+def ssim_scratch_bytes(width, height):
+    """schro_hip_ssim_scratch_bytes: the scratch one picture of Context.ssim_batch needs (0: no such picture)."""
+    return int(_lib.load().schro_hip_ssim_scratch_bytes(width, height))
+
+
 ROUGH_WAVES = 16                # SCHRO_HIP_ROUGH_WAVES (include/schro_hip.h): the most waves a rough-search workgroup has
 MAX_HIER_LEVELS = _lib.MAX_HIER_LEVELS
 
@@ -907,6 +988,90 @@ class Context:
             assert (d.height, d.width) == ((s.height + 1) // 2 + 2 * ext, (s.width + 1) // 2 + 2 * ext), (d.height, d.width)
             arr[k] = _lib.DownsamplePlane(s.ptr, s.stride, s.width, s.height, d.ptr + ext * d.stride + ext, d.stride, ext)
         check(self.lib.schro_hip_downsample_batch(self.h, arr, n))
+
+    # ---- picture statistics ----
+
+    def plane_sums_batch(self, jobs):
+        """schro_hip_plane_sums_batch.  jobs: (a,), (a, b) or (a, b, result) per job -- a: a u8 or s16 plane, b: a u8 plane of
+        a's size or None, result: two int64 words of the caller's (.ptr).  Enqueued, not waited for.  Returns the njobs x 2
+        int64 DevicePlane [sum of a, sum of (a - b)^2] of the jobs without a result of their own (None when all have one);
+        its download () waits."""
+        n = len(jobs)
+        own = [k for k, t in enumerate(jobs) if len(t) < 3 or t[2] is None]
+        res = DevicePlane(self, max(len(own), 1), 2, np.int64, stride=16) if own else None
+        full = []
+        for k, t in enumerate(jobs):
+            r = res.rows_view(own.index(k), 1) if k in own else t[2]
+            full.append((t[0], t[1] if len(t) > 1 else None, r))
+        check(self.lib.schro_hip_plane_sums_batch(self.h, sums_jobs(full), n))
+        return res
+
+    def lowpass2_batch(self, planes):
+        """schro_hip_lowpass2_batch: planes filtered IN PLACE.  planes: (plane, h, v) or (plane, h, v, counter) per plane --
+        plane u8 or s16, h and v a sigma or the four coefficients, counter a uint32 word of the caller's (.ptr) that the call
+        ADDS its out-of-range samples to.  Returns the nplanes' x 1 uint32 DevicePlane (cleared) of the planes without a
+        counter of their own, None when all have one."""
+        n = len(planes)
+        own = [k for k, t in enumerate(planes) if len(t) < 4 or t[3] is None]
+        cnt = DevicePlane(self, max(len(own), 1), 1, np.uint32, stride=4).fill(0) if own else None
+        full = [(t[0], t[1], t[2], cnt.rows_view(own.index(k), 1) if k in own else t[3]) for k, t in enumerate(planes)]
+        check(self.lib.schro_hip_lowpass2_batch(self.h, lowpass2_planes(full), n))
+        return cnt
+
+    def ssim_batch(self, pictures):
+        """schro_hip_ssim_batch.  pictures: (a, b), (a, b, map) or (a, b, map, scratch, result) per picture -- a, b u8 planes
+        of one size; map: True for a float64 DevicePlane of the per-pixel values, a plane of the caller's, or None; scratch
+        (a span of ssim_scratch_bytes bytes) and result (SSIM_RESULT_DTYPE, 32 bytes) the caller's or allocated here.
+        Enqueued, not waited for.  Returns per picture (result, map, scratch): download result and view it as
+        SSIM_RESULT_DTYPE (ssim_result); keep scratch until the queue has been waited for."""
+        full, out = [], []
+        for t in pictures:
+            a, b = t[0], t[1]
+            m = t[2] if len(t) > 2 else None
+            if m is True:
+                m = DevicePlane(self, a.height, a.width, np.float64)
+            scratch = t[3] if len(t) > 3 and t[3] is not None else DevicePlane(self, 1, max(ssim_scratch_bytes(a.width, a.height), 16), np.uint8)
+            result = t[4] if len(t) > 4 and t[4] is not None else DevicePlane(self, 1, SSIM_RESULT_DTYPE.itemsize, np.uint8)
+            full.append((a, b, m, scratch, result))
+            out.append((result, m, scratch))
+        check(self.lib.schro_hip_ssim_batch(self.h, ssim_pictures(full), len(full)))
+        return out
+
+    @staticmethod
+    def ssim_result(result):
+        """(sum, [out_of_range x 5]) of one picture's result plane (waits: a download)."""
+        r = result.download().reshape(-1).view(SSIM_RESULT_DTYPE)[0]
+        return float(r["sum"]), [int(v) for v in r["out_of_range"]]
+
+    def average_luma(self, frame):
+        """schro_hipframe_calculate_average_luma of a device frame (frames.DeviceFrame / PlaneFrame): the reference's value,
+        its int accumulator's wrap included."""
+        out = C.c_double()
+        check(self.lib.schro_hipframe_calculate_average_luma(frame.ptr(), C.byref(out)))
+        return out.value
+
+    def mean_squared_error(self, a, b):
+        """schro_hipframe_mean_squared_error of two u8 device frames: [mse Y, U, V]."""
+        out = (C.c_double * 3)()
+        check(self.lib.schro_hipframe_mean_squared_error(a.ptr(), b.ptr(), out))
+        return [float(v) for v in out]
+
+    def ssim(self, a, b):
+        """schro_hipframe_ssim of two u8 device frames: mssim of the luma planes."""
+        out = C.c_double()
+        check(self.lib.schro_hipframe_ssim(a.ptr(), b.ptr(), C.byref(out)))
+        return out.value
+
+    def filter_lowpass2(self, frame, sigma):
+        """schro_hipframe_filter_lowpass2: the u8 or s16 device frame low-passed in place (the pre-filter `filtering = 2`)."""
+        check(self.lib.schro_hipframe_filter_lowpass2(frame.ptr(), float(sigma)))
+
+    def scene_change_score(self, frame1, frame2, average_luma):
+        """schro_engine_get_scene_change_score_hip: frame1, frame2 the coarsest pyramid levels of a picture and its
+        predecessor, average_luma that of frame1 (Context.average_luma)."""
+        out = C.c_double()
+        check(self.lib.schro_engine_get_scene_change_score_hip(frame1.ptr(), frame2.ptr(), float(average_luma), C.byref(out)))
+        return out.value
 
     def metric_scan_batch(self, pictures, tables=True):
         """The SAD scans of schro_metric_scan_do_scan + schro_metric_scan_get_min.  pictures: [(frame, ref, extension,

@@ -76,6 +76,10 @@ EXPORTED_SYMBOLS = [
     "schro_frame_inverse_iwt_transform_combine_convert_hip", "schro_frame_inverse_iwt_transform_shift_convert_hip",
     "schro_upsampled_hipframe_upsample",
     "schro_motion_render_hip", "schro_hipframe_convert", "schro_hipframe_convert_input", "schro_hipframe_unpack_iwt_transform",
+    "schro_hip_plane_sums_batch", "schro_hip_plane_sums_check", "schro_hip_lowpass2_coeff", "schro_hip_lowpass2_batch",
+    "schro_hip_lowpass2_check", "schro_hip_ssim_scratch_bytes", "schro_hip_picture_stats_geometry", "schro_hip_ssim_batch", "schro_hip_ssim_check",
+    "schro_hipframe_calculate_average_luma", "schro_hipframe_mean_squared_error", "schro_hipframe_ssim",
+    "schro_hipframe_filter_lowpass2", "schro_engine_get_scene_change_score_hip",
 ]
 
 
@@ -97,6 +101,30 @@ class IwtFwdPlane(C.Structure):
 class DownsamplePlane(C.Structure):
     _fields_ = [("src", C.c_void_p), ("src_stride", C.c_int), ("src_width", C.c_int), ("src_height", C.c_int),
                 ("dst", C.c_void_p), ("dst_stride", C.c_int), ("dst_extension", C.c_int)]
+
+
+class SumsJob(C.Structure):
+    """SchroHipSumsJob: one plane (and its optional second plane) of schro_hip_plane_sums_batch."""
+    _fields_ = [("a", C.c_void_p), ("a_stride", C.c_int), ("bytes_per_sample", C.c_int), ("width", C.c_int), ("height", C.c_int),
+                ("b", C.c_void_p), ("b_stride", C.c_int), ("b_width", C.c_int), ("b_height", C.c_int), ("result", C.c_void_p)]
+
+
+class Lowpass2Plane(C.Structure):
+    """SchroHipLowpass2Plane: one plane of schro_hip_lowpass2_batch."""
+    _fields_ = [("data", C.c_void_p), ("stride", C.c_int), ("bytes_per_sample", C.c_int), ("width", C.c_int), ("height", C.c_int),
+                ("h_coeff", C.c_double * 4), ("v_coeff", C.c_double * 4), ("out_of_range", C.c_void_p)]
+
+
+class SsimResult(C.Structure):
+    _fields_ = [("sum", C.c_double), ("out_of_range", C.c_uint32 * 5), ("reserved", C.c_uint32)]
+
+
+class SsimPicture(C.Structure):
+    """SchroHipSsimPicture: one picture of schro_hip_ssim_batch."""
+    _fields_ = [("a", C.c_void_p), ("a_stride", C.c_int), ("width", C.c_int), ("height", C.c_int),
+                ("b", C.c_void_p), ("b_stride", C.c_int), ("b_width", C.c_int), ("b_height", C.c_int),
+                ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t), ("result", C.c_void_p),
+                ("map", C.c_void_p), ("map_stride", C.c_int)]
 
 
 class MetricScan(C.Structure):
@@ -866,6 +894,35 @@ def load():
     L.schro_hipframe_convert_input.restype = i
     L.schro_hipframe_unpack_iwt_transform.argtypes = [C.POINTER(Frame), C.POINTER(Frame), C.POINTER(Params), i, i]
     L.schro_hipframe_unpack_iwt_transform.restype = i
+    d = C.c_double
+    L.schro_hip_plane_sums_batch.argtypes = [vp, C.POINTER(SumsJob), i]
+    L.schro_hip_plane_sums_batch.restype = i
+    L.schro_hip_plane_sums_check.argtypes = [C.POINTER(SumsJob), i]
+    L.schro_hip_plane_sums_check.restype = i
+    L.schro_hip_lowpass2_coeff.argtypes = [d, C.POINTER(d)]
+    L.schro_hip_lowpass2_coeff.restype = None
+    L.schro_hip_lowpass2_batch.argtypes = [vp, C.POINTER(Lowpass2Plane), i]
+    L.schro_hip_lowpass2_batch.restype = i
+    L.schro_hip_lowpass2_check.argtypes = [C.POINTER(Lowpass2Plane), i]
+    L.schro_hip_lowpass2_check.restype = i
+    L.schro_hip_ssim_scratch_bytes.argtypes = [i, i]
+    L.schro_hip_ssim_scratch_bytes.restype = sz
+    L.schro_hip_picture_stats_geometry.argtypes = [C.POINTER(i)]
+    L.schro_hip_picture_stats_geometry.restype = None
+    L.schro_hip_ssim_batch.argtypes = [vp, C.POINTER(SsimPicture), i]
+    L.schro_hip_ssim_batch.restype = i
+    L.schro_hip_ssim_check.argtypes = [C.POINTER(SsimPicture), i]
+    L.schro_hip_ssim_check.restype = i
+    L.schro_hipframe_calculate_average_luma.argtypes = [C.POINTER(Frame), C.POINTER(d)]
+    L.schro_hipframe_calculate_average_luma.restype = i
+    L.schro_hipframe_mean_squared_error.argtypes = [C.POINTER(Frame), C.POINTER(Frame), C.POINTER(d)]
+    L.schro_hipframe_mean_squared_error.restype = i
+    L.schro_hipframe_ssim.argtypes = [C.POINTER(Frame), C.POINTER(Frame), C.POINTER(d)]
+    L.schro_hipframe_ssim.restype = i
+    L.schro_hipframe_filter_lowpass2.argtypes = [C.POINTER(Frame), d]
+    L.schro_hipframe_filter_lowpass2.restype = i
+    L.schro_engine_get_scene_change_score_hip.argtypes = [C.POINTER(Frame), C.POINTER(Frame), d, C.POINTER(d)]
+    L.schro_engine_get_scene_change_score_hip.restype = i
     _lib = L
     return L
 

@@ -1693,6 +1693,171 @@ schro_hipframe_downsample (SchroHipFrame * dest, SchroHipFrame * src)
   return stage_done (frame_ctx (dest), schro_hip_downsample_batch (frame_ctx (dest), planes, 3));
 }
 
+// ---- picture statistics: the plane layer's sums, low-pass and SSIM (plane_stats.cpp) on frames.  All synchronous: each
+// hands a host number back (or, the pre-filter, is the reference's plain call), whatever the stage-completion setting.
+
+static int
+stats_frame (const char *who, const SchroHipFrame * f, bool u8_only)
+{
+  SCHRO_HIP_REQUIRE (f && frame_ctx (f), "%s: needs a device frame", who);
+  const int bpp = format_bpp (f->format);
+  SCHRO_HIP_REQUIRE (!(f->format & 0x100) && !f->is_upsampled && (bpp == 1 || (bpp == 2 && !u8_only)), "%s: needs a planar %s frame", who,
+      u8_only ? "u8" : "u8 or s16");
+  return 0;
+}
+
+// the first `bytes` of the queue's scratch to the host, complete on return
+static int
+stats_fetch (SchroHipContext * ctx, void *host, size_t bytes)
+{
+  SCHRO_HIP_CHECK (hipMemcpyAsync (host, ctx->scratch_ref (), bytes, hipMemcpyDeviceToHost, ctx->stream));
+  SCHRO_HIP_CHECK (hipStreamSynchronize (ctx->stream));
+  return 0;
+}
+
+constexpr size_t kStatsHead = 64;       // the result words at the head of the scratch
+
+int
+schro_hipframe_calculate_average_luma (SchroHipFrame * frame, double *out)
+{
+  SCHRO_HIP_TRY (stats_frame ("hipframe_calculate_average_luma", frame, false));
+  SCHRO_HIP_REQUIRE (out, "hipframe_calculate_average_luma: no result");
+  SchroHipContext *ctx = frame_ctx (frame);
+  (void) hipSetDevice (ctx->device);
+  SCHRO_HIP_TRY (ensure_scratch (ctx, kStatsHead));
+  const SchroHipFrameData & c = frame->components[0];
+  SchroHipSumsJob job;
+  memset (&job, 0, sizeof (job));
+  job.a = c.data;
+  job.a_stride = c.stride;
+  job.bytes_per_sample = format_bpp (frame->format);
+  job.width = c.width;
+  job.height = c.height;
+  job.result = (int64_t *) ctx->scratch_ref ();
+  SCHRO_HIP_TRY (schro_hip_plane_sums_batch (ctx, &job, 1));
+  int64_t words[2];
+  SCHRO_HIP_TRY (stats_fetch (ctx, words, sizeof (words)));
+  // schroframe.c:1652, :1678: `int sum` takes the rows' int32 sums and wraps, `int n` is the product of two ints
+  const int sum = (int) (uint32_t) (uint64_t) words[0];
+  const int n = (int) ((uint32_t) c.height * (uint32_t) c.width);
+  *out = (double) sum / n;
+  return 0;
+}
+
+int
+schro_hipframe_mean_squared_error (SchroHipFrame * a, SchroHipFrame * b, double mse[3])
+{
+  const char *who = "hipframe_mean_squared_error";
+  SCHRO_HIP_TRY (stats_frame (who, a, true));
+  SCHRO_HIP_TRY (stats_frame (who, b, true));
+  SCHRO_HIP_REQUIRE (mse && a->domain == b->domain, "%s: needs two frames of one domain and the result", who);
+  SchroHipContext *ctx = frame_ctx (a);
+  (void) hipSetDevice (ctx->device);
+  SCHRO_HIP_TRY (ensure_scratch (ctx, kStatsHead));
+  SchroHipSumsJob jobs[3];
+  memset (jobs, 0, sizeof (jobs));
+  for (int k = 0; k < 3; k++) {
+    const SchroHipFrameData & ca = a->components[k], &cb = b->components[k];
+    // orc_sum_square_diff_u8 leaves a row's sum in an int32 (schroanalysis.c:55-60)
+    SCHRO_HIP_REQUIRE (ca.width <= 33025, "%s: component %d: a row of %d samples can overflow the reference's int32 row sum", who, k, ca.width);
+    jobs[k].a = ca.data;
+    jobs[k].a_stride = ca.stride;
+    jobs[k].bytes_per_sample = 1;
+    jobs[k].width = ca.width;
+    jobs[k].height = ca.height;
+    jobs[k].b = (const uint8_t *) cb.data;
+    jobs[k].b_stride = cb.stride;
+    jobs[k].b_width = cb.width;
+    jobs[k].b_height = cb.height;
+    jobs[k].result = (int64_t *) ctx->scratch_ref () + 2 * k;
+  }
+  SCHRO_HIP_TRY (schro_hip_plane_sums_batch (ctx, jobs, 3));
+  int64_t words[6];
+  SCHRO_HIP_TRY (stats_fetch (ctx, words, sizeof (words)));
+  for (int k = 0; k < 3; k++) {
+    // the rows' sums added as doubles are exact below 2^53: the integer sum converted once is the same double
+    const double n = (int) ((uint32_t) a->components[k].width * (uint32_t) a->components[k].height);       // (an int product there)
+    mse[k] = (double) words[2 * k + 1] / n;
+  }
+  return 0;
+}
+
+int
+schro_hipframe_ssim (SchroHipFrame * a, SchroHipFrame * b, double *mssim)
+{
+  const char *who = "hipframe_ssim";
+  SCHRO_HIP_TRY (stats_frame (who, a, true));
+  SCHRO_HIP_TRY (stats_frame (who, b, true));
+  SCHRO_HIP_REQUIRE (mssim && a->domain == b->domain, "%s: needs two frames of one domain and the result", who);
+  SchroHipContext *ctx = frame_ctx (a);
+  const SchroHipFrameData & ca = a->components[0], &cb = b->components[0];
+  SchroHipSsimPicture pic;
+  memset (&pic, 0, sizeof (pic));
+  pic.a = (const uint8_t *) ca.data;
+  pic.a_stride = ca.stride;
+  pic.width = ca.width;
+  pic.height = ca.height;
+  pic.b = (const uint8_t *) cb.data;
+  pic.b_stride = cb.stride;
+  pic.b_width = cb.width;
+  pic.b_height = cb.height;
+  pic.scratch_bytes = schro_hip_ssim_scratch_bytes (ca.width, ca.height);
+  SCHRO_HIP_REQUIRE (pic.scratch_bytes, "%s: a picture of %d x %d", who, ca.width, ca.height);
+  (void) hipSetDevice (ctx->device);
+  SCHRO_HIP_TRY (ensure_scratch (ctx, kStatsHead + pic.scratch_bytes));
+  pic.result = (SchroHipSsimResult *) ctx->scratch_ref ();
+  pic.scratch = (char *) ctx->scratch_ref () + kStatsHead;
+  SCHRO_HIP_TRY (schro_hip_ssim_batch (ctx, &pic, 1));
+  SchroHipSsimResult res;
+  SCHRO_HIP_TRY (stats_fetch (ctx, &res, sizeof (res)));
+  *mssim = res.sum / (ca.width * ca.height);    // schrossim.c:124
+  return 0;
+}
+
+int
+schro_hipframe_filter_lowpass2 (SchroHipFrame * frame, double sigma)
+{
+  SCHRO_HIP_TRY (stats_frame ("hipframe_filter_lowpass2", frame, false));
+  SchroHipContext *ctx = frame_ctx (frame);
+  (void) hipSetDevice (ctx->device);
+  SCHRO_HIP_TRY (ensure_scratch (ctx, kStatsHead));
+  SCHRO_HIP_CHECK (hipMemsetAsync (ctx->scratch_ref (), 0, kStatsHead, ctx->stream));
+  // schrofilter.c:790-791
+  const double chroma_sigma_h = sigma / (1 << SCHRO_HIP_FORMAT_H_SHIFT (frame->format));
+  const double chroma_sigma_v = sigma / (1 << SCHRO_HIP_FORMAT_V_SHIFT (frame->format));
+  SchroHipLowpass2Plane planes[3];
+  memset (planes, 0, sizeof (planes));
+  for (int k = 0; k < 3; k++) {
+    const SchroHipFrameData & c = frame->components[k];
+    planes[k].data = c.data;
+    planes[k].stride = c.stride;
+    planes[k].bytes_per_sample = format_bpp (frame->format);
+    planes[k].width = c.width;
+    planes[k].height = c.height;
+    schro_hip_lowpass2_coeff (k ? chroma_sigma_h : sigma, planes[k].h_coeff);
+    schro_hip_lowpass2_coeff (k ? chroma_sigma_v : sigma, planes[k].v_coeff);
+    planes[k].out_of_range = (uint32_t *) ctx->scratch_ref () + k;
+  }
+  SCHRO_HIP_TRY (schro_hip_lowpass2_batch (ctx, planes, 3));
+  SCHRO_HIP_CHECK (hipStreamSynchronize (ctx->stream));
+  return 0;
+}
+
+int
+schro_engine_get_scene_change_score_hip (SchroHipFrame * frame1, SchroHipFrame * frame2, double average_luma, double *score)
+{
+  SCHRO_HIP_REQUIRE (score, "engine_get_scene_change_score_hip: no result");
+  // schroengine.c:327-336
+  const double luma = average_luma - 16.0;
+  if (luma > 0.01) {
+    double mse[3];
+    SCHRO_HIP_TRY (schro_hipframe_mean_squared_error (frame1, frame2, mse));
+    *score = mse[0] / (luma * luma);
+  } else
+    *score = 1.0;
+  return 0;
+}
+
 int
 schro_rough_me_heirarchical_scan_nohint_hip (SchroHipFrame * frame, SchroHipFrame * ref_frame, const SchroHipParams * params, int shift,
     int distance, int ref, void *motion_vectors)

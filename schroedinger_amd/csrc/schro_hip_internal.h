@@ -581,6 +581,47 @@ struct HistJob {
 
 constexpr int kMaxJobs = 256;
 
+// ---- picture statistics (picture_sums.hip, lowpass2.hip, ssim.hip; plane_stats.cpp) ----
+struct SumsJob {
+  const void *a;
+  const uint8_t *b;             // or NULL
+  unsigned long long *result;   // two words
+  int a_stride, b_stride;
+  int w, h, bps;
+  int tiles_x;
+  int tile_base;
+  int pad;
+};
+struct LowpassJob {
+  void *data;
+  uint32_t *out_of_range;
+  double hc[4], vc[4];
+  int stride, w, h, bps;
+  int row_base;                 // first workgroup of the row kernel (kLowpassRows rows each)
+  int col_base;                 // ... of the column kernel (kLowpassCols columns each)
+};
+struct SsimJob {
+  const uint8_t *a, *b;
+  uint8_t *a_low, *b_low;       // scratch, stride8
+  int16_t *ab, *aa, *bb;        // scratch, stride16
+  double *partial;              // scratch: one double per tile
+  SchroHipSsimResult *result;
+  double *map;                  // or NULL
+  int a_stride, b_stride, stride8, stride16, map_stride;
+  int w, h;
+  int tiles_x, ntiles;
+  int tile_base;
+};
+// tile geometry of the kernels, for the plane layer's tables and the tests' edge sizes
+constexpr int kSumsTileBytes = 1024, kSumsTileRows = 16;
+constexpr int kLowpassRows = 64, kLowpassChunk = 128, kLowpassCols = 64, kLowpassColRows = 8;
+constexpr int kSsimTileCols = 256, kSsimTileRows = 8;
+int launch_plane_sums (hipStream_t stream, const SumsJob * d_jobs, int njobs, int total_tiles);
+int launch_lowpass2 (hipStream_t stream, const LowpassJob * d_jobs, int njobs, int row_groups, int col_groups);
+int launch_ssim_prepare (hipStream_t stream, const SsimJob * d_jobs, int njobs, int total_tiles);
+int launch_ssim_products (hipStream_t stream, const SsimJob * d_jobs, int njobs, int total_tiles);
+int launch_ssim_final (hipStream_t stream, const SsimJob * d_jobs, int njobs, int total_tiles);
+
 // XCD-aware workgroup order.  The dispatcher deals workgroups round-robin over
 // the 8 XCDs (each with its own 4 MiB L2), so neighbouring tiles -- which share
 // lifting halos and reference windows -- would land on 8 different L2s and each
