@@ -401,6 +401,13 @@ typedef struct {
 
 int schro_hip_unpack_iwt_batch (SchroHipContext * ctx, const SchroHipUnpackIwtPicture * pictures, int npictures, int depth,
     int filter, int bytes_per_sample);
+/* The tile lengths of the two calls above, for tests and tools that place pictures around them (host only, no context):
+ * values[0], values[1] = destination bytes of a row and rows of a schro_hip_unpack_batch tile; then, for wavelet filter
+ * f = 0 .. 6 and coefficient size b = 0 (s16), 1 (s32), values[2 + 4 * (2 * f + b) ..] = the forward wavelet tile's useful
+ * column pairs and useful row pairs (a tile writes 2 x that many samples and rows of its level) and the column pairs and
+ * row pairs of halo its region reads beyond them on every side. */
+#define SCHRO_HIP_UNPACK_GEOMETRY 58
+void schro_hip_unpack_geometry (int values[SCHRO_HIP_UNPACK_GEOMETRY]);
 
 /* ---- encoder analysis: the downsample pyramid and the SAD scan (schroanalysis.c:8-28, schrometric.c:31-214) ----
  *

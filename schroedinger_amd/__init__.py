@@ -70,6 +70,19 @@ def picture_stats_geometry():
     return dict(zip(PICTURE_STATS_GEOMETRY, (int(x) for x in v)))
 
 
+UNPACK_GEOMETRY = 58            # SCHRO_HIP_UNPACK_GEOMETRY (include/schro_hip.h)
+
+
+def unpack_geometry():
+    """The tile lengths of the encoder's way in, from the library (schro_hip_unpack_geometry): {"tile_bytes", "tile_rows":
+    destination bytes of a row and rows of an unpack_batch tile; "iwt": {(filter, bytes per sample): (useful column pairs,
+    useful row pairs, halo column pairs, halo row pairs) of the forward wavelet's tile}}."""
+    v = (C.c_int * UNPACK_GEOMETRY)()
+    _lib.load().schro_hip_unpack_geometry(v)
+    iwt = {(f, bpp): tuple(int(x) for x in v[2 + 4 * (2 * f + b):6 + 4 * (2 * f + b)]) for f in range(7) for b, bpp in enumerate((2, 4))}
+    return dict(tile_bytes=int(v[0]), tile_rows=int(v[1]), iwt=iwt)
+
+
 SSIM_RESULT_DTYPE = np.dtype([("sum", "<f8"), ("out_of_range", "<u4", (5,)), ("reserved", "<u4")])
 
 

@@ -76,6 +76,7 @@ EXPORTED_SYMBOLS = [
     "schro_frame_inverse_iwt_transform_combine_convert_hip", "schro_frame_inverse_iwt_transform_shift_convert_hip",
     "schro_upsampled_hipframe_upsample",
     "schro_motion_render_hip", "schro_hipframe_convert", "schro_hipframe_convert_input", "schro_hipframe_unpack_iwt_transform",
+    "schro_hip_unpack_geometry",
     "schro_hip_plane_sums_batch", "schro_hip_plane_sums_check", "schro_hip_lowpass2_coeff", "schro_hip_lowpass2_batch",
     "schro_hip_lowpass2_check", "schro_hip_ssim_scratch_bytes", "schro_hip_picture_stats_geometry", "schro_hip_ssim_batch", "schro_hip_ssim_check",
     "schro_hipframe_calculate_average_luma", "schro_hipframe_mean_squared_error", "schro_hipframe_ssim",
@@ -907,6 +908,8 @@ def load():
     L.schro_hip_lowpass2_check.restype = i
     L.schro_hip_ssim_scratch_bytes.argtypes = [i, i]
     L.schro_hip_ssim_scratch_bytes.restype = sz
+    L.schro_hip_unpack_geometry.argtypes = [C.POINTER(i)]
+    L.schro_hip_unpack_geometry.restype = None
     L.schro_hip_picture_stats_geometry.argtypes = [C.POINTER(i)]
     L.schro_hip_picture_stats_geometry.restype = None
     L.schro_hip_ssim_batch.argtypes = [vp, C.POINTER(SsimPicture), i]

@@ -613,6 +613,22 @@ geometry (int filter, int *uc, int *ur)
   }
 }
 
+// the halo a tile's region has around its useful part: columns per half on either side, row pairs above and below
+template < typename T >
+void
+halo (int filter, int *hc, int *hr)
+{
+  switch (filter) {
+    case 0: *hc = FwdGeo < T, 0 >::HC; *hr = FwdGeo < T, 0 >::H; break;
+    case 1: *hc = FwdGeo < T, 1 >::HC; *hr = FwdGeo < T, 1 >::H; break;
+    case 2: *hc = FwdGeo < T, 2 >::HC; *hr = FwdGeo < T, 2 >::H; break;
+    case 3: *hc = FwdGeo < T, 3 >::HC; *hr = FwdGeo < T, 3 >::H; break;
+    case 4: *hc = FwdGeo < T, 4 >::HC; *hr = FwdGeo < T, 4 >::H; break;
+    case 5: *hc = FwdGeo < T, 5 >::HC; *hr = FwdGeo < T, 5 >::H; break;
+    default: *hc = FwdGeo < T, 6 >::HC; *hr = FwdGeo < T, 6 >::H; break;
+  }
+}
+
 }                               // namespace
 
 void
@@ -622,6 +638,15 @@ iwt_fwd_tile_geometry (int filter, int bpp, int *useful_cols, int *useful_row_pa
     geometry < int16_t > (filter, useful_cols, useful_row_pairs);
   else
     geometry < int32_t > (filter, useful_cols, useful_row_pairs);
+}
+
+void
+iwt_fwd_tile_halo (int filter, int bpp, int *halo_cols, int *halo_row_pairs)
+{
+  if (bpp == 2)
+    halo < int16_t > (filter, halo_cols, halo_row_pairs);
+  else
+    halo < int32_t > (filter, halo_cols, halo_row_pairs);
 }
 
 int

@@ -434,6 +434,21 @@ schro_hip_unpack_iwt_batch (SchroHipContext * ctx, const SchroHipUnpackIwtPictur
   return 0;
 }
 
+void
+schro_hip_unpack_geometry (int values[SCHRO_HIP_UNPACK_GEOMETRY])
+{
+  int px, rows;
+  unpack_tile_geometry (&px, &rows);
+  values[0] = 16 * px;
+  values[1] = rows;
+  for (int f = 0; f < 7; f++)
+    for (int b = 0; b < 2; b++) {
+      int *v = values + 2 + 4 * (2 * f + b);
+      iwt_fwd_tile_geometry (f, b ? 4 : 2, &v[0], &v[1]);
+      iwt_fwd_tile_halo (f, b ? 4 : 2, &v[2], &v[3]);
+    }
+}
+
 int
 schro_hip_unpack_routes (SchroHipContext * ctx, long long counts[SCHRO_HIP_UNPACK_ROUTES], int reset)
 {

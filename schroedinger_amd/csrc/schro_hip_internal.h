@@ -845,6 +845,8 @@ void iiwt_tile_geometry (int filter, int bpp, int *useful_cols,
     int *useful_row_pairs);
 // one level of the forward wavelet (iwt_fwd.hip)
 void iwt_fwd_tile_geometry (int filter, int bpp, int *useful_cols, int *useful_row_pairs);
+// ... and the halo of its region: columns per half on either side, row pairs above and below
+void iwt_fwd_tile_halo (int filter, int bpp, int *halo_cols, int *halo_row_pairs);
 int launch_iwt_fwd_level (hipStream_t stream, const IwtFwdJob * d_jobs, int njobs, int total_tiles, int filter, int bpp);
 // ... level 0 with the packed fetch stage (the same tile geometry)
 int launch_iwt_fwd_packed (hipStream_t stream, const IwtFwdPackedJob * d_jobs, int njobs, int total_tiles, int filter, int bpp);

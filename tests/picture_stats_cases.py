@@ -30,6 +30,28 @@ LOWPASS_SIZES = ([(w, h) for w in (1, 2, 3, 63, 64, 65, 130) for h in (1, 2, 5, 
                  + [(5, h) for h in around(LOWPASS_ROWS, LOWPASS_COL_ROWS, 2 * LOWPASS_COL_ROWS)])
 
 SSIM_SIZES = [(48, 40), (130, 67), (257, 5)]
+# the SSIM tile arithmetic: widths below the eight result words' lanes, one below / at / one above both tile lengths, several
+# tiles across AND down, more tiles than ssim_sum_kernel has lanes (3 x 2049: its strided loop's second turn), and the two
+# widths on either side of generate_coeff's branch (width / 256 * 1.5 against 2.5)
+SSIM_GEOMETRY_SIZES = [(1, 1), (2, 3), (7, 9), (255, 7), (256, 8), (257, 9), (257, 17), (3, 2049), (426, 9), (427, 9), (513, 17)]
+SSIM_SUM_LANES = SSIM_TILE_COLS                 # (ssim.hip: a lane owns a column of the tile, and a tile's sum in the last kernel)
+
+# the most entries a call takes (kMaxJobs, kMaxSsimPictures: what the _check twins refuse above) and the 64 a table lookup
+# probes per round (find_job, lowpass_find)
+TABLE_ROUND = 64
+FULL_TABLE_JOBS = (65, 130, 256)
+FULL_TABLE_PLANES = (65, 129, 256)
+FULL_TABLE_PICTURES = (22, 33, 64)              # x 2 u8 and x 3 s16 low-pass planes: 66 .. 192 entries
+
+
+def tiny_size(k):
+    """1 .. 9 by 1 .. 9, unlike from entry to entry, and every 23rd 65 x 3: what fills a table without filling a test."""
+    return (65, 3) if k % 23 == 5 else (1 + (k * 7) % 9, 1 + (k * 5 + k // 9) % 9)
+
+
+def long_stride(k, row_bytes):
+    """Longer than the row, even, unlike from entry to entry."""
+    return (row_bytes + 1) // 2 * 2 + 2 * (k % 7) + (62 if k % 5 == 0 else 0)
 
 
 def sigma_pair(k):

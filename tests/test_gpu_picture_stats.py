@@ -3,7 +3,9 @@ frame-layer calls -- against tests/picture_stats_ref.py, bit for bit: the sums a
 and out-of-range count, every pixel of the SSIM map.  Only mssim is compared within a bound, the one two orders of adding
 the same doubles can differ by, computed from the restatement's map (picture_stats_ref.mssim_bound).  The planes stand
 around every tile and chunk length of the kernels (tests/picture_stats_cases.py names them); the write footprint of the
-low-pass and of SSIM is checked with tests/guard_lib.py."""
+low-pass and of SSIM is checked with tests/guard_lib.py.  Further down: tables of more entries than a round of the job
+lookups probes, the SSIM tile arithmetic, windows of one buffer side by side, and the frame layer at 4:2:2, odd sizes and on
+the second queue."""
 import numpy as np
 import pytest
 
@@ -173,20 +175,23 @@ def test_planes_may_share_a_counter_which_is_added_to(ctx):
 
 # ---- SSIM ----
 
-@pytest.mark.parametrize("kind", ["same", "noisy", "unrelated"])
-def test_ssim_three_unlike_pictures_in_one_call(ctx, kind):
-    pairs = [K.ssim_pair(kind, w, h, 3 + n) for n, (w, h) in enumerate(K.SSIM_SIZES)]
+def run_ssim(ctx, kind, sizes):
+    """One call of all sizes, twice: every pixel of the map and the five counters bit for bit, mssim within the bound of the
+    two orders of adding, the second run's bits the first's.  Returns the restatement's counters per picture."""
+    pairs = [K.ssim_pair(kind, w, h, 3 + n) for n, (w, h) in enumerate(sizes)]
     dev = [(ctx.upload(a), ctx.upload(b, stride=(b.shape[1] + 127) // 64 * 64)) for a, b in pairs]
     runs = []
     for _ in range(2):
         out = ctx.ssim_batch([(a, b, True) for a, b in dev])
         runs.append([(sa.Context.ssim_result(r), m.download()) for r, m, _s in out])
         [p.free() for t in out for p in t]
+    all_counts = []
     for n, (a, b) in enumerate(pairs):
         values, counts = R.ssim_map(a, b)
         (total, got_counts), got_map = runs[0][n]
-        assert np.array_equal(got_map.view(np.uint64), values.view(np.uint64)), (kind, K.SSIM_SIZES[n])       # bit for bit
-        assert got_counts == counts
+        assert np.array_equal(got_map.view(np.uint64), values.view(np.uint64)), (kind, sizes[n])       # bit for bit
+        assert got_counts == counts, (kind, sizes[n])
+        all_counts.append(counts)
         got = total / (a.shape[0] * a.shape[1])
         want, bound = R.mssim(values), R.mssim_bound(values)
         print("ssim %s %dx%d: mssim %.17g, restatement %.17g, |difference| %.3g, bound %.3g" % (
@@ -197,7 +202,42 @@ def test_ssim_three_unlike_pictures_in_one_call(ctx, kind):
         # two runs: identical bits
         assert np.float64(runs[1][n][0][0]).view(np.uint64) == np.float64(total).view(np.uint64)
         assert np.array_equal(runs[1][n][1].view(np.uint64), got_map.view(np.uint64))
+        assert runs[1][n][0][1] == got_counts
     [p.free() for t in dev for p in t]
+    return all_counts
+
+
+@pytest.mark.parametrize("kind", ["same", "noisy", "unrelated"])
+def test_ssim_three_unlike_pictures_in_one_call(ctx, kind):
+    run_ssim(ctx, kind, K.SSIM_SIZES)
+
+
+@pytest.mark.parametrize("kind", ["same", "noisy", "unrelated"])
+def test_ssim_tile_arithmetic(ctx, kind):
+    """K.SSIM_GEOMETRY_SIZES in one call: pictures narrower than the result's eight words, around both tile lengths, tiles
+    across and down at once, 257 tiles under the 256 lanes that add them, both branches of generate_coeff.  The narrow
+    pictures sharpen (sigma = width / 256 * 1.5 is far below 0.7) and leave the range: the counters are compared exactly."""
+    counts = run_ssim(ctx, kind, K.SSIM_GEOMETRY_SIZES)
+    assert all(c > 0 for c in counts[K.SSIM_GEOMETRY_SIZES.index((3, 2049))])           # thousands in each of the five planes
+
+
+def ssim_tiles(w, h):
+    return -(-w // K.SSIM_TILE_COLS) * -(-h // K.SSIM_TILE_ROWS)
+
+
+def test_the_ssim_sizes_stand_around_the_tile_lengths_the_sum_lanes_and_the_coefficient_branch():
+    sizes = K.SSIM_GEOMETRY_SIZES
+    widths, heights = {w for w, _h in sizes}, {h for _w, h in sizes}
+    assert {K.SSIM_TILE_COLS - 1, K.SSIM_TILE_COLS, K.SSIM_TILE_COLS + 1} <= widths
+    assert {K.SSIM_TILE_ROWS - 1, K.SSIM_TILE_ROWS, K.SSIM_TILE_ROWS + 1} <= heights
+    assert any(w > K.SSIM_TILE_COLS and h > K.SSIM_TILE_ROWS for w, h in sizes)         # tiles across and down at once
+    assert any(w > 2 * K.SSIM_TILE_COLS and h > 2 * K.SSIM_TILE_ROWS for w, h in sizes)
+    assert any(ssim_tiles(w, h) > K.SSIM_SUM_LANES for w, h in sizes)                   # the strided loop's second turn
+    assert all(ssim_tiles(w, h) <= K.SSIM_SUM_LANES for w, h in K.SSIM_SIZES)           # (what the first list reaches)
+    assert any(w < 8 for w in widths) and (1, 1) in sizes                               # fewer lanes in the picture than result words
+    below = {w for w in widths if w / 256.0 * 1.5 < 2.5}
+    assert any(w + 1 in widths - below for w in below)                                  # adjacent widths, one on either side
+    assert all(w / 256.0 * 1.5 < 2.5 for w, _h in K.SSIM_SIZES)
 
 
 def test_ssim_in_the_sharpening_regime_counts_out_of_range_samples(ctx):
@@ -296,3 +336,241 @@ def test_ssim_writes_only_its_scratch_result_and_map(ctx):
     total, got_counts = sa.Context.ssim_result(block[result])
     assert got_counts == counts and abs(total / (w * h) - R.mssim(values)) <= R.mssim_bound(values)
     block.free()
+
+
+# ---- full tables: more entries than one round of the job lookups probes ----
+# Tiny planes (K.tiny_size), so that the table is what the test is about.  Everything lies in one guarded block: what a call
+# may write is its results (or planes and counters, or scratch, result and map), and every result starts as canary bytes, so
+# a result that was never cleared, or an entry looked up wrongly, shows.
+
+def test_the_full_tables_pass_one_round_of_the_lookups():
+    for counts in (K.FULL_TABLE_JOBS, K.FULL_TABLE_PLANES):
+        assert min(counts) == K.TABLE_ROUND + 1 and sorted(counts)[1] > 2 * K.TABLE_ROUND and max(counts) == 4 * K.TABLE_ROUND
+    # SSIM hands 2 u8 and 3 s16 low-pass planes per picture to the low-pass table
+    assert [2 * n > K.TABLE_ROUND for n in K.FULL_TABLE_PICTURES] == [False, True, True]
+    assert all(3 * n > K.TABLE_ROUND for n in K.FULL_TABLE_PICTURES) and max(K.FULL_TABLE_PICTURES) == K.TABLE_ROUND
+
+
+@pytest.mark.parametrize("njobs", K.FULL_TABLE_JOBS)
+def test_sums_full_table(ctx, njobs):
+    lay, specs, want = G.Layout(), [], []
+    arrays = []
+    for k in range(njobs):
+        w, h = K.tiny_size(k)
+        if k % 3 == 2:                                  # s16, full range, alone
+            a, b = K.full_range_s16(w, h, 700 + k), None
+        else:                                           # u8 alone, or against a second plane
+            a, b = K.noise(w, h, np.uint8, 700 + k), (K.noise(w, h, np.uint8, 1700 + k) if k % 3 == 1 else None)
+        sa_ = lay.plane(h, w, a.dtype, stride=K.long_stride(k, w * a.dtype.itemsize), align=2, footprint=None, name="a%d" % k)
+        sb = lay.plane(h, w, np.uint8, stride=K.long_stride(k + 3, w), align=1, footprint=None, name="b%d" % k) if b is not None else None
+        res = lay.span(16, align=8, footprint=("bytes", 16), name="result%d" % k)
+        specs.append((sa_, sb, res))
+        arrays.append((a, b))
+        want.append(np.array([R.plane_sums(a, b) if b is not None else R.plane_sums(a)], np.int64))
+    blk = G.GuardedBlock(ctx, lay, seed=njobs)
+    try:
+        jobs = []
+        for (sa_, sb, res), (a, b) in zip(specs, arrays):
+            blk[sa_].upload(a)
+            if sb is not None:
+                blk[sb].upload(b)
+            jobs.append((blk[sa_], blk[sb] if sb is not None else None, blk[res]))
+        expected = {res: w.view(np.uint8).reshape(1, 16) for (_a, _b, res), w in zip(specs, want)}
+        for _ in range(2):                              # (the second call finds the first's sums in the results, not the canary)
+            assert ctx.plane_sums_batch(jobs) is None
+            ctx.synchronize()
+            blk.check(expected)
+    finally:
+        blk.free()
+
+
+@pytest.mark.parametrize("nplanes", K.FULL_TABLE_PLANES)
+def test_lowpass_full_table(ctx, nplanes):
+    lay, specs, inputs, expected = G.Layout(), [], [], {}
+    for k in range(nplanes):
+        w, h = K.tiny_size(k)
+        dtype = (np.uint8, np.int16)[(k // 2 + k // 7) % 2]
+        kinds = ("noise", "steps") if dtype == np.uint8 else ("noise", "steps", "full")
+        a = K.lowpass_input(kinds[k % len(kinds)], w, h, dtype, 900 + k)
+        hs, vs = K.sigma_pair(k)
+        bps = np.dtype(dtype).itemsize
+        p = lay.plane(h, w, dtype, stride=K.long_stride(k, w * bps), align=2, name="plane%d" % k)
+        c = lay.span(4, align=4, footprint=("bytes", 4), name="counter%d" % k)
+        out, bad = R.lowpass2(a, R.generate_coeff(hs), R.generate_coeff(vs))
+        specs.append((p, c, hs, vs))
+        inputs.append(a)
+        expected[p] = out
+        expected[c] = np.array([[(7 * k + bad) & 0xffffffff]], np.uint32).view(np.uint8).reshape(1, 4)
+    assert {np.dtype(a.dtype).name for a in inputs} == {"uint8", "int16"}
+    blk = G.GuardedBlock(ctx, lay, seed=nplanes)
+    try:
+        for _ in range(2):                              # in place: the inputs and the counters go up again
+            planes = []
+            for k, ((p, c, hs, vs), a) in enumerate(zip(specs, inputs)):
+                blk[p].upload(a)
+                blk[c].upload(np.array([[7 * k]], np.uint32).view(np.uint8).reshape(1, 4))
+                planes.append((blk[p], hs, vs, blk[c]))
+            ctx.synchronize()
+            assert ctx.lowpass2_batch(planes) is None
+            ctx.synchronize()
+            blk.check(expected)
+    finally:
+        blk.free()
+
+
+@pytest.mark.parametrize("npictures", K.FULL_TABLE_PICTURES)
+def test_ssim_full_table(ctx, npictures):
+    lay, specs, pairs = G.Layout(), [], []
+    kinds = ("noisy", "unrelated", "same")
+    for k in range(npictures):
+        w, h = K.tiny_size(k + 1)
+        a, b = K.ssim_pair(kinds[k % 3], w, h, 40 + k)
+        sa_ = lay.plane(h, w, np.uint8, stride=K.long_stride(k, w), align=1, footprint=None, name="a%d" % k)
+        sb = lay.plane(h, w, np.uint8, stride=K.long_stride(k + 2, w), align=1, footprint=None, name="b%d" % k)
+        nbytes = sa.ssim_scratch_bytes(w, h)
+        scratch = lay.span(nbytes, align=16, footprint=("bytes", nbytes), name="scratch%d" % k)
+        result = lay.span(32, align=8, footprint=("bytes", 32), name="result%d" % k)
+        mp = lay.plane(h, w, np.uint64, stride=8 * w + 8 * (k % 4), align=8, name="map%d" % k) if k % 3 != 1 else None   # (the doubles' bits)
+        specs.append((sa_, sb, scratch, result, mp))
+        pairs.append((a, b))
+    blk = G.GuardedBlock(ctx, lay, seed=npictures)
+    try:
+        pictures = []
+        for (sa_, sb, scratch, result, mp), (a, b) in zip(specs, pairs):
+            blk[sa_].upload(a)
+            blk[sb].upload(b)
+            pictures.append((blk[sa_], blk[sb], blk[mp] if mp is not None else None, blk[scratch], blk[result]))
+        want = [R.ssim_map(a, b) for a, b in pairs]
+        expected = {mp: values.view(np.uint64) for (_a, _b, _s, _r, mp), (values, _c) in zip(specs, want) if mp is not None}
+        results = []
+        for _ in range(2):
+            ctx.ssim_batch(pictures)
+            ctx.synchronize()
+            blk.check(expected)                         # the maps bit for bit, nothing written outside scratch, result and map
+            results.append([blk[result].download().tobytes() for (_a, _b, _s, result, _m) in specs])
+        assert results[0] == results[1]                 # the sums, the counters and the reserved word: the same bits
+        for k, ((values, counts), (_a, _b, _s, result, _m)) in enumerate(zip(want, specs)):
+            total, got_counts = sa.Context.ssim_result(blk[result])
+            assert got_counts == counts, k
+            assert abs(total / values.size - R.mssim(values)) <= R.mssim_bound(values), k
+    finally:
+        blk.free()
+
+
+# ---- windows of one buffer, side by side ----
+
+class Window:
+    """Columns x0 .. x0 + width - 1 of every row of a plane, as the wrappers take a plane."""
+
+    def __init__(self, plane, x0, width):
+        self.dtype, self.stride, self.height, self.width = plane.dtype, plane.stride, plane.height, width
+        self.ptr = plane.ptr + x0 * plane.dtype.itemsize
+
+
+def test_lowpass_windows_side_by_side_share_rows_and_nothing_else(ctx):
+    """Two and three windows of one u8 buffer and of one s16 buffer in one call (rects_overlap, plane_stats.cpp, lets them
+    pass): each window is the restatement's low-pass of itself, the column between two windows, the padding and every other
+    byte of the block keep their bytes."""
+    w, h = K.LOWPASS_CHUNK + 70, K.LOWPASS_ROWS + 3
+    cuts = {2: [(0, 37), (37, w - 37)], 3: [(0, 5), (6, 64), (70, w - 70)]}             # (first column, width); column 5 is nobody's
+    lay, buffers = G.Layout(), []
+    for dtype in (np.uint8, np.int16):
+        bps = np.dtype(dtype).itemsize
+        for n in (2, 3):
+            stride = w * bps + 6
+            spec = lay.plane(h, w, dtype, stride=stride, align=2,
+                             footprint=[(x0 * bps, stride, ww * bps, h) for x0, ww in cuts[n]], name="%s x %d" % (np.dtype(dtype).name, n))
+            buffers.append((spec, dtype, cuts[n]))
+    counter = lay.span(4, align=4, footprint=("bytes", 4), name="counter")
+    blk = G.GuardedBlock(ctx, lay, seed=77)
+    try:
+        planes, expected, bad_total = [], {}, 0
+        for m, (spec, dtype, cut) in enumerate(buffers):
+            a = K.lowpass_input("steps" if m & 1 else "noise", w, h, dtype, 60 + m)
+            blk[spec].upload(a)
+            want = a.copy()
+            for k, (x0, ww) in enumerate(cut):
+                hs, vs = K.sigma_pair(m + 2 * k)
+                out, bad = R.lowpass2(np.ascontiguousarray(a[:, x0:x0 + ww]), R.generate_coeff(hs), R.generate_coeff(vs))
+                want[:, x0:x0 + ww] = out
+                bad_total += bad
+                planes.append((Window(blk[spec], x0, ww), hs, vs, blk[counter]))
+            expected[spec] = want
+        blk[counter].upload(np.array([[5]], np.uint32).view(np.uint8).reshape(1, 4))
+        expected[counter] = np.array([[5 + bad_total]], np.uint32).view(np.uint8).reshape(1, 4)
+        assert len(planes) == 10
+        sa.lowpass2_check(planes)                        # (accepted on the host too)
+        assert ctx.lowpass2_batch(planes) is None
+        ctx.synchronize()
+        blk.check(expected)
+    finally:
+        blk.free()
+
+
+# ---- frame layer: the other chroma format, odd sizes, the second queue ----
+
+def frame_planes(w, h, h_shift, v_shift):
+    cw, ch = (w + (1 << h_shift) - 1) >> h_shift, (h + (1 << v_shift) - 1) >> v_shift    # rounded up
+    pa = [K.picture(w, h, 1), K.picture(cw, ch, 2), K.picture(cw, ch, 3)]
+    pb = [np.clip(p.astype(np.int32) + np.random.default_rng(9 + k).integers(-9, 10, p.shape), 0, 255).astype(np.uint8) for k, p in enumerate(pa)]
+    return pa, pb
+
+
+def five_frame_calls(ctx, w, h, h_shift, v_shift):
+    """The five calls on w x h frames, every value against the restatement; returns them (mssim as its bits)."""
+    pa, pb = frame_planes(w, h, h_shift, v_shift)
+    fa, fb = device_frame(ctx, pa, h_shift, v_shift), device_frame(ctx, pb, h_shift, v_shift)
+    out = []
+    average = ctx.average_luma(fa)
+    assert average == R.average_luma(pa[0])
+    out.append(average)
+    mse = ctx.mean_squared_error(fa, fb)
+    assert mse == R.mean_squared_error(pa, pb)
+    out.append(mse)
+    values, _ = R.ssim_map(pa[0], pb[0])
+    mssim = ctx.ssim(fa, fb)
+    assert abs(mssim - R.mssim(values)) <= R.mssim_bound(values)
+    assert ctx.ssim(fa, fa) == 1.0
+    out.append(np.float64(mssim).view(np.uint64))
+    for luma in (average, 16.005, 16.02):
+        score = ctx.scene_change_score(fa, fb, luma)
+        assert score == R.scene_change_score(luma, pa[0], pb[0])
+        out.append(score)
+    for planes, sigma in ((pa, 0.75), (pa, 5), ([(p.astype(np.int16) - 128) * 64 for p in pa], 1.5)):
+        f = device_frame(ctx, planes, h_shift, v_shift)
+        ctx.filter_lowpass2(f, sigma)
+        got = f.download()
+        for g, want in zip(got, R.frame_lowpass2(planes, sigma, h_shift, v_shift)):
+            assert np.array_equal(g, want), sigma
+        out.append([g.tobytes() for g in got])
+        f.unref()
+    [x.unref() for x in (fa, fb)]
+    return out
+
+
+FRAME_CASES = [(130, 68, 1, 0), (131, 67, 1, 1), (131, 67, 1, 0), (131, 67, 0, 0), (1, 1, 1, 1), (1, 1, 0, 0)]
+
+
+@pytest.mark.parametrize("w,h,h_shift,v_shift", FRAME_CASES)
+def test_the_five_frame_calls_at_422_odd_sizes_and_one_sample(ctx, w, h, h_shift, v_shift):
+    five_frame_calls(ctx, w, h, h_shift, v_shift)
+
+
+def test_the_five_frame_calls_on_the_second_queue(ctx):
+    """The results pass through the selected queue's scratch head: queue 0 first runs a larger SSIM, so that its scratch has
+    grown and queue 1's has not; then every case on queue 0 and on queue 1 -- the same values, the same bits."""
+    assert ctx.queue() == 0
+    pa, pb = frame_planes(300, 200, 1, 1)
+    fa, fb = device_frame(ctx, pa, 1, 1), device_frame(ctx, pb, 1, 1)
+    ctx.ssim(fa, fb)
+    [x.unref() for x in (fa, fb)]
+    try:
+        for case in FRAME_CASES:
+            ctx.select_queue(0)
+            first = five_frame_calls(ctx, *case)
+            ctx.select_queue(1)
+            assert ctx.queue() == 1
+            assert five_frame_calls(ctx, *case) == first, case
+    finally:
+        ctx.select_queue(0)
+    assert ctx.queue() == 0

@@ -6,7 +6,8 @@ the picture (the edge extension) and removes the offset in registers.  Every cas
 launches nothing of the "convert" profile class; sources and coefficient planes are carved out of a guarded block
 (tests/guard_lib.py).  The transform sizes 352 x 160 (picture 331 x 150) and 160 x 64 (picture 150 x 62) are several tiles
 across and down for every filter's tile with partial last tiles, the picture's edge inside a tile's halo and inside its
-useful part; 44 x 12 (picture 41 x 11) at depth 1 has sub-band rows that are no whole vectors."""
+useful part; 44 x 12 (picture 41 x 11) at depth 1 has sub-band rows that are no whole vectors.  EXTENSION_SIZES holds
+pictures far smaller than their transform: whole tiles lie in the edge extension, one picture is a deep crop."""
 import os
 
 import numpy as np
@@ -180,6 +181,52 @@ def test_equals_the_plane_layers_chain(ctx, dtype):
         blk.check(expected)
     finally:
         blk.free()
+
+
+# (transform size, picture size, source size less the picture size): pictures far smaller than their transform, so that whole
+# tiles of the packed level 0 lie in the edge extension -- every coordinate rows_load_packed clamps is xmax / ymax there --,
+# one of them cropped out of a source larger than it by more than a tile, and the smallest picture there is
+EXTENSION_SIZES = [((352, 160), (41, 11), (1, 0)), ((352, 160), (40, 12), (360, 158)), ((352, 160), (6, 2), (0, 0)),
+                   ((64, 32), (1, 1), (1, 0))]
+
+
+def tiles_wholly_in_the_extension(size, filt, dtype):
+    """The luma tiles (tx, ty) of the forward wavelet's level 0 whose region -- useful part and halo, from the library's
+    own tile lengths (sa.unpack_geometry) -- begins right of and below the last picture sample."""
+    (iw, ih), (w, h), _delta = size
+    uc, ur, hc, hr = sa.unpack_geometry()["iwt"][(filt, np.dtype(dtype).itemsize)]
+    return [(tx, ty) for ty in range(-(-(ih // 2) // ur)) for tx in range(-(-(iw // 2) // uc))
+            if 2 * (tx * uc - hc) >= w and 2 * (ty * ur - hr) >= h]
+
+
+@pytest.mark.parametrize("dtype", [np.int16, np.int32], ids=["s16", "s32"])
+@pytest.mark.parametrize("filt", range(7))
+def test_the_cases_hold_tiles_that_lie_wholly_in_the_extension(filt, dtype):
+    for size in EXTENSION_SIZES[:3]:
+        assert tiles_wholly_in_the_extension(size, filt, dtype), (size, filt)
+    # the deep crop: the source exceeds the picture by more than a tile's useful part either way
+    uc, ur, _hc, _hr = sa.unpack_geometry()["iwt"][(filt, np.dtype(dtype).itemsize)]
+    assert EXTENSION_SIZES[1][2][0] > 2 * uc and EXTENSION_SIZES[1][2][1] > 2 * ur
+    # (what the sizes further up reach: pictures within 21 samples of their transform have no such tile)
+    for size in SIZES + [DEPTH1_SIZE]:
+        assert not tiles_wholly_in_the_extension(size, filt, dtype), size
+
+
+@pytest.mark.parametrize("dtype", [np.int16, np.int32], ids=["s16", "s32"])
+@pytest.mark.parametrize("depth", [1, 3])
+@pytest.mark.parametrize("filt", range(7))
+def test_tiles_in_the_extension_and_deep_crops_on_both_routes(ctx, filt, depth, dtype):
+    """Every format at every size of EXTENSION_SIZES with an aligned source (FUSED where the combination is), and in the same
+    call one picture per size whose source stride or pointer sends it to the two passes."""
+    pictures = [pic(fmt, size) for fmt in U.PACKED for size in EXTENSION_SIZES]
+    for n, size in enumerate(EXTENSION_SIZES):
+        fmt = U.PACKED[(n + filt) % len(U.PACKED)]
+        pictures.append(pic(fmt, size, **({"src_pad": 2} if n & 1 else {"src_skew": 4 if fmt != U.AY64 else 2})))
+    routes = {expected_route(p, filt, dtype) for p in pictures}
+    bpp = np.dtype(dtype).itemsize
+    some_fused = not FORCED_TWO_PASS and (FORCED_FUSED or any(filt in FUSED_FILTERS[(fmt, bpp)] for fmt in U.PACKED))
+    assert "two_pass" in routes and ("fused" in routes) == some_fused       # (s16 Fidelity has no FUSED combination)
+    run(ctx, pictures, depth, filt, dtype, seed=200 + 10 * filt + depth)
 
 
 def test_refusals_are_the_chains(ctx):
