@@ -287,7 +287,11 @@ class Decoder:
         return pic
 
     # ---- block data ----------------------------------------------------------------------
-    def decode_block_data(self, pic):
+    def decode_block_data(self, pic, log=None):
+        """log: nine lists, one per section of the motion data (split, modes, ref-1 x / y, ref-2 x / y, DC Y / U / V).
+        Every value a section's arithmetic decoder yields at the top level is appended to the section's list in stream
+        order -- the uint of a split, each mode bit, the sint of a vector or DC residual --: what the reference's encoder
+        coded, before any prediction is added."""
         nx, ny = pic.x_num_blocks, pic.y_num_blocks
         mode = np.zeros((ny, nx), np.int32)
         split = np.zeros((ny, nx), np.int32)
@@ -297,6 +301,14 @@ class Decoder:
 
         def short(v):
             return ((v + 32768) & 0xffff) - 32768
+
+        def rec(section, value):
+            if log is not None:
+                log[section].append(value)
+            return value
+
+        def residual(section, cont, value, sign):
+            return rec(section, ar[section].sint(cont, value, sign))
 
         def mode_pred(x, y):
             if y == 0:
@@ -339,22 +351,22 @@ class Decoder:
 
         def unit(x, y):
             m = mode_pred(x, y)
-            m ^= ar[A_MODE].bit(CTX_MODE_REF1)
+            m ^= rec(A_MODE, ar[A_MODE].bit(CTX_MODE_REF1))
             if pic.num_refs > 1:
-                m ^= ar[A_MODE].bit(CTX_MODE_REF2) << 1
+                m ^= rec(A_MODE, ar[A_MODE].bit(CTX_MODE_REF2)) << 1
             mode[y, x] = m
             if m == 0:
                 for i, a in enumerate((A_DC0, A_DC1, A_DC2)):
-                    vec[y, x, i] = short(dc_pred(x, y, i) + ar[a].sint(CTX_DC_CONT1, CTX_DC_VALUE, CTX_DC_SIGN))
+                    vec[y, x, i] = short(dc_pred(x, y, i) + residual(a, CTX_DC_CONT1, CTX_DC_VALUE, CTX_DC_SIGN))
                 return
             if m & 1:
                 px, py = mv_pred(x, y, 1)
-                vec[y, x, 0] = short(px + ar[A_X1].sint(CTX_MV_CONT1, CTX_MV_VALUE, CTX_MV_SIGN))
-                vec[y, x, 2] = short(py + ar[A_Y1].sint(CTX_MV_CONT1, CTX_MV_VALUE, CTX_MV_SIGN))
+                vec[y, x, 0] = short(px + residual(A_X1, CTX_MV_CONT1, CTX_MV_VALUE, CTX_MV_SIGN))
+                vec[y, x, 2] = short(py + residual(A_Y1, CTX_MV_CONT1, CTX_MV_VALUE, CTX_MV_SIGN))
             if m & 2:
                 px, py = mv_pred(x, y, 2)
-                vec[y, x, 1] = short(px + ar[A_X2].sint(CTX_MV_CONT1, CTX_MV_VALUE, CTX_MV_SIGN))
-                vec[y, x, 3] = short(py + ar[A_Y2].sint(CTX_MV_CONT1, CTX_MV_VALUE, CTX_MV_SIGN))
+                vec[y, x, 1] = short(px + residual(A_X2, CTX_MV_CONT1, CTX_MV_VALUE, CTX_MV_SIGN))
+                vec[y, x, 3] = short(py + residual(A_Y2, CTX_MV_CONT1, CTX_MV_VALUE, CTX_MV_SIGN))
 
         def copy(ys, xs, y0, x0):
             mode[ys, xs] = mode[y0, x0]
@@ -369,7 +381,7 @@ class Decoder:
                     sp = split[j - 4, 0]
                 else:
                     sp = (split[j - 4, i] + split[j, i - 4] + split[j - 4, i - 4] + 1) // 3
-                s = (sp + ar[A_SB].uint(CTX_SB_F1, CTX_SB_DATA)) % 3
+                s = (sp + rec(A_SB, ar[A_SB].uint(CTX_SB_F1, CTX_SB_DATA))) % 3
                 split[j, i] = s
                 if s == 0:
                     unit(i, j)

@@ -11,6 +11,10 @@ rules for hostile input that the reference leaves undefined:
     codes it can be asked for at all (blocks; superblocks for the splits), asked for or not;
   - a split is (pred + value) % 3 without a second wrap; vectors and DCs are (int16_t) (pred + value).
 
+Pinned by the hand-derived byte strings of tests/test_motion_dec_ref.py and, on reference-produced data, by
+tests/test_noarith_twin.py: `decode` reads the stream's fields back from the noarith twin of the reference's own stream
+(tests/noarith_twin.py) for all 96 inter pictures, every counter 0.
+
 Three forms, held equal by tests/test_motion_dec_ref.py: decode (the reference's serial order), decode_wavefront (the
 phases of motion_dec.hip: splits over anti-diagonals of superblocks, unit prefix sum, modes over anti-diagonals of blocks,
 code-index prefix sums, values over anti-diagonals of blocks) and, for the code extraction alone, extract_chunked (64-bit

@@ -6,7 +6,9 @@ Encoder: what schro_encoder_encode_picture appends between the prediction parame
 schro_motion_get_global_prediction (:213-239), schro_motion_vector_prediction (:315-368), schro_motion_split_prediction
 (:371-399), schro_motion_get_mode_prediction (:402-430) and the bit writer of schropack.c:79-178 (noarith_enc_ref.Pack).
 The reference's encoder cannot be built without liborc, so tests/test_motion_enc_ref.py pins this file with hand-derived
-byte strings and with the round trip.
+byte strings and with the round trip, and tests/test_noarith_twin.py with the noarith twin of the reference's own stream
+(tests/noarith_twin.py, made without this file): `encode` writes the twin's bytes for all 96 inter pictures.  The stream
+has split 2, full-pel vectors and no global motion only; the rest stays with the hand-derived strings.
 
 Decoder: schro_decoder_parse_block_data, schro_decoder_decode_block_data / _decode_macroblock / _decode_prediction_unit
 (schrodecoder.c:2525-2814) for noarith, with the bit reader of schrounpack.c (noarith_enc_ref.Unpack).

@@ -11,6 +11,10 @@ more than one codeblock, sub-band 0 included, and a quant offset whenever codebl
 in compat mode and the sub-band has one codeblock.  The two agree where sub-band 0 has 1 x 1 codeblocks and either the
 mode is 0 or compat is on.
 
+Pinned by the hand-derived byte strings of tests/test_noarith_dec_ref.py and, on reference-produced data, by
+tests/test_noarith_twin.py: the quantised planes of the reference's own stream through `write_transform_data` decode to the
+stream's coefficients for all 100 pictures (s16, one quant index per sub-band, one codeblock in sub-band 0).
+
 Where the reference is undefined, this file defines (and schro_hip_noarith_decode_batch follows):
   * a code of 31 or more data bits (`1 << count` overflows in schro_unpack_decode_uint): v = 1; per data bit
     v = (v << 1 | b) mod 2^32; the magnitude is v - 1 mod 2^32; a code with data bits always has a sign bit (the reference

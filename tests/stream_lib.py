@@ -26,8 +26,10 @@ def load_stream():
     return open(os.path.join(GOLDEN, "test_stream.drc"), "rb").read()
 
 
-def decode_stream(data, tables, limit=None, quantised=False):
-    """Yields per picture (coded order) a dict with everything decoded.  quantised: also
+def decode_stream(data, tables, limit=None, quantised=False, detail=False):
+    """Yields per picture (coded order) a dict with everything decoded.  detail: also "picture" (the parsed
+    dirac_stream.Picture), "compat" (the decoder's compat_quant_offset state in front of the picture) and, for a picture
+    with references, "motion_log" (the values dirac_stream.Decoder.decode_block_data records).  quantised: also
     "quant" (int32 planes of quantised values) and "codeblocks" (per component, see
     dirac_stream.Decoder.decode_coefficients): the hand-over point of device-side
     dequantisation.  The compatibility heuristic of old streams carries state from sub-band to
@@ -42,6 +44,7 @@ def decode_stream(data, tables, limit=None, quantised=False):
             pic = dec.parse_picture(code, payload)
             fmt = dec.fmt
             dims = [(pic.height, pic.width), (pic.ch, pic.cw), (pic.ch, pic.cw)]
+            compat = dec.compat_quant_offset
             if pic.zero_residual:
                 res = None
                 coeffs = None
@@ -61,7 +64,8 @@ def decode_stream(data, tables, limit=None, quantised=False):
             if pic.num_refs == 0:
                 out = [O.convert_u8(res[k], dims[k][1], dims[k][0]) for k in range(3)]
             else:
-                mv = dec.decode_block_data(pic)
+                log = [[] for _ in range(9)] if detail else None
+                mv = dec.decode_block_data(pic, log)
                 P = dict(x_num_blocks=pic.x_num_blocks, y_num_blocks=pic.y_num_blocks, xblen_luma=pic.xblen,
                          yblen_luma=pic.yblen, xbsep_luma=pic.xbsep, ybsep_luma=pic.ybsep,
                          mv_precision=pic.mv_precision, picture_weight_bits=pic.weight_bits,
@@ -75,8 +79,12 @@ def decode_stream(data, tables, limit=None, quantised=False):
                     residual = res[k] if res is not None else np.zeros((h, w), np.int16)
                     out.append(O.motion_render(mv, op, k, u[0], u[1] if len(u) > 1 else None, residual, w, h))
                 rec.update(mv=mv, params=P)
+                if detail:
+                    rec["motion_log"] = log
             if not pic.zero_residual:
                 rec.update(depth=pic.depth, wavelet=pic.wavelet)
+            if detail:
+                rec.update(picture=pic, compat=compat)
             rec["out"] = out
             rec["md5"] = D.frame_md5(out)
             if pic.is_ref:
