@@ -1533,7 +1533,8 @@ int schro_hip_noarith_encode_check (const SchroHipNoarithPicture * pictures, int
  * :3279-3449, :3525-3625) for params->is_noarith: the picture's transform-data bytes go in, from a synchronised position;
  * the completely filled, dequantised coefficient planes come out.  A sub-band of length 0 is zero-filled, a codeblock whose
  * zero flag is set is zero-filled, every other sample is dequantised with the decoder's arithmetic (s16 planes: the 16-bit
- * Orc program; s32 planes: C int -- the same two forms schro_hip_dequant_batch has).  The arithmetic decoder stays host code.
+ * Orc program; s32 planes: C int -- the same two forms schro_hip_dequant_batch has).  Arithmetic-coded pictures take
+ * schro_hip_arith_decode_batch, further down.
  *
  * These are the DECODER's rules; the encoder's (schro_hip_noarith_encode_batch above) differ.  Per component and sub-band
  * the outer unpack reads: byte sync, uint (length); length 0: byte sync; else uint (quant index), byte sync and `length`
@@ -1609,6 +1610,80 @@ int schro_hip_noarith_decode_check (const SchroHipNoarithDecodePicture * picture
 /* host only: the words of queue scratch the call takes for these pictures (5 per chunk slot -- data_bytes / 8 + sub-bands
  * + 1 slots per picture --, 3 per codeblock, 8 per sub-band, 2 per picture), or < 0 on refusal. */
 int64_t schro_hip_noarith_decode_scratch_words (const SchroHipNoarithDecodePicture * pictures, int npictures, int bytes_per_sample);
+
+/* ---- decoder: arithmetic-coded core-syntax transform data, read on the device -------------------
+ *
+ * schro_decoder_parse_transform_data (schrodecoder.c:2939-2987) and schro_decoder_decode_transform_data (:2990-3015) for
+ * !params->is_noarith -- the form every default encoder writes: schro_decoder_decode_subband (:3525-3638) over
+ * schro_decoder_decode_codeblock (:3452-3522), the generic line decoder (:3018-3217; its three _p_ forms compute the same)
+ * and the binary arithmetic decoder (schroarith.h:147-210, schroarith.c:211-239, 283-288, 642-668).  The headers, the
+ * codeblock counts and rectangles, have_zero_flags, have_quant_offset and the state compat_quant_offset are those of the
+ * VLC call above; only the payloads differ.
+ *
+ * The coder: range 0xffff0000, the code is the payload's first four bytes (0xff for a byte that does not exist), offset
+ * 3, cntr 16, every probability 0x8000 per sub-band.  A bin renormalises while range <= 0x40000000 -- two bytes enter every
+ * 16 shifts, 0xff behind the payload's end --, then range_x_prob = ((range >> 16) * p) & 0xffff0000, bit = code >=
+ * range_x_prob, and p moves by the 256-entry table.  uint: bits = 1; while the continuation bin is 0: bits = bits << 1 |
+ * (data bin), the continuation context moves on; the value is (int) (bits - 1).  The quant offset is a sint whose loop also
+ * stops after 30 data bins.  Per coefficient the continuation context comes from parent != 0 (sub-band index - 3 at
+ * (x >> 1, y >> 1), from position 4 on) and from the OR of the left, upper and upper-left values; the sign context from
+ * the left value (horizontally oriented bands), the upper value (vertically oriented) or none -- each the STORED value,
+ * dequantised and truncated to the sample type.  A non-zero value v is stored as +- ((offset + factor * v + 2) >> 2) in C
+ * int for both sample sizes (NOT the 16-bit Orc form of the VLC path), offsets _1_2 when is_intra, else _3_8.
+ *
+ * schro_decoder_test_quant_offset_compat peeks a sint with a COPY of the fresh coder of sub-band 0 (one codeblock, an
+ * offset, coded); otherwise as above.  The LL band of an intra picture is NOT DC-predicted here (as above).
+ *
+ * Where the reference is undefined the call is defined and bounded; the input is fetched as the aligned dwords that hold
+ * its bytes and nothing else is read:
+ *  - a uint of 32 or more data bins wraps: bits is kept mod 2^32 (a wrapped value of 0 has no sign bin, as the reference's
+ *    `if (v)`); from 31 data bins on (int) (bits - 1) is negative.  Codes of 31 or more data bins count in long_codes.
+ *  - offset + factor * v + 2 past 2^31: 32-bit two's-complement wrap, an arithmetic shift, a wrapping negation.  This is
+ *    what the x86-64 build of the reference computes; it is undefined in C and NOT pinned against the reference.
+ *  - quant index + offset is formed in 64 bits and clamped to 0 .. 60 (clamped_quant counts).
+ *  - a header quant index above 60, a length past the input's end (the payload goes on with 0xff bytes, the reference's
+ *    own rule for the end of a buffer): as above.
+ *  - after a sub-band schro_arith_decode_flush; offset < length - 1 counts in not_consumed, offset > length + 4 in overran.
+ * Running time is bounded by the input alone: see DESIGN 4.24. */
+typedef struct {
+  uint32_t bytes_read;          /* whole bytes the outer unpack consumed (rounded up; saturates at 2^32 - 1) */
+  uint32_t error, first_error;  /* quant index > 60 in a header: nothing written */
+  uint32_t compat_quant_offset; /* the instance's state after this picture */
+  uint32_t truncated, not_consumed, overran, long_codes, clamped_quant;
+  uint32_t subband_length[3][SCHRO_HIP_NOARITH_MAX_SUBBANDS];
+  uint8_t subband_quant_index[3][SCHRO_HIP_NOARITH_MAX_SUBBANDS];       /* of codeblock (0,0), as the header states it */
+  uint32_t bins;                /* binary decisions decoded for the picture (the compat peeks not counted; saturates at 2^32 - 1) */
+} SchroHipArithDecodeResult;
+
+/* The fields of SchroHipNoarithDecodePicture with the same meanings. */
+typedef struct {
+  const uint8_t *data;          /* device: the transform data, from a synchronised position */
+  size_t data_bytes;            /* host: at most this many bytes are ever used (below 2^29) */
+  const uint32_t *bytes_on_device;      /* optional, device, 4-byte aligned: min (*bytes_on_device, data_bytes) is the length */
+  void *coeffs[3];              /* device: Y, U, V coefficient planes (s16 or s32) */
+  size_t bytes[3];              /* what each plane spans */
+  int stride[3];                /* bytes between rows, of coeffs and of quant */
+  void *quant[3];               /* optional, same layout: the values as read, not dequantised (all three or none) */
+  int iwt_width[3], iwt_height[3], transform_depth;
+  int horiz_codeblocks[7], vert_codeblocks[7], codeblock_mode_index;
+  int is_intra;                 /* num_refs == 0: offsets _1_2, else _3_8; no DC prediction (see above) */
+  int compat_quant_offset;      /* the instance's state before this picture */
+  SchroHipArithDecodeResult *result;    /* device, 4-byte aligned: cleared and filled by the call */
+} SchroHipArithDecodePicture;
+
+/* Pictures of unlike geometry and depth in one call: a header launch (the serial chain of sub-band headers per picture,
+ * with the compat peeks), a clear launch (the planes of every picture without the error, so that zero sub-bands and zero
+ * codeblocks read as zero to their children and neighbours) and a decode launch.  Its unit is the TOWER: sub-band i >= 4
+ * reads sub-band i - 3, so a component is four serial chains -- LL, and per orientation the levels from coarse to fine --
+ * and a picture twelve; a wave decodes a tower, one lane deciding, one bin per trip of its loop.  Enqueues, does not synchronise; bytes
+ * between a row's width and the stride and everything outside the planes are not written.  The refusals are those of
+ * schro_hip_noarith_decode_batch. */
+int schro_hip_arith_decode_batch (SchroHipContext * ctx, const SchroHipArithDecodePicture * pictures, int npictures,
+    int bytes_per_sample);
+/* host only: the refusals of schro_hip_arith_decode_batch without a context.  No pointer is dereferenced. */
+int schro_hip_arith_decode_check (const SchroHipArithDecodePicture * pictures, int npictures, int bytes_per_sample);
+/* host only: the words of queue scratch the call takes for these pictures (8 per sub-band), or < 0 on refusal. */
+int64_t schro_hip_arith_decode_scratch_words (const SchroHipArithDecodePicture * pictures, int npictures, int bytes_per_sample);
 
 /* ---- encoder: the motion data of a noarith (VLC) picture, written on the device ----------------
  *
@@ -2136,6 +2211,18 @@ SCHRO_HIP_LAYOUT (SchroHipMotionDecodePicture, bytes_on_device, 16);
 SCHRO_HIP_LAYOUT (SchroHipMotionDecodePicture, num_refs, 32);
 SCHRO_HIP_LAYOUT (SchroHipMotionDecodePicture, motion, 40);
 SCHRO_HIP_LAYOUT (SchroHipMotionDecodePicture, result, 48);
+SCHRO_HIP_SIZE (SchroHipArithDecodeResult, 328);
+SCHRO_HIP_LAYOUT (SchroHipArithDecodeResult, clamped_quant, 32);
+SCHRO_HIP_LAYOUT (SchroHipArithDecodeResult, subband_length, 36);
+SCHRO_HIP_LAYOUT (SchroHipArithDecodeResult, subband_quant_index, 264);
+SCHRO_HIP_LAYOUT (SchroHipArithDecodeResult, bins, 324);
+SCHRO_HIP_SIZE (SchroHipArithDecodePicture, 216);
+SCHRO_HIP_LAYOUT (SchroHipArithDecodePicture, bytes_on_device, 16);
+SCHRO_HIP_LAYOUT (SchroHipArithDecodePicture, stride, 72);
+SCHRO_HIP_LAYOUT (SchroHipArithDecodePicture, quant, 88);
+SCHRO_HIP_LAYOUT (SchroHipArithDecodePicture, transform_depth, 136);
+SCHRO_HIP_LAYOUT (SchroHipArithDecodePicture, codeblock_mode_index, 196);
+SCHRO_HIP_LAYOUT (SchroHipArithDecodePicture, result, 208);
 SCHRO_HIP_SIZE (SchroHipUnpackPicture, 120);
 SCHRO_HIP_LAYOUT (SchroHipUnpackPicture, src_stride, 24);
 SCHRO_HIP_LAYOUT (SchroHipUnpackPicture, format, 36);
@@ -2363,6 +2450,12 @@ int schro_hipframe_dequantise (SchroHipFrame * transform_frame, const SchroHipQu
  * (a header quant index above 60) returns SCHRO_HIP_EINVAL with the frame untouched.  Waits for the result. */
 int schro_hipframe_decode_transform_data_noarith (SchroHipFrame * transform_frame, const uint8_t * host_data, size_t length,
     SchroHipParams * params, int *compat_quant_offset, SchroHipNoarithDecodeResult * result);
+
+/* The same for an arithmetic-coded picture (schro_hip_arith_decode_batch): uploads, decodes, DC-predicts the LL bands of
+ * an intra picture once picture->error is known to be 0, and waits.  params->is_noarith and params->is_lowdelay are
+ * refused with SCHRO_HIP_EINVAL. */
+int schro_hipframe_decode_transform_data_arith (SchroHipFrame * transform_frame, const uint8_t * host_data, size_t length,
+    SchroHipParams * params, int *compat_quant_offset, SchroHipArithDecodeResult * result);
 
 /* schro_upsampled_gpuframe_upsample (schrogpuframe.h:27) replacement:
  * dest (device, is_upsampled) <- half-pel images of src (device u8). */

@@ -420,7 +420,11 @@ def noarith_decode_pictures(pictures):
     vert_codeblocks, codeblock_mode_index, is_intra, compat_quant_offset, result)]: data, bytes_on_device, result -- device
     memory (anything with ptr, or an address) or None; coeffs -- the Y, U, V planes at the transform's size (anything with
     ptr, stride, width, height); quant -- three planes of the same layout or None."""
-    arr = (_lib.NoarithDecodePicture * len(pictures))()
+    return _fill_decode_pictures((_lib.NoarithDecodePicture * len(pictures))(), pictures)
+
+
+def _fill_decode_pictures(arr, pictures):
+    """The fields the VLC and the arithmetic decode pictures share."""
     addr = lambda m: None if m is None else getattr(m, "ptr", m)
     for a, (data, nbytes, on_device, coeffs, quant, depth, hc, vc, mode, is_intra, compat, result) in zip(arr, pictures):
         a.data, a.data_bytes, a.bytes_on_device = addr(data), nbytes, addr(on_device)
@@ -455,6 +459,35 @@ def noarith_decode_result(words):
     out = {k: int(v) for k, v in zip(names, w[:9])}
     out["subband_length"] = w[9:9 + n].astype(np.int64).reshape(3, _lib.NOARITH_MAX_SUBBANDS)
     out["subband_quant_index"] = w[9 + n:].view(np.uint8)[:n].astype(np.int64).reshape(3, _lib.NOARITH_MAX_SUBBANDS)
+    return out
+
+
+def arith_decode_pictures(pictures):
+    """The SchroHipArithDecodePicture array of the twelve entries noarith_decode_pictures takes, with the same meanings."""
+    return _fill_decode_pictures((_lib.ArithDecodePicture * len(pictures))(), pictures)
+
+
+def arith_decode_check(pictures, bpp):
+    """The refusals of Context.arith_decode_batch on the host, without a context (schro_hip_arith_decode_check)."""
+    check(_lib.load().schro_hip_arith_decode_check(arith_decode_pictures(pictures), len(pictures), bpp))
+
+
+def arith_decode_scratch_words(pictures, bpp):
+    """The words of queue scratch Context.arith_decode_batch takes for these pictures (schro_hip_arith_decode_scratch_words)."""
+    n = int(_lib.load().schro_hip_arith_decode_scratch_words(arith_decode_pictures(pictures), len(pictures), bpp))
+    if n < 0:
+        check(n)
+    return n
+
+
+def arith_decode_result(words):
+    """A downloaded SchroHipArithDecodeResult (uint32 words, or the ctypes structure) as a dict: the entries of
+    noarith_decode_result with the arithmetic decoder's meanings, and bins."""
+    if isinstance(words, _lib.ArithDecodeResult):
+        words = np.frombuffer(bytes(words), np.uint32)
+    w = np.ascontiguousarray(np.asarray(words, np.uint32).ravel()[:C.sizeof(_lib.ArithDecodeResult) // 4])
+    out = noarith_decode_result(w)
+    out["bins"] = int(w[_lib.ArithDecodeResult.bins.offset // 4])
     return out
 
 
@@ -1635,6 +1668,50 @@ class Context:
         if rc != 0 and not (rc == -1 and res.error):
             check(rc)
         return noarith_decode_result(res), int(compat.value), rc
+
+    def arith_decode_batch(self, pictures):
+        """schro_hip_arith_decode_batch: Context.noarith_decode_batch for arithmetic-coded transform data (the form a default
+        encoder writes), with the same two shapes of `pictures`.  Where the bytes and the result are the call's own, waits
+        and returns an arith_decode_result dict per picture; with caller-owned buffers the call is asynchronous and returns
+        None.  The LL bands of an intra picture are not DC-predicted (dc_predict_batch)."""
+        bpp = np.dtype(pictures[0][3][0].dtype if len(pictures[0]) == 12 else pictures[0][1][0].dtype).itemsize
+        own, full = [], []
+        words = C.sizeof(_lib.ArithDecodeResult) // 4
+        try:
+            for pic in pictures:
+                if len(pic) == 12:
+                    full.append(tuple(pic))
+                    continue
+                data, coeffs, quant, depth, hc, vc, mode, is_intra, compat = pic
+                raw = np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, np.uint8)
+                dev = DevicePlane(self, 1, max(raw.size, 1), np.uint8)
+                res = DevicePlane(self, 1, words, np.uint32)
+                own.append((dev, res))
+                if raw.size:
+                    dev.upload(raw.reshape(1, -1))
+                full.append((dev, int(raw.size), None, coeffs, quant, depth, hc, vc, mode, is_intra, compat, res))
+            check(self.lib.schro_hip_arith_decode_batch(self.h, arith_decode_pictures(full), len(full), bpp))
+            if not own:
+                return None
+            return [arith_decode_result(res.download()) for dev, res in own]
+        finally:
+            for dev, res in own:
+                dev.free()
+                res.free()
+
+    def decode_transform_data_arith(self, transform_frame, data, params, compat_quant_offset):
+        """schro_hipframe_decode_transform_data_arith on a device frame (frames.DeviceFrame, s16 / s32): the HOST bytes go
+        up, the frame is filled as schro_hipframe_dequantise leaves it.  Returns (arith_decode_result dict, the compat
+        state after the picture, status) -- status 0, or SCHRO_HIP_EINVAL (-1) with result["error"] set when a header holds
+        a quant index above 60 (the frame is untouched); any other status raises (params.is_noarith, params.is_lowdelay)."""
+        raw = np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, np.uint8)
+        compat = C.c_int(int(bool(compat_quant_offset)))
+        res = _lib.ArithDecodeResult()
+        rc = self.lib.schro_hipframe_decode_transform_data_arith(transform_frame.ptr(), raw.ctypes.data if raw.size else None, raw.size,
+                                                                 C.byref(params), C.byref(compat), C.byref(res))
+        if rc != 0 and not (rc == -1 and res.error):
+            check(rc)
+        return arith_decode_result(res), int(compat.value), rc
 
     def motion_encode_batch(self, pictures, capacity=None):
         """schro_hip_motion_encode_batch.  pictures: per picture (motion, x_num_blocks, y_num_blocks, num_refs,

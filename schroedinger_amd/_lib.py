@@ -59,6 +59,8 @@ EXPORTED_SYMBOLS = [
     "schro_hip_encode_transform_data_noarith",
     "schro_hip_noarith_decode_batch", "schro_hip_noarith_decode_check", "schro_hip_noarith_decode_scratch_words",
     "schro_hipframe_decode_transform_data_noarith",
+    "schro_hip_arith_decode_batch", "schro_hip_arith_decode_check", "schro_hip_arith_decode_scratch_words",
+    "schro_hipframe_decode_transform_data_arith",
     "schro_hip_motion_encode_bound", "schro_hip_motion_encode_batch", "schro_hip_motion_encode_check",
     "schro_hip_encode_motion_data_noarith",
     "schro_hip_motion_decode_batch", "schro_hip_motion_decode_check", "schro_hip_motion_decode_scratch_words",
@@ -335,6 +337,16 @@ class NoarithDecodePicture(C.Structure):
                 ("iwt_height", C.c_int * 3), ("transform_depth", C.c_int), ("horiz_codeblocks", C.c_int * 7),
                 ("vert_codeblocks", C.c_int * 7), ("codeblock_mode_index", C.c_int), ("is_intra", C.c_int),
                 ("compat_quant_offset", C.c_int), ("result", C.c_void_p)]
+
+
+class ArithDecodeResult(C.Structure):
+    """SchroHipArithDecodeResult: what schro_hip_arith_decode_batch leaves on the device per picture."""
+    _fields_ = NoarithDecodeResult._fields_ + [("bins", C.c_uint32)]
+
+
+class ArithDecodePicture(C.Structure):
+    """SchroHipArithDecodePicture (include/schro_hip.h): one picture of schro_hip_arith_decode_batch."""
+    _fields_ = NoarithDecodePicture._fields_
 
 
 MOTION_SECTIONS = 9             # SCHRO_HIP_MOTION_SECTIONS (include/schro_hip.h)
@@ -785,6 +797,15 @@ def load():
     L.schro_hipframe_decode_transform_data_noarith.argtypes = [C.POINTER(Frame), vp, C.c_size_t, C.POINTER(Params), C.POINTER(C.c_int),
                                                                C.POINTER(NoarithDecodeResult)]
     L.schro_hipframe_decode_transform_data_noarith.restype = i
+    L.schro_hip_arith_decode_batch.argtypes = [vp, C.POINTER(ArithDecodePicture), i, i]
+    L.schro_hip_arith_decode_batch.restype = i
+    L.schro_hip_arith_decode_check.argtypes = [C.POINTER(ArithDecodePicture), i, i]
+    L.schro_hip_arith_decode_check.restype = i
+    L.schro_hip_arith_decode_scratch_words.argtypes = [C.POINTER(ArithDecodePicture), i, i]
+    L.schro_hip_arith_decode_scratch_words.restype = C.c_int64
+    L.schro_hipframe_decode_transform_data_arith.argtypes = [C.POINTER(Frame), vp, C.c_size_t, C.POINTER(Params), C.POINTER(C.c_int),
+                                                             C.POINTER(ArithDecodeResult)]
+    L.schro_hipframe_decode_transform_data_arith.restype = i
     L.schro_hip_motion_encode_bound.argtypes = [i, i, i, i]
     L.schro_hip_motion_encode_bound.restype = C.c_int64
     L.schro_hip_motion_encode_batch.argtypes = [vp, C.POINTER(MotionEncodePicture), i]

@@ -1097,6 +1097,67 @@ schro_hipframe_decode_transform_data_noarith (SchroHipFrame * transform_frame, c
   return stage_done (ctx, r);
 }
 
+// ... and for an arithmetic-coded picture (schro_hip_arith_decode_batch)
+static_assert (sizeof (SchroHipArithDecodeResult) <= kNoarithDecodeFront, "the result sits in front of the bytes");
+int
+schro_hipframe_decode_transform_data_arith (SchroHipFrame * transform_frame, const uint8_t * host_data, size_t length,
+    SchroHipParams * params, int *compat_quant_offset, SchroHipArithDecodeResult * result)
+{
+  const char *who = "hipframe_decode_transform_data_arith";
+  SCHRO_HIP_REQUIRE (transform_frame && frame_ctx (transform_frame) && params && compat_quant_offset && result
+      && (host_data || length == 0), "%s: bad arguments (the transform frame must be a device frame)", who);
+  SCHRO_HIP_REQUIRE (!params->is_noarith && !params->is_lowdelay, "%s: the picture is %s, not arithmetic-coded core syntax", who,
+      params->is_lowdelay ? "low delay" : "noarith (VLC)");
+  SchroHipContext *ctx = frame_ctx (transform_frame);
+  const int bpp = format_bpp (transform_frame->format);
+  SCHRO_HIP_REQUIRE ((bpp == 2 || bpp == 4) && !(transform_frame->format & 0x100), "%s: the frame must be a planar s16 or s32 frame", who);
+  const int depth = params->transform_depth;
+  SCHRO_HIP_REQUIRE (depth >= 0 && depth <= 6, "%s: transform_depth %d", who, depth);
+  SCHRO_HIP_REQUIRE (length < ((size_t) 1 << 29), "%s: %zu bytes (below 2^29)", who, length);
+  (void) hipSetDevice (ctx->device);
+  const int intra = params->num_refs == 0;
+  SchroHipArithDecodePicture pic;
+  fill_noarith_header (pic, params);
+  pic.is_intra = intra;
+  pic.compat_quant_offset = *compat_quant_offset != 0;
+  for (int k = 0; k < 3; k++) {
+    const SchroHipFrameData & c = transform_frame->components[k];
+    const IwtSize s = iwt_size (params, k);
+    SCHRO_HIP_TRY (require_holds (who, k, c, s, bpp));
+    pic.coeffs[k] = c.data;
+    pic.bytes[k] = (size_t) c.stride * (size_t) s.h;
+    pic.stride[k] = c.stride;
+    pic.iwt_width[k] = s.w;
+    pic.iwt_height[k] = s.h;
+  }
+  SyncBlock blk (ctx, kNoarithDecodeFront, 0, length);
+  if (!blk.d)
+    return SCHRO_HIP_ENOMEM;
+  pic.result = (SchroHipArithDecodeResult *) blk.part (kFront);
+  pic.data = (const uint8_t *) blk.part (kBytes);
+  pic.data_bytes = length;
+  int r = 0;
+  if (length && hipMemcpyAsync (blk.part (kBytes), host_data, length, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+    r = set_error (SCHRO_HIP_EDEVICE, "%s: copy of %zu bytes failed", who, length);
+  if (!r)
+    r = schro_hip_arith_decode_batch (ctx, &pic, 1, bpp);
+  memset (result, 0, sizeof (*result));
+  if (!r && hipMemcpyAsync (result, blk.part (kFront), sizeof (*result), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+    r = set_error (SCHRO_HIP_EDEVICE, "%s: copy of the result failed", who);
+  if ((r = blk.finish (r)))
+    return r;
+  if (result->error)
+    return set_status (SCHRO_HIP_EINVAL, "%s: quant index above 60 in the header of component %u, sub-band %u", who,
+        result->first_error / SCHRO_HIP_NOARITH_MAX_SUBBANDS, result->first_error % SCHRO_HIP_NOARITH_MAX_SUBBANDS);
+  *compat_quant_offset = (int) result->compat_quant_offset;
+  if (intra) {
+    SchroHipDcPlane ll[3];
+    ll_planes (ll, transform_frame, params);
+    r = schro_hip_dc_predict_batch (ctx, ll, 3, bpp);
+  }
+  return stage_done (ctx, r);
+}
+
 int
 schro_upsampled_hipframe_upsample (SchroHipFrame * dest, SchroHipFrame * src)
 {

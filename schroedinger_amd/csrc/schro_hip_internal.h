@@ -1044,6 +1044,40 @@ nd_scratch_words (size_t chunks, size_t codeblocks, size_t subbands, size_t pict
 // stages: 1 header, 2 summary, 4 chain, 8 decode + fill
 int launch_noarith_decode (hipStream_t stream, const NdSubband * d_sbs, int nsbs, const NdPicture * d_pics, int npics,
     const NdScratch & S, int bpp, int lane_x, int fill_x, int stages);
+// arith_dec.hip: the same headers in front of arithmetic-coded payloads.  The sub-bands are NdSubband records (cb_base is
+// not used), a component's 1 + 3 * depth of them one behind the other, so that sub-band index - 3 is the record 3 in front.
+struct AdPicture {
+  const uint8_t *data;
+  const uint32_t *bytes_on_device;      // NULL: data_bytes is the length
+  SchroHipArithDecodeResult *result;
+  void *coeffs[3], *quant[3];   // the planes, for the clear launch (quant all NULL or none)
+  int stride[3], width[3], height[3];
+  uint32_t data_bytes;
+  int sb_first, nsb;            // its sub-bands in the call's table, stream order
+  int mode, is_intra, compat;
+};
+// a serial chain: the LL band of a component, or the bands of one orientation from the coarsest level to the finest
+struct AdTower {
+  int sb_first;                 // its first sub-band in the call's table; the next one is 3 further on
+  int nbands;
+  int pic;
+  int pad;
+};
+// what ad_header_kernel finds in the stream, per sub-band (8 words of queue scratch)
+struct AdBand {
+  uint32_t first_byte;          // of the payload, from `data`
+  uint32_t bytes;               // of the payload, cut at the input's end
+  uint32_t length;              // as stated
+  uint32_t quant_index;
+  uint32_t flags;               // 1 coded, 2 have_zero_flags, 4 have_quant_offset
+  uint32_t pad[3];
+};
+constexpr int kAdBandWords = 8;
+constexpr int kAdContexts = 22; // the contexts transform data uses
+constexpr int kAdClearGridX = 64;       // workgroups per plane of the clear launch: more rows are walked in strides
+// stages: 1 header, 2 clear, 4 decode.  per_lane: a tower per lane instead of per wave (the measured alternative)
+int launch_arith_decode (hipStream_t stream, const NdSubband * d_sbs, const AdPicture * d_pics, int npics, const AdTower * d_towers,
+    int ntowers, AdBand * bands, int bpp, int stages, int per_lane);
 // motion_enc.hip: one picture's motion data.  A superblock owns kMeSbWords words of the call's scratch: what the count
 // launch found in it and where the layout launch put it.
 struct MePicture {
