@@ -562,6 +562,45 @@ def motion_decode_result(words):
             "first_unverified": int(w[6 + 3 * n:7 + 3 * n].view(np.int32)[0])}
 
 
+def motion_arith_decode_pictures(pictures):
+    """The SchroHipMotionArithDecodePicture array of [(data, data_bytes, bytes_on_device, x_num_blocks, y_num_blocks,
+    num_refs, have_global_motion, motion, result)], as motion_decode_pictures takes them."""
+    arr = (_lib.MotionArithDecodePicture * len(pictures))()
+    addr = lambda m: None if m is None else getattr(m, "ptr", m)
+    for a, (data, data_bytes, word, nbx, nby, num_refs, hg, motion, result) in zip(arr, pictures):
+        a.data, a.data_bytes, a.bytes_on_device = addr(data), data_bytes, addr(word)
+        a.x_num_blocks, a.y_num_blocks, a.num_refs, a.have_global_motion = nbx, nby, num_refs, int(hg)
+        a.motion, a.result = addr(motion), addr(result)
+    return arr
+
+
+def motion_arith_decode_check(pictures):
+    """The refusals of Context.motion_arith_decode_batch on the host, without a context
+    (schro_hip_motion_arith_decode_check)."""
+    check(_lib.load().schro_hip_motion_arith_decode_check(motion_arith_decode_pictures(pictures), len(pictures)))
+
+
+def motion_arith_decode_scratch_words(pictures):
+    """schro_hip_motion_arith_decode_scratch_words: the words of queue scratch Context.motion_arith_decode_batch takes."""
+    n = _lib.load().schro_hip_motion_arith_decode_scratch_words(motion_arith_decode_pictures(pictures), len(pictures))
+    if n < 0:
+        check(int(n))
+    return int(n)
+
+
+def motion_arith_decode_result(words):
+    """A downloaded SchroHipMotionArithDecodeResult (uint32 words) as a dict: bytes, section_bytes, section_units,
+    section_offset, section_bins (9 each), truncated, overran, not_consumed (masks over sections), long_codes, unverified,
+    first_unverified."""
+    w = np.asarray(words, np.uint32).ravel()
+    n = _lib.MOTION_SECTIONS
+    return {"bytes": int(w[0]), "section_bytes": [int(x) for x in w[1:1 + n]], "section_units": [int(x) for x in w[1 + n:1 + 2 * n]],
+            "section_offset": [int(x) for x in w[1 + 2 * n:1 + 3 * n]], "section_bins": [int(x) for x in w[1 + 3 * n:1 + 4 * n]],
+            "truncated": int(w[1 + 4 * n]), "overran": int(w[2 + 4 * n]), "not_consumed": int(w[3 + 4 * n]),
+            "long_codes": int(w[4 + 4 * n]), "unverified": int(w[5 + 4 * n]),
+            "first_unverified": int(w[6 + 4 * n:7 + 4 * n].view(np.int32)[0])}
+
+
 # SchroHipQuantChoice (include/schro_hip.h) as a numpy record
 QUANT_CHOICE_DTYPE = np.dtype([("frame_lambda", "<f8"), ("sum", "<f8"), ("chosen_entropy", "<f8", (3, _lib.QUANT_CHOOSE_BANDS)),
                                ("chosen_error", "<f8", (3, _lib.QUANT_CHOOSE_BANDS)), ("quant_index", "<i4", (3, _lib.QUANT_CHOOSE_BANDS)),
@@ -1806,6 +1845,50 @@ class Context:
         check(self.lib.schro_hip_decode_motion_data_noarith(self.h, raw.ctypes.data if raw.size else None, raw.size, C.byref(params),
                                                             C.byref(motion), C.byref(res)))
         return field, motion_decode_result(np.frombuffer(bytes(res), np.uint32))
+
+    def motion_arith_decode_batch(self, pictures):
+        """schro_hip_motion_arith_decode_batch, as motion_decode_batch: per picture (data, x_num_blocks, y_num_blocks,
+        num_refs, have_global_motion) -- data: the HOST bytes -- or the nine members of motion_arith_decode_pictures with
+        caller-owned device buffers.  Mirrors schrodecoder.c:2531-2814 for !is_noarith.  Where the buffers are the call's
+        own it waits and returns per picture (field of MV_DTYPE records, motion_arith_decode_result dict); with
+        caller-owned buffers the call is asynchronous and returns None."""
+        own, full = [], []
+        words = C.sizeof(_lib.MotionArithDecodeResult) // 4
+        try:
+            for pic in pictures:
+                if len(pic) == 9:
+                    full.append(tuple(pic))
+                    continue
+                data, nbx, nby, num_refs, hg = pic
+                raw = np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, np.uint8)
+                dev = DevicePlane(self, 1, max(raw.size, 1), np.uint8)
+                field = DevicePlane(self, 1, nbx * nby * MV_DTYPE.itemsize, np.uint8)
+                res = DevicePlane(self, 1, words, np.uint32)
+                own.append((dev, field, res))
+                if raw.size:
+                    dev.upload(raw.reshape(1, -1))
+                full.append((dev, raw.size, None, nbx, nby, num_refs, hg, field, res))
+            check(self.lib.schro_hip_motion_arith_decode_batch(self.h, motion_arith_decode_pictures(full), len(full)))
+            if not own:
+                return None
+            return [(field.download().reshape(-1).view(MV_DTYPE).copy(), motion_arith_decode_result(res.download()))
+                    for dev, field, res in own]
+        finally:
+            for bufs in own:
+                for b in bufs:
+                    b.free()
+
+    def decode_motion_data_arith(self, data, params):
+        """schro_hip_decode_motion_data_arith: the HOST bytes to the HOST field of params.x_num_blocks x y_num_blocks
+        MV_DTYPE records and the motion_arith_decode_result dict."""
+        raw = np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, np.uint8)
+        field = np.full(params.x_num_blocks * params.y_num_blocks, 0xff, np.uint8).repeat(MV_DTYPE.itemsize).view(MV_DTYPE)
+        motion = _lib.Motion()
+        motion.motion_vectors = field.ctypes.data
+        res = _lib.MotionArithDecodeResult()
+        check(self.lib.schro_hip_decode_motion_data_arith(self.h, raw.ctypes.data if raw.size else None, raw.size, C.byref(params),
+                                                          C.byref(motion), C.byref(res)))
+        return field, motion_arith_decode_result(np.frombuffer(bytes(res), np.uint32))
 
     def encode_transform_data_noarith(self, quant_frame, params, quant_indices, capacity):
         """schro_hip_encode_transform_data_noarith on a device frame (frames.DeviceFrame, s16 / s32) that

@@ -65,6 +65,8 @@ EXPORTED_SYMBOLS = [
     "schro_hip_encode_motion_data_noarith",
     "schro_hip_motion_decode_batch", "schro_hip_motion_decode_check", "schro_hip_motion_decode_scratch_words",
     "schro_hip_decode_motion_data_noarith",
+    "schro_hip_motion_arith_decode_batch", "schro_hip_motion_arith_decode_check", "schro_hip_motion_arith_decode_scratch_words",
+    "schro_hip_decode_motion_data_arith",
     "schro_hip_dequant_batch", "schro_hip_quantise_batch", "schro_hip_subtract_batch", "schro_hipframe_subtract",
     "schro_hipframe_quantise", "schro_hip_histogram_batch", "schro_hipframe_subband_histograms",
     "schro_hip_quant_choose_tables", "schro_hip_quant_choose_batch", "schro_hip_quant_choose_check",
@@ -378,6 +380,19 @@ class MotionDecodePicture(C.Structure):
     _fields_ = [("data", C.c_void_p), ("data_bytes", C.c_size_t), ("bytes_on_device", C.c_void_p), ("x_num_blocks", C.c_int),
                 ("y_num_blocks", C.c_int), ("num_refs", C.c_int), ("have_global_motion", C.c_int), ("motion", C.c_void_p),
                 ("result", C.c_void_p)]
+
+
+class MotionArithDecodeResult(C.Structure):
+    """SchroHipMotionArithDecodeResult: what schro_hip_motion_arith_decode_batch leaves on the device per picture."""
+    _fields_ = [("bytes", C.c_uint32), ("section_bytes", C.c_uint32 * MOTION_SECTIONS),
+                ("section_units", C.c_uint32 * MOTION_SECTIONS), ("section_offset", C.c_uint32 * MOTION_SECTIONS),
+                ("section_bins", C.c_uint32 * MOTION_SECTIONS), ("truncated", C.c_uint32), ("overran", C.c_uint32),
+                ("not_consumed", C.c_uint32), ("long_codes", C.c_uint32), ("unverified", C.c_uint32), ("first_unverified", C.c_int32)]
+
+
+class MotionArithDecodePicture(C.Structure):
+    """SchroHipMotionArithDecodePicture (include/schro_hip.h): one picture of schro_hip_motion_arith_decode_batch."""
+    _fields_ = MotionDecodePicture._fields_
 
 
 HISTOGRAM_BINS = 104           # SCHRO_HIP_HISTOGRAM_BINS (include/schro_hip.h)
@@ -824,6 +839,15 @@ def load():
     L.schro_hip_decode_motion_data_noarith.argtypes = [vp, vp, C.c_size_t, C.POINTER(Params), C.POINTER(Motion),
                                                        C.POINTER(MotionDecodeResult)]
     L.schro_hip_decode_motion_data_noarith.restype = i
+    L.schro_hip_motion_arith_decode_batch.argtypes = [vp, C.POINTER(MotionArithDecodePicture), i]
+    L.schro_hip_motion_arith_decode_batch.restype = i
+    L.schro_hip_motion_arith_decode_check.argtypes = [C.POINTER(MotionArithDecodePicture), i]
+    L.schro_hip_motion_arith_decode_check.restype = i
+    L.schro_hip_motion_arith_decode_scratch_words.argtypes = [C.POINTER(MotionArithDecodePicture), i]
+    L.schro_hip_motion_arith_decode_scratch_words.restype = C.c_int64
+    L.schro_hip_decode_motion_data_arith.argtypes = [vp, vp, C.c_size_t, C.POINTER(Params), C.POINTER(Motion),
+                                                     C.POINTER(MotionArithDecodeResult)]
+    L.schro_hip_decode_motion_data_arith.restype = i
     L.schro_hip_dc_predict_batch.argtypes = [vp, C.POINTER(DcPlane), i, i]
     L.schro_hip_dc_predict_batch.restype = i
     L.schro_hip_shift_right_batch.argtypes = [vp, C.POINTER(DcPlane), i, i, i]

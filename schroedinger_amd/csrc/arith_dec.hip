@@ -32,6 +32,7 @@
 #include "schro_hip_internal.h"
 #include "dequant_one.h"
 #include "na_chunks.h"
+#include "arith_bin.h"
 
 namespace schro {
 namespace {
@@ -72,68 +73,6 @@ ad_follow (uint32_t c)
 {
   const uint32_t step = (c == kCtxZpznF1 || c == kCtxNpznF1) ? 2u : (c == kCtxQCont || c == kCtxZpF6 || c == kCtxNpF6) ? 0u : 1u;
   return c + step;
-}
-
-// ---- the coder ---------------------------------------------------------------------------------------------------------
-
-struct AdCoder {
-  uint32_t range, code;
-  uint32_t offset;              // of the last byte taken
-  uint32_t cntr;
-};
-
-// byte `off` of the payload; 0xff behind its end (schroarith.h:162-173)
-__device__ __forceinline__ uint32_t
-ad_byte (const NdBits & B, uint32_t off)
-{
-  const uint32_t at = B.first + off;
-  if (at >= B.end)
-    return 0xffu;
-  return (nd_word (B, at >> 2) >> (24u - 8u * (at & 3u))) & 0xffu;
-}
-
-// schro_arith_decode_init
-__device__ __forceinline__ void
-ad_init (AdCoder & a, const NdBits & B)
-{
-  a.range = 0xffff0000u;
-  a.code = (ad_byte (B, 0) << 24) | (ad_byte (B, 1) << 16) | (ad_byte (B, 2) << 8) | ad_byte (B, 3);
-  a.offset = 3;
-  a.cntr = 16;
-}
-
-// _schro_arith_decode_bit with the probability in *p.  The renormalisation loop shifts one bit at a time while
-// range <= 0x40000000; here the number of shifts comes from the range's leading zeros and they are taken in runs that end
-// where two bytes enter.  range is never 0: its low 16 bits are, p stays within 0xfe .. 0xff01 (lut[0] is 0), and
-// (range >> 16) >= 0x4001 behind the renormalisation.
-template < typename P > __device__ __forceinline__ uint32_t
-ad_bin (AdCoder & a, const NdBits & B, P * p, const uint16_t * lut)
-{
-  uint32_t range = a.range, code = a.code;
-  if (range <= 0x40000000u) {
-    const uint32_t k = 31u - (uint32_t) __clz ((int) range);
-    uint32_t s = 30u - k + ((range & (range - 1u)) == 0u ? 1u : 0u);
-#pragma unroll 1
-    while (s) {
-      const uint32_t n = min (s, a.cntr);
-      range <<= n;
-      code <<= n;
-      s -= n;
-      a.cntr -= n;
-      if (a.cntr == 0) {
-        code |= (ad_byte (B, a.offset + 1) << 8) | ad_byte (B, a.offset + 2);
-        a.offset += 2;
-        a.cntr = 16;
-      }
-    }
-  }
-  const uint32_t prob = *p;
-  const uint32_t rxp = ((range >> 16) * prob) & 0xffff0000u;
-  const uint32_t bit = code >= rxp ? 1u : 0u;
-  *p = (P) (bit ? prob - lut[prob >> 8] : prob + lut[255u - (prob >> 8)]);
-  a.code = bit ? code - rxp : code;
-  a.range = bit ? range - rxp : rxp;
-  return bit;
 }
 
 // ---- header ------------------------------------------------------------------------------------------------------------

@@ -114,7 +114,7 @@ fill_fused_picture (Picture & pic, const SchroHipFrame * packed, const SchroHipF
 // gives r or else what the wait said.
 constexpr size_t kResultFront = 256, kNoarithDecodeFront = 512;
 static_assert (sizeof (SchroHipNoarithResult) <= kResultFront && sizeof (SchroHipMotionEncodeResult) <= kResultFront
-    && sizeof (SchroHipMotionDecodeResult) <= kResultFront, "the result sits in front of the field and the bytes");
+    && sizeof (SchroHipMotionDecodeResult) <= kResultFront && sizeof (SchroHipMotionArithDecodeResult) <= kResultFront, "the result sits in front of the field and the bytes");
 static_assert (sizeof (SchroHipNoarithDecodeResult) <= kNoarithDecodeFront, "the result sits in front of the bytes");
 
 enum { kFront, kField, kBytes };        // (the parts of a call with a result)
@@ -939,6 +939,48 @@ schro_hip_decode_motion_data_noarith (SchroHipContext * ctx, const void *data, s
   if (!r)
     r = schro_hip_motion_decode_batch (ctx, &pic, 1);
   SchroHipMotionDecodeResult res;
+  memset (&res, 0, sizeof (res));
+  if (!r && (hipMemcpyAsync (&res, blk.part (kFront), sizeof (res), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess
+          || hipMemcpyAsync (motion->motion_vectors, blk.part (kField), field_bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess))
+    r = set_error (SCHRO_HIP_EDEVICE, "%s: copy of the field failed", who);
+  if ((r = blk.finish (r)))
+    return r;
+  if (result)
+    *result = res;
+  return 0;
+}
+
+// The same for an arithmetic-coded picture.
+int
+schro_hip_decode_motion_data_arith (SchroHipContext * ctx, const void *data, size_t length, const SchroHipParams * params,
+    SchroHipMotion * motion, SchroHipMotionArithDecodeResult * result)
+{
+  const char *who = "decode_motion_data_arith";
+  SCHRO_HIP_REQUIRE (ctx && (data || length == 0) && params && motion && motion->motion_vectors, "%s: bad arguments", who);
+  SCHRO_HIP_REQUIRE (!params->is_noarith, "%s: the picture is noarith (schro_hip_decode_motion_data_noarith)", who);
+  SCHRO_HIP_REQUIRE (params->x_num_blocks > 0 && params->y_num_blocks > 0 && params->x_num_blocks <= kMaxMotionBlocks
+      && params->y_num_blocks <= kMaxMotionBlocks, "%s: %d x %d blocks", who, params->x_num_blocks, params->y_num_blocks);
+  SCHRO_HIP_REQUIRE (length < ((size_t) 1 << 29), "%s: %zu bytes (below 2^29)", who, length);
+  const size_t field_bytes = (size_t) params->x_num_blocks * params->y_num_blocks * kMvBytes;
+  SyncBlock blk (ctx, kResultFront, field_bytes, length);
+  if (!blk.d)
+    return SCHRO_HIP_ENOMEM;
+  SchroHipMotionArithDecodePicture pic;
+  memset (&pic, 0, sizeof (pic));
+  pic.data = (const uint8_t *) blk.part (kBytes);
+  pic.data_bytes = length;
+  pic.x_num_blocks = params->x_num_blocks;
+  pic.y_num_blocks = params->y_num_blocks;
+  pic.num_refs = params->num_refs;
+  pic.have_global_motion = params->have_global_motion;
+  pic.motion = blk.part (kField);
+  pic.result = (SchroHipMotionArithDecodeResult *) blk.part (kFront);
+  int r = 0;
+  if (length && hipMemcpyAsync (blk.part (kBytes), data, length, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+    r = set_error (SCHRO_HIP_EDEVICE, "%s: copy of the bytes failed", who);
+  if (!r)
+    r = schro_hip_motion_arith_decode_batch (ctx, &pic, 1);
+  SchroHipMotionArithDecodeResult res;
   memset (&res, 0, sizeof (res));
   if (!r && (hipMemcpyAsync (&res, blk.part (kFront), sizeof (res), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess
           || hipMemcpyAsync (motion->motion_vectors, blk.part (kField), field_bytes, hipMemcpyDeviceToHost, ctx->stream) != hipSuccess))

@@ -1130,6 +1130,29 @@ md_picture_words (size_t data_bytes, uint64_t blocks)
 }
 // stages: 1 header, 2 summary, 4 scan, 8 extract, 16 split walk, 32 mode walk, 64 value walk
 int launch_motion_decode (hipStream_t stream, const MdPicture * d_pics, int npics, uint32_t * scratch, int lane_x, int stages);
+// motion_arith_dec.hip: the same sections behind nine arithmetic coders.  A picture owns ma_picture_words words of the
+// call's scratch, from scratch_first on: the sections (kMaSecWords each), per superblock the split residual, the split and
+// the first unit (the three together padded to an even count), per block the mode bins of unit n (bit 0 ref-1, bit 1
+// ref-2), seven residuals (sections 2 .. 8), the flags and two code indices (ref-1 or DC, ref-2).
+struct MaPicture {
+  const uint8_t *data;
+  const uint32_t *bytes_on_device;      // NULL: data_bytes is the length
+  uint8_t *motion;
+  SchroHipMotionArithDecodeResult *result;
+  uint64_t scratch_first;
+  uint32_t data_bytes, pad;
+  int nbx, nby;
+  int num_refs, have_global;
+};
+constexpr int kMaSecWords = 4;
+static inline uint64_t
+ma_picture_words (uint64_t blocks)
+{
+  const uint64_t nsb = blocks / 16;
+  return (uint64_t) kMdSections * kMaSecWords + ((3 * nsb + 1) & ~1ull) + 11 * blocks;
+}
+// stages: 1 header, 2 split chain, 4 split walk, 8 mode chain, 16 mode walk, 32 value chains, 64 value walk
+int launch_motion_arith_decode (hipStream_t stream, const MaPicture * d_pics, int npics, uint32_t * scratch, int stages);
 // quant_choose.hip: one picture of the quantiser choice.  Its estimates live in the call's scratch: picture p owns
 // 2 * kQcEstimates doubles from p * 2 * kQcEstimates on -- est_entropy [3][19][60], then est_error.
 constexpr int kQcBands = SCHRO_HIP_NOARITH_MAX_SUBBANDS, kQcIndices = SCHRO_HIP_QUANT_CHOOSE_INDICES;
